@@ -14,6 +14,11 @@ backward + flat-bucket gradient all-reduce + Adam(amsgrad) update, on inputs alr
 Rank 0 prints ONE JSON line of < 4 KB (`compact_line`: the contract keys, `roofline`, `cpu_baseline`, a few scalars - no prose) and
 writes the full detail object (every secondary leg, per-kernel tables, notes) to `--detail` (default gpurun_out/bench_detail.json);
 see DESIGN.md §Measurement for the roofline / cpu_baseline definitions.
+
+A plain run measures the headline alone: set-up, warm-up, the N timed steps (no kernel brackets inside them) and the line, whose
+roofline / cpu_baseline / secondary keys are then null and which writes no detail file.  `--full` adds everything else as before:
+the HIP-event-bracketed step and the roofline, the secondary legs, the CPU baseline, the exact-fp32 child run and the detail file.
+`--dump-outputs DIR` writes what the last timed step computed (loss, gradients, updated parameters) as DIR/*.npy.
 """
 import argparse
 import json
@@ -345,7 +350,7 @@ def exact_fp32_companion(args):
     exec: this process keeps its GPU context; the precision switches are read at import), short loop, no secondary legs."""
     env = dict(os.environ, STIN_GEMM_FWD='0', STIN_GEMM_BWD='0')
     cmd = [sys.executable, os.path.abspath(__file__), '--gpus', '1', '--steps', '15', '--warmup', '5', '--vertices', str(args.vertices),
-           '--levels', str(args.levels), '--no-secondary', '--no-cpu-baseline', '--no-live-traffic',
+           '--levels', str(args.levels), '--full', '--no-secondary', '--no-cpu-baseline', '--no-live-traffic',
            '--detail', os.path.splitext(args.detail)[0] + '_exact_fp32.json']
     try:
         r = subprocess.run(cmd, env=env, stdout=subprocess.PIPE, stderr=subprocess.DEVNULL, timeout=300)
@@ -581,6 +586,35 @@ def rccl_debug_parse(path, nbytes):
     return out
 
 
+DUMP_BUDGET_BYTES = 64_000_000     # --dump-outputs writes at most this much array data in all
+
+
+def dump_sample_index(n, k):
+    """The fixed, seeded sample --dump-outputs takes of an n-entry vector when all n do not fit: k distinct indices, ascending,
+    from torch.randperm(n, generator=torch.Generator().manual_seed(0)).  None when k >= n (everything is written)."""
+    if k >= n:
+        return None
+    return torch.randperm(n, generator=torch.Generator().manual_seed(0))[:k].sort().values
+
+
+def dump_outputs(path, loss, step, budget=DUMP_BUDGET_BYTES):
+    """What the last timed step computed, as a caller of TrainStep holds it afterwards: the loss it returned, the flat gradient
+    bucket (all-reduced) and the updated parameters (flattened in bucket order) -> path/{loss,grads,params}.npy (float64 /
+    float32).  Both vectors in full while they fit in `budget` bytes (2 x 16.8 MB for the 3-D config at 3 levels); beyond
+    that (4 levels: 134 MB, 5 levels: 537 MB) the same dump_sample_index() entries of each, so that the files stay within it."""
+    import numpy as np
+    os.makedirs(path, exist_ok=True)
+    grads = step.bucket.flat.detach().float()
+    params = torch.cat([p.detach().float().reshape(-1) for p in step.bucket.params])
+    idx = dump_sample_index(grads.numel(), max(0, budget - 8 - 3 * 128) // 8)   # 4 + 4 bytes per entry; loss, .npy headers
+    if idx is not None:
+        idx = idx.to(grads.device)
+        grads, params = grads[idx], params[idx]
+    arrays = {'loss': loss.detach().double().reshape(1), 'grads': grads, 'params': params}
+    for name, a in arrays.items():
+        np.save(os.path.join(path, name + '.npy'), a.cpu().numpy())
+
+
 def _free_port():
     s = socket.socket()
     s.bind(('127.0.0.1', 0))
@@ -660,8 +694,20 @@ def main():
                     help="activation storage: f32 = the headline (reference numerics); bf16 = the build's "
                          "mixed-precision mode of BASELINE configs 3/5 (NOT the headline, stated tolerance)")
     ap.add_argument('--detail', default=os.path.join(ROOT, 'gpurun_out', 'bench_detail.json'),
-                    help='file the FULL detail object goes to (stdout carries only the compact line)')
+                    help='file the FULL detail object goes to with --full (stdout carries only the compact line)')
+    ap.add_argument('--full', action='store_true',
+                    help='also run what the headline does not need: kernel brackets + roofline, secondary legs, CPU baseline, '
+                         'exact-fp32 child run, detail file (a plain run times the N steps and prints the line)')
+    ap.add_argument('--dump-outputs', metavar='DIR', default=None,
+                    help='after the timed steps, write what the last one computed (loss, flat gradient bucket, updated '
+                         'parameters) as DIR/<name>.npy (rank 0); at most 64 MB in all: larger vectors are written as the '
+                         'same fixed, seeded sample of entries (bench.dump_sample_index)')
     args = ap.parse_args()
+    if not args.full:
+        # a plain run: only the headline figure (the --no-* switches of the legs below are implied)
+        args.no_secondary = args.no_cpu_baseline = args.no_exact_fp32 = args.no_live_traffic = True
+        if args.time_gemms:
+            ap.error('--time-gemms brackets kernels inside the timed steps: it needs --full')
 
     if args.gpus > 1 and 'WORLD_SIZE' not in os.environ:
         self_launch(args)                                     # does not return
@@ -681,7 +727,7 @@ def main():
     if world > 1:
         os.environ.setdefault('MASTER_ADDR', '127.0.0.1')
         if args.backend == 'nccl':
-            rccl_log = rccl_debug_setup(rank)
+            rccl_log = rccl_debug_setup(rank) if args.full else None
             dist.init_process_group('nccl', rank=rank, world_size=world, device_id=device)
         else:
             dist.init_process_group(args.backend, rank=rank, world_size=world)
@@ -700,7 +746,7 @@ def main():
     net = S.define_G(**cfg).to(device)
     if args.dtype == 'bf16':
         net.set_activation_dtype(torch.bfloat16)
-    step = TrainStep(net, lr=7e-5, amsgrad=True, time_allreduce=world > 1, graph=args.graph, freeze_gc=True)
+    step = TrainStep(net, lr=7e-5, amsgrad=True, time_allreduce=world > 1 and args.full, graph=args.graph, freeze_gc=True)
     if args.crops > 0:
         from surface_texture_inpainting_net_amd.data import collate
         sizes = [12_000 + (16_000 * i) // max(args.crops - 1, 1) for i in range(args.crops)]
@@ -774,18 +820,20 @@ def main():
     # the same fast host path as every other step (the per-kernel path cost ~1.5 ms more for that one step); GEMM brackets
     # (--time-gemms) and models that do not take the whole-network path still use the per-kernel path.
     in_net = not args.time_gemms
-    SF.KernelTimer.start(timed, max_records=1_000_000, in_net=in_net)
-    eager_step()                                            # one more untimed step: counts the bracketed launches per step
-    if in_net and not SF.KernelTimer.records:
-        in_net = False
+    per_step = 1
+    if args.full:                                           # (a plain run brackets nothing)
+        SF.KernelTimer.start(timed, max_records=1_000_000, in_net=in_net)
+        eager_step()                                        # one more untimed step: counts the bracketed launches per step
+        if in_net and not SF.KernelTimer.records:
+            in_net = False
+            SF.KernelTimer.stop()
+            SF.KernelTimer.start(timed, max_records=1_000_000)
+            eager_step()
+        per_step = max(1, len(SF.KernelTimer.records))
         SF.KernelTimer.stop()
-        SF.KernelTimer.start(timed, max_records=1_000_000)
-        eager_step()
-    per_step = max(1, len(SF.KernelTimer.records))
-    SF.KernelTimer.stop()
-    fence()
+        fence()
     step.bucket.allreduce_log = []
-    if not args.graph:
+    if args.full and not args.graph:
         # (ONE bracketed step per run: a bracketed step takes the per-kernel host path and costs ~1.5 ms more than a plain one)
         SF.KernelTimer.start(timed, max_records=1_000_000 if args.time_gemms else per_step, in_net=in_net)
     bracketed = SF.KernelTimer.enabled
@@ -799,7 +847,9 @@ def main():
                                                             # waits and, on the shared pool hosts, other tenants' interference)
     fence()
     dt = time.perf_counter() - t0
-    if args.graph:                                          # kernel brackets from two eager steps AFTER the timed replays
+    if args.dump_outputs and rank == 0:                     # before any later leg trains the model further
+        dump_outputs(args.dump_outputs, loss, step)
+    if args.full and args.graph:                            # kernel brackets from two eager steps AFTER the timed replays
         SF.KernelTimer.start(timed, max_records=1_000_000, in_net=in_net)
         for _ in range(2):
             eager_step()
@@ -873,8 +923,8 @@ def main():
         nv = torch.tensor([float(n0), 1.0], dtype=torch.float64, device=device)
         dist.all_reduce(nv, op=dist.ReduceOp.SUM)
         total_vertices, ranks_counted = float(nv[0].item()), int(round(float(nv[1].item())))
-        identical = replicas_identical(net)                 # parameters bit-identical across ranks after the run
-        if not identical:
+        identical = replicas_identical(net) if args.full else None   # parameters bit-identical across ranks after the run
+        if identical is False:
             sys.stderr.write('bench.py: replicas diverged (parameters differ across ranks after %d steps)\n' % args.steps)
     else:
         total_vertices, ranks_counted, identical = float(n0), 1, True
@@ -905,31 +955,33 @@ def main():
         # "scatter-add ... vs HBM roofline" = the aggregation) that moves the most algorithmic bytes, i.e. the level-0 forward
         # kernel of the mesh (with ~3 bracketed launches per shape in a short run the "largest total time" used before
         # flipped between shapes from run to run); the backward kernels are in edge_kernels
-        fwd_rows = [r for r in table if r['kernel'].startswith('stin_edge_relu_mean_fwd')] or table
-        dom = max(fwd_rows, key=lambda r: r['algorithmic_MB'])
-        edge_total_ms = sum(r['total_ms'] for r in table) / (sum(r['launches'] for r in table) / per_step)
-        roofline = {'bound': 'hbm', 'kernel': '%s[N=%d,E=%d,H=%d]' % (dom['kernel'], dom['N'], dom['E'], dom['H']),
-                    'achieved': dom['GBps'], 'peak': HBM_PEAK_GBS, 'unit': 'GB/s', 'frac': dom['GBps'] / HBM_PEAK_GBS,
-                    'traffic': None,
-                    'traffic_unit': 'not measured in this run (the live rocprofv3 --pmc passes run only in the default single-GPU fp32 '
-                                    'headline run; committed passes of every edge kernel: profiles/r*_pmc_traffic.json = %s bytes for this kernel)'
-                                    % pmc_traffic_bytes(dom['kernel'], dom['N'], dom['E'], dom['H']),
-                    'avg_us': dom['avg_us'], 'each_us': dom['each_us'], 'algorithmic_bytes': dom['algorithmic_MB'] * 1e6,
-                    'convention': 'algorithmic bytes (SURVEY 8d): every gathered row charged once per edge; at 200k vertices the '
-                                  'gathered operand (102 MB) is Infinity-Cache resident - see hbm_honest for the HBM-served size',
-                    'selection': 'the forward edge-stage (aggregation, HBM-bound) launch with the most algorithmic bytes = the '
-                                 'level-0 forward kernel (chosen by the workload, not by measured time); every edge kernel/shape '
-                                 'incl. the backward ones is in edge_kernels, the GEMMs (MFMA side, a larger share of the step) '
-                                 'are in roofline_gemm'}
-        contention = None
-        ck = [(k, v) for k, v in ctimes.items() if k[0] == dom['kernel'] and k[1] == (dom['N'], dom['E'], dom['H'])]
-        if ck:
-            cavg = sum(ck[0][1]) / len(ck[0][1])
-            contention = {'kernel': roofline['kernel'], 'avg_us': cavg * 1e6, 'frac': dom['algorithmic_MB'] * 1e6 / cavg / 1e9 / HBM_PEAK_GBS,
-                          'slowdown_vs_roofline_bracket': cavg * 1e6 / dom['avg_us'],
-                          'note': 'the roofline kernel bracketed in a step whose NEXT plan is being built on the side streams at the '
-                                  'same time (prefetch on, as in the un-bracketed timed steps); the `roofline` bracket runs with the '
-                                  'side streams idle'}
+        roofline = contention = edge_total_ms = None
+        if table:                                           # the bracketed step's launches (--full)
+            fwd_rows = [r for r in table if r['kernel'].startswith('stin_edge_relu_mean_fwd')] or table
+            dom = max(fwd_rows, key=lambda r: r['algorithmic_MB'])
+            edge_total_ms = sum(r['total_ms'] for r in table) / (sum(r['launches'] for r in table) / per_step)
+            roofline = {'bound': 'hbm', 'kernel': '%s[N=%d,E=%d,H=%d]' % (dom['kernel'], dom['N'], dom['E'], dom['H']),
+                        'achieved': dom['GBps'], 'peak': HBM_PEAK_GBS, 'unit': 'GB/s', 'frac': dom['GBps'] / HBM_PEAK_GBS,
+                        'traffic': None,
+                        'traffic_unit': 'not measured in this run (the live rocprofv3 --pmc passes run only in a --full single-GPU fp32 '
+                                        'headline run; committed passes of every edge kernel: profiles/r*_pmc_traffic.json = %s bytes for this kernel)'
+                                        % pmc_traffic_bytes(dom['kernel'], dom['N'], dom['E'], dom['H']),
+                        'avg_us': dom['avg_us'], 'each_us': dom['each_us'], 'algorithmic_bytes': dom['algorithmic_MB'] * 1e6,
+                        'convention': 'algorithmic bytes (SURVEY 8d): every gathered row charged once per edge; at 200k vertices the '
+                                      'gathered operand (102 MB) is Infinity-Cache resident - see hbm_honest for the HBM-served size',
+                        'selection': 'the forward edge-stage (aggregation, HBM-bound) launch with the most algorithmic bytes = the '
+                                     'level-0 forward kernel (chosen by the workload, not by measured time); every edge kernel/shape '
+                                     'incl. the backward ones is in edge_kernels, the GEMMs (MFMA side, a larger share of the step) '
+                                     'are in roofline_gemm'}
+            contention = None
+            ck = [(k, v) for k, v in ctimes.items() if k[0] == dom['kernel'] and k[1] == (dom['N'], dom['E'], dom['H'])]
+            if ck:
+                cavg = sum(ck[0][1]) / len(ck[0][1])
+                contention = {'kernel': roofline['kernel'], 'avg_us': cavg * 1e6, 'frac': dom['algorithmic_MB'] * 1e6 / cavg / 1e9 / HBM_PEAK_GBS,
+                              'slowdown_vs_roofline_bracket': cavg * 1e6 / dom['avg_us'],
+                              'note': 'the roofline kernel bracketed in a step whose NEXT plan is being built on the side streams at the '
+                                      'same time (prefetch on, as in the un-bracketed timed steps); the `roofline` bracket runs with the '
+                                      'side streams idle'}
         out = {
             'metric': 'vertices/sec forward+backward on 200k-vert ScanNet mesh; scatter-add GB/s vs HBM roofline',
             'value': total_vertices * args.steps / dt, 'unit': 'vertices/s', 'n_gpus': ranks_counted, 'steps': args.steps,
@@ -992,7 +1044,7 @@ def main():
                          '(profiles/r02_bf16_sensitivity.md) - what certifies the mode is the training curve'}),
             'loss': float(loss),
             'priming_steps': priming,
-            'brackets_inside_network_call': bool(in_net),
+            'brackets_inside_network_call': bool(in_net) if args.full else None,   # (a plain run brackets nothing)
             'host_enqueue_ms_per_step': dt_enqueue / args.steps * 1e3,   # < ms_per_step: the GPU, not the host, bounds the step
             'host_thread_cpu_ms_per_step': dt_cpu / args.steps * 1e3,    # CPU time of the main thread only (backward's Python runs in autograd's device thread)
             'fwd_loss_bwd_only': None if args.no_secondary else {
@@ -1100,11 +1152,11 @@ def main():
                                 'note': 'eval mode, torch.no_grad(), plan resident, rank 0; no ReLU mask store, shared block temporaries'}
             if not args.no_cpu_baseline:
                 out['cpu_baseline'] = cpu_baseline(args.vertices, args.levels, seed=0, headline_mesh=not args.quick_cpu_baseline)
-        print(compact_line(out, write_detail(out, args.detail)), flush=True)
+        print(compact_line(out, write_detail(out, args.detail) if args.full else None), flush=True)
     if world > 1:
         dist.barrier()
         dist.destroy_process_group()
-        if not identical:
+        if identical is False:
             sys.exit(3)
 
 

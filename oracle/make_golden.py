@@ -11,6 +11,7 @@ weights, expected outputs / gradients.
 
     python oracle/make_golden.py            # rewrites tests/golden/
 """
+import copy
 import json
 import os
 import sys
@@ -51,7 +52,47 @@ def _pack_sample(d, sample):
             d['s.' + k] = _np(v)
 
 
-def _model_fixture(name, stin, trainer_mod, cfg, sample, seed, adam_step=False):
+MAX_FILE_BYTES = 1 << 20      # no committed file above 1 MiB: a larger fixture is split into name.npz + name.part2.npz ...
+
+
+def _save_npz(name, d):
+    """np.savez_compressed(tests/golden/<name>.npz), split by key into parts of at most MAX_FILE_BYTES each when one file would be
+    larger (tests/_golden.load_npz merges the parts)."""
+    keys = list(d)
+    for parts in range(1, len(keys) + 1):
+        total = sum(d[k].nbytes for k in keys)
+        groups, cur, acc = [], [], 0
+        for k in keys:                                  # contiguous groups of about total / parts raw bytes
+            if cur and acc + d[k].nbytes > total / parts * 1.05 and len(groups) < parts - 1:
+                groups.append(cur)
+                cur, acc = [], 0
+            cur.append(k)
+            acc += d[k].nbytes
+        groups.append(cur)
+        paths = [os.path.join(OUT, name + ('.npz' if i == 0 else '.part%d.npz' % (i + 1))) for i in range(len(groups))]
+        for f in os.listdir(OUT):
+            if f.startswith(name + '.part') and f.endswith('.npz'):
+                os.remove(os.path.join(OUT, f))
+        for path, g in zip(paths, groups):
+            np.savez_compressed(path, **{k: d[k] for k in g})
+        if all(os.path.getsize(path) <= MAX_FILE_BYTES for path in paths):
+            return
+    raise RuntimeError('%s: one array alone is larger than %d bytes compressed' % (name, MAX_FILE_BYTES))
+
+
+def _fp64_run(net, T, sample):
+    """The same forward + loss + backward with the network and the float inputs in float64 -> (out, d loss / d x)."""
+    net = copy.deepcopy(net).double()
+    net.zero_grad(set_to_none=True)
+    s = HierarchicalBatch(**sample._store)
+    s.x, s.color, s.mask = sample.x.detach().double().requires_grad_(True), sample.color.double(), sample.mask.double()
+    fake = types.SimpleNamespace(models={'graph': net}, criterion=torch.nn.L1Loss(reduction='none'))
+    out = net(s)
+    T.compute_loss(fake, T._graph_forward(fake, s, s.color), s.color, weights=s.mask).backward()
+    return out, s.x.grad
+
+
+def _model_fixture(name, stin, trainer_mod, cfg, sample, seed, adam_step=False, fp64=False):
     torch.manual_seed(seed)
     gen = torch.Generator().manual_seed(seed + 1)
     net = stin.define_G(**cfg)
@@ -62,6 +103,9 @@ def _model_fixture(name, stin, trainer_mod, cfg, sample, seed, adam_step=False):
     _pack_sample(d, sample)
     fake = types.SimpleNamespace(models={'graph': net}, criterion=torch.nn.L1Loss(reduction='none'))
     T = trainer_mod.Inpainting3DTrainer
+    if fp64:                                    # out64 / gx64: the reference's float64 run of the same weights and sample
+        out64, gx64 = _fp64_run(net, T, sample)
+        d['out64'], d['gx64'] = _np(out64), _np(gx64)
     x = sample.x.clone().requires_grad_(True)
     sample.x = x
     out = net(sample)
@@ -80,7 +124,7 @@ def _model_fixture(name, stin, trainer_mod, cfg, sample, seed, adam_step=False):
         for k, v in net.state_dict().items():
             d['sd1.' + k] = _np(v)
     sample.x = x.detach()
-    np.savez_compressed(os.path.join(OUT, name + '.npz'), **d)
+    _save_npz(name, d)
     print(name, 'N0 =', sample.x.shape[0], 'loss =', float(loss), 'params =',
           sum(p.numel() for p in net.parameters()))
 
@@ -436,7 +480,34 @@ def g13_five_levels(stin, trainer_mod):
     s = make_synthetic_mesh(3000, 5, seed=13, dilations=(2,))
     cfg = dict(input_nc=10, output_nc=3, ngf=4, filter_type='edgeconvtransinv', norm='instance', n_blocks=2, n_levels=4,
                pooling_type='max', dilations=[1, 2], checkpoint_bottleneck=True)
-    _model_fixture('g13_5level', stin, trainer_mod, cfg, s, seed=1313)
+    _model_fixture('g13_5level', stin, trainer_mod, cfg, s, seed=1313, fp64=True)
+
+
+def _sha256_state(sd):
+    """[key, dtype, shape, sha256 of the bytes] per state_dict entry, in state_dict order."""
+    import hashlib
+    return [[k, str(v.dtype), list(v.shape), hashlib.sha256(v.detach().contiguous().cpu().numpy().tobytes()).hexdigest()]
+            for k, v in sd.items()]
+
+
+def g14_live_reference(stin):
+    """What the two former side-by-side tests compared live: (a) the reference's forward of a fresh-seed random config on a
+    synthetic mesh (seed 1234 weights, mesh seed 99), (b) the reference's seeded initialisation of the shipped 3-D config (seed
+    49, 4 202 051 parameters) as one sha256 per state_dict entry."""
+    from surface_texture_inpainting_net_amd.synthetic import make_synthetic_mesh as mesh
+    cfg = dict(input_nc=10, output_nc=3, ngf=8, filter_type='edgeconvtransinv', norm='instance', n_blocks=3,
+               n_levels=2, pooling_type='max', dilations=[1, 2, 4], checkpoint_bottleneck=True)
+    torch.manual_seed(1234)
+    ref = stin.define_G(**cfg)
+    out = ref(mesh(900, 3, seed=99, dilations=(2, 4)))
+    cfg3d = dict(input_nc=10, output_nc=3, ngf=64, filter_type='edgeconvtransinv', norm='instance', n_blocks=9,
+                 n_levels=2, pooling_type='max', dilations=[1, 1, 1, 2, 4, 8, 16, 1, 1], checkpoint_bottleneck=True)
+    torch.manual_seed(49)
+    init = _sha256_state(stin.define_G(**cfg3d).state_dict())
+    np.savez_compressed(os.path.join(OUT, 'g14_live_reference.npz'), out=_np(out),
+                        cfg=np.frombuffer(json.dumps(cfg).encode(), dtype=np.uint8),
+                        init_sha256=np.frombuffer(json.dumps(init).encode(), dtype=np.uint8))
+    print('g14_live_reference', tuple(out.shape), len(init), 'state entries')
 
 
 def param_counts(stin):
@@ -476,6 +547,7 @@ def main():
     g11_scene_reader()
     g12_batchnorm_step(stin, trainer_mod)
     g13_five_levels(stin, trainer_mod)
+    g14_live_reference(stin)
     param_counts(stin)
 
 

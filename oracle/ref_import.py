@@ -1,9 +1,8 @@
 """Import the reference's own hot-path classes in THIS container only.
 
-TEST INFRASTRUCTURE (oracle pinning).  /root/reference is read-only, is never
-copied, and does not exist on the GPU box: this module is used only by
-oracle/make_golden.py and by the `reference`-marked CPU tests, which skip when
-/root/reference is absent.
+TEST INFRASTRUCTURE (oracle pinning).  The reference tree is read-only, is never
+copied, and exists only where the fixtures are generated: this module is used
+only by oracle/make_golden.py, whose output the tests read from tests/golden/.
 
 Recipe: put oracle/pyg_shim first on sys.path (build-owned
 restatement of the absent third-party torch_geometric/torch_scatter/torch_sparse

@@ -40,9 +40,9 @@ def level0_fwd_avg_us(stats_csv):
 
 
 d, dd = line(S + '/bench_final.json'), line(S + '/bench_default.json')
-head = ('# Round %s, fp32 headline: `rocprofv3 --kernel-trace --stats --output-format csv -- python3 bench.py --steps 10 --warmup 5 '
-        '--no-cpu-baseline --no-secondary` (200 704-vertex mesh, 1x MI355X; un-profiled `python bench.py --steps 30 --warmup 5`: '
-        '%.2f ms/step = %.1f M vertices/s, %s_bench_final.json; the no-flag default run: %s_bench_default.json, %.2f ms).\n\n'
+head = ('# Round %s, fp32 headline: `rocprofv3 --kernel-trace --stats --output-format csv -- python3 bench.py --full --steps 10 --warmup 5 '
+        '--no-cpu-baseline --no-secondary` (200 704-vertex mesh, 1x MI355X; un-profiled `python bench.py --full --steps 30 --warmup 5`: '
+        '%.2f ms/step = %.1f M vertices/s, %s_bench_final.json; the `--full` default run: %s_bench_default.json, %.2f ms).\n\n'
         'Under the profiler the host is slower than un-profiled, so the timeline below carries more idle time than the bench line; '
         'kernel durations are what the table is for.  The weight-gradient work (`k_gemm_tn_ws`, `k_gemm_tn_*`, `k_wgrad_finalize`, '
         '`k_reduce_slabs`) and the next step\'s plan build (`k_count`, `k_rows`, `k_fill`, `k_rank`) run on side streams beside '
@@ -67,22 +67,22 @@ for tag, jf, pd, title, flags, nsteps in [('hl', 'bench_final', 'prof', 'headlin
     check.append('| %s | `%s` | %.1f | %.1f | %.3f | %.1f (%d) | %.3f | %.3f |' % (
         title, r['kernel'], r['algorithmic_bytes'] / 1e6, r['avg_us'], r['frac'], us, calls, f_prof, r['frac'] / f_prof))
     if tag != 'hl':
-        body = ('# Round %s, config %s under `rocprofv3 --kernel-trace --stats`: `bench.py %s --no-cpu-baseline --no-secondary` '
+        body = ('# Round %s, config %s under `rocprofv3 --kernel-trace --stats`: `bench.py %s --full --no-cpu-baseline --no-secondary` '
                 '(%d profiled steps incl. warm-up)\n\n```\n' % (RN[1:], title, flags, nsteps))
         body += '\n'.join(tool('gaps.py', '%s/%s/run_kernel_trace.csv' % (S, pd), '--steps', str(nsteps - 4)).splitlines()[:6]) + '\n```\n\n'
         body += tool('summarize.py', '%s/%s/run_kernel_stats.csv' % (S, pd), str(nsteps))
         open('%s_config_%s_kernel_stats.md' % (P, tag), 'w').write(body)
 
-rows = [('2: one ~150 k-vertex scene, 3 levels, fp32', '`bench.py --vertices 150000 --steps 30 --warmup 5`', 'config_c2'),
-        ('3: batch of 8 unequal crops (161 k vertices), 4 levels, bf16', '`bench.py --crops 8 --levels 4 --dtype bf16 --steps 30 --warmup 5`', 'config_c3'),
-        ('5: 1 M vertices / 6 M edges, 5 levels, bf16 (one rank of the 8)', '`bench.py --vertices 1000000 --levels 5 --dtype bf16 --steps 8 --warmup 3`', 'config_c5_bf16'),
+rows = [('2: one ~150 k-vertex scene, 3 levels, fp32', '`bench.py --full --vertices 150000 --steps 30 --warmup 5`', 'config_c2'),
+        ('3: batch of 8 unequal crops (161 k vertices), 4 levels, bf16', '`bench.py --full --crops 8 --levels 4 --dtype bf16 --steps 30 --warmup 5`', 'config_c3'),
+        ('5: 1 M vertices / 6 M edges, 5 levels, bf16 (one rank of the 8)', '`bench.py --full --vertices 1000000 --levels 5 --dtype bf16 --steps 8 --warmup 3`', 'config_c5_bf16'),
         ('5 in fp32', 'same without `--dtype bf16`', 'config_c5_f32'),
-        ('headline in bf16 storage', '`bench.py --steps 30 --warmup 5 --dtype bf16`', 'bench_bf16'),
-        ('headline shape on the irregular (Delaunay, degree 3..~20) hierarchy', '`bench.py --steps 30 --warmup 5 --irregular`', 'bench_irregular'),
-        ('20 k-vertex crop, eager', '`bench.py --vertices 20000 --steps 40 --warmup 5`', 'small_20k_eager'),
-        ('20 k-vertex crop, HIP graph', '`bench.py --vertices 20000 --steps 40 --warmup 5 --graph`', 'small_20k_graph')]
+        ('headline in bf16 storage', '`bench.py --full --steps 30 --warmup 5 --dtype bf16`', 'bench_bf16'),
+        ('headline shape on the irregular (Delaunay, degree 3..~20) hierarchy', '`bench.py --full --steps 30 --warmup 5 --irregular`', 'bench_irregular'),
+        ('20 k-vertex crop, eager', '`bench.py --full --vertices 20000 --steps 40 --warmup 5`', 'small_20k_eager'),
+        ('20 k-vertex crop, HIP graph', '`bench.py --full --vertices 20000 --steps 40 --warmup 5 --graph`', 'small_20k_graph')]
 out = ['# Round %s: the other BASELINE configurations on 1 x MI355X (parity-test cases, not the bench line)' % RN[1:], '',
-       'All with `--no-cpu-baseline --no-secondary`; one box, back to back (`profiles/collect_round.sh`, published with '
+       'All with `--full --no-cpu-baseline --no-secondary`; one box, back to back (`profiles/collect_round.sh`, published with '
        '`profiles/publish_round.sh`).  Host enqueue time per step is box-dependent (+-0.5 ms for the same step on different boxes of '
        'the pool).', '',
        '| config | command | ms/step | vertices/s | host enqueue ms | `roofline.frac` (level-0 forward, bracketed) |', '|---|---|---|---|---|---|']

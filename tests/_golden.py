@@ -15,8 +15,14 @@ MODEL_FIXTURES = ['g1_imagegraph_edgeconv', 'g2_3level_transinv_max', 'g2_3level
 
 
 def load_npz(name):
-    with np.load(os.path.join(GOLDEN, name + '.npz')) as z:
-        return {k: z[k] for k in z.files}
+    """tests/golden/<name>.npz, merged with its <name>.part2.npz ... when the fixture is split (no committed file above 1 MiB)."""
+    parts = sorted((f for f in os.listdir(GOLDEN) if f.startswith(name + '.part') and f.endswith('.npz')),
+                   key=lambda f: int(f[len(name) + 5:-4]))
+    out = {}
+    for f in [name + '.npz'] + parts:
+        with np.load(os.path.join(GOLDEN, f)) as z:
+            out.update({k: z[k] for k in z.files})
+    return out
 
 
 class ModelFixture:
@@ -31,6 +37,9 @@ class ModelFixture:
         self.pred = torch.from_numpy(z['pred'])
         self.loss = torch.from_numpy(z['loss'])
         self.gx = torch.from_numpy(z['gx'])
+        # the reference's float64 run of the same weights and sample (five-level fixture only), else None
+        self.out64 = torch.from_numpy(z['out64']) if 'out64' in z else None
+        self.gx64 = torch.from_numpy(z['gx64']) if 'gx64' in z else None
         self._sample = {k[2:]: torch.from_numpy(v) for k, v in z.items() if k.startswith('s.')}
 
     def sample(self, device='cpu'):

@@ -1,5 +1,7 @@
 """The CPU oracle (oracle/stin_oracle.py) against the golden vectors produced by the
 REFERENCE's own classes (oracle/make_golden.py) - runs on CPU, no GPU needed."""
+import copy
+
 import numpy as np
 import pytest
 import torch
@@ -25,7 +27,21 @@ def test_oracle_model_matches_reference_fixture(name):
     assert float((pred - fx.pred).abs().max()) <= 2e-5
     assert abs(float(loss.detach()) - float(fx.loss)) <= 1e-6
     loss.backward()
-    assert rel_err(s.x.grad, fx.gx) < 1e-5
+    if fx.gx64 is None:
+        assert rel_err(s.x.grad, fx.gx) < 1e-5
+    else:
+        # five graph levels: the reference's own fp32 input gradient lies 1.3e-5 (relative) from its fp64 run, so another CPU's
+        # BLAS moves the fp32 comparison past 1e-5 (measured 5.4e-7 on the recording host, 1.8e-5 with MKL's AVX2 path, 2.3e-5
+        # on an AMD EPYC host): the fp32 bar of this fixture is 5e-5.  Beside it, the oracle in fp64 against the reference's
+        # fp64 run is independent of the host and far tighter (measured 0 / 9e-16).
+        assert rel_err(s.x.grad, fx.gx) < 5e-5
+        net64 = copy.deepcopy(net).double()
+        s64 = fx.sample()
+        s64.x, s64.color, s64.mask = s64.x.double().requires_grad_(True), s64.color.double(), s64.mask.double()
+        out64 = net64(s64)
+        stin_oracle.compute_loss(stin_oracle.graph_forward(net64, s64), s64.color, weights=s64.mask).backward()
+        assert float((out64 - fx.out64).abs().max()) <= 1e-12
+        assert rel_err(s64.x.grad, fx.gx64) < 1e-12
     # some grads are analytically zero (a bias in front of an instance norm): compare against the
     # fixture-wide gradient scale, not per tensor
     scale = max(float(g.abs().max()) for g in fx.grads.values())
@@ -181,77 +197,45 @@ def test_oracle_batchnorm_step_fixture():
             assert float((sd[k] - v).abs().max()) <= 1e-6, k
 
 
-@pytest.mark.reference
 def test_oracle_against_live_reference_random_config():
-    """Build-container only: run the reference's own class side by side (fresh seed)."""
-    from oracle import ref_import
+    """A fresh-seed config the other fixtures do not cover, against the reference's own forward recorded by
+    oracle/make_golden.py (fixture g14: the reference's seed-1234 weights, synthetic mesh seed 99)."""
+    import json
     from surface_texture_inpainting_net_amd.synthetic import make_synthetic_mesh
-    stin = ref_import.load_model_module()
-    cfg = dict(input_nc=10, output_nc=3, ngf=8, filter_type='edgeconvtransinv', norm='instance', n_blocks=3,
-               n_levels=2, pooling_type='max', dilations=[1, 2, 4], checkpoint_bottleneck=True)
-    torch.manual_seed(1234)
-    ref = stin.define_G(**cfg)
+    z = load_npz('g14_live_reference')
+    cfg = json.loads(bytes(z['cfg']).decode())
+    assert cfg == dict(input_nc=10, output_nc=3, ngf=8, filter_type='edgeconvtransinv', norm='instance', n_blocks=3,
+                       n_levels=2, pooling_type='max', dilations=[1, 2, 4], checkpoint_bottleneck=True)
+    torch.manual_seed(1234)                     # = the reference's seeded weights (test below)
     net = stin_oracle.define_G(**cfg)
-    net.load_state_dict(ref.state_dict())
     s = make_synthetic_mesh(900, 3, seed=99, dilations=(2, 4))
-    import warnings
-    with warnings.catch_warnings():
-        warnings.simplefilter('ignore')
-        a = ref(s)
-    assert torch.equal(a, net(s))
+    with torch.no_grad():
+        out = net(s)
+    want = torch.from_numpy(z['out'])
+    assert out.shape == want.shape
+    # bit-exact on the host that recorded the fixture (also with 1 or 3 threads); another CPU's BLAS may sum in a different
+    # order, hence the bound of the other model fixtures instead of torch.equal
+    assert float((out - want).abs().max()) <= 2e-5
 
 
-@pytest.mark.reference
 def test_seeded_init_equals_reference_for_product_and_oracle():
     """Same torch seed -> the reference's define_G, the oracle's and the product's produce identical
-    parameters (same construction order), for the shipped 3-D config (4 202 051 parameters)."""
+    parameters (same construction order), for the shipped 3-D config (4 202 051 parameters): every state_dict entry's
+    key, dtype, shape and sha256 against the reference's, recorded by oracle/make_golden.py (fixture g14)."""
+    import hashlib
+    import json
     import warnings
-    from oracle import ref_import
     from surface_texture_inpainting_net_amd import surfacetextureinpaintingnet as S
-    stin = ref_import.load_model_module()
+    want = json.loads(bytes(load_npz('g14_live_reference')['init_sha256']).decode())
+    assert sum(int(np.prod(shape)) for _, _, shape, _ in want) == 4_202_051
     cfg = dict(input_nc=10, output_nc=3, ngf=64, filter_type='edgeconvtransinv', norm='instance', n_blocks=9,
                n_levels=2, pooling_type='max', dilations=[1, 1, 1, 2, 4, 8, 16, 1, 1], checkpoint_bottleneck=True)
-    nets = []
-    for mod in (stin, stin_oracle, S):
+    for mod in (stin_oracle, S):
         torch.manual_seed(49)
         with warnings.catch_warnings():
             warnings.simplefilter('ignore')
-            nets.append(mod.define_G(**cfg))
-    ref_sd = nets[0].state_dict()
-    for other in nets[1:]:
-        sd = other.state_dict()
-        assert list(sd.keys()) == list(ref_sd.keys())
-        assert all(torch.equal(sd[k], ref_sd[k]) for k in sd)
-
-
-@pytest.mark.reference
-def test_pinning_recipe_runs_end_to_end_and_reproduces_every_fixture(tmp_path):
-    """`python oracle/make_golden.py` as documented: main() in ONE process (the g1 loader's stub modules must not break
-    the g11 loader), every array of every fixture compared with the committed tests/golden/ (integers and bytes
-    identical, floats to 1e-6: BLAS summation order of the host)."""
-    import json
-    import os
-    from oracle import make_golden
-    from _golden import GOLDEN as GOLDEN_DIR
-    old = make_golden.OUT
-    make_golden.OUT = str(tmp_path)
-    try:
-        make_golden.main()
-    finally:
-        make_golden.OUT = old
-    committed = sorted(f for f in os.listdir(GOLDEN_DIR) if f.endswith(('.npz', '.json')))
-    assert sorted(os.listdir(tmp_path)) == committed
-    for f in committed:
-        if f.endswith('.json'):
-            assert json.load(open(os.path.join(tmp_path, f))) == json.load(open(os.path.join(GOLDEN_DIR, f))), f
-            continue
-        new, ref = np.load(os.path.join(tmp_path, f), allow_pickle=True), np.load(os.path.join(GOLDEN_DIR, f), allow_pickle=True)
-        assert sorted(new.files) == sorted(ref.files), f
-        for k in ref.files:
-            a, b = new[k], ref[k]
-            assert a.shape == b.shape and a.dtype == b.dtype, (f, k)
-            if np.issubdtype(a.dtype, np.floating):
-                scale = max(1.0, float(np.abs(b).max())) if b.size else 1.0
-                assert float(np.abs(a.astype(np.float64) - b.astype(np.float64)).max()) <= 1e-6 * scale if b.size else True, (f, k)
-            else:
-                assert np.array_equal(a, b), (f, k)
+            sd = mod.define_G(**cfg).state_dict()
+        got = [[k, str(v.dtype), list(v.shape), hashlib.sha256(v.detach().contiguous().numpy().tobytes()).hexdigest()]
+               for k, v in sd.items()]
+        assert [g[0] for g in got] == [w[0] for w in want], mod.__name__
+        assert got == want, mod.__name__

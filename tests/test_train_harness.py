@@ -174,6 +174,41 @@ def test_bench_compact_line_is_short_and_carries_the_contract_keys():
     assert line['cpu_baseline'] is None and line['exact_fp32_ms_per_step'] is None and line['roofline']['frac'] == 0.8625
 
 
+def test_bench_dump_outputs_full_within_budget_and_a_seeded_sample_beyond(tmp_path):
+    """bench.dump_outputs: loss (float64) + flat gradient bucket + flattened parameters (float32) in full while they fit the
+    budget; beyond it the same fixed, seeded, ascending sample of entries of both, with the files inside the budget."""
+    import types
+    import numpy as np
+    sys.path.insert(0, ROOT)
+    import bench
+    torch.manual_seed(0)
+    params = [torch.randn(300, 7), torch.randn(50)]
+    step = types.SimpleNamespace(bucket=types.SimpleNamespace(flat=torch.randn(2150), params=params))
+    flat_params = torch.cat([p.reshape(-1) for p in params])
+    loss = torch.tensor(0.25)
+
+    def load(d):
+        return {n: np.load(os.path.join(d, n + '.npy')) for n in ('loss', 'grads', 'params')}
+
+    bench.dump_outputs(str(tmp_path / 'full'), loss, step)
+    full = load(str(tmp_path / 'full'))
+    assert full['loss'].dtype == np.float64 and full['loss'].tolist() == [0.25]
+    assert full['grads'].dtype == np.float32 and np.array_equal(full['grads'], step.bucket.flat.numpy())
+    assert full['params'].dtype == np.float32 and np.array_equal(full['params'], flat_params.numpy())
+    budget = 8 + 3 * 128 + 8 * 1000                                  # room for 1000 of the 2150 entries
+    for tag in ('a', 'b'):
+        bench.dump_outputs(str(tmp_path / tag), loss, step, budget=budget)
+    a, b = load(str(tmp_path / 'a')), load(str(tmp_path / 'b'))
+    idx = bench.dump_sample_index(2150, 1000).numpy()
+    assert len(idx) == 1000 and np.all(np.diff(idx) > 0)
+    assert np.array_equal(a['grads'], step.bucket.flat.numpy()[idx]) and np.array_equal(a['params'], flat_params.numpy()[idx])
+    assert all(np.array_equal(a[n], b[n]) for n in a) and a['loss'].tolist() == [0.25]
+    assert sum(os.path.getsize(str(tmp_path / 'a' / (n + '.npy'))) for n in a) <= budget
+    # the sample the default budget takes (5 levels: 537 MB of gradients + parameters) fits the 64 MB the option promises
+    k = (bench.DUMP_BUDGET_BYTES - 8 - 3 * 128) // 8
+    assert bench.DUMP_BUDGET_BYTES <= 64_000_000 and 8 + 3 * 128 + 8 * k <= bench.DUMP_BUDGET_BYTES
+
+
 # ------------------------------------------------------------------------------------------------- GPU
 def _free_port():
     s = socket.socket()
@@ -184,11 +219,38 @@ def _free_port():
 
 
 @pytest.mark.gpu
+def test_bench_plain_run_is_the_headline_alone_and_dumps_the_last_step(tmp_path):
+    """A plain `bench.py --gpus 1` run: the contract keys are there, everything --full measures is null, no detail file is written,
+    and --dump-outputs leaves loss (float64) and the flat gradient bucket / parameters (float32, one entry per parameter)."""
+    import numpy as np
+    env = {k: v for k, v in os.environ.items() if k not in ('WORLD_SIZE', 'RANK', 'LOCAL_RANK', 'MASTER_PORT')}
+    detail, dump = tmp_path / 'd.json', tmp_path / 'dump'
+    r = subprocess.run([sys.executable, os.path.join(ROOT, 'bench.py'), '--gpus', '1', '--steps', '3', '--warmup', '1',
+                        '--vertices', '3000', '--detail', str(detail), '--dump-outputs', str(dump)], env=env,
+                       capture_output=True, text=True, timeout=600)
+    assert r.returncode == 0, r.stderr[-2000:]
+    lines = [ln for ln in r.stdout.splitlines() if ln.startswith('{')]
+    assert len(lines) == 1
+    line = json.loads(lines[0])
+    assert line['steps'] == 3 and line['warmup'] == 1 and line['ms_per_step'] > 0 and line['value'] > 0
+    assert line['unit'] == 'vertices/s' and line['higher_is_better'] is True and line['dtype'] == 'f32'
+    assert line['detail'] is None and not detail.exists()
+    assert line['cpu_baseline'] is None and all(v is None for v in line['roofline'].values())
+    for k in ('exact_fp32_ms_per_step', 'hbm_honest_frac', 'scatter_add_frac', 'gpu_idle_ms', 'fwd_loss_bwd_only_ms',
+              'inference_ms', 'edge_stage_ms_per_step', 'gemm_ms_per_step_standalone'):
+        assert line[k] is None, k
+    loss, grads, params = (np.load(str(dump / (n + '.npy'))) for n in ('loss', 'grads', 'params'))
+    assert loss.dtype == np.float64 and loss.shape == (1,) and abs(float(loss[0]) - line['loss']) <= 1e-5 * abs(line['loss'])
+    assert grads.dtype == np.float32 and params.dtype == np.float32 and grads.shape == params.shape == (4_202_051,)
+    assert np.isfinite(grads).all() and np.isfinite(params).all() and np.abs(grads).max() > 0
+
+
+@pytest.mark.gpu
 def test_bench_self_launches_two_ranks_from_a_plain_python_invocation(tmp_path):
     """`python bench.py --gpus 2 --backend gloo` on a 1-GPU box: the parent starts two ranks itself, the line reports the
     all-reduced rank count, per-rank times, the all-reduce bracket and bit-identical replicas."""
     env = {k: v for k, v in os.environ.items() if k not in ('WORLD_SIZE', 'RANK', 'LOCAL_RANK', 'MASTER_PORT')}
-    r = subprocess.run([sys.executable, os.path.join(ROOT, 'bench.py'), '--gpus', '2', '--backend', 'gloo', '--steps', '3',
+    r = subprocess.run([sys.executable, os.path.join(ROOT, 'bench.py'), '--gpus', '2', '--backend', 'gloo', '--full', '--steps', '3',
                         '--warmup', '1', '--vertices', '20000', '--no-cpu-baseline', '--detail', str(tmp_path / 'd.json')], env=env,
                        capture_output=True, text=True, timeout=600)
     assert r.returncode == 0, r.stderr[-2000:]
@@ -207,7 +269,7 @@ def test_bench_eight_rank_self_launch_dry_run_on_one_gpu(tmp_path):
     self-launch (free port, 127.0.0.1 rendezvous), the core-affinity shares (cores // 8 per rank), OMP_NUM_THREADS, the
     all-reduced rank count, per-rank times and bit-identical replicas - everything but RCCL itself."""
     env = {k: v for k, v in os.environ.items() if k not in ('WORLD_SIZE', 'RANK', 'LOCAL_RANK', 'MASTER_PORT')}
-    r = subprocess.run([sys.executable, os.path.join(ROOT, 'bench.py'), '--gpus', '8', '--backend', 'gloo', '--steps', '2',
+    r = subprocess.run([sys.executable, os.path.join(ROOT, 'bench.py'), '--gpus', '8', '--backend', 'gloo', '--full', '--steps', '2',
                         '--warmup', '1', '--vertices', '3000', '--no-cpu-baseline', '--detail', str(tmp_path / 'd.json')], env=env,
                        capture_output=True, text=True, timeout=900)
     assert r.returncode == 0, r.stderr[-3000:]
@@ -229,7 +291,7 @@ def test_bench_two_rank_unequal_scenes_reports_the_straggler_figures(tmp_path):
     vertices, one per rank) on two gloo ranks sharing one device: the line carries the per-rank scene sizes, every rank's time inside
     the all-reduce bracket and north_star's 1 / 2 / 4 / 8 table row; replicas stay bit-identical."""
     env = {k: v for k, v in os.environ.items() if k not in ('WORLD_SIZE', 'RANK', 'LOCAL_RANK', 'MASTER_PORT')}
-    r = subprocess.run([sys.executable, os.path.join(ROOT, 'bench.py'), '--gpus', '2', '--backend', 'gloo', '--steps', '2', '--warmup', '1',
+    r = subprocess.run([sys.executable, os.path.join(ROOT, 'bench.py'), '--gpus', '2', '--backend', 'gloo', '--full', '--steps', '2', '--warmup', '1',
                         '--unequal-scenes', '--no-cpu-baseline', '--no-secondary', '--detail', str(tmp_path / 'd.json')], env=env,
                        capture_output=True, text=True, timeout=900)
     assert r.returncode == 0, r.stderr[-3000:]
