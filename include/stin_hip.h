@@ -574,6 +574,29 @@ size_t stin_masked_l1_workspace_bytes(int64_t N, int C);
 int stin_masked_l1_loss_f32(const float* out, const float* color, const int64_t* mask, int64_t N, int C,
                             int use_weight, float* loss, float* grad, void* workspace, size_t workspace_bytes,
                             stin_stream_t stream);
+/* segmentation: the criterion of the segmentation trainer (trainers/segmentation_trainer.py:54, torch.nn.CrossEntropyLoss with
+ * weight and ignore_index, reduction 'mean') and its confusion matrix (ConfusionMatrixDCM.add, :125-166 / :206-235) in ONE pass
+ * over fp32 logits [., C] of row stride ld (STIN_SEG_MIN_CLASSES <= C <= STIN_SEG_MAX_CLASSES), int64 targets [N], optional fp32
+ * class weights [C].  rows (optional, int64 [N]): target i reads logits row rows[i] of the M rows (the evaluation's
+ * output[original_index_traces] without materialising it); without rows, M >= N and target i reads row i.
+ *   loss (optional): loss[0] = sum w_y nll_i / sum w_y over the targets != ignore_index (fp32; fp64 block partials summed in a
+ *     fixed order, the grid depends on N only: same bits on every run and device); den[0] = sum w_y (fp64, for the backward).
+ *     Needs den and a workspace of stin_seg_ce_workspace_bytes(N).
+ *   confusion (optional): int64 [C][C] += counts of (target, first arg-max of the row; NaN maximal), rows = target; a target
+ *     equal to ignore_index that is a valid class IS counted (as the reference's matrix does).  Integer atomics: exact.
+ * At least one of loss / confusion.  A target outside [0, C) other than ignore_index (any target outside [0, C) when loss is
+ * NULL), or a rows[i] outside [0, M), adds to neither and sets *bad = 1 (bad may be NULL).
+ * bwd: dlogits[i, :] = g w_y (softmax(z_i) - onehot(y_i)) / den with g = grad_loss[0] and den from the forward, both read on
+ * the device; rows whose target is ignored or invalid get zeros.  No row gather. */
+#define STIN_SEG_MIN_CLASSES 2
+#define STIN_SEG_MAX_CLASSES 128
+size_t stin_seg_ce_workspace_bytes(int64_t N);
+int stin_seg_ce_fwd_f32(const float* logits, int64_t ld, int64_t M, const int64_t* rows, const int64_t* target, int64_t N, int C,
+                        const float* weight, int64_t ignore_index, float* loss, double* den, int64_t* confusion, int32_t* bad,
+                        void* workspace, size_t workspace_bytes, stin_stream_t stream);
+int stin_seg_ce_bwd_f32(const float* logits, int64_t ld, const int64_t* target, int64_t N, int C, const float* weight,
+                        int64_t ignore_index, const float* grad_loss, const double* den, float* dlogits, int64_t ldd,
+                        stin_stream_t stream);
 /* graph total variation, the per-step smoothness metric of the trainer (utils/metrics/graph_metrics.py:34-38,
  * trainers/inpainting3d_trainer.py:254-263): out[0] = sum_e sum_c |x[src_e, c] - x[dst_e, c]| / (N * C) over the
  * destination CSR the forward pass has built (rowptr_dst / col_dst), fp64 partial sums in a fixed order. */

@@ -107,6 +107,10 @@ SIGNATURES = {
     'stin_norm_bwd_coef_f32': (c_int, [c_ptr, c_ptr, c_ptr, c_ptr, c_int, c_int, c_ptr, c_ptr, c_ptr]),
     'stin_masked_l1_workspace_bytes': (c_size, [c_i64, c_int]),
     'stin_masked_l1_loss_f32': (c_int, [c_ptr, c_ptr, c_ptr, c_i64, c_int, c_int, c_ptr, c_ptr, c_ptr, c_size, c_ptr]),
+    'stin_seg_ce_workspace_bytes': (c_size, [c_i64]),
+    'stin_seg_ce_fwd_f32': (c_int, [c_ptr, c_i64, c_i64, c_ptr, c_ptr, c_i64, c_int, c_ptr, c_i64, c_ptr, c_ptr, c_ptr, c_ptr,
+                                    c_ptr, c_size, c_ptr]),
+    'stin_seg_ce_bwd_f32': (c_int, [c_ptr, c_i64, c_ptr, c_i64, c_int, c_ptr, c_i64, c_ptr, c_ptr, c_ptr, c_i64, c_ptr]),
     'stin_total_variation_workspace_bytes': (c_size, [c_i64]),
     'stin_total_variation_f32': (c_int, [c_ptr, c_i64, c_ptr, c_ptr, c_i64, c_int, c_ptr, c_ptr, c_size, c_ptr]),
     'stin_graph_laplace_f32': (c_int, [c_ptr, c_i64, c_ptr, c_ptr, c_i64, c_int, c_ptr, c_i64, c_ptr]),

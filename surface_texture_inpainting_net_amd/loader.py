@@ -13,7 +13,10 @@ training) or a batch of crops per step.  This module is the MI355X-side equivale
   every rank runs the same number of steps - the gradient all-reduce needs that).
 
 Items are ``(graph_path, mask_path)`` pairs in the reference's on-disk schema (scene_io.load_scene), already built CPU
-``HierarchicalBatch`` objects, or zero-argument callables returning one.
+``HierarchicalBatch`` objects, or zero-argument callables returning one (the segmentation experiment's label scenes:
+``functools.partial(scene_io.load_label_scene, path, end_level, is_train)``).  Keys other than the per-step features -
+``labels`` and an evaluation scene's ``original_index_traces`` among them - belong to a scene's immutable part: they are
+cached with its graph and never renumbered (the plan's locality renumbering relabels only its own copies of the indices).
 """
 import collections
 import concurrent.futures
@@ -271,8 +274,9 @@ class SceneLoader:
         if self.model is not None and hasattr(self.model, 'build_plan'):
             plan = out._plan_cache = self.model.build_plan(out, after=uploaded, reorder=self._reorder_flag())
         if self.cache is not None:
-            if plan is None:
-                plan = self.model.prefetch_plan(out, reorder=self._reorder_flag()) if self.model is not None else _plan.plan_for(out)
+            if plan is None:                                  # (a model without plan hooks - SingleConvMeshNet - keeps its own indices)
+                plan = (self.model.prefetch_plan(out, reorder=self._reorder_flag()) if hasattr(self.model, 'prefetch_plan')
+                        else _plan.plan_for(out))
             graph = {k: v for k, v in dev.items() if k not in _FEATURE_KEYS}
             self._pending = (key, graph, plan)
         return out

@@ -13,6 +13,10 @@ datasets/scannetcolorgraph_dataloader.py:83-156 hands to the model (same feature
 fall-back to the previous dilation distance when one is empty), plus the CoordsNormalization transform
 (transform/coords_normalization.py:16: x[:, 6:9] /= max_sizes).  Everything stays on the CPU (worker side);
 ``sample.to(device)`` and the GPU plan build happen in the training process.
+
+The semantic-segmentation experiment reads LABEL-graph files of the same schema plus ``labels`` (int64, one per vertex of
+level 0 for a training crop, one per ORIGINAL mesh vertex for an evaluation scene) and without masks:
+``load_label_scene`` / ``label_sample_from_tensors`` restate datasets/scannetlabelgraph_dataloader.py:62-101.
 """
 import numpy as np
 import torch
@@ -77,6 +81,69 @@ def load_scene(graph_path, mask_path, end_level=3, cropped=False, coords_max_siz
         sample, order = renumber_by_locality(sample)
         sample['vertex_order'] = order
     return sample
+
+
+def label_sample_from_tensors(saved, end_level=4, is_train=True, name=None, with_labels=True):
+    """The semantic-segmentation sample (datasets/scannetlabelgraph_dataloader.py:62-101, ScanNetLabelDataSet.__getitem__)
+    from the dict of a label-graph file: x = [colour, normal, position] = [vertices[0][:, 3:9], vertices[0][:, :3]]
+    (9 channels, no normalisation - the experiment's transform lists are empty), per-vertex `labels` (int64 [N0]; left out
+    with with_labels=False, the reference's benchmark mode), and the two trace conventions: a training crop (is_train) takes
+    traces[:end_level - 1] as the hierarchy; an evaluation scene keeps traces[0] (level-0 vertex of every ORIGINAL mesh
+    vertex) as `original_index_traces` and takes traces[1:end_level]."""
+    coords = [torch.as_tensor(v) for v in saved['vertices'][:end_level]]
+    edges = saved['edges'][:end_level]
+    x = torch.cat([coords[0][:, 3:9], coords[0][:, :3]], dim=-1).float()
+    s = HierarchicalBatch(x=x, edge_index=torch.as_tensor(edges[0]).t().contiguous().long())
+    if with_labels:
+        s['labels'] = torch.as_tensor(saved['labels']).long()
+    if name is not None:
+        s['name'] = name
+    if is_train:
+        traces = saved['traces'][:end_level - 1]
+    else:
+        s['original_index_traces'] = torch.as_tensor(saved['traces'][0]).long()
+        traces = saved['traces'][1:end_level]
+    nv = [int(coords[0].shape[0])]
+    for lvl in range(1, len(edges)):
+        s['hierarchy_edge_index_%d' % lvl] = torch.as_tensor(edges[lvl]).t().contiguous().long()
+        tr = torch.as_tensor(traces[lvl - 1]).long()
+        s['hierarchy_trace_index_%d' % lvl] = tr
+        nv.append(int(tr.max()) + 1)
+    s['num_vertices'] = torch.tensor([nv], dtype=torch.int32)
+    s['batch'] = torch.zeros(nv[0], dtype=torch.long)
+    return s
+
+
+def load_label_scene(graph_path, end_level=4, is_train=True, with_labels=True):
+    """A label-graph file of the segmentation experiment (training crop: is_train=True; full evaluation scene with the
+    trace to the original mesh: is_train=False) -> HierarchicalBatch (CPU).  Items of loader.SceneLoader as
+    `functools.partial(load_label_scene, path, 4, False)`."""
+    saved = torch.load(graph_path, map_location='cpu', weights_only=False)
+    name = str(graph_path).rsplit('/', 1)[-1]                                 # the reference keeps the file name (:64-66)
+    return label_sample_from_tensors(saved, end_level, is_train, name, with_labels)
+
+
+def label_graph_tensors(sample, labels, original_index_traces=None):
+    """A single-graph HierarchicalBatch (synthetic.make_synthetic_mesh layout) + per-vertex labels -> the dict of a label-graph
+    file (test / synthetic-data helper): vertices[0] = [pos, rgb, normal, id] [N0, 10], coarser levels [N_l, 3], edges [E_l, 2],
+    traces = [original_index_traces] + level traces for an evaluation scene (labels then belong to the ORIGINAL mesh's
+    vertices), the level traces alone for a training crop."""
+    L = int(sample.num_vertices.shape[-1])
+    x = sample.x
+    n0 = x.shape[0]
+    v0 = torch.zeros(n0, 10)
+    v0[:, 0:3] = x[:, 6:9] * 1.5
+    v0[:, 3:6] = (sample.color + 1.0) / 2.0
+    v0[:, 6:9] = x[:, 3:6]
+    v0[:, 9] = torch.arange(n0)
+    vertices, edges, traces = [v0], [sample.edge_index.t().contiguous()], []
+    if original_index_traces is not None:
+        traces.append(torch.as_tensor(original_index_traces).long())
+    for lvl in range(1, L):
+        vertices.append(torch.zeros(int(sample.num_vertices.reshape(-1)[lvl]), 3))
+        edges.append(sample['hierarchy_edge_index_%d' % lvl].t().contiguous())
+        traces.append(sample['hierarchy_trace_index_%d' % lvl])
+    return {'vertices': vertices, 'edges': edges, 'traces': traces, 'labels': torch.as_tensor(labels).long()}
 
 
 def save_scene_like_reference(sample, graph_path, mask_path, dilation_dists=(2, 4, 8, 16)):
