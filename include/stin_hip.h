@@ -907,6 +907,39 @@ int stin_coalesce_pairs_i64(const int64_t* a, const int64_t* b, const int64_t* m
                             int64_t* out_a, int64_t* out_b, int64_t* state, void* workspace, size_t workspace_bytes,
                             stin_stream_t stream);
 
+/* circle masks: the reference's circle inpainting masks (preprocessing/observed_texture_map_generation.py:530-603,
+ * process_frame_circles) and the training transforms of the 3-D inpainting recipe, on the device.
+ * stin_mask_adjacency_i64: both directions of every (src[e], dst[e]) pair -> int32 CSR rowptr [N + 1], col [2E] (order within a
+ *     row unspecified; duplicates and self loops are kept - harmless to a hop distance).  Pairs with an endpoint outside [0, N)
+ *     are left out and set *bad.  Workspace >= stin_mask_adjacency_workspace_bytes(N).
+ * stin_circle_mask_run: dist[m][v] = min(R, hop distance from v to the nearest centre of mask m), mask[m][v] = R - dist (mask may
+ *     be NULL).  Graph g owns vertices [ptr[g], ptr[g + 1]) (edges never cross graphs).  Each (mask, graph) instance j = m * B + g
+ *     runs the reference's batch loop: k = min(10, n); after each batch total += k, cur = masked / n (fp64), stop when
+ *     cur >= frac, else k = min(n, int(total * (frac / cur - 1))) and stop when k <= 0; centres of batch b are drawn with
+ *     replacement from the graph's range by a counter-based hash of (seed, m, b, i); graph_seeds (HOST array of B <= 64 values, or
+ *     NULL) gives graph g the seed graph_seeds[g] instead (a graph's masks then do not depend on the batch it is collated in).  Exactly max_iters batch launches (no host
+ *     synchronisation); an instance still running after max_iters batches is flagged as capped.  centres != NULL (one mask, one
+ *     graph): a single batch over the given global vertex ids instead.
+ *     info: [M * B][5 + 2 * max_iters] int64 = batches run, done, capped, masked vertices, total centres, the batch sizes, the
+ *     masked count after each batch; then one status word: bit 0 = the overflow drain did not finish, bit 1 = centre_log too short.
+ *     centre_log (may be NULL): [M * B][log_cap] int64, the centres drawn by each instance in order.
+ *     Needs M * N < 2^31 and a workspace of stin_circle_mask_workspace_bytes(N, M, B).  The distances are independent of the
+ *     schedule (integer atomicMin, a vertex expanded only by the workgroup that lowered it).
+ * stin_augment_rewrite_f32: one pass over x [N, ldx >= 10] of the sample: dist != NULL: x[:, 0:3] = color * known, x[:, 9] = known,
+ *     mask[v] = R - dist[v] (known = dist >= R); rot != NULL: x[:, 3:6] = x[:, 3:6] @ rot; lin / rot: x[:, 6:9] = (x[:, 6:9] @ lin)
+ *     @ rot with the product rounded to fp32 in between.  lin, rot: HOST pointers to 9 floats (row-major 3 x 3) or NULL. */
+size_t stin_mask_adjacency_workspace_bytes(int64_t N);
+int stin_mask_adjacency_i64(const int64_t* src, const int64_t* dst, int64_t E, int64_t N, int32_t* rowptr, int32_t* col,
+                            int32_t* bad, void* workspace, size_t workspace_bytes, stin_stream_t stream);
+size_t stin_circle_mask_workspace_bytes(int64_t N, int num_masks, int num_graphs);
+int stin_circle_mask_run(const int32_t* rowptr, const int32_t* col, int64_t N, const int64_t* ptr, int num_graphs, int num_masks,
+                         int radius, double frac, uint64_t seed, const int64_t* graph_seeds, int max_iters, const int64_t* centres,
+                         int64_t num_centres,
+                         int32_t* dist, int64_t* mask, int64_t* info, int64_t* centre_log, int64_t log_cap, void* workspace,
+                         size_t workspace_bytes, stin_stream_t stream);
+int stin_augment_rewrite_f32(float* x, int64_t ldx, const float* color, int64_t ldc, const int32_t* dist, int radius, int64_t* mask,
+                             int64_t N, const float* lin, const float* rot, stin_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -186,6 +186,12 @@ SIGNATURES['stin_bn_affine_res_fwd_f32'] = (c_int, [c_ptr, c_i64, c_ptr, c_ptr, 
 SIGNATURES['stin_relu_mask_bwd_f32'] = (c_int, [c_ptr, c_i64, c_ptr, c_i64, c_ptr, c_i64, c_int, c_int, c_ptr, c_ptr, c_ptr])
 SIGNATURES['stin_concat_unpool_f32'] = (c_int, [c_ptr, c_i64, c_ptr, c_i64, c_ptr, c_i64, c_int, c_int, c_ptr, c_i64, c_ptr])
 SIGNATURES['stin_bn_act_fwd_f32'] = (c_int, [c_ptr, c_i64, c_ptr, c_ptr, c_ptr, c_ptr, c_i64, c_int, c_int, c_ptr, c_i64, c_ptr])
+SIGNATURES['stin_mask_adjacency_workspace_bytes'] = (c_size, [c_i64])
+SIGNATURES['stin_mask_adjacency_i64'] = (c_int, [c_ptr, c_ptr, c_i64, c_i64, c_ptr, c_ptr, c_ptr, c_ptr, c_size, c_ptr])
+SIGNATURES['stin_circle_mask_workspace_bytes'] = (c_size, [c_i64, c_int, c_int])
+SIGNATURES['stin_circle_mask_run'] = (c_int, [c_ptr, c_ptr, c_i64, c_ptr, c_int, c_int, c_int, c_f64, ctypes.c_uint64, c_ptr, c_int, c_ptr, c_i64,
+                                              c_ptr, c_ptr, c_ptr, c_ptr, c_i64, c_ptr, c_size, c_ptr])
+SIGNATURES['stin_augment_rewrite_f32'] = (c_int, [c_ptr, c_i64, c_ptr, c_i64, c_ptr, c_int, c_ptr, c_i64, c_ptr, c_ptr, c_ptr])
 SIGNATURES['stin_bn_act_bwd_f32'] = (c_int, [c_ptr, c_i64, c_ptr, c_i64, c_ptr, c_ptr, c_ptr, c_ptr, c_ptr, c_ptr, c_f32, c_i64, c_int,
                                              c_int, c_ptr, c_i64, c_ptr])
 

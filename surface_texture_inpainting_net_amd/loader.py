@@ -31,6 +31,7 @@ from .data import HierarchicalBatch, collate, sample_keys
 from .scene_io import load_scene
 
 _FEATURE_KEYS = ('x', 'color', 'mask', 'batch', 'name')
+_ADJ_KEY = '_mask_adjacency'          # cache-entry key of the circle-mask pass's level-0 adjacency (never a sample key)
 
 
 def shard_indices(n, epoch, seed=0, shuffle=True, rank=0, world_size=1, sizes=None):
@@ -148,8 +149,13 @@ class SceneLoader:
 
     def __init__(self, items, device, batch_size=1, shuffle=True, seed=0, rank=0, world_size=1, prefetch=2,
                  cache_bytes=32 << 30, end_level=3, cropped=False, model=None, host_cache_bytes=64 << 30, worker_threads=4, workers=2,
-                 sizes=None, locality_order=True):
+                 sizes=None, locality_order=True, augment=None):
         self.items = list(items)
+        # augment (optional, an augment.Compose): the training transforms and / or a fresh circle mask per visit, applied to the
+        # DEVICE copy of every batch on the compute stream after its upload (the host-cached scene is never touched); x and mask
+        # stay in file order.  Per-item randomness from (seed, epoch, item index) only.  None: no change at all.
+        self.augment = augment
+        self._epoch = 0
         # locality_order (round 6, default on): the plan of a scene whose graph part stays resident in HBM (the cache below)
         # is built with the vertices renumbered by locality (plan.GraphPlan(reorder=True): Morton order at level 0, first-child order
         # above).  The renumbering is paid ONCE per scene - the permutation lives in the cached plan - and every later step gathers
@@ -253,17 +259,23 @@ class SceneLoader:
         main.wait_stream(self._copy_stream)
         if entry is not None:                                 # resident graph part + its plan: nothing to upload or build
             graph, plan, _ = entry
-            out = HierarchicalBatch(**graph)
+            out = HierarchicalBatch(**{k: v for k, v in graph.items() if k != _ADJ_KEY})
             for k in _FEATURE_KEYS:
                 if k in dev:
                     out[k] = dev[k]
             plan._sample = out
             out._plan_cache = plan
+            if self.augment is not None:
+                self._augment(ids, out, cpu_batch, graph.get(_ADJ_KEY))
             return out
         if key is not None and any(k not in dev for k in ('edge_index', 'num_vertices')):
             # the worker skipped the graph tensors expecting a cache hit, but the entry was evicted meanwhile: reload
             return self._to_device(ids, next(self._reload(ids)))
         out = HierarchicalBatch(**dev)
+        adj = None
+        if self.augment is not None:
+            adj = self._augment(ids, out, cpu_batch, None)
+            uploaded = main.record_event()                    # the plan's locality order reads x: it starts after the rewrite
         if 'num_vertices' in cpu_batch:
             out._nv_host = cpu_batch['num_vertices'].clone()    # level sizes for the plan without a device sync (a copy:
                                                                 # the staging slot is overwritten by a later batch)
@@ -278,8 +290,31 @@ class SceneLoader:
                 plan = (self.model.prefetch_plan(out, reorder=self._reorder_flag()) if hasattr(self.model, 'prefetch_plan')
                         else _plan.plan_for(out))
             graph = {k: v for k, v in dev.items() if k not in _FEATURE_KEYS}
+            if adj is not None:
+                graph[_ADJ_KEY] = adj                         # the mask pass's adjacency stays with the scene (counts toward cache_bytes)
             self._pending = (key, graph, plan)
         return out
+
+    def _augment(self, ids, out, cpu_batch, adj):
+        """Apply self.augment to the device batch `out` in place (compute stream, no host synchronisation) -> the level-0 mask
+        adjacency it used (None without a CircleMask)."""
+        from . import preprocessing
+        aug = self.augment
+        params = [aug.params_for(self.seed, self._epoch, i) for i in ids]
+        n = int(out['x'].shape[0])
+        if aug.mask is not None and adj is None:
+            adj = preprocessing.mask_adjacency(out['edge_index'], n, check=False)
+        rows, ptr = None, None
+        if len(ids) > 1:
+            nv0 = [int(v) for v in cpu_batch['num_vertices'][:, 0].tolist()]
+            b, rows = 0, []
+            for v in nv0:
+                rows.append((b, b + v))
+                b += v
+            ptr = torch.zeros(len(nv0) + 1, dtype=torch.int64, device=self.device)
+            torch.cumsum(out['num_vertices'][:, 0].long(), 0, out=ptr[1:])
+        aug.apply_(out, params if len(ids) > 1 else params[0], adjacency=adj, ptr=ptr, rows=rows)
+        return adj
 
     def _reorder_flag(self):
         """True where the plan being built will be kept (graph cache on): renumber by locality once; None = the module default."""
@@ -305,6 +340,7 @@ class SceneLoader:
         to the GPU, so a slot is never overwritten before its uploads were issued (and `slot.done` covers their
         completion)."""
         tasks = self._batch_ids(epoch)
+        self._epoch = int(epoch)
 
         def init():
             torch.set_num_threads(self.worker_threads)

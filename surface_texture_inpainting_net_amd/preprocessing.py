@@ -7,8 +7,13 @@
 * ``vertex_clustering`` - ``preprocessing/graph_level_generation.vertex_clustering`` (:193-244), the Rossignac voxel
   clustering alternative to QEM for building the hierarchy (trace + coarse edges + coarse coordinates): one 63-bit voxel key
   per vertex, a stable radix sort and a scan (``stin_voxel_cluster_f64``), the coarse edges through ``stin_coalesce_pairs_i64``.
+* ``circle_masks``      - ``preprocessing/observed_texture_map_generation.process_frame_circles`` (:530-603, ``generate_masks.sh
+  circles``): circles of hop radius R around random centres until a fraction of the vertices is masked, the value being
+  R - (hop distance to the nearest centre).  The python heap BFS per circle becomes one launch per batch of centres
+  (``stin_circle_mask_run``), every mask of a scene and every graph of a collated batch in the same launches, with no host
+  synchronisation; ``circle_mask_from_centres`` is the distance pass alone for given centres.
 
-Both take and return tensors in the reference's own formats.  QEM decimation itself stays out of scope (it shells out
+All take and return tensors in the reference's own formats.  QEM decimation itself stays out of scope (it shells out
 to vcglib's ``tridecimator``).
 """
 import ctypes
@@ -111,3 +116,137 @@ def vertex_clustering(coords, edge_index, voxel_size):
     else:
         ce = edge_index.reshape(2, 0)
     return new_coords[:nc], trace, ce.t().contiguous()
+
+
+def edges_from_faces(faces, num_nodes):
+    """Triangles [F, 3] (int, CUDA) -> the symmetric, coalesced edge_index [2, E] of their sides (what open3d's
+    compute_adjacency_list gives the reference's mask generation), through ``coalesce``."""
+    f = faces.long()
+    if f.numel() == 0:
+        return f.new_zeros(2, 0)
+    a = torch.cat([f[:, 0], f[:, 1], f[:, 2], f[:, 1], f[:, 2], f[:, 0]])
+    b = torch.cat([f[:, 1], f[:, 2], f[:, 0], f[:, 0], f[:, 1], f[:, 2]])
+    return coalesce(torch.stack([a, b]), num_nodes, drop_loops=True)
+
+
+def mask_adjacency(edge_index, num_nodes, check=True):
+    """The undirected int32 CSR of the mask pass: both directions of every edge_index column (duplicates and self loops are
+    harmless to a hop distance) -> (rowptr [N + 1], col [2E]).  No host synchronisation unless `check` (which raises IndexError
+    for an endpoint outside [0, num_nodes))."""
+    if not edge_index.is_cuda:
+        raise TypeError('mask_adjacency runs on the GPU only')
+    lib = _lib.load()
+    ei = edge_index.long().contiguous()
+    n, e, dev = int(num_nodes), int(ei.shape[1]), ei.device
+    rowptr = torch.empty(n + 1, dtype=torch.int32, device=dev)
+    col = torch.empty(max(2 * e, 1), dtype=torch.int32, device=dev)
+    bad = torch.empty(1, dtype=torch.int32, device=dev)
+    ws_bytes = lib.stin_mask_adjacency_workspace_bytes(n)
+    ws = torch.empty(ws_bytes, dtype=torch.uint8, device=dev)
+    _lib.check(lib.stin_mask_adjacency_i64(_ptr(ei[0]) if e else None, _ptr(ei[1]) if e else None, e, n, _ptr(rowptr), _ptr(col),
+                                           _ptr(bad), _ptr(ws), ws_bytes, _stream(ei)), 'stin_mask_adjacency_i64')
+    if check and int(bad.item()) != 0:
+        raise IndexError('edge_index refers to a vertex outside [0, %d)' % n)
+    return rowptr, col
+
+
+INFO_HEAD = 5          # per (mask, graph) row of stin_circle_mask_run's info: batches, done, capped, masked, total
+
+
+def _circle_dist(adjacency, num_nodes, radius, frac, num_masks, seed, ptr, max_iters, centres=None, log_cap=0, want_mask=False,
+                 graph_seeds=None):
+    """-> (dist int32 [M, N], mask int64 [M, N] or None, info int64, centre_log or None); everything stays on the device and
+    nothing synchronises the host.  graph_seeds: one int per graph (host) instead of `seed`."""
+    lib = _lib.load()
+    rowptr, col = adjacency
+    n, dev = int(num_nodes), rowptr.device
+    if ptr is None:
+        ptr = torch.arange(2, dtype=torch.int64, device=dev) * n         # [0, n] without a host-to-device copy
+    ptr = ptr.to(device=dev, dtype=torch.int64).contiguous()
+    B, M = int(ptr.numel()) - 1, int(num_masks)
+    if int(radius) < 1:
+        raise ValueError('radius must be >= 1')
+    iters = 1 if centres is not None else int(max_iters)
+    dist = torch.empty(M, max(n, 1), dtype=torch.int32, device=dev)[:, :n]
+    mask = torch.empty(M, n, dtype=torch.int64, device=dev) if want_mask else None
+    info = torch.empty(M * B * (INFO_HEAD + 2 * iters) + 1, dtype=torch.int64, device=dev)
+    clog = torch.full((M * B, max(int(log_cap), 1)), -1, dtype=torch.int64, device=dev) if log_cap else None
+    ws_bytes = lib.stin_circle_mask_workspace_bytes(n, M, B)
+    ws = torch.empty(ws_bytes, dtype=torch.uint8, device=dev)
+    c = centres.to(device=dev, dtype=torch.int64).contiguous() if centres is not None else None
+    gs = None
+    if graph_seeds is not None:
+        if len(graph_seeds) != B:
+            raise ValueError('graph_seeds needs one seed per graph')
+        gs = (ctypes.c_int64 * B)(*[int(v) & ((1 << 63) - 1) for v in graph_seeds])
+    _lib.check(lib.stin_circle_mask_run(_ptr(rowptr), _ptr(col), n, _ptr(ptr), B, M, int(radius), float(frac), int(seed) & ((1 << 64) - 1),
+                                        gs, iters, _ptr(c) if c is not None and c.numel() else None,
+                                        int(c.numel()) if c is not None else 0, _ptr(dist), _ptr(mask), _ptr(info), _ptr(clog),
+                                        int(log_cap), _ptr(ws), ws_bytes, _stream(rowptr)), 'stin_circle_mask_run')
+    return dist, mask, info, clog
+
+
+def circle_mask_from_centres(edge_index, num_nodes, radius, centres):
+    """The distance pass alone: mask[v] = max(0, R - hop distance from v to the nearest of `centres`) (int64 [N], CUDA) over
+    edge_index taken as undirected - the value process_frame_circles writes for these centres (:570-584)."""
+    n = int(num_nodes)
+    c = torch.as_tensor(centres, dtype=torch.int64).reshape(-1).to(edge_index.device)
+    if c.numel() and (int(c.min()) < 0 or int(c.max()) >= n):
+        raise IndexError('a centre lies outside [0, %d)' % n)
+    adj = mask_adjacency(edge_index, n)
+    if c.numel() == 0:
+        return torch.zeros(n, dtype=torch.int64, device=edge_index.device)
+    _, mask, info, _ = _circle_dist(adj, n, radius, 0.0, 1, 0, None, 1, centres=c, want_mask=True)
+    if int(info[-1]) != 0:
+        raise RuntimeError('circle_mask_from_centres: the overflow drain did not finish (status %d)' % int(info[-1]))
+    return mask[0]
+
+
+def circle_masks(edge_index, num_nodes, radius=16, frac_masked_vertices=0.25, num_masks=1, seed=0, ptr=None,
+                 return_centres=False, max_iters=32, adjacency=None):
+    """Circle masks as ``generate_masks.sh circles --radius R --frac_masked_vertices F --masks_per_scene num_masks`` makes
+    them, on the GPU: int64 [num_masks, N], mask[v] = max(0, R - hop distance to the nearest centre).  edge_index is taken as
+    undirected.  ptr (optional, [B + 1]): the vertex ranges of the graphs of a collated batch - every graph gets its own
+    masks (own count, own batch sizes, centres from its own range).  Per (mask, graph) the reference's loop: 10 centres, then
+    k = int(total * (frac / cur - 1)) more until cur = masked / n >= frac or k <= 0; centres are drawn with replacement by a
+    counter-based hash of (seed, mask, batch, i) (the reference samples without replacement from Python's random), k is
+    clamped to n (the reference would raise), and at most max_iters batches are run.
+    return_centres=True: also a dict with, per mask m and graph g, 'centres'[m][g] (one int64 tensor of global vertex ids per
+    batch), 'sizes' / 'counts' (int64 [M, B, max_iters]: batch sizes and the masked count after each batch; zero after the last
+    batch), 'batches' and 'capped' ([M, B])."""
+    n = int(num_nodes)
+    dev = edge_index.device
+    adj = adjacency if adjacency is not None else mask_adjacency(edge_index, n)
+    log_cap = 0
+    if return_centres:
+        log_cap = min(max(int(max_iters) * max(n, 1), 16), 1 << 16)
+    dist, mask, info, clog = _circle_dist(adj, n, radius, frac_masked_vertices, num_masks, seed, ptr, max_iters, log_cap=log_cap,
+                                          want_mask=True)
+    if not return_centres:
+        return mask
+    M, B = int(num_masks), (1 if ptr is None else int(torch.as_tensor(ptr).numel()) - 1)
+    it = int(max_iters)
+    inf = info.cpu()
+    status = int(inf[-1])
+    if status & 2:
+        raise RuntimeError('circle_masks: more centres than the log holds (%d per mask and graph)' % log_cap)
+    if status & 1:
+        raise RuntimeError('circle_masks: the overflow drain did not finish')
+    rows = inf[:-1].reshape(M, B, INFO_HEAD + 2 * it)
+    clog = clog.cpu().reshape(M, B, -1)
+    centres = []
+    for m in range(M):
+        per_g = []
+        for g in range(B):
+            sizes = rows[m, g, INFO_HEAD:INFO_HEAD + it]
+            nb = int(rows[m, g, 0])
+            out, pos = [], 0
+            for b in range(nb):
+                k = int(sizes[b])
+                out.append(clog[m, g, pos:pos + k].to(dev))
+                pos += k
+            per_g.append(out)
+        centres.append(per_g)
+    return mask, dict(centres=centres, sizes=rows[:, :, INFO_HEAD:INFO_HEAD + it].clone(),
+                      counts=rows[:, :, INFO_HEAD + it:].clone(), batches=rows[:, :, 0].clone(), capped=rows[:, :, 2].bool(),
+                      masked=rows[:, :, 3].clone())

@@ -171,3 +171,33 @@ def save_scene_like_reference(sample, graph_path, mask_path, dilation_dists=(2, 
     torch.save({'vertices': vertices, 'edges': edges, 'traces': traces, 'dilated_edges': dilated,
                 'dilation_dists': list(dilation_dists)}, graph_path)
     np.savez(mask_path, vertex_mask=sample.mask.reshape(-1).numpy())
+
+
+MIN_FRAC_MASKED_VERTS = 0.02            # preprocessing/observed_texture_map_generation.py:54
+
+
+def write_circle_masks(graph_path, masks_dir, masks):
+    """approve_and_write_out_mask (preprocessing/observed_texture_map_generation.py:616-652) for one graph file: every full-mesh
+    mask (masks: [num_masks, N_orig] int, e.g. preprocessing.circle_masks on the original mesh) is gathered to the file's level 0
+    by round(vertices[0][:, -1]), rejected when less than MIN_FRAC_MASKED_VERTS of those vertices are masked, else written as
+    masks_dir/'{:06d}.npz' (key vertex_mask) numbered by mask index - rejected masks leave gaps.  -> the paths written.
+    load_scene(graph_path, path) reads each back unchanged."""
+    import os
+    saved = torch.load(graph_path, map_location='cpu', weights_only=False)
+    v0 = saved['vertices'][0]
+    v0 = v0.numpy() if torch.is_tensor(v0) else np.asarray(v0)
+    vertex_indices = np.round(v0[:, -1]).astype(int)
+    if torch.is_tensor(masks):
+        masks = masks.detach().cpu().numpy()
+    written = []
+    for mask_num, vertex_mask in enumerate(masks):
+        out = np.asarray(vertex_mask)[vertex_indices]
+        counts = np.bincount((out == 0).astype(int))
+        if counts.size == 0 or counts[0] / counts.sum() < MIN_FRAC_MASKED_VERTS:
+            continue
+        os.makedirs(masks_dir, exist_ok=True)
+        path = os.path.join(masks_dir, '{:06d}.npz'.format(mask_num))
+        with open(path, 'wb') as f:
+            np.savez_compressed(f, vertex_mask=out)
+        written.append(path)
+    return written
