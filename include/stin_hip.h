@@ -940,6 +940,61 @@ int stin_circle_mask_run(const int32_t* rowptr, const int32_t* col, int64_t N, c
 int stin_augment_rewrite_f32(float* x, int64_t ldx, const float* color, int64_t ldc, const int32_t* dist, int radius, int64_t* mask,
                              int64_t N, const float* lin, const float* rot, stin_stream_t stream);
 
+/* training crops: the reference's preprocessing/crop_training_samples.py (`process_frame` :51-237) for ALL crops of a scene in one
+ * batched pass.  The scene is a DEVICE table of segments (built by the caller); `n` = elements per crop, `base` = first index of
+ * the segment's [n_crops][n] block in the flat flag / position arrays (blocks do not overlap; `total` = their summed size):
+ *   STIN_CROP_VERTICES  src = float rows [n, width >= 3] (x, y, z first), ibase = first index of its [n_crops][n] block in `inbox`,
+ *                       out = kept rows (float, same width), ids_out (may be NULL) = the kept rows' original indices (int64);
+ *   STIN_CROP_EDGES     src = int64 [n, 2], vseg = index of the level's VERTICES segment, out = int64 [., 2] relabelled rows;
+ *   STIN_CROP_DILATED   as EDGES; a row is kept when both endpoints are KEPT vertices; aux = -1: relabelled by the level's new ids,
+ *                       aux = index of an OCCURS segment: by the rank among the vertices that occur in this filtered set (what the
+ *                       reference's np.unique(..., return_inverse=True) yields);
+ *   STIN_CROP_OCCURS    n = the level's vertex count; flags only;
+ *   STIN_CROP_TRACE     (no flags: base unused) n = fine vertex count, vseg / aux = the fine / coarse VERTICES segments, src = the
+ *                       scene's fine -> coarse map (int64 [n]), out = int64 trace per kept fine vertex, p0 = int32 query list (same
+ *                       length), p1 = uint8 "has a predecessor" per kept coarse vertex (zeroed by the caller), ibase = row of the
+ *                       segment in `info`.
+ * The output of a segment is the concatenation of its crops in crop order; bounds[seg][c] (int64 [n_segs][n_crops + 1]) are the
+ * crop boundaries in it, bounds[seg][n_crops] - bounds[seg][0] rows in all: the caller reads the table once to size the outputs.
+ *   stin_crop_mark:   boxes = double [n_crops][4] (lo_x, hi_x, lo_y, hi_y; closed; z unbounded), inbox uint8 [inbox_total], flags
+ *                     uint8 [total + 1], pos int32 [total + 1] (exclusive scan of flags), status int32 [2]: status[0] != 0 = an edge
+ *                     endpoint outside its level.  Needs total + 1 < 2^31 and stin_crop_workspace_bytes(total).
+ *   stin_crop_gather: writes every `out` / `ids_out` of the table (segments with out == NULL are skipped).
+ *   stin_crop_traces: after the gather (it reads the kept positions from the VERTICES outputs).  info int32 [n_trace][n_crops][4],
+ *                     zeroed by the caller: [0] redirected vertices (target not kept: nearest kept coarse vertex to the vertex's
+ *                     own position, fp64 ((dx dx + dy dy) + dz dz), lowest index on a tie), [1] != 0: some vertex kept its
+ *                     target, [2] kept coarse vertices without a predecessor (the caller repairs these).  status[1] != 0 = a
+ *                     trace value outside the coarse level.
+ *   stin_label_pool_i64: out[v] = most frequent labels[i] over trace0[i] == v (lowest label on a tie, 0 without any), v < n0;
+ *                     integer histogram in the workspace; *status != 0: a trace or label value out of range.
+ * max_n = the largest n of the table (sizes the grid).  Nothing allocates or synchronises. */
+#define STIN_CROP_VERTICES 0
+#define STIN_CROP_EDGES 1
+#define STIN_CROP_DILATED 2
+#define STIN_CROP_OCCURS 3
+#define STIN_CROP_TRACE 4
+#define STIN_CROP_MAX_SEGS 1024
+#define STIN_CROP_MAX_CROPS 65535
+typedef struct stin_crop_seg {
+    int64_t kind, level, vseg, aux, n, base, width, ibase;
+    const void* src;
+    void* out;
+    int64_t* ids_out;
+    void *p0, *p1;
+    int64_t reserved[3];
+} stin_crop_seg_t;                                     /* 16 x 8 = 128 bytes */
+size_t stin_crop_workspace_bytes(int64_t total);
+int stin_crop_mark(const stin_crop_seg_t* segs, int n_segs, int64_t max_n, const double* boxes, int n_crops, int64_t total,
+                   int64_t inbox_total, uint8_t* inbox, uint8_t* flags, int32_t* pos, int64_t* bounds, int32_t* status,
+                   void* workspace, size_t workspace_bytes, stin_stream_t stream);
+int stin_crop_gather(const stin_crop_seg_t* segs, int n_segs, int64_t max_n, int n_crops, const uint8_t* flags, const int32_t* pos,
+                     stin_stream_t stream);
+int stin_crop_traces(const stin_crop_seg_t* segs, int n_segs, int64_t max_n, int n_crops, const uint8_t* flags, const int32_t* pos,
+                     int32_t* info, int32_t* status, stin_stream_t stream);
+size_t stin_label_pool_workspace_bytes(int64_t n0, int n_labels);
+int stin_label_pool_i64(const int64_t* trace0, const int64_t* labels, int64_t n_orig, int64_t n0, int n_labels, int64_t* out,
+                        int32_t* status, void* workspace, size_t workspace_bytes, stin_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

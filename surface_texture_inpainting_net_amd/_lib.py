@@ -194,6 +194,12 @@ SIGNATURES['stin_circle_mask_run'] = (c_int, [c_ptr, c_ptr, c_i64, c_ptr, c_int,
 SIGNATURES['stin_augment_rewrite_f32'] = (c_int, [c_ptr, c_i64, c_ptr, c_i64, c_ptr, c_int, c_ptr, c_i64, c_ptr, c_ptr, c_ptr])
 SIGNATURES['stin_bn_act_bwd_f32'] = (c_int, [c_ptr, c_i64, c_ptr, c_i64, c_ptr, c_ptr, c_ptr, c_ptr, c_ptr, c_ptr, c_f32, c_i64, c_int,
                                              c_int, c_ptr, c_i64, c_ptr])
+SIGNATURES['stin_crop_workspace_bytes'] = (c_size, [c_i64])
+SIGNATURES['stin_crop_mark'] = (c_int, [c_ptr, c_int, c_i64, c_ptr, c_int, c_i64, c_i64, c_ptr, c_ptr, c_ptr, c_ptr, c_ptr, c_ptr, c_size, c_ptr])
+SIGNATURES['stin_crop_gather'] = (c_int, [c_ptr, c_int, c_i64, c_int, c_ptr, c_ptr, c_ptr])
+SIGNATURES['stin_crop_traces'] = (c_int, [c_ptr, c_int, c_i64, c_int, c_ptr, c_ptr, c_ptr, c_ptr, c_ptr])
+SIGNATURES['stin_label_pool_workspace_bytes'] = (c_size, [c_i64, c_int])
+SIGNATURES['stin_label_pool_i64'] = (c_int, [c_ptr, c_ptr, c_i64, c_i64, c_int, c_ptr, c_ptr, c_ptr, c_size, c_ptr])
 
 _lib = None
 

@@ -250,3 +250,263 @@ def circle_masks(edge_index, num_nodes, radius=16, frac_masked_vertices=0.25, nu
     return mask, dict(centres=centres, sizes=rows[:, :, INFO_HEAD:INFO_HEAD + it].clone(),
                       counts=rows[:, :, INFO_HEAD + it:].clone(), batches=rows[:, :, 0].clone(), capped=rows[:, :, 2].bool(),
                       masked=rows[:, :, 3].clone())
+
+
+# ------------------------------------------------------------------------------------------------------------- training crops
+MIN_NUM_MAXIMALLY_DECIMATED_VERTS = 50      # preprocessing/crop_training_samples.py:24
+_SEG_WORDS = 16                             # int64 words of a stin_crop_seg_t
+_SEG_VERTICES, _SEG_EDGES, _SEG_DILATED, _SEG_OCCURS, _SEG_TRACE = range(5)
+
+
+def crop_positions(vertices0, stride):
+    """The reference's get_sampling_positions (crop_training_samples.py:27-48): centres of the crop grid along x and y -
+    np.arange(min, max, stride) on the float32 extent of level 0, centred by (max - last) / 2.  -> (xs, ys) float64 numpy arrays.
+    vertices0: [N0, >= 3] tensor (any device) or array."""
+    import numpy as np
+    v = vertices0[:, :3] if torch.is_tensor(vertices0) else torch.as_tensor(np.asarray(vertices0)[:, :3])
+    mins, maxs = v.min(dim=0).values.cpu().numpy(), v.max(dim=0).values.cpu().numpy()
+    out = []
+    for a in (0, 1):
+        p = np.arange(mins[a], maxs[a], stride)
+        out.append(np.asarray(p + (maxs[a] - p[-1]) / 2, dtype=np.float64))
+    return out[0], out[1]
+
+
+def pooled_labels(trace0, labels, n0):
+    """Label of every level-0 vertex from the labels of the ORIGINAL mesh's vertices (crop_training_samples.py:119-125): the most
+    frequent label among trace0 == v, the lowest on a tie, 0 for a vertex without originals.  int64 [n0], on the device; an integer
+    histogram (stin_label_pool_i64), so the result does not depend on the schedule."""
+    if not (trace0.is_cuda and labels.is_cuda):
+        raise TypeError('pooled_labels runs on the GPU only')
+    lib = _lib.load()
+    t, lab = trace0.long().contiguous(), labels.long().contiguous()
+    if t.numel() != lab.numel():
+        raise ValueError('labels and traces[0] must have one entry per vertex of the original mesh')
+    n_labels = int(lab.max()) + 1 if lab.numel() else 1
+    if n_labels < 1:
+        raise IndexError('negative label')
+    out = torch.empty(int(n0), dtype=torch.int64, device=t.device)
+    status = torch.empty(1, dtype=torch.int32, device=t.device)
+    ws_bytes = lib.stin_label_pool_workspace_bytes(int(n0), n_labels)
+    ws = torch.empty(ws_bytes, dtype=torch.uint8, device=t.device)
+    _lib.check(lib.stin_label_pool_i64(_ptr(t), _ptr(lab), int(t.numel()), int(n0), n_labels, _ptr(out), _ptr(status), _ptr(ws),
+                                       ws_bytes, _stream(t)), 'stin_label_pool_i64')
+    if int(status.item()) != 0:
+        raise IndexError('traces[0] refers to a vertex outside [0, %d) or a label is negative' % int(n0))
+    return out
+
+
+def _repair_trace(trace, fine, coarse):
+    """The reference's fix for coarse vertices without a predecessor (crop_training_samples.py:168-189), on the host: the missing
+    ones in ascending order; for each, the kept fine vertices by ascending distance (stable), the first whose target has more than
+    one predecessor is re-pointed.  trace int64 [nf] (modified), fine / coarse float32 [., >= 3] numpy.  -> False: no candidate."""
+    import numpy as np
+    counts = np.bincount(trace, minlength=coarse.shape[0])
+    f = fine[:, :3].astype(np.float64)
+    for m in np.flatnonzero(counts == 0):
+        c = coarse[m, :3].astype(np.float64)
+        dx, dy, dz = c[0] - f[:, 0], c[1] - f[:, 1], c[2] - f[:, 2]
+        for nb in np.argsort((dx * dx + dy * dy) + dz * dz, kind='stable'):
+            if counts[trace[nb]] > 1:
+                counts[trace[nb]] -= 1
+                counts[m] += 1
+                trace[nb] = m
+                break
+        else:
+            return False
+    return True
+
+
+def _crop_chunk(saved, boxes, pooled, reference_dilated_labels, min_coarsest):
+    """All crops of `boxes` (float64 [C, 4] numpy) in one batched pass -> per crop None (rejected by size), False (skipped) or
+    (crop dict, kept ids per level)."""
+    import numpy as np
+    lib = _lib.load()
+    verts = [v.float().contiguous() for v in saved['vertices']]
+    dev = verts[0].device
+    L, C = len(verts), int(boxes.shape[0])
+    edges = [e.long().reshape(-1, 2).contiguous() for e in saved['edges']]
+    traces = [t.long().contiguous() for t in saved['traces']]
+    dil_in = saved.get('dilated_edges') or [None] * L
+    if len(edges) != L or len(traces) != L or len(dil_in) != L:
+        raise ValueError('vertices, edges, traces and dilated_edges need one entry per level')
+    for l in range(1, L):
+        if traces[l].numel() != verts[l - 1].shape[0]:
+            raise ValueError('traces[%d] needs one entry per vertex of level %d' % (l, l - 1))
+    # ---- segment table: one row per vertex set, edge list, dilated set (and its occurrence flags) and trace
+    rows = []
+    base = ibase = 0
+
+    def add(kind, level, n, src=None, vseg=-1, aux=-1, width=0, flagged=True, ib=0):
+        nonlocal base
+        rows.append(dict(kind=kind, level=level, vseg=vseg, aux=aux, n=int(n), base=base if flagged else 0, width=width, ibase=ib,
+                         src=src, out=None, ids=None, p0=None, p1=None))
+        if flagged:
+            base += C * int(n)
+        return len(rows) - 1
+
+    vseg = []
+    for l in range(L):
+        if verts[l].dim() != 2 or verts[l].shape[1] < 3:
+            raise ValueError('vertices[%d] must be [N, >= 3]' % l)
+        vseg.append(add(_SEG_VERTICES, l, verts[l].shape[0], verts[l], width=int(verts[l].shape[1]), ib=ibase))
+        ibase += C * int(verts[l].shape[0])
+    eseg = [add(_SEG_EDGES, l, edges[l].shape[0], edges[l], vseg=vseg[l]) for l in range(L)]
+    dseg = []
+    for l in range(L):
+        if dil_in[l] is None:
+            dseg.append(None)
+            continue
+        cur = []
+        for s in dil_in[l]:
+            if not torch.is_tensor(s) or s.numel() == 0:
+                cur.append(None)                                   # an empty list stays an empty list
+                continue
+            s = s.long().reshape(-1, 2).contiguous()
+            occ = add(_SEG_OCCURS, l, verts[l].shape[0], vseg=vseg[l]) if reference_dilated_labels else -1
+            cur.append(add(_SEG_DILATED, l, s.shape[0], s, vseg=vseg[l], aux=occ))
+        dseg.append(cur)
+    tseg = [add(_SEG_TRACE, l, verts[l].shape[0], traces[l + 1], vseg=vseg[l], aux=vseg[l + 1], flagged=False, ib=l)
+            for l in range(L - 1)]
+    total, inbox_total, n_segs = base, ibase, len(rows)
+    max_n = max(r['n'] for r in rows)
+    if total + 1 >= 2 ** 31 - 1:
+        raise ValueError('too many crops for one pass')           # (crop_scene splits the crop list before this can happen)
+
+    def table():
+        t = np.zeros((n_segs, _SEG_WORDS), dtype=np.int64)
+        for i, r in enumerate(rows):
+            t[i, :8] = (r['kind'], r['level'], r['vseg'], r['aux'], r['n'], r['base'], r['width'], r['ibase'])
+            t[i, 8:13] = [0 if r[k] is None else r[k].data_ptr() for k in ('src', 'out', 'ids', 'p0', 'p1')]
+        return torch.from_numpy(t).to(dev)
+
+    stream = _stream(verts[0])
+    boxes_d = torch.from_numpy(np.ascontiguousarray(boxes, dtype=np.float64)).to(dev)
+    inbox = torch.empty(max(inbox_total, 1), dtype=torch.uint8, device=dev)
+    flags = torch.empty(total + 1, dtype=torch.uint8, device=dev)
+    pos = torch.empty(total + 1, dtype=torch.int32, device=dev)
+    bounds = torch.empty(n_segs, C + 1, dtype=torch.int64, device=dev)
+    status = torch.empty(2, dtype=torch.int32, device=dev)
+    ws_bytes = lib.stin_crop_workspace_bytes(total)
+    ws = torch.empty(ws_bytes, dtype=torch.uint8, device=dev)
+    segs = table()
+    _lib.check(lib.stin_crop_mark(_ptr(segs), n_segs, max_n, _ptr(boxes_d), C, total, inbox_total, _ptr(inbox), _ptr(flags), _ptr(pos),
+                                  _ptr(bounds), _ptr(status), _ptr(ws), ws_bytes, stream), 'stin_crop_mark')
+    bnd = bounds.cpu().numpy()                                     # the one read that sizes the outputs
+    bnd = bnd - bnd[:, :1]
+    # ---- outputs: every segment's crops back to back
+    for i, r in enumerate(rows):
+        n_out = int(bnd[i, C])
+        if r['kind'] == _SEG_VERTICES:
+            r['out'] = torch.empty(max(n_out, 1), r['width'], dtype=torch.float32, device=dev)
+            r['ids'] = torch.empty(max(n_out, 1), dtype=torch.int64, device=dev)
+        elif r['kind'] in (_SEG_EDGES, _SEG_DILATED):
+            r['out'] = torch.empty(max(n_out, 1), 2, dtype=torch.int64, device=dev)
+    for l, i in enumerate(tseg):
+        nf, nc = int(bnd[vseg[l], C]), int(bnd[vseg[l + 1], C])
+        rows[i]['out'] = torch.empty(max(nf, 1), dtype=torch.int64, device=dev)
+        rows[i]['p0'] = torch.empty(max(nf, 1), dtype=torch.int32, device=dev)
+        rows[i]['p1'] = torch.zeros(max(nc, 1), dtype=torch.uint8, device=dev)
+    segs = table()
+    _lib.check(lib.stin_crop_gather(_ptr(segs), n_segs, max_n, C, _ptr(flags), _ptr(pos), stream), 'stin_crop_gather')
+    info = torch.zeros(max(L - 1, 1), C, 4, dtype=torch.int32, device=dev)
+    if L > 1:
+        _lib.check(lib.stin_crop_traces(_ptr(segs), n_segs, max_n, C, _ptr(flags), _ptr(pos), _ptr(info), _ptr(status), stream),
+                   'stin_crop_traces')
+    word = torch.cat([status, info.reshape(-1)]).cpu().numpy()     # the status word of the scene: read once
+    if word[0] != 0:
+        raise IndexError('an edge or dilated edge refers to a vertex outside its level')
+    if word[1] != 0:
+        raise IndexError('a trace refers to a vertex outside the next level')
+    info_h = word[2:].reshape(max(L - 1, 1), C, 4)
+    labels_flat = pooled[rows[vseg[0]]['ids'][:int(bnd[vseg[0], C])]] if pooled is not None else None
+    out = []
+    for c in range(C):
+        def part(i, _c=c):
+            return rows[i]['out'][int(bnd[i, _c]):int(bnd[i, _c + 1])]
+        counts = [int(bnd[vseg[l], c + 1] - bnd[vseg[l], c]) for l in range(L)]
+        if min(counts) == 0 or counts[-1] < min_coarsest:         # rejected by size: before the traces are looked at (:136)
+            out.append((None, counts))
+            continue
+        ok = True
+        tr = []
+        for l in range(L - 1):
+            if info_h[l, c, 1] == 0:                               # no fine vertex kept its target (the reference: IndexError)
+                ok = False
+                break
+            t = rows[tseg[l]]['out'][int(bnd[vseg[l], c]):int(bnd[vseg[l], c + 1])]   # one entry per kept fine vertex
+            if info_h[l, c, 2] != 0:                               # rare: a coarse vertex without predecessor -> host repair
+                th = t.cpu().numpy().copy()
+                if not _repair_trace(th, part(vseg[l]).cpu().numpy(), part(vseg[l + 1]).cpu().numpy()):
+                    ok = False
+                    break
+                t = torch.from_numpy(th).to(dev)
+            tr.append(t)
+        if not ok:
+            out.append((False, counts))
+            continue
+        crop = {'vertices': [part(vseg[l]) for l in range(L)], 'edges': [part(eseg[l]) for l in range(L)],
+                'dilated_edges': [None if dseg[l] is None else [[] if i is None else part(i) for i in dseg[l]] for l in range(L)],
+                'dilation_dists': saved.get('dilation_dists'), 'traces': tr}
+        if labels_flat is not None:
+            crop['labels'] = labels_flat[int(bnd[vseg[0], c]):int(bnd[vseg[0], c + 1])]
+        kept = [rows[vseg[l]]['ids'][int(bnd[vseg[l], c]):int(bnd[vseg[l], c + 1])] for l in range(L)]
+        out.append(((crop, kept), counts))
+    return out
+
+
+def crop_scene(saved, block_size=3.0, stride=1.5, positions=None, min_coarsest=MIN_NUM_MAXIMALLY_DECIMATED_VERTS,
+               reference_dilated_labels=False, return_kept=False):
+    """Training crops of one scene, the reference's preprocessing/crop_training_samples.py `process_frame` (:51-237), with every
+    crop of the sampling grid cut in ONE batched pass on the GPU (the crop index is a grid dimension of the kernels).
+
+    saved: the dict of a graphs/<scene>.pt file - vertices[L] (level 0: [N0, 10]), edges[L] [E, 2] int64, traces[L] (traces[0]
+    maps the original mesh to level 0, traces[l + 1] level l to level l + 1), dilated_edges[L] (None or a list of [E_d, 2] tensors /
+    empty lists), dilation_dists, optional labels (of the ORIGINAL mesh's vertices) - with its tensors on a CUDA device.
+    -> [(counter, crop)]: crop has the keys and dtypes the reference writes (vertices float32; edges, traces, dilated_edges, labels
+    int64; dilation_dists passed through), tensors on the device (views of one buffer per level and kind);
+    scene_io.sample_from_tensors(crop, mask, end_level, cropped=True) takes it as it is.  return_kept=True: (counter, crop, kept)
+    with kept[l] = the scene rows of the crop's level-l vertices (int64).
+
+    Per grid position of crop_positions (x outer loop, y inner loop) the box is position -/+ block_size / 2 in float64, closed,
+    z unbounded.  Per level: edges with both endpoints in the box, in their order; vertices = the endpoints of those edges,
+    renumbered in their order; dilated rows between kept vertices; traces of kept targets relabelled, the others redirected to
+    the kept coarse vertex nearest to the vertex's own position (float64, lowest index on a tie); coarse vertices left without a
+    predecessor repaired as the reference does (ascending).  A crop with an empty level or fewer than min_coarsest vertices on the
+    last one is left out, as is one that cannot be repaired or in which no vertex of a level keeps its target.
+    counter: the number the reference puts into the file name - its block_counter advances by 1 per grid position and by 2 for a
+    position rejected by the size rule (`block_counter += 1; continue` runs the `finally` increment as well); a crop skipped
+    otherwise advances it by 1.  positions: explicit [(x, y)] centres instead of the grid; the counter is then the list index.
+    reference_dilated_labels: relabel each dilated set by the rank among the vertices that occur in THAT filtered set - the
+    reference's np.unique(..., return_inverse=True), which mislabels the set whenever a crop vertex has no dilated edge.  Off by
+    default (the level's new ids, like data.collate(fix_dilated_offsets=True)); on for file parity."""
+    import numpy as np
+    v0 = saved['vertices'][0]
+    if not all(torch.is_tensor(v) and v.is_cuda for v in saved['vertices']):
+        raise TypeError('crop_scene runs on the GPU only (no CPU fallback exists)')
+    if positions is None:
+        xs, ys = crop_positions(v0, stride)
+        centres = np.asarray([(x, y) for x in xs for y in ys], dtype=np.float64).reshape(-1, 2)
+    else:
+        centres = np.asarray([(float(x), float(y)) for x, y in positions], dtype=np.float64).reshape(-1, 2)
+    if centres.shape[0] == 0:
+        return []
+    h = block_size / 2
+    boxes = np.stack([centres[:, 0] - h, centres[:, 0] + h, centres[:, 1] - h, centres[:, 1] + h], 1)
+    pooled = pooled_labels(saved['traces'][0], saved['labels'], v0.shape[0]) if 'labels' in saved else None   # once per scene
+    per_crop = sum(2 * int(v.shape[0]) for v in saved['vertices']) + sum(int(e.numel()) // 2 for e in saved['edges'])
+    for x in saved.get('dilated_edges') or []:
+        per_crop += sum(int(s.numel()) // 2 + int(s.numel() > 0) * max(int(v.shape[0]) for v in saved['vertices'])
+                        for s in (x or []) if torch.is_tensor(s))
+    step = int(max(1, min(65535, (2 ** 31 - 16) // max(per_crop, 1))))     # flags of a pass are indexed with int32
+    res = []
+    for i in range(0, boxes.shape[0], step):
+        res.extend(_crop_chunk(saved, boxes[i:i + step], pooled, bool(reference_dilated_labels), int(min_coarsest)))
+    out, counter = [], 0
+    for i, (what, counts) in enumerate(res):
+        size_rejected = min(counts) == 0 or counts[-1] < int(min_coarsest)
+        if not size_rejected and what:
+            cnt = counter if positions is None else i
+            out.append((cnt, what[0], what[1]) if return_kept else (cnt, what[0]))
+        counter += 2 if size_rejected else 1
+    return out

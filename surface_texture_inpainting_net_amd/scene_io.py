@@ -25,7 +25,8 @@ from .data import HierarchicalBatch
 
 
 def sample_from_tensors(saved, vertex_mask, end_level, cropped=False, coords_max_sizes=(1.5, 1.5, 1.5), name=None):
-    """saved: the dict of a graphs/<scene>.pt file; vertex_mask: int array [N0]."""
+    """saved: the dict of a graphs/<scene>.pt file (or a crop of preprocessing.crop_scene); vertex_mask: int array or tensor [N0].
+    The tensors may live on any device (all on the same one): the sample comes out there."""
     coords = [v.clone() if torch.is_tensor(v) else torch.as_tensor(v) for v in saved['vertices'][:end_level]]
     coords[0][:, 3:6] = coords[0][:, 3:6] * 2.0 - 1.0                       # colour to [-1, 1] (:95)
     edges = saved['edges'][:end_level]
@@ -35,7 +36,11 @@ def sample_from_tensors(saved, vertex_mask, end_level, cropped=False, coords_max
         dil = dil[:end_level]
     else:
         dil, dists = None, None
-    mask = torch.as_tensor(np.asarray(vertex_mask)).unsqueeze(1)
+    dev = coords[0].device
+    if torch.is_tensor(vertex_mask):
+        mask = vertex_mask.to(dev).unsqueeze(1)
+    else:
+        mask = torch.as_tensor(np.asarray(vertex_mask)).to(dev).unsqueeze(1)
     known = (mask == 0)
     x = torch.cat([coords[0][:, 3:6] * known, coords[0][:, 6:9], coords[0][:, :3], known], dim=-1).float()   # (:115)
     s = HierarchicalBatch(x=x, color=coords[0][:, 3:6].float(), mask=mask.long(),
@@ -57,10 +62,10 @@ def sample_from_tensors(saved, vertex_mask, end_level, cropped=False, coords_max
         tr = torch.as_tensor(traces[lvl - 1]).long()
         s['hierarchy_trace_index_%d' % lvl] = tr
         nv.append(int(tr.max()) + 1)
-    s['num_vertices'] = torch.tensor([nv], dtype=torch.int32)
-    s['batch'] = torch.zeros(nv[0], dtype=torch.long)
+    s['num_vertices'] = torch.tensor([nv], dtype=torch.int32, device=dev)
+    s['batch'] = torch.zeros(nv[0], dtype=torch.long, device=dev)
     if coords_max_sizes is not None:                                         # CoordsNormalization on the position channels
-        s['x'][:, 6:9] = s['x'][:, 6:9] / torch.tensor(coords_max_sizes, dtype=s['x'].dtype)
+        s['x'][:, 6:9] = s['x'][:, 6:9] / torch.tensor(coords_max_sizes, dtype=s['x'].dtype, device=dev)
     return s
 
 
@@ -199,5 +204,35 @@ def write_circle_masks(graph_path, masks_dir, masks):
         path = os.path.join(masks_dir, '{:06d}.npz'.format(mask_num))
         with open(path, 'wb') as f:
             np.savez_compressed(f, vertex_mask=out)
+        written.append(path)
+    return written
+
+
+def write_crops(graph_path, out_dir, block_size=3.0, stride=1.5, **kw):
+    """preprocessing/crop_training_samples.py for one graph file, on the GPU (preprocessing.crop_scene: all crops of the sampling
+    grid in one batched pass): writes out_dir/<scene>_<counter>.pt with CPU tensors, named by the reference's counters.  **kw goes
+    to crop_scene (positions, min_coarsest, reference_dilated_labels) except device= (default 'cuda').  With
+    reference_dilated_labels=True torch.load of each file equals what the reference's script writes for that scene (keys, dtypes,
+    shapes, values); the default writes the dilated sets with the level's own ids (see crop_scene).  load_scene(path, mask,
+    cropped=True), load_label_scene(path, is_train=True) and write_circle_masks(path, ...) read the files.  -> the paths written."""
+    import os
+    from .preprocessing import crop_scene
+
+    def to(v, d):
+        if torch.is_tensor(v):
+            return v.to(d)
+        if isinstance(v, (list, tuple)) and any(torch.is_tensor(y) or isinstance(y, (list, tuple)) for y in v):
+            return [to(y, d) for y in v]
+        return v
+
+    saved = torch.load(graph_path, map_location='cpu', weights_only=False)
+    name = os.path.basename(str(graph_path)).rsplit('.', 1)[0]
+    device = kw.pop('device', 'cuda')
+    crops = crop_scene({k: to(v, device) for k, v in saved.items()}, block_size, stride, **kw)
+    os.makedirs(out_dir, exist_ok=True)
+    written = []
+    for counter, crop in crops:
+        path = os.path.join(out_dir, '%s_%d.pt' % (name, counter))
+        torch.save({k: to(v, 'cpu') for k, v in crop.items()}, path)       # (.to('cpu') of a view copies only the view)
         written.append(path)
     return written
