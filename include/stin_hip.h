@@ -608,6 +608,32 @@ int stin_total_variation_f32(const float* x, int64_t ldx, const int32_t* rowptr_
  * fp32 adds in edge order - the numbers of the reference's composition, bit for bit. */
 int stin_graph_laplace_f32(const float* x, int64_t ldx, const int32_t* rowptr_dst, const int32_t* col_dst, int64_t N, int C,
                            float* out, int64_t ldo, stin_stream_t stream);
+/* the trainer's seven per-step metrics in one call (trainers/inpainting3d_trainer.py:254-271: loss, l1, mse, graph_tv, graph_lap_var,
+ * psnr, psnr_mask_only), written as ONE row of 8 floats into a caller-owned device table - nothing is read back, so a training
+ * loop pays no queue drain per metric.  P = composite ? where(mask > 0, out, color) : out, G = color, n = N * C:
+ *   row_out[0] loss            sum |P - G| (use_weight ? 0.99^mask : 1) / n; with loss != NULL: loss[0] (computed elsewhere) copied
+ *   row_out[1] l1              sum |P - G| / n
+ *   row_out[2] mse             sum (P - G)^2 / n
+ *   row_out[3] graph_tv        sum_e sum_c |P[src_e, c] - P[dst_e, c]| / n
+ *   row_out[4] graph_lap_var   population variance over the vertices of L_i = sum_{j -> i} g_j - deg_i g_i, g = 0.299 R + 0.587 G +
+ *                              0.114 B of P; L_i as stin_graph_laplace_f32 forms it (fp32 adds in CSR = edge order).  C == 1: NaN
+ *   row_out[5] psnr            -10 log10(mse / data_range^2 + 1e-8)
+ *   row_out[6] psnr_mask_only  the same over the rows with mask > 0; NaN when there are none (as the reference)
+ *   row_out[7] number of rows with mask > 0 (exact: N <= 2^24 is required)
+ * out [N, C] fp32 with leading dimension ldo, color [N, C] contiguous, mask int64 [N], C = 1 or 3 (STIN_E_SIZE otherwise);
+ * rowptr_dst / col_dst = the destination CSR of level 0.  perm (optional, int32 [N]): CSR row r is the caller's row perm[r] (a plan
+ * whose vertices were renumbered by locality: GraphPlan.order0); NULL = identity.  fp32 terms, fp64 block partials folded in a
+ * fixed order by the finaliser (divisions, log10 and variance in double): same bits on every run; no float atomics.
+ * layout: STIN_METRICS_ONE_PASS (2 launches, every neighbour's P row rebuilt from out / color / mask: 32 bytes per edge) or
+ * STIN_METRICS_STAGED (3 launches, P rows + gray staged as float4 in the workspace in CSR row order: 16 bytes per edge); the
+ * two give identical bits.  Workspace: stin_inpaint_metrics_workspace_bytes(N) for either layout. */
+#define STIN_METRICS_ONE_PASS 0
+#define STIN_METRICS_STAGED 1
+size_t stin_inpaint_metrics_workspace_bytes(int64_t N);
+int stin_inpaint_metrics_f32(const float* out, int64_t ldo, const float* color, const int64_t* mask, const int32_t* rowptr_dst,
+                             const int32_t* col_dst, const int32_t* perm, int64_t N, int C, int composite, int use_weight,
+                             float data_range, const float* loss, int layout, float* row_out, void* workspace,
+                             size_t workspace_bytes, stin_stream_t stream);
 int stin_adam_f32(float* p, const float* g, float* m, float* v, float* vmax, int64_t n, double lr, double beta1,
                   double beta2, double eps, double weight_decay, int step, int amsgrad, stin_stream_t stream);
 

@@ -192,6 +192,9 @@ SIGNATURES['stin_circle_mask_workspace_bytes'] = (c_size, [c_i64, c_int, c_int])
 SIGNATURES['stin_circle_mask_run'] = (c_int, [c_ptr, c_ptr, c_i64, c_ptr, c_int, c_int, c_int, c_f64, ctypes.c_uint64, c_ptr, c_int, c_ptr, c_i64,
                                               c_ptr, c_ptr, c_ptr, c_ptr, c_i64, c_ptr, c_size, c_ptr])
 SIGNATURES['stin_augment_rewrite_f32'] = (c_int, [c_ptr, c_i64, c_ptr, c_i64, c_ptr, c_int, c_ptr, c_i64, c_ptr, c_ptr, c_ptr])
+SIGNATURES['stin_inpaint_metrics_workspace_bytes'] = (c_size, [c_i64])
+SIGNATURES['stin_inpaint_metrics_f32'] = (c_int, [c_ptr, c_i64, c_ptr, c_ptr, c_ptr, c_ptr, c_ptr, c_i64, c_int, c_int, c_int, c_f32, c_ptr, c_int,
+                                                  c_ptr, c_ptr, c_size, c_ptr])
 SIGNATURES['stin_bn_act_bwd_f32'] = (c_int, [c_ptr, c_i64, c_ptr, c_i64, c_ptr, c_ptr, c_ptr, c_ptr, c_ptr, c_ptr, c_f32, c_i64, c_int,
                                              c_int, c_ptr, c_i64, c_ptr])
 SIGNATURES['stin_crop_workspace_bytes'] = (c_size, [c_i64])

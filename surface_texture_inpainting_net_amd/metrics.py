@@ -67,3 +67,143 @@ def psnr(x, y, data_range=1.0, convert_to_greyscale=False):
         x, y = grayscale(x), grayscale(y)
     mse = torch.mean((x - y) ** 2, dim=[0, 1])
     return -10 * torch.log10(mse + 1e-8)
+
+
+# ---------------------------------------------------------------------------------------------------------------------------------
+# The trainer's per-step metrics without a host round trip (trainers/inpainting3d_trainer.py:254-271): one HIP call per step
+# writes a row of a device table, the host reads the table once per epoch.
+def _step_row_torch(out, color, mask, edge_index, composite, use_weight, data_range, loss):
+    """The row stin_inpaint_metrics_f32 writes, through torch (CPU tensors): fp32 terms, L_i by fp32 adds in edge order, sums in
+    double, one final cast.  -> float32 [8]."""
+    m = mask.reshape(-1)
+    inside = m > 0
+    out = out.float()
+    P = torch.where(inside[:, None], out, color) if composite else out
+    n, C = P.shape
+    d = P - color
+    a, q = d.abs(), d * d
+    w = torch.pow(0.99, m.float())[:, None] if use_weight else torch.ones(n, 1)
+    cnt = int(inside.sum())
+    mse = q.double().sum() / (n * C)
+    mse_in = q[inside].double().sum() / (cnt * C) if cnt else torch.tensor(float('nan'), dtype=torch.float64)
+    src, dst = edge_index[0], edge_index[1]
+    tv = (P[src] - P[dst]).abs().sum(dim=1).double().sum() / (n * C)
+    if C == 3:
+        g = grayscale(P)[:, 0]
+        s = torch.zeros(n).index_add_(0, dst, g[src])                   # (CPU index_add_: sequential, edge order)
+        deg = torch.zeros(n).index_add_(0, dst, torch.ones(dst.numel()))
+        lap_var = (s - deg * g).double().var(unbiased=False)
+    else:
+        lap_var = torch.tensor(float('nan'), dtype=torch.float64)
+    r2 = float(data_range) ** 2
+    row = torch.stack([(a * w).double().sum() / (n * C), a.double().sum() / (n * C), mse, tv, lap_var,
+                       -10 * torch.log10(mse / r2 + 1e-8), -10 * torch.log10(mse_in / r2 + 1e-8),
+                       torch.tensor(float(cnt), dtype=torch.float64)]).float()
+    if loss is not None:
+        row[0] = torch.as_tensor(loss, dtype=torch.float32).reshape(())
+    return row
+
+
+class StepMetrics:
+    """The reference's MetricTracker for the inpainting trainer's seven step metrics, kept on the device: ``update`` is one HIP
+    call (stin_inpaint_metrics_f32, no host synchronisation) that writes row ``len(self)`` of a ``[capacity, 8]`` table,
+    ``rows()`` / ``result()`` read the table back once - per epoch, not per metric and step.  Column 8 of a row is the number of
+    masked vertices of that step.  CPU tensors take a torch path with the same semantics."""
+
+    KEYS = ('loss', 'l1', 'mse', 'graph_tv', 'graph_lap_var', 'psnr', 'psnr_mask_only')
+    # kernel layout (include/stin_hip.h): 1 = P rows staged in CSR row order, 16 bytes per edge; 0 = one pass, 32 bytes per edge.
+    # The two give identical bits; which is faster: profiles/r09_step_metrics.md.
+    LAYOUT = 1
+
+    def __init__(self, device, capacity=1024, use_mask_weighted_loss=True, data_range=2.0):
+        self.device = torch.device(device)
+        self.use_mask_weighted_loss = bool(use_mask_weighted_loss)
+        self.data_range = float(data_range)
+        self.table = torch.zeros(max(1, int(capacity)), 8, dtype=torch.float32, device=self.device)
+        self._n = 0
+        self._ws = None
+
+    def __len__(self):
+        return self._n
+
+    def reset(self):
+        self._n = 0
+
+    def _row(self):
+        """The next row of the table as a device view (the table doubles, with a device-side copy, when it is full)."""
+        if self._n == self.table.shape[0]:
+            grown = torch.zeros(2 * self.table.shape[0], 8, dtype=torch.float32, device=self.device)
+            grown[:self._n].copy_(self.table)
+            self.table = grown
+        self._n += 1
+        return self.table[self._n - 1]
+
+    def update(self, out, sample, loss=None, composite=True):
+        """One step: ``out`` = the raw network output [N, C] (composite=True forms where(mask > 0, out, color) itself; False takes
+        ``out`` as the prediction), ``sample`` supplies color, mask and the level-0 edges (the cached plan's edge set in the
+        plan's own vertex order when there is one - no second sort), ``loss`` = a loss computed elsewhere (0-dim tensor on the
+        device), else the masked weighted L1 of the trainer is computed.  -> the row, a device view [8]."""
+        out = out.detach()
+        if out.dtype != torch.float32:
+            out = out.float()
+        color, mask = sample.color, sample.mask.reshape(-1)
+        if not out.is_cuda:
+            row = self._row()
+            row.copy_(_step_row_torch(out, color, mask, sample.edge_index, composite, self.use_mask_weighted_loss,
+                                      self.data_range, None if loss is None else loss.detach() if torch.is_tensor(loss) else loss))
+            return row
+        from . import _lib
+        from .plan import _ptr, _stream
+        n = out.shape[0]
+        plan = getattr(sample, '_plan_cache', None)
+        perm = None
+        if plan is not None and plan.device == out.device:
+            e = plan.edges('edge_index', 0)
+            perm = plan.order0
+        else:
+            e = _edges(sample.edge_index, n)
+        out, ldo = SF._mat(out)
+        color, _ = SF._mat(color if color.is_contiguous() else color.contiguous())
+        if mask.dtype != torch.int64 or not mask.is_contiguous():
+            mask = mask.to(torch.int64).contiguous()
+        if loss is not None:
+            loss = loss.detach()
+            if loss.dtype != torch.float32 or loss.device != out.device:
+                loss = loss.to(out.device, torch.float32)
+        lib = _lib.load()
+        ws_bytes = lib.stin_inpaint_metrics_workspace_bytes(n)
+        if self._ws is None or self._ws.numel() < ws_bytes:
+            self._ws = torch.empty(ws_bytes, dtype=torch.uint8, device=out.device)
+        row = self._row()
+        SF._call('stin_inpaint_metrics_f32', _ptr(out), ldo, _ptr(color), _ptr(mask), _ptr(e.by_dst.rowptr), _ptr(e.by_dst.col),
+                 _ptr(perm), n, out.shape[1], int(bool(composite)), int(self.use_mask_weighted_loss), self.data_range,
+                 _ptr(loss), self.LAYOUT, _ptr(row), _ptr(self._ws), self._ws.numel(), _stream(out))
+        return row
+
+    def rows(self):
+        """-> [steps, 8] CPU tensor, one copy (this is the epoch's one host synchronisation)."""
+        return self.table[:self._n].cpu()
+
+    def result(self):
+        """{key: mean of the per-step values, in double}: MetricTracker.result() of the reference for n = 1 updates (a NaN step
+        makes the average NaN, as there)."""
+        r = self.rows().double()
+        return {k: (float(r[:, i].sum() / r.shape[0]) if r.shape[0] else 0.0) for i, k in enumerate(self.KEYS)}
+
+
+def evaluate(model, samples, tracker=None, **tracker_kw):
+    """The body of the trainer's _valid_epoch / _eval (:204-252, :89-125): eval mode, no_grad, one tracker row per sample;
+    the previous train / eval mode is restored.  -> the tracker (per-scene losses: ``tracker.rows()[:, 0]``)."""
+    was_training = model.training
+    model.eval()
+    try:
+        with torch.no_grad():
+            for sample in samples:
+                if tracker is None:
+                    tracker = StepMetrics(sample.color.device, **tracker_kw)
+                tracker.update(model(sample), sample)
+    finally:
+        model.train(was_training)
+    if tracker is None:
+        tracker = StepMetrics(next(model.parameters()).device, **tracker_kw)
+    return tracker

@@ -478,12 +478,21 @@ class TrainStep:
     (warm-up: lazy initialisations, host-side constants, index validation), the second captures, later ones copy the
     sample into the graph's input tensors and replay.  The gradient all-reduce and the Adam update stay outside the
     graph (Adam's bias corrections are host scalars that change every step).  Up to `graph_cache` signatures are kept
-    (least recently used dropped), all in one memory pool."""
+    (least recently used dropped), all in one memory pool.
+
+    metrics = a metrics.StepMetrics: every call also records the trainer's seven step metrics (inpainting3d_trainer.py:254-271)
+    as one row of the tracker's device table; the step itself - loss, gradients, parameters - is unchanged."""
 
     def __init__(self, model, lr=7e-5, weight_decay=0.0, amsgrad=True, use_mask_weighted_loss=True, group=None,
                  accumulate=1, overlap_allreduce_min_bytes=None, time_allreduce=False, graph=False, graph_cache=8,
-                 loss_fn=None, freeze_gc=False):
+                 loss_fn=None, freeze_gc=False, metrics=None):
         self.model = model
+        # metrics (optional, a metrics.StepMetrics): one row of the trainer's seven step metrics per call, written on the device
+        # right after the loss (every micro-step of an accumulation window: the reference logs every batch) - no host sync
+        if metrics is not None and (loss_fn is not None or graph):
+            raise ValueError('metrics= records the inpainting trainer\'s step metrics: it needs the default loss (loss_fn=None) '
+                             'and an eager step (graph=False)')
+        self.metrics = metrics
         # freeze_gc: the model, the optimizer state and whatever the data pipeline has built so far are long-lived; Python's
         # cyclic collector would otherwise re-scan that heap in the young-generation collections the ~100 k short-lived
         # objects of every step trigger, and its generation-2 passes land in the first tens of steps: measured at the
@@ -560,10 +569,15 @@ class TrainStep:
                 loss = self.loss_fn(self.model, sample)
             elif self.on_gpu:
                 from . import functional as SF
-                loss = SF.masked_l1_loss(self.model(sample), sample.color, sample.mask, self.use_mask_weighted_loss)
+                out = self.model(sample)
+                loss = SF.masked_l1_loss(out, sample.color, sample.mask, self.use_mask_weighted_loss)
+                if self.metrics is not None:
+                    self.metrics.update(out.detach(), sample, loss=loss.detach())
             else:
                 pred = graph_forward(self.model, sample)
                 loss = compute_loss(pred, sample.color, sample.mask if self.use_mask_weighted_loss else None)
+                if self.metrics is not None:            # (pred is already the composite; forming it again changes nothing)
+                    self.metrics.update(pred.detach(), sample, loss=loss.detach())
             if grad_scale == 1.0:
                 if self.loss_fn is None and self.on_gpu and loss.dtype == torch.float32 and loss.dim() == 0:
                     from . import functional as SF
