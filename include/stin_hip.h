@@ -1021,6 +1021,52 @@ size_t stin_label_pool_workspace_bytes(int64_t n0, int n_labels);
 int stin_label_pool_i64(const int64_t* trace0, const int64_t* labels, int64_t n_orig, int64_t n0, int n_labels, int64_t* out,
                         int32_t* status, void* workspace, size_t workspace_bytes, stin_stream_t stream);
 
+/* graph levels: the python around the decimator of the reference's preprocessing/graph_level_generation.py (csv2npy :135-191,
+ * get_color_and_labels :98-116, nearest_neighbor_interpolation_for_unassigned_traces :284-295) reduced to one primitive and a
+ * few integer kernels (stin_levels.hip).
+ *   stin_nearest_f64: for query i < Q the index of the nearest of points [P, 3] (fp64, row-major), with
+ *                     d = (dx dx + dy dy) + dz dz in fp64 without contraction and strict < in ascending index order (the lowest
+ *                     index wins a tie) - numpy's argmin of the same expression.  queries: fp64 [n_query_rows, 3].
+ *                     q_index == NULL: query i is row i and out_index[i] / out_d2[i] (may be NULL: squared distance) its answer
+ *                     (Q <= n_query_rows).  q_index != NULL (int64 [Q]): query i is row q_index[i] and the answer goes to
+ *                     out_index[q_index[i]] (out arrays of n_query_rows entries; rows not listed are left alone).
+ *                     q_count (may be NULL): DEVICE word, only the first min(Q, *q_count) queries are run.
+ *                     chunks: the points are cut into this many parts (1 .. 64; stin_nearest_chunks(Q, P) picks it from the
+ *                     device's CU count), each writing partial (d, index) pairs [chunks][Q] into the workspace
+ *                     (stin_nearest_workspace_bytes(Q, chunks); 0 for chunks <= 1) that a second launch folds by the same rule.
+ *                     flags: one DEVICE int64 word, OR-ed (never cleared here): 1 = non-finite query, 2 = non-finite point,
+ *                     4 = q_index entry outside [0, n_query_rows).  Q == 0: nothing is done; P == 0 (with Q > 0): STIN_E_SIZE;
+ *                     P >= 2^31 - 1: STIN_E_UNSUPPORTED.
+ *   traces (csv2npy): R rows of a decimator's CSV, row r = new vertex new_id[r] and the old vertices old_id[row_ptr[r] ..
+ *                     row_ptr[r + 1]) (row_of[t] = the row of entry t).  state: int64 [5] on the device -
+ *                     [0] old vertices named by more than one entry, [1] new vertices for which a row came after an earlier row
+ *                     WITH old vertices (an earlier row without any is tolerated, as in the reference), [2] new vertices that no
+ *                     row and no old vertex points to, [3] flag word (the bits of stin_nearest_f64; 8 = an id out of range,
+ *                     16 = a trace entry still unassigned or out of range at the check), [4] number of unassigned old vertices.
+ *     stin_trace_scatter_i64    clears state and workspace; trace[:] = -1; trace[old_id[t]] = new_id[row_of[t]]; counts hits per
+ *                               old vertex and rows / rows with entries / the last row per new vertex.
+ *     stin_trace_unassigned_i64 list[0 .. state[4]) = the old vertices with trace == -1 (order unspecified; state[4] is reset first).
+ *                               Meant as q_index / q_count of stin_nearest_f64 with out_index = trace.
+ *     stin_trace_check_i64      after the fill: state[0], state[1], state[2] from the counts in the SAME workspace.
+ *   Workspace of the three: stin_trace_workspace_bytes(n_old, n_new).  Nothing allocates or synchronises.
+ *   stin_cluster_mean_f32: out[c] = float32 mean of coords[order[seg_ptr[c] .. seg_ptr[c + 1])] (float32 [n, 3]) accumulated one
+ *                     row after the other in float32 - what numpy's mean(axis=0) gives the reference's vertex clustering when a
+ *                     level is clustered from float32 positions (every level after the first). */
+int stin_nearest_chunks(int64_t Q, int64_t P);
+size_t stin_nearest_workspace_bytes(int64_t Q, int chunks);
+int stin_nearest_f64(const double* queries, int64_t n_query_rows, const double* points, int64_t P, const int64_t* q_index,
+                     const int64_t* q_count, int64_t Q, int chunks, int64_t* out_index, double* out_d2, int64_t* flags,
+                     void* workspace, size_t workspace_bytes, stin_stream_t stream);
+size_t stin_trace_workspace_bytes(int64_t n_old, int64_t n_new);
+int stin_trace_scatter_i64(const int64_t* new_id, const int64_t* row_ptr, int64_t R, const int64_t* old_id, const int64_t* row_of,
+                           int64_t n_entries, int64_t n_old, int64_t n_new, int64_t* trace, int64_t* state, void* workspace,
+                           size_t workspace_bytes, stin_stream_t stream);
+int stin_trace_unassigned_i64(const int64_t* trace, int64_t n_old, int64_t* list, int64_t* state, stin_stream_t stream);
+int stin_trace_check_i64(const int64_t* trace, int64_t n_old, const int64_t* row_ptr, int64_t R, int64_t n_new, int64_t* state,
+                         void* workspace, size_t workspace_bytes, stin_stream_t stream);
+int stin_cluster_mean_f32(const float* coords, int64_t n, const int64_t* order, const int64_t* seg_ptr, int64_t n_seg, float* out,
+                          stin_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

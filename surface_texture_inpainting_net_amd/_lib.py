@@ -203,6 +203,14 @@ SIGNATURES['stin_crop_gather'] = (c_int, [c_ptr, c_int, c_i64, c_int, c_ptr, c_p
 SIGNATURES['stin_crop_traces'] = (c_int, [c_ptr, c_int, c_i64, c_int, c_ptr, c_ptr, c_ptr, c_ptr, c_ptr])
 SIGNATURES['stin_label_pool_workspace_bytes'] = (c_size, [c_i64, c_int])
 SIGNATURES['stin_label_pool_i64'] = (c_int, [c_ptr, c_ptr, c_i64, c_i64, c_int, c_ptr, c_ptr, c_ptr, c_size, c_ptr])
+SIGNATURES['stin_nearest_chunks'] = (c_int, [c_i64, c_i64])
+SIGNATURES['stin_nearest_workspace_bytes'] = (c_size, [c_i64, c_int])
+SIGNATURES['stin_nearest_f64'] = (c_int, [c_ptr, c_i64, c_ptr, c_i64, c_ptr, c_ptr, c_i64, c_int, c_ptr, c_ptr, c_ptr, c_ptr, c_size, c_ptr])
+SIGNATURES['stin_trace_workspace_bytes'] = (c_size, [c_i64, c_i64])
+SIGNATURES['stin_trace_scatter_i64'] = (c_int, [c_ptr, c_ptr, c_i64, c_ptr, c_ptr, c_i64, c_i64, c_i64, c_ptr, c_ptr, c_ptr, c_size, c_ptr])
+SIGNATURES['stin_trace_unassigned_i64'] = (c_int, [c_ptr, c_i64, c_ptr, c_ptr, c_ptr])
+SIGNATURES['stin_trace_check_i64'] = (c_int, [c_ptr, c_i64, c_ptr, c_i64, c_i64, c_ptr, c_ptr, c_size, c_ptr])
+SIGNATURES['stin_cluster_mean_f32'] = (c_int, [c_ptr, c_i64, c_ptr, c_ptr, c_i64, c_ptr, c_ptr])
 
 _lib = None
 

@@ -13,8 +13,18 @@
   (``stin_circle_mask_run``), every mask of a scene and every graph of a collated batch in the same launches, with no host
   synchronisation; ``circle_mask_from_centres`` is the distance pass alone for given centres.
 
-All take and return tensors in the reference's own formats.  QEM decimation itself stays out of scope (it shells out
-to vcglib's ``tridecimator``).
+* ``graph_levels``      - the body of ``preprocessing/graph_level_generation.process_frame`` (:298-539): mesh -> level hierarchy
+  -> the dict of ``graphs/<scene>.pt``, in vertex-clustering mode fully on the GPU and in decimator mode from the decimator's
+  outputs.  Its parts: ``nearest`` (exact fp64 nearest neighbour between two large point sets, tiled brute force:
+  ``stin_nearest_f64``), ``read_trace_csv`` / ``trace_from_csv`` (``csv2npy`` :135-191: two batched searches, an integer scatter and
+  one state vector instead of one BallTree query per CSV coordinate), ``fill_unassigned_trace``
+  (``nearest_neighbor_interpolation_for_unassigned_traces`` :284-295), ``colors_and_labels`` (``get_color_and_labels`` :98-116) and
+  ``remap_scannet_labels``; ``LevelError`` where the reference raises ``QEMError`` or trips an assert.
+
+All take and return tensors in the reference's own formats.  Out of scope: the QEM decimator itself (the reference shells out
+to vcglib's ``tridecimator``; its mesh and trace file are inputs here), reading mesh files and computing vertex normals from faces
+(neither open3d nor plyfile exists here to pin a reader against: vertices, faces, colours and normals are inputs), and the
+Matterport and S3DIS label paths.
 """
 import ctypes
 
@@ -509,4 +519,328 @@ def crop_scene(saved, block_size=3.0, stride=1.5, positions=None, min_coarsest=M
             cnt = counter if positions is None else i
             out.append((cnt, what[0], what[1]) if return_kept else (cnt, what[0]))
         counter += 2 if size_rejected else 1
+    return out
+
+
+# ------------------------------------------------------------------------------------------------------------- graph levels
+SCANNET_CLASS_REMAP = (0, 1, 2, 3, 4, 5, 6, 7, 8, 9, 10, 11, 12, 0, 13, 0, 14, 0, 0, 0, 0, 0, 0, 0, 15, 0, 0, 0, 16, 0, 0, 0, 0, 17, 18,
+                       0, 19, 0, 0, 20, 0)      # nyu40 id -> ScanNet benchmark class (graph_level_generation.py:26-47)
+_NEAREST_FLAGS = ((1, 'a query coordinate is not finite'), (2, 'a point coordinate is not finite'),
+                  (4, 'a query index lies outside the query array'), (8, 'an id lies outside its vertex set'),
+                  (16, 'a trace entry is unassigned or outside the coarse level'))
+
+
+class LevelError(ValueError):
+    """A decimator trace that the reference refuses (its QEMError / failed asserts in csv2npy)."""
+
+
+def remap_scannet_labels(labels):
+    """The ScanNet label fix of process_frame (:345-349): ids above 40 become 0, then SCANNET_CLASS_REMAP.  Tensor (any device) or
+    array of ints -> int64 of the same kind."""
+    if torch.is_tensor(labels):
+        ids = labels.long()
+        ids = torch.where(ids > 40, torch.zeros_like(ids), ids)
+        return torch.tensor(SCANNET_CLASS_REMAP, dtype=torch.int64, device=ids.device)[ids]
+    import numpy as np
+    ids = np.asarray(labels).astype(np.int64)
+    ids = np.where(ids > 40, 0, ids)
+    return np.asarray(SCANNET_CLASS_REMAP, dtype=np.int64)[ids]
+
+
+def _flag_text(word):
+    return '; '.join(t for b, t in _NEAREST_FLAGS if word & b)
+
+
+def _xyz64(t, what):
+    if not torch.is_tensor(t) or not t.is_cuda:
+        raise TypeError('%s must be a CUDA tensor (no CPU fallback exists)' % what)
+    if t.dtype not in (torch.float32, torch.float64):
+        raise TypeError('%s must be float32 or float64' % what)
+    if t.dim() != 2 or t.shape[1] < 3:
+        raise ValueError('%s must be [N, >= 3]' % what)
+    return t[:, :3].double().contiguous()
+
+
+def _nearest_launch(q64, p64, out, flags, q_index=None, q_count=None, n_queries=None, chunks=None, d2=None):
+    """stin_nearest_f64 on fp64 [., 3] tensors; nothing synchronises.  flags: an int64 device word (OR-ed)."""
+    lib = _lib.load()
+    nq = int(q64.shape[0]) if n_queries is None else int(n_queries)
+    P = int(p64.shape[0])
+    if nq == 0:
+        return
+    if P == 0:
+        raise ValueError('nearest: no points to search')
+    c = int(chunks) if chunks is not None else int(lib.stin_nearest_chunks(nq, P))
+    ws_bytes = lib.stin_nearest_workspace_bytes(nq, c)
+    ws = torch.empty(max(ws_bytes, 1), dtype=torch.uint8, device=q64.device)
+    _lib.check(lib.stin_nearest_f64(_ptr(q64), int(q64.shape[0]), _ptr(p64), P, _ptr(q_index), _ptr(q_count), nq, c, _ptr(out), _ptr(d2),
+                                    _ptr(flags), _ptr(ws), ws_bytes, _stream(q64)), 'stin_nearest_f64')
+
+
+def nearest(queries, points, return_sq_dist=False, chunks=None):
+    """Exact nearest neighbour: for every row of queries [Q, >= 3] the index (int64 [Q], CUDA) of the nearest row of points
+    [P, >= 3], by d = (dx dx + dy dy) + dz dz in fp64 (float32 input is promoted), the lowest index on a tie - numpy's argmin of
+    the same expression, which is what sklearn's BallTree.query(k=1) answers in the reference whenever the nearest point is unique.
+    Tiled brute force (stin_nearest_f64).  return_sq_dist: also the squared distances (float64 [Q]).  chunks: parts the points
+    are cut into (default: chosen from Q and the device's CU count).  ValueError for P == 0 or non-finite coordinates."""
+    q64, p64 = _xyz64(queries, 'queries'), _xyz64(points, 'points')
+    nq = int(q64.shape[0])
+    out = torch.empty(nq, dtype=torch.int64, device=q64.device)
+    d2 = torch.empty(nq, dtype=torch.float64, device=q64.device) if return_sq_dist else None
+    if nq:
+        flags = torch.zeros(1, dtype=torch.int64, device=q64.device)
+        _nearest_launch(q64, p64, out, flags, chunks=chunks, d2=d2)
+        word = int(flags.item())
+        if word:
+            raise ValueError('nearest: ' + _flag_text(word))
+    return (out, d2) if return_sq_dist else out
+
+
+def read_trace_csv(path):
+    """The decimator's trace file (host): `;`-separated ragged rows `new xyz; old xyz; old xyz; ...`, a row with zero old
+    coordinates allowed, empty lines skipped.  -> (new_xyz float64 [R, 3], old_xyz float64 [T, 3], row_ptr int64 [R + 1]) numpy
+    arrays; row r names old_xyz[row_ptr[r]:row_ptr[r + 1]].  As csv2npy (:147-161): the first three fields are the new vertex,
+    len(row) // 3 - 1 triples follow (trailing fields short of a triple - a `;` at the end of the line - are ignored)."""
+    import numpy as np
+    new, old, ptr = [], [], [0]
+    with open(path, 'r') as f:
+        for line in f:
+            line = line.rstrip('\r\n')
+            if not line:
+                continue
+            row = line.split(';')
+            new.append([float(r) for r in row[:3]])
+            for i in range(len(row) // 3 - 1):
+                old.append([float(r) for r in row[3 + 3 * i:6 + 3 * i]])
+            ptr.append(len(old))
+    return (np.asarray(new, dtype=np.float64).reshape(-1, 3), np.asarray(old, dtype=np.float64).reshape(-1, 3),
+            np.asarray(ptr, dtype=np.int64))
+
+
+def _fill_unassigned(new64, old64, trace, state):
+    """trace (int64 [n_old], -1 = unassigned, modified in place): every unassigned old vertex goes to its nearest new vertex.
+    state: int64 [5] device vector ([3] flag word, [4] receives the unassigned count).  Nothing synchronises."""
+    lib = _lib.load()
+    n_old = int(trace.numel())
+    if n_old == 0:
+        return
+    todo = torch.empty(n_old, dtype=torch.int64, device=trace.device)
+    _lib.check(lib.stin_trace_unassigned_i64(_ptr(trace), n_old, _ptr(todo), _ptr(state), _stream(trace)), 'stin_trace_unassigned_i64')
+    _nearest_launch(old64, new64, trace, state[3:4], q_index=todo, q_count=state[4:5], n_queries=n_old)
+
+
+def fill_unassigned_trace(new_coords, old_coords, trace):
+    """The reference's nearest_neighbor_interpolation_for_unassigned_traces (:284-295): entries of trace (int [n_old]) equal to
+    -1 become the index of the new vertex nearest to that old vertex; the others are kept.  -> int64 [n_old] (a new tensor)."""
+    new64, old64 = _xyz64(new_coords, 'new_coords'), _xyz64(old_coords, 'old_coords')
+    out = trace.to(device=old64.device, dtype=torch.int64).clone().contiguous()
+    if out.numel() != old64.shape[0]:
+        raise ValueError('trace needs one entry per old vertex')
+    state = torch.zeros(5, dtype=torch.int64, device=old64.device)
+    if new64.shape[0] == 0:
+        if bool((out == -1).any()):
+            raise LevelError('unassigned old vertices and no new vertex to send them to')
+        return out
+    _fill_unassigned(new64, old64, out, state)
+    word = int(state[3].item())
+    if word:
+        raise LevelError('fill_unassigned_trace: ' + _flag_text(word))
+    return out
+
+
+def trace_from_csv(csv, old_vertices, new_vertices):
+    """The reference's csv2npy (:135-191) on the GPU: the fine -> coarse trace (int64 [n_old], CUDA) of one decimation from the
+    decimator's trace file.  csv: a path or the (new_xyz, old_xyz, row_ptr) of read_trace_csv.
+    1. every row's new coordinate -> its nearest vertex of new_vertices; 2. every old coordinate -> its nearest vertex of
+    old_vertices (two `nearest` calls instead of one BallTree query per coordinate); 3. trace[old] = new, scattered; 4. every
+    old vertex that no row names goes to its nearest new vertex.  LevelError where the reference raises QEMError or trips an
+    assert: an old vertex named by two entries; a row that resolves to a new vertex which an earlier row WITH old vertices
+    already took (an earlier row without any is tolerated); a new vertex that no row and no old vertex reaches.  All
+    conditions are gathered in one device vector that is read once, after the last launch."""
+    import numpy as np
+    lib = _lib.load()
+    old64, new64 = _xyz64(old_vertices, 'old_vertices'), _xyz64(new_vertices, 'new_vertices')
+    dev = old64.device
+    new_xyz, old_xyz, row_ptr = read_trace_csv(csv) if isinstance(csv, (str, bytes)) or hasattr(csv, '__fspath__') else csv
+    new_xyz = np.ascontiguousarray(new_xyz, dtype=np.float64).reshape(-1, 3)
+    old_xyz = np.ascontiguousarray(old_xyz, dtype=np.float64).reshape(-1, 3)
+    row_ptr = np.ascontiguousarray(row_ptr, dtype=np.int64)
+    R, n_ent, n_old, n_new = int(new_xyz.shape[0]), int(old_xyz.shape[0]), int(old64.shape[0]), int(new64.shape[0])
+    if row_ptr.shape[0] != R + 1 or int(row_ptr[-1]) != n_ent or row_ptr[0] != 0 or np.any(np.diff(row_ptr) < 0):
+        raise ValueError('row_ptr does not describe the rows')
+    if n_new == 0 or n_old == 0:
+        raise LevelError('a level without vertices')
+    row_of = np.repeat(np.arange(R, dtype=np.int64), np.diff(row_ptr))
+    rp_d, ro_d = torch.from_numpy(row_ptr).to(dev), torch.from_numpy(row_of).to(dev)
+    state = torch.empty(5, dtype=torch.int64, device=dev)
+    trace = torch.empty(n_old, dtype=torch.int64, device=dev)
+    new_id = torch.empty(R, dtype=torch.int64, device=dev)
+    old_id = torch.empty(n_ent, dtype=torch.int64, device=dev)
+    ws_bytes = lib.stin_trace_workspace_bytes(n_old, n_new)
+    ws = torch.empty(ws_bytes, dtype=torch.uint8, device=dev)
+    first = torch.zeros(1, dtype=torch.int64, device=dev)              # flag word of the two matching passes
+    _nearest_launch(torch.from_numpy(new_xyz).to(dev), new64, new_id, first)
+    _nearest_launch(torch.from_numpy(old_xyz).to(dev), old64, old_id, first)
+    _lib.check(lib.stin_trace_scatter_i64(_ptr(new_id), _ptr(rp_d), R, _ptr(old_id), _ptr(ro_d), n_ent, n_old, n_new, _ptr(trace),
+                                          _ptr(state), _ptr(ws), ws_bytes, _stream(trace)), 'stin_trace_scatter_i64')
+    _fill_unassigned(new64, old64, trace, state)
+    _lib.check(lib.stin_trace_check_i64(_ptr(trace), n_old, _ptr(rp_d), R, n_new, _ptr(state), _ptr(ws), ws_bytes, _stream(trace)),
+               'stin_trace_check_i64')
+    st = torch.cat([state, first]).cpu().tolist()                      # the one read
+    word = int(st[3]) | int(st[5])
+    if word & ~16:
+        raise LevelError('trace_from_csv: ' + _flag_text(word & ~16))
+    if st[1]:
+        raise LevelError('trace_from_csv: %d new vertices are matched by a row after an earlier row with old vertices' % st[1])
+    if st[2]:
+        raise LevelError('trace_from_csv: %d new vertices are reached by no row and no old vertex' % st[2])
+    if st[0]:
+        raise LevelError('trace_from_csv: %d old vertices are named by more than one entry' % st[0])
+    if word:
+        raise LevelError('trace_from_csv: ' + _flag_text(word))
+    return trace
+
+
+def colors_and_labels(original_vertices, level_coords):
+    """The reference's get_color_and_labels (:98-116): for each entry of level_coords ([N_l, >= 3] positions) the columns 3: of the
+    nearest row of original_vertices ([N, 3 + C]: position first) - one `nearest` per level and a gather.
+    -> list of [N_l, C] tensors in original_vertices' dtype."""
+    return [c for c, _ in _colors_and_labels(original_vertices, level_coords)]
+
+
+def _colors_and_labels(original_vertices, level_coords):
+    out = []
+    for c in level_coords:
+        idx = nearest(c, original_vertices)
+        out.append((original_vertices[idx][:, 3:], idx))
+    return out
+
+
+def _cluster_level_f32(coords32, edge_index, voxel_size):
+    """vertex_clustering for a level whose positions are float32 (every level after the first in the reference's vertex-clustering
+    mode): numpy evaluates `coords // voxel_size` and the centres of gravity in float32 there, so the voxel size is rounded to
+    float32 and the means are accumulated in float32, member after member (stin_cluster_mean_f32)."""
+    import numpy as np
+    lib = _lib.load()
+    _, trace, ce = vertex_clustering(coords32, edge_index, float(np.float32(voxel_size)))
+    n = int(trace.numel())
+    order = torch.sort(trace, stable=True).indices.contiguous()
+    nc = int(trace.max()) + 1 if n else 0
+    seg = torch.zeros(nc + 1, dtype=torch.int64, device=trace.device)
+    if n:
+        seg[1:] = torch.cumsum(torch.bincount(trace, minlength=nc), 0)
+    c32 = coords32.float().contiguous()
+    out = torch.empty(max(nc, 1), 3, dtype=torch.float32, device=trace.device)
+    _lib.check(lib.stin_cluster_mean_f32(_ptr(c32), n, _ptr(order), _ptr(seg), nc, _ptr(out), _stream(c32)), 'stin_cluster_mean_f32')
+    return out[:nc], trace, ce
+
+
+def _mesh_edges(faces, n):
+    """[E, 2] int64 rows (vertex, neighbour) of a triangle mesh, sorted by (row 0, row 1): the reference's edges_from_faces +
+    flattening, whose order inside a vertex group is a CPython set order."""
+    return edges_from_faces(faces, n).t().contiguous()
+
+
+def graph_levels(mesh, levels, dilated_levels, dilation_dists, labels=None, reference_vc_normals=False):
+    """The body of the reference's process_frame (preprocessing/graph_level_generation.py:298-539) on the GPU: from a mesh and, per
+    level, either a voxel size or a decimator's output to the dict the reference passes to torch.save for graphs/<scene>.pt
+    (scene_io.write_graph_levels writes it; crop_scene, circle_masks / write_circle_masks, load_scene and load_label_scene read it).
+
+    mesh: dict of CUDA tensors - vertices [N, 3] float64, faces [F, 3] int, colors [N, 3], normals [N, 3].
+    levels: one entry per --level_params item, all of one mode:
+      * vertex-clustering mode (--vertex_clustering): every entry a voxel size (float / int).  Level l clusters level l - 1 (the
+        first one the mesh itself) with `vertex_clustering`; runs fully on the GPU.
+      * decimator mode (--qem): each entry is '100' (the plain current mesh with an identity trace: extract_plain_mesh), a dict
+        (vertices [n, 3] float64, faces, csv = path or read_trace_csv tuple, normals) with a decimator's result for the current
+        mesh (extract_qem_mesh: trace_from_csv against the previous level), or a dict without 'csv' - an externally clustered
+        mesh (the trimesh_clustering branch) whose trace is nearest(ORIGINAL mesh vertices, its vertices), as the reference has
+        it, whatever the previous level was.
+    dilated_levels: one 0 / 1 per level - 1: dilated_edges(level edges, positions, normals, dilation_dists) is stored for it.
+    labels: int [N] labels of the original mesh (train mode: already remapped, see remap_scannet_labels); None: the --test mode.
+    -> {'vertices': [level 0: float32 [N_0, 10] pos, colour, normal, original index (train) or every column (test); others
+        float32 [N_l, 3]], 'labels': int64 [N] (train), 'edges': int64 [E_l, 2], 'traces': int64, one per level (traces[0] from the
+        original mesh), 'dilated_edges': None or the list of dilated_edges, 'dilation_dists': as given}, tensors on the device.
+
+    Differences from the reference: each level's edges come sorted by (row 0, row 1) instead of in CPython
+    set order; and in vertex-clustering mode the normals of a dilated level are those of each coarse vertex's nearest original
+    vertex - the reference walks with rows 0 .. N_l - 1 of the INPUT mesh's normals there because it never updates its current
+    mesh (reference_vc_normals=True reproduces that for file parity).
+    Out of scope: the decimator itself (vcglib's tridecimator), reading mesh files, computing vertex normals from faces (normals
+    are inputs) and the Matterport / S3DIS label paths."""
+    if len(levels) != len(dilated_levels):
+        raise ValueError('levels and dilated_levels need one entry per level')
+    if len(levels) == 0:
+        raise ValueError('at least one level is needed')
+    verts = mesh['vertices']
+    if not (torch.is_tensor(verts) and verts.is_cuda):
+        raise TypeError('graph_levels runs on the GPU only (no CPU fallback exists)')
+    dev = verts.device
+    v64 = verts.double().contiguous()
+    n = int(v64.shape[0])
+    dists = [int(d) for d in dilation_dists] if dilation_dists is not None else []
+    normals0 = mesh['normals'].to(dev).double()
+    cols = [v64, mesh['colors'].to(dev).double(), normals0, torch.arange(n, device=dev, dtype=torch.float64).unsqueeze(1)]
+    if labels is not None:
+        cols.append(torch.as_tensor(labels).to(dev).double().reshape(n, 1))
+    original = torch.cat(cols, dim=1)
+    vc_mode = all(isinstance(x, (int, float)) and not isinstance(x, bool) for x in levels)
+    if not vc_mode and any(not (isinstance(x, dict) or str(x) == '100') for x in levels):
+        raise ValueError("levels: all voxel sizes (vertex-clustering mode), or each '100' or a dict (decimator mode)")
+    coords = [v64]
+    edges, traces, level_normals = [], [], []
+    cur = dict(vertices=v64, faces=mesh['faces'].to(dev), normals=normals0)           # the reference's curr_mesh
+    cur_edges = _mesh_edges(cur['faces'], n)
+    for l, spec in enumerate(levels):
+        if vc_mode:
+            prev = coords[-1]
+            ei = cur_edges.t().contiguous()
+            if prev.dtype == torch.float64:
+                c_l, tr, e_l = vertex_clustering(prev, ei, float(spec))
+            else:
+                c_l, tr, e_l = _cluster_level_f32(prev, ei, float(spec))
+            cur_edges = e_l
+            nrm = None                                                            # filled in after the colour lookup
+        elif isinstance(spec, dict) and 'csv' not in spec:
+            c_l = spec['vertices'].to(dev).double().contiguous()
+            e_l = _mesh_edges(spec['faces'].to(dev), c_l.shape[0])
+            tr = nearest(coords[0], c_l)
+            cur = dict(vertices=c_l, faces=spec['faces'].to(dev), normals=spec['normals'].to(dev).double())
+            nrm = cur['normals']
+        elif isinstance(spec, dict):
+            c_l = spec['vertices'].to(dev).double().contiguous()
+            e_l = _mesh_edges(spec['faces'].to(dev), c_l.shape[0])
+            tr = trace_from_csv(spec['csv'], coords[-1], c_l)
+            cur = dict(vertices=c_l, faces=spec['faces'].to(dev), normals=spec['normals'].to(dev).double())
+            nrm = cur['normals']
+        else:
+            c_l = cur['vertices']
+            e_l = _mesh_edges(cur['faces'], c_l.shape[0])
+            tr = torch.arange(c_l.shape[0], dtype=torch.int64, device=dev)
+            nrm = cur['normals']
+        coords.append(c_l)
+        edges.append(e_l)
+        traces.append(tr.long())
+        level_normals.append(nrm)
+    looked = _colors_and_labels(original, coords)
+    dilated = []
+    for l in range(len(levels)):
+        if int(dilated_levels[l]) != 1:
+            dilated.append(None)
+            continue
+        c_l = coords[l + 1]
+        nrm = level_normals[l]
+        if nrm is None:
+            nrm = normals0[:c_l.shape[0]] if reference_vc_normals else normals0[looked[l + 1][1]]
+        dilated.append(dilated_edges(edges[l].t().contiguous(), c_l.double().contiguous(), nrm.double().contiguous(), dists))
+    ccl = [torch.cat([coords[i].double(), looked[i][0]], dim=1) for i in range(len(coords))]
+    out = {}
+    if labels is not None:
+        out['vertices'] = [ccl[1][:, :-1].float()] + [ccl[i][:, :3].float() for i in range(2, len(ccl))]
+        out['labels'] = ccl[0][:, -1].long()
+    else:
+        out['vertices'] = [ccl[1].float()] + [ccl[i][:, :3].float() for i in range(2, len(ccl))]
+    out['edges'] = [e.long() for e in edges]
+    out['traces'] = traces
+    out['dilated_edges'] = dilated
+    out['dilation_dists'] = dilation_dists
     return out

@@ -236,3 +236,31 @@ def write_crops(graph_path, out_dir, block_size=3.0, stride=1.5, **kw):
         torch.save({k: to(v, 'cpu') for k, v in crop.items()}, path)       # (.to('cpu') of a view copies only the view)
         written.append(path)
     return written
+
+
+def write_graph_levels(out_dir, scene_name, mesh, levels, dilated_levels, dilation_dists, labels=None, device='cuda', **kw):
+    """preprocessing/graph_level_generation.py for one scene, on the GPU (preprocessing.graph_levels: the arguments are its own;
+    tensors or arrays of `mesh`, the level dicts and `labels` are moved to `device`): writes out_dir/<scene_name>.pt with CPU
+    tensors in the reference's schema - the file load_scene, load_label_scene(is_train=False), write_crops and write_circle_masks
+    read.  **kw goes to graph_levels (reference_vc_normals).  -> the path written."""
+    import os
+    from .preprocessing import graph_levels
+
+    def to(v, d):
+        if torch.is_tensor(v):
+            return v.to(d)
+        if isinstance(v, np.ndarray):
+            return torch.from_numpy(v).to(d)
+        if isinstance(v, (list, tuple)) and any(torch.is_tensor(y) or isinstance(y, (list, tuple)) for y in v):
+            return [to(y, d) for y in v]
+        return v
+
+    def level(x):
+        return {k: (v if k == 'csv' else to(v, device)) for k, v in x.items()} if isinstance(x, dict) else x
+
+    saved = graph_levels({k: to(v, device) for k, v in mesh.items()}, [level(x) for x in levels], dilated_levels, dilation_dists,
+                         labels=None if labels is None else to(labels, device), **kw)
+    os.makedirs(out_dir, exist_ok=True)
+    path = os.path.join(out_dir, '%s.pt' % scene_name)
+    torch.save({k: to(v, 'cpu') for k, v in saved.items()}, path)
+    return path
