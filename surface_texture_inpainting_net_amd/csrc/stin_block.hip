@@ -492,8 +492,6 @@ extern "C" int stin_edgeconv_chain_bwd(int storage, const stin_chain_job_t* jobs
 // ---------------------------------------------------------------------------------------------------------------------
 // The graph part of the network as one op list per direction (include/stin_hip.h: stin_net_op_t).  Only loops: every op is
 // one of the existing entry points with the pointers of the host array.
-static_assert(sizeof(stin_net_op_t) == 16 * 4 + 8 + 7 * 8 + 2 * 8 + 42 * 8, "stin_net_op_t layout (functional._net_struct packs it)");
-
 extern "C" int stin_net_fwd(int storage, const stin_net_op_t* ops, int n_ops, stin_stream_t stream) {
     STIN_REQUIRE(n_ops >= 0 && (n_ops == 0 || ops != nullptr), STIN_E_NULL);
     STIN_REQUIRE(storage == 0 || storage == 1, STIN_E_UNSUPPORTED);

@@ -16,8 +16,13 @@ from .plan import _ptr, _stream
 EPS = 1e-5
 # save the edge-stage ReLU decisions as a bit-mask in forward (STIN_EDGE_MASK=0: recompute them in backward)
 USE_EDGE_MASK = os.environ.get('STIN_EDGE_MASK', '1') != '0'
-RED_SUM, RED_CSQ, RED_DOT_ELU, RED_COEF_XC, RED_MOMENTS, RED_DOT_BN, RED_DOT_BN_RELU = 0, 1, 2, 3, 4, 5, 6
-POST_NONE, POST_SCALE, POST_RSTD, POST_NORM_COEF = 0, 1, 2, 3
+_C = _lib.CONSTANTS                 # the integer #defines of include/stin_hip.h
+RED_SUM, RED_CSQ, RED_DOT_ELU, RED_COEF_XC, RED_MOMENTS, RED_DOT_BN, RED_DOT_BN_RELU = (_C[n] for n in (
+    'STIN_RED_SUM', 'STIN_RED_CSQ', 'STIN_RED_DOT_ELU', 'STIN_RED_COEF_XC', 'STIN_RED_MOMENTS', 'STIN_RED_DOT_BN',
+    'STIN_RED_DOT_BN_RELU'))
+POST_NONE, POST_SCALE, POST_RSTD, POST_NORM_COEF = (_C[n] for n in (
+    'STIN_POST_NONE', 'STIN_POST_SCALE', 'STIN_POST_RSTD', 'STIN_POST_NORM_COEF'))
+SEG_NONTEMPORAL = _C['STIN_SEG_NONTEMPORAL']
 
 
 def _mat(t):
@@ -203,8 +208,8 @@ def edge_relu_mean_bwd_src(A, B, G, inv_deg, csr_src, dB):
 def segment_sum(src, rowptr, col, n_rows, mean=False):
     src, ld = _mat(src)
     out = torch.empty(n_rows, src.shape[1], dtype=src.dtype, device=src.device)
-    # (STIN_SEG_NONTEMPORAL = 2: a source that cannot be Infinity-Cache resident is read with non-temporal loads)
-    flags = int(mean) | (2 if (src.dtype == torch.float32 and src.shape[0] * ld * 4 > (256 << 20)) else 0)
+    # (a source that cannot be Infinity-Cache resident is read with non-temporal loads)
+    flags = int(mean) | (SEG_NONTEMPORAL if (src.dtype == torch.float32 and src.shape[0] * ld * 4 > (256 << 20)) else 0)
     _call('stin_segment_sum' + _sfx(src), _ptr(src), ld, _ptr(rowptr), _ptr(col), n_rows, src.shape[1], flags, _ptr(out),
           out.stride(0) if n_rows > 1 else src.shape[1], _stream(src), tag=(int(src.shape[0]), int(n_rows), int(src.shape[1])))
     return out
@@ -321,7 +326,8 @@ def instance_norm_act_bwd(x, gout, mean, rstd, groups, act=True, out=None):
     return dx
 
 
-GEMM_F32, GEMM_BF16X3, GEMM_BF16X6, GEMM_F16X3 = 0, 2, 3, 4
+GEMM_F32, GEMM_BF16X3, GEMM_BF16X6, GEMM_F16X3 = (_C[n] for n in (
+    'STIN_GEMM_F32', 'STIN_GEMM_BF16X3', 'STIN_GEMM_BF16X6', 'STIN_GEMM_F16X3'))
 PREC_NAMES = {GEMM_F32: 'fp32', GEMM_BF16X3: 'bf16x3', GEMM_BF16X6: 'bf16x6', GEMM_F16X3: 'fp16x3'}
 # matrix-core path per GEMM role (env override for A/B experiments: STIN_GEMM_FWD / STIN_GEMM_BWD = 0 | 2 | 3 | 4)
 # Defaults: forward GEMMs on the 2-piece fp16 split (3 MFMAs; rms 1-5e-7 against fp64 = the fp32 MFMA chain's
@@ -330,11 +336,11 @@ PREC_NAMES = {GEMM_F32: 'fp32', GEMM_BF16X3: 'bf16x3', GEMM_BF16X6: 'bf16x6', GE
 # rms 4e-6, far inside the 1e-3 gradient tolerance).
 PREC_FWD = int(os.environ.get('STIN_GEMM_FWD', GEMM_F16X3))
 PREC_BWD = int(os.environ.get('STIN_GEMM_BWD', GEMM_BF16X3))
-GEMM_W_PRESPLIT = 0x100            # nt: the weight operand already holds its two 16-bit pieces (stin_hip.h)
-GEMM_W_BF16 = 0x200                # stin_gemm_nt_bf16: the weight operand holds bf16 [Nc][K] (stin_hip.h)
+GEMM_W_PRESPLIT = _C['STIN_GEMM_W_PRESPLIT']   # nt: the weight operand already holds its two 16-bit pieces (stin_hip.h)
+GEMM_W_BF16 = _C['STIN_GEMM_W_BF16']           # stin_gemm_nt_bf16: the weight operand holds bf16 [Nc][K] (stin_hip.h)
 # pre-split operands in MFMA fragment order where the shape allows (stin_hip.h STIN_GEMM_W_FRAG): what the resident-strip NT
 # kernel reads.  STIN_NT_STRIP=0 keeps the k-group layout and with it the tiled kernel (A/B aid).
-GEMM_W_FRAG = 0x400                 # (a module constant since round 6; tests flip the attribute)
+GEMM_W_FRAG = _C['STIN_GEMM_W_FRAG']           # (a module constant since round 6; tests flip the attribute)
 WEIGHT_PRESPLIT = True
 # one C call per GraphResnetBlock and direction (stin_edgeconv_block_fwd/bwd enqueue the same kernels in the same order
 # as the per-kernel path below): removes ~25 Python-level foreign calls per block.  STIN_BLOCK_CALL=0 = per-kernel path.
@@ -781,7 +787,7 @@ def block_split_modes(prec_fwd, b16, Cout):
 # [-W1 ; W1] product wrote up to one ulp of its accumulator - and the backward pass carries D = dB - dA in H columns.  Half the first Linear's GEMM work in
 # every direction.  fp32 storage with a saved-mask hidden width; STIN_TI_COMPACT=0 keeps both halves materialised (A/B switch).
 TI_COMPACT = os.environ.get('STIN_TI_COMPACT', '1') != '0'
-TI_MODE_COMPACT = 2
+TI_MODE_COMPACT = _C['STIN_TI_COMPACT']
 
 
 def trans_inv_mode(trans_inv, b16, H):
@@ -796,7 +802,8 @@ def block_yw(H, Cout, has_shortcut, ti_mode):
     return (H if ti_mode == TI_MODE_COMPACT else 2 * H) + (Cout if has_shortcut else 0)
 
 
-BLOCK_PACKED = 0x800
+BLOCK_PACKED = _C['STIN_BLOCK_PACKED']
+_PACK_JOB = _lib.STRUCTS['stin_pack_job_t']
 USE_PACK_MANY = True
 
 
@@ -808,7 +815,6 @@ class PackSet:
 
     def __init__(self, specs, dev, b16=False, transposes=()):
         import ctypes
-        import struct
         lib = _lib.load()
         self.key = self.key_of(specs) + (bool(b16),) + tuple((_ptr(W), tuple(W.shape)) for W in transposes)
         self.b16 = bool(b16)
@@ -835,8 +841,8 @@ class PackSet:
             wcat, w2s, bcat = (base + o.value for o in off)
             W1c, W2c = W1.contiguous(), W2.contiguous()
             assert W1c.data_ptr() == W1.data_ptr() and W2c.data_ptr() == W2.data_ptr(), 'pack_many needs contiguous weights'
-            blob += struct.pack('<10Q8i', _ptr(W1), _ptr(b1), _ptr(Ws), _ptr(bs), _ptr(W2), wcat, bcat, _ptr(wts),
-                                _ptr(wts) + 4 * Yw * Cp, w2s if jf else 0, Cin, Cp, H, Cout, int(has_sc), ti, jf, jb)
+            blob += _PACK_JOB.pack(_ptr(W1), _ptr(b1), _ptr(Ws), _ptr(bs), _ptr(W2), wcat, bcat, _ptr(wts),
+                                   _ptr(wts) + 4 * Yw * Cp, w2s if jf else 0, Cin, Cp, H, Cout, int(has_sc), ti, jf, jb)
             self.max_elems = max(self.max_elems, Yw * Cp + H * Cout)
             # (the two backward operands as ready-made views: no tensor views are created inside autograd.Function.forward)
             self.buffers.append((ws, wts, fsp, bsp, wts[:Yw * Cp].view(Cp, Yw), wts[Yw * Cp:].view(H, Cout), bool(b16)))
@@ -847,7 +853,7 @@ class PackSet:
             Nc, K = W.shape
             assert W.is_contiguous() and W.dtype == torch.float32
             wT = torch.empty(K, Nc, dtype=torch.float32, device=dev)
-            blob += struct.pack('<10Q8i', 0, 0, 0, 0, _ptr(W), 0, 0, 0, _ptr(wT), 0, 0, 0, K, Nc, 0, 0, 0, 0)
+            blob += _PACK_JOB.pack(0, 0, 0, 0, _ptr(W), 0, 0, 0, _ptr(wT), 0, 0, 0, K, Nc, 0, 0, 0, 0)
             self.max_elems = max(self.max_elems, K * Nc)
             self.transposed.append(wT)
         self.jobs = torch.frombuffer(bytearray(blob), dtype=torch.uint8).to(dev)
@@ -1088,15 +1094,7 @@ class EdgeConvBlockFn(torch.autograd.Function):
 
 # ---- a chain of fused blocks of one level in ONE autograd node ------------------------------------------------------------
 USE_CHAIN = True
-_CHAIN_JOB = None
-
-
-def _chain_struct():
-    global _CHAIN_JOB
-    if _CHAIN_JOB is None:
-        import struct
-        _CHAIN_JOB = struct.Struct('<27Q4i')             # stin_chain_job_t (include/stin_hip.h): 232 bytes
-    return _CHAIN_JOB
+_CHAIN_JOB = _lib.STRUCTS['stin_chain_job_t']
 
 
 def chain_eligible(blocks, x, edges_list, groups):
@@ -1169,7 +1167,7 @@ class EdgeConvChainFn(torch.autograd.Function):
         if not packed:                                                        # the block calls run their own pack: own buffers
             wts = torch.empty(n, wts_n, dtype=torch.float32, device=dev)
             ws = torch.empty(n, ws_bytes, dtype=torch.uint8, device=dev)
-        st = _chain_struct()
+        st = _CHAIN_JOB
         blob, moff = [], 0
         pY, pH, pA, pO, pS, pM = _ptr(Y), _ptr(hE), _ptr(agg), _ptr(outs), _ptr(stats), _ptr(mask)
         for i in range(n):
@@ -1250,7 +1248,7 @@ class EdgeConvChainFn(torch.autograd.Function):
                 for t in grads:
                     if t is not None:
                         t.record_stream(side.stream)
-        st = _chain_struct()
+        st = _CHAIN_JOB
         blob, moff = [], 0
         pY, pH, pA, pO, pS, pM, pW = _ptr(Y), _ptr(hE), _ptr(agg), _ptr(outs), _ptr(stats), _ptr(mask), _ptr(ws)
         for i in range(n):
@@ -1300,17 +1298,8 @@ def edgeconv_chain(x, blocks, edges_list, groups, eps, prec_fwd):
 
 # ---- the graph part of the network in ONE autograd node ----------------------------------------------------------------------
 USE_NET_CALL = os.environ.get('STIN_NET_CALL', '1') != '0'
-_NET_OP = None
-OP_BLOCK, OP_POOL_MAX, OP_UNPOOL = 0, 1, 2
-
-
-def _net_struct():
-    global _NET_OP
-    if _NET_OP is None:
-        import struct
-        _NET_OP = struct.Struct('<16ifi7q2Q42Q')             # stin_net_op_t (include/stin_hip.h): 480 bytes
-        assert _NET_OP.size == 480
-    return _NET_OP
+_NET_OP = _lib.STRUCTS['stin_net_op_t']
+OP_BLOCK, OP_POOL_MAX, OP_UNPOOL = _C['STIN_OP_BLOCK'], _C['STIN_OP_POOL_MAX'], _C['STIN_OP_UNPOOL']
 
 
 def _align256(n):
@@ -1450,7 +1439,7 @@ class NetFn(torch.autograd.Function):
         base, p_out = _ptr(arena), _ptr(out)
         assert base % 256 == 0
         # ---- pass 2: the op table
-        stc = _net_struct()
+        stc = _NET_OP
         blob = []
         xin, ldx = _ptr(xp), xp.stride(0)
         for d in plan:
@@ -1598,7 +1587,7 @@ class NetFn(torch.autograd.Function):
                 for t in grads:
                     if t is not None:
                         t.record_stream(side.stream)
-        stc = _net_struct()
+        stc = _NET_OP
         blob, bi = [], 0
         for i, d in enumerate(plan):
             p_dx = (_ptr(dx0) if i == 0 else p_scr + (i & 1) * dx_bytes)

@@ -12,7 +12,6 @@ Indices are int64 at the Python boundary (as in the reference) and int32 inside.
 """
 import collections
 import ctypes
-import struct
 
 import torch
 
@@ -125,8 +124,8 @@ class CSR:
         self.n_rows, self.n_entries = n_rows, n_entries
 
 
-_JOB = struct.Struct('<2Q3q3QQ3QQQ2i')     # stin_plan_job_t (include/stin_hip.h): 120 bytes
-JOBS_MAX = 16                              # STIN_PLAN_MAX_JOBS
+_JOB = _lib.STRUCTS['stin_plan_job_t']
+JOBS_MAX = _lib.CONSTANTS['STIN_PLAN_MAX_JOBS']
 
 
 class PlanJobs:
@@ -400,7 +399,7 @@ class GraphPlan:
             order0 = torch.empty(sizes[0], dtype=torch.int32, device=dev)
             ws_bytes = lib.stin_vertex_order_workspace_bytes(max(sizes))
             ws = torch.empty(ws_bytes, dtype=torch.uint8, device=dev)
-            st = struct.Struct('<q3Q')
+            st = _lib.STRUCTS['stin_order_level_t']
             blob, keep = [], []
             for lvl, n in enumerate(sizes):
                 tr = None
@@ -452,7 +451,7 @@ class GraphPlan:
         """items: [('e', edge tensor [2, E] int64, level) | ('p', trace [n_fine] int64, level)] -> relabelled tensors in ONE launch
         per 16 arrays (stin_relabel_many_i64): 'e' -> new [2, E] int64; 'p' -> (coarse_new, fine_new, trace_new) as PoolMap wants."""
         lib = _lib.load()
-        st = struct.Struct('<QqQqQQQQ')
+        st = _lib.STRUCTS['stin_relabel_job_t']
         blobs, outs, keep = [], [], []
         for kind, t, level in items:
             t = t.contiguous()

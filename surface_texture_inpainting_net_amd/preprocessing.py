@@ -264,8 +264,9 @@ def circle_masks(edge_index, num_nodes, radius=16, frac_masked_vertices=0.25, nu
 
 # ------------------------------------------------------------------------------------------------------------- training crops
 MIN_NUM_MAXIMALLY_DECIMATED_VERTS = 50      # preprocessing/crop_training_samples.py:24
-_SEG_WORDS = 16                             # int64 words of a stin_crop_seg_t
-_SEG_VERTICES, _SEG_EDGES, _SEG_DILATED, _SEG_OCCURS, _SEG_TRACE = range(5)
+_SEG_WORDS = _lib.STRUCTS['stin_crop_seg_t'].size // 8         # int64 words of a stin_crop_seg_t
+_SEG_VERTICES, _SEG_EDGES, _SEG_DILATED, _SEG_OCCURS, _SEG_TRACE = (_lib.CONSTANTS[n] for n in (
+    'STIN_CROP_VERTICES', 'STIN_CROP_EDGES', 'STIN_CROP_DILATED', 'STIN_CROP_OCCURS', 'STIN_CROP_TRACE'))
 
 
 def crop_positions(vertices0, stride):

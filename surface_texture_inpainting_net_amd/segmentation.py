@@ -28,8 +28,8 @@ import torch.nn.functional as F
 from . import _lib
 from .plan import _ptr, _stream
 
-MIN_CLASSES = 2
-MAX_CLASSES = 128      # STIN_SEG_MAX_CLASSES: the per-block C x C int32 histogram is 64 KB of LDS there
+MIN_CLASSES = _lib.CONSTANTS['STIN_SEG_MIN_CLASSES']
+MAX_CLASSES = _lib.CONSTANTS['STIN_SEG_MAX_CLASSES']      # the per-block C x C int32 histogram is 64 KB of LDS there
 
 
 class _DeferredFlag:

@@ -36,6 +36,116 @@ def test_library_exports_every_declared_symbol():
     assert set(syms) == set(_lib.SIGNATURES.keys())
 
 
+_I, _L, _Z, _U, _F, _D, _P = (ctypes.c_int, ctypes.c_int64, ctypes.c_size_t, ctypes.c_uint64, ctypes.c_float, ctypes.c_double,
+                              ctypes.c_void_p)
+
+
+@pytest.mark.parametrize('name,want', [
+    ('stin_csr_workspace_bytes', (_Z, [_L, _L])),                                             # a size_t return
+    ('stin_error_string', (ctypes.c_char_p, [_I])),                                           # the const char* return
+    ('stin_circle_mask_run', (_I, [_P, _P, _L, _P, _I, _I, _I, _D, _U, _P, _I, _P, _L, _P, _P, _P, _P, _L, _P, _Z, _P])),
+    ('stin_adam_f32', (_I, [_P, _P, _P, _P, _P, _L, _D, _D, _D, _D, _D, _I, _I, _P])),        # doubles by value
+    ('stin_cols_axpy_rowmask_f32', (_I, [_P, _L, _P, _L, _P, _L, _I, _I, _F, _P])),           # a float by value
+    ('stin_net_fwd', (_I, [_I, _P, _I, _P])),                                                 # a struct pointer
+    ('stin_dilated_walk_f64', (_I, [_P, _P, _P, _P, _P, _L, _L, _P, _I, _P, _P])),            # the host `dilations` array
+])
+def test_derived_signatures_match_hand_written_ones(name, want):
+    assert _lib.SIGNATURES[name] == want
+
+
+def test_longest_prototype_is_read_argument_by_argument():
+    res, args = _lib.SIGNATURES['stin_edgeconv_block_bwd']
+    assert res is _I and len(args) == 50 == max(len(a) for _, a in _lib.SIGNATURES.values())
+    other = {0: _I, 2: _L, 4: _L, 5: _L, 6: _I, 7: _I, 8: _I, 9: _I, 10: _I, 11: _I, 13: _L, 15: _L, 28: _I, 32: _I, 33: _I,
+             35: _L, 43: _Z, 49: _I}
+    assert args == [other.get(i, _P) for i in range(50)]
+
+
+def test_struct_layouts_have_the_sizes_the_c_side_asserts():
+    """The same literals as the static_asserts of csrc/stin_common.h."""
+    sizes = {'stin_plan_job_t': 120, 'stin_order_level_t': 32, 'stin_relabel_job_t': 64, 'stin_pack_job_t': 112,
+             'stin_chain_job_t': 232, 'stin_net_op_t': 480, 'stin_crop_seg_t': 128}
+    assert {k: v.size for k, v in _lib.STRUCTS.items()} == sizes
+    common = open(os.path.join(ROOT, 'surface_texture_inpainting_net_amd', 'csrc', 'stin_common.h')).read()
+    for name, size in sizes.items():
+        assert 'static_assert(sizeof(%s) == %d,' % (name, size) in common
+    assert _lib.STRUCTS['stin_net_op_t'].format == '<' + 'i' * 16 + 'f' + 'i' + 'q' * 7 + 'Q' * 2 + 'Q' * 42
+    assert _lib.STRUCTS['stin_plan_job_t'].format == '<QQqqqQQQQQQQQQii'
+    assert _lib.STRUCTS['stin_crop_seg_t'].format == '<' + 'q' * 8 + 'Q' * 5 + 'q' * 3                # `int64_t reserved[3]`
+
+
+def test_constants_come_from_the_header():
+    c = _lib.CONSTANTS
+    assert c['STIN_E_WORKSPACE'] == -4 and c['STIN_E_NULL'] == -1 and c['STIN_OK'] == 0 and c['STIN_VERSION'] == 100
+    assert c['STIN_GEMM_W_FRAG'] == 0x400 and c['STIN_BLOCK_PACKED'] == 0x800 and c['STIN_GEMM_F16X3'] == 4
+    assert c['STIN_SEG_MAX_CLASSES'] == 128 and c['STIN_CROP_TRACE'] == 4 and c['STIN_PLAN_MAX_JOBS'] == 16
+    assert all(k.startswith('STIN_') and isinstance(v, int) for k, v in c.items()) and 'STIN_HIP_H' not in c
+    from surface_texture_inpainting_net_amd import functional as F
+    assert (F.GEMM_F32, F.GEMM_BF16X3, F.GEMM_BF16X6, F.GEMM_F16X3, F.GEMM_W_PRESPLIT, F.GEMM_W_BF16) == (0, 2, 3, 4, 0x100, 0x200)
+
+
+_SMALL_HEADER = """/* a header in the style of stin_hip.h; stin_ghost(int) in a comment is no prototype */
+#ifndef STIN_HIP_H
+#define STIN_HIP_H
+#include <stdint.h>
+#define STIN_E_SIZE (-2)   /* comment */
+#define STIN_FLAG 0x10
+typedef void* stin_stream_t;
+typedef struct stin_job {
+    const float *a, *b;
+    int64_t n[2];
+    int32_t k, reserved;
+} stin_job_t;
+size_t stin_bytes(void);
+int stin_run(const stin_job_t* jobs, int n_jobs, float eps,
+             stin_stream_t stream);
+#endif
+"""
+
+
+def test_header_reader_is_strict():
+    from surface_texture_inpainting_net_amd import _abi
+    sig, structs, consts = _abi.parse_header(_SMALL_HEADER)
+    assert sig == {'stin_bytes': (_Z, []), 'stin_run': (_I, [_P, _I, _F, _P])}
+    assert structs['stin_job_t'].format == '<QQqqii' and consts == {'STIN_E_SIZE': -2, 'STIN_FLAG': 16}
+
+    def broken(old, new, line):
+        assert old in _SMALL_HEADER
+        with pytest.raises(_lib.StinLibraryError, match=r':%d: ' % line):
+            _abi.parse_header(_SMALL_HEADER.replace(old, new))
+    broken('int n_jobs', 'long n_jobs', 14)                                     # a type the reader does not know
+    broken('float eps', 'stin_job_t job', 14)                                   # a struct by value
+    broken('size_t stin_bytes(void);', 'size_t stin_bytes(void)', 13)           # a prototype without its `;`
+    broken('const stin_job_t* jobs', 'const stin_job_t*', 14)                   # a parameter without a name
+    broken('int n_jobs', 'int dims[3]', 14)                                     # array parameters: pointers in C
+    broken('int n_jobs', 'const int dilations[]', 14)
+    broken('stin_stream_t stream)', 'stin_stream_t stream,)', 15)               # an empty parameter
+    broken('size_t stin_bytes(void);', 'size_t stin_bytes();', 13)
+    broken('stin_run(', 'stin_bytes(', 14)                                      # a second declaration
+    broken('size_t stin_bytes(void);', '#ifdef __cplusplus\nint stin_hidden(long x);\n#endif', 14)     # read, not skipped
+    broken('#include <stdint.h>', '#ifndef STIN_OTHER', 4)                      # a conditional besides the include guard
+    broken('int32_t k, reserved;', 'int32_t k : 8, reserved;', 11)              # a bit-field
+    broken('int64_t n[2];', 'int64_t n[2]', 10)                                 # a field without its `;`
+    broken('size_t stin_bytes(void);', 'static inline int stin_twice(int x) { return 2 * x; }', 13)
+    broken('size_t stin_bytes(void);', 'float* stin_buffer(void);', 13)         # a pointer return other than const char*
+    broken('int32_t k, reserved;', 'int32_t k;', 12)                            # the C layout would pad: 28 bytes packed, 32 in C
+    broken('#define STIN_FLAG 0x10', '#define STIN_FLAG (1 << 4)', 6)           # not an integer literal
+    broken('#include <stdint.h>', '#if 0', 4)                                   # a directive that could hide declarations
+    with pytest.raises(_lib.StinLibraryError, match='nope.h'):
+        _abi.read_header(os.path.join(ROOT, 'include', 'nope.h'))
+
+
+def test_no_struct_format_is_typed_by_hand():
+    """Record layouts come from STRUCTS (the header), never from a format string in the package."""
+    pkg = os.path.join(ROOT, 'surface_texture_inpainting_net_amd')
+    for dirpath, _, files in os.walk(pkg):
+        for f in files:
+            if f.endswith('.py'):
+                src = open(os.path.join(dirpath, f)).read().replace('"', "'")
+                for call in ("struct.Struct('<", "struct.pack('<", "struct.unpack('<", "struct.pack_into('<"):
+                    assert call not in src, '%s holds a struct format literal' % f
+
+
 def test_library_host_only_entry_points():
     lib = _lib.load()                       # no GPU needed for these calls
     assert lib.stin_version() == 100
