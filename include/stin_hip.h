@@ -33,7 +33,7 @@
 extern "C" {
 #endif
 
-#define STIN_VERSION 100           /* major*10000 + minor*100 + patch */
+#define STIN_VERSION 101           /* major*10000 + minor*100 + patch */
 
 #define STIN_OK 0
 #define STIN_E_NULL (-1)           /* required pointer is NULL */
@@ -117,9 +117,9 @@ int stin_plan_build_many(const stin_plan_job_t* jobs, int n_jobs, int32_t* bad, 
  *     rank int32 [n + 1] (old id -> new id, rank[n] = n) and order int32 [n] (new -> old; may be NULL).  Level 0: stable sort
  *     by the 30-bit Morton code on the bounding box; level l >= 1: stable sort by the smallest new id among the children under
  *     levels[l].trace (the level l - 1 -> l map, int64 [n_{l-1}]).  Deterministic.
- *   stin_relabel_many_i64: out[i] = rank[in[i]] (limit where in[i] is outside [0, limit): the CSR build then flags and drops
+ *   stin_relabel_many_i64: out[i] = rank[ids[i]] (limit where ids[i] is outside [0, limit): the CSR build then flags and drops
  *     it exactly like an out-of-range original id) for up to 16 index arrays in one launch.  A job with rank_fine != NULL is a
- *     TRACE (in = trace [n_fine], rank = the coarse level's): it also writes fine_out[i] = rank_fine[i] (the pair's second
+ *     TRACE (ids = trace [n_fine], rank = the coarse level's): it also writes fine_out[i] = rank_fine[i] (the pair's second
  *     member, int64 for stin_plan_build_many) and trace_out[rank_fine[i]] = out[i] (int32: new fine id -> new coarse id, 0
  *     where out of range).  Index arrays keep their ORDER: CSR rows and children lists built from them keep the reference's. */
 typedef struct stin_order_level {
@@ -133,7 +133,7 @@ int stin_vertex_order_f32(const float* pos, int64_t ld_pos, const stin_order_lev
                           size_t workspace_bytes, stin_stream_t stream);
 #define STIN_RELABEL_MAX_JOBS 16
 typedef struct stin_relabel_job {
-    const int64_t* in;
+    const int64_t* ids;
     int64_t n;
     const int32_t* rank;
     int64_t limit;
@@ -783,39 +783,6 @@ int stin_edgeconv_block_bwd(int storage, const void* g, int64_t ldg, const void*
                             float* dW1, float* db1, float* dW2, float* db2, float* dWs, float* dbs, void* workspace,
                             size_t workspace_bytes, stin_stream_t stream, stin_stream_t wgrad_stream, stin_event_t ev_dagg,
                             stin_event_t ev_dy, stin_event_t ev_done, int join);
-
-/* A CHAIN of fused blocks of one level in one call per direction (round 3): the n consecutive identity-residual blocks of
- * the bottleneck (models/surfacetextureinpaintingnet.py:437-443: `for i in range(n_blocks): x = bottleneck_blocks[i](x, ...)`)
- * share N, the width (Cin = Cout, no shortcut) and the norm groups; block i reads block i - 1's output, the edge set may
- * differ per block (dilations).  The calls only loop over stin_edgeconv_block_fwd / _bwd with the per-block pointers of the
- * HOST job array - identical kernels in identical order, one foreign call and one autograd node instead of n.
- *   fwd: x [N, Cp] feeds job 0; job i writes the tensors backward needs (Y, hE, mask, agg, mean, rstd, wcatT, w2T) and `out`.
- *   bwd: g = dL/d(out of the last job); job i's input gradient goes to scratch[i & 1] ([N, Cp] each) and is job i - 1's g;
- *        job 0's goes to dx (may be NULL).  Every job needs its OWN bwd workspace while a weight-gradient stream is in use
- *        (its kernels read dagg / dY from it after the call has returned).  ev_dy / ev_done per job as in block_bwd. */
-typedef struct stin_chain_job {
-    const float *W1, *b1, *W2, *b2;
-    float *wcatT, *w2T;
-    void* fwd_ws;
-    const int32_t *rowptr_dst, *col_dst, *rowptr_src, *col_src, *xslot;
-    const float* w_src;
-    void *Y, *hE;
-    uint32_t* mask;
-    void* agg;
-    float *mean, *rstd;
-    void* out;
-    float *dW1, *db1, *dW2, *db2;
-    void* bwd_ws;
-    stin_event_t ev_dy, ev_done;
-    int32_t trans_inv, fwd_split, bwd_split, prec_fwd;
-} stin_chain_job_t;                                   /* 27 pointers + 4 int32 = 232 bytes */
-int stin_edgeconv_chain_fwd(int storage, const stin_chain_job_t* jobs, int n_jobs, const void* x, int64_t ldx, int64_t N,
-                            int C, int Cp, int H, const int32_t* ptr_sum, int B, const int32_t* gid, const float* inv_cnt,
-                            int slice_quirk, float eps, size_t fwd_ws_bytes, stin_stream_t stream);
-int stin_edgeconv_chain_bwd(int storage, const stin_chain_job_t* jobs, int n_jobs, const void* g, int64_t ldg, const void* x,
-                            int64_t ldx, int64_t N, int C, int Cp, int H, const int32_t* ptr_true, int B, const int32_t* gid,
-                            const int32_t* sid, const float* inv_cnt, int prec_bwd, void* dx, int64_t lddx, void* scratch0,
-                            void* scratch1, size_t bwd_ws_bytes, stin_stream_t stream, stin_stream_t wgrad_stream);
 
 /* The WHOLE graph part of the network in one call per direction (round 3): every fused EdgeConv + instance-norm block and the
  * pool / unpool steps between them, in network order (models/surfacetextureinpaintingnet.py:404-455: input blocks, `for`

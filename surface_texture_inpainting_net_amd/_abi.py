@@ -27,8 +27,39 @@ _STRUCT = re.compile(r'typedef\s+struct\s+\w+\s*\{([^{}]*)\}\s*(\w+)\s*;')
 _TYPEDEF = re.compile(r'typedef\s+(\w+)\s*(\*|\s)\s*(\w+)\s*;')
 _PROTOTYPE = re.compile(r'(const\s+char\s*\*|\w+)\s*(stin_\w+)\s*\(([^()]*)\)\s*;')
 _FIELD = re.compile(r'\s*(?:const\s+)?(\w+)\b(.*)$', re.S)              # type, then comma separated declarators:
-_DECLARATOR = re.compile(r'\s*(\*?)\s*\w+\s*(?:\[(\d+)\])?\s*$')        # `x`, `*x` or `x[3]`
+_DECLARATOR = re.compile(r'\s*(\*?)\s*(\w+)\s*(?:\[(\d+)\])?\s*$')      # `x`, `*x` or `x[3]`
 _PARAMETER = re.compile(r'\s*(?:const\s+)?(\w+)\s*(\*|\s)\s*\w+\s*$')  # type, `*` or a space, a name; never a `[`
+
+
+class Record:
+    """One struct of the header, packed by FIELD NAME only: `fields` in declaration order, `format` / `size` of the packed
+    little-endian layout.  pack(name=value, ...) -> bytes; a field that is not named is zero, an array field (`int64_t
+    reserved[3]`) is one name that takes a sequence of its length.  Names were resolved to positions when the header was
+    read: a call copies the row of zeros, assigns and packs."""
+    __slots__ = ('name', 'fields', 'format', 'size', '_pack', '_zeros', '_at')
+
+    def __init__(self, name, fields):
+        """fields: [(field name, struct code, element count)]"""
+        self.name, self.fields = name, tuple(f for f, _, _ in fields)
+        packed = '<' + ''.join(code * n for _, code, n in fields)               # little-endian, no padding
+        st = struct.Struct(packed)
+        self.format, self.size, self._pack = st.format, st.size, st.pack
+        self._at, at = {}, 0
+        for f, _, n in fields:
+            self._at[f] = at if n == 1 else slice(at, at + n)
+            at += n
+        self._zeros = [0] * at
+
+    def pack(self, **values):
+        row, at = self._zeros[:], self._at
+        try:
+            for f, v in values.items():
+                row[at[f]] = v
+            return self._pack(*row)
+        except KeyError:
+            raise StinLibraryError('%s has no field %r' % (self.name, f)) from None
+        except (struct.error, TypeError) as e:      # a value of the wrong kind, or an array field given another length
+            raise StinLibraryError('%s: cannot pack %s (%s)' % (self.name, ', '.join(sorted(values)), e)) from None
 
 
 def _pieces(text, sep, start):
@@ -93,18 +124,21 @@ class _Header:
         *fields, tail = _pieces(m.group(1), ';', m.start(1))
         if tail[0].strip() or not fields:
             self.fail(tail[1], 'struct field without `;`')
-        codes = ''
+        named = []
         for field, at in fields:
             f = _FIELD.match(field)
             for declarator in f.group(2).split(',') if f else ['']:
                 d = _DECLARATOR.match(declarator)
                 if d is None:
                     self.fail(at, 'cannot split the declarator %r' % ' '.join(field.split()))
-                codes += self.kind(f.group(1), d.group(1), at)[1] * int(d.group(2) or 1)
-        packed = '<' + codes                        # little-endian, no padding: right only if the C layout has none either
-        if struct.calcsize(packed) != struct.calcsize('@%s0%s' % (codes, max(codes, key=struct.calcsize))):
+                if any(d.group(2) == n for n, _, _ in named):
+                    self.fail(at, 'second field %r' % d.group(2))
+                named.append((d.group(2), self.kind(f.group(1), d.group(1), at)[1], int(d.group(3) or 1)))
+        record = Record(m.group(2), named)          # (packed without padding: right only if the C layout has none either)
+        codes = record.format[1:]
+        if record.size != struct.calcsize('@%s0%s' % (codes, max(codes, key=struct.calcsize))):
             self.fail(m.start(2), '%s needs padding in C' % m.group(2))
-        self.structs[m.group(2)] = struct.Struct(packed)
+        self.structs[m.group(2)] = record
 
     def prototype(self, m):
         ret, name, params = m.groups()

@@ -26,7 +26,7 @@ class StinError(RuntimeError):
     pass
 
 
-# SIGNATURES: name -> (restype, argtypes); STRUCTS: typedef name -> struct.Struct; CONSTANTS: STIN_* #define -> int
+# SIGNATURES: name -> (restype, argtypes); STRUCTS: typedef name -> _abi.Record (pack by field name); CONSTANTS: STIN_* #define -> int
 SIGNATURES, STRUCTS, CONSTANTS = read_header()
 
 _lib = None

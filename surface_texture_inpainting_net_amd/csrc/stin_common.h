@@ -11,7 +11,6 @@ static_assert(sizeof(stin_plan_job_t) == 120, "stin_plan_job_t layout");
 static_assert(sizeof(stin_order_level_t) == 32, "stin_order_level_t layout");
 static_assert(sizeof(stin_relabel_job_t) == 64, "stin_relabel_job_t layout");
 static_assert(sizeof(stin_pack_job_t) == 112, "stin_pack_job_t layout");
-static_assert(sizeof(stin_chain_job_t) == 232, "stin_chain_job_t layout");
 static_assert(sizeof(stin_net_op_t) == 480, "stin_net_op_t layout");
 static_assert(sizeof(stin_crop_seg_t) == 128, "stin_crop_seg_t layout");
 

@@ -117,7 +117,7 @@ __global__ __launch_bounds__(T) void k_relabel(const RelabelBatch b) {
     const stin_relabel_job_t& J = b.j[ji];
     const int64_t i = (int64_t)(blockIdx.x - b.blk[ji]) * T + threadIdx.x;
     if (i >= J.n) return;
-    const int64_t old = J.in[i];
+    const int64_t old = J.ids[i];
     const int64_t neu = (old >= 0 && old < J.limit) ? (int64_t)J.rank[old] : J.limit;
     J.out[i] = neu;
     if (J.rank_fine != nullptr) {                             // a trace: also the pair's second member and the new fine -> coarse map
@@ -206,7 +206,7 @@ extern "C" int stin_relabel_many_i64(const stin_relabel_job_t* jobs, int n_jobs,
         const stin_relabel_job_t& J = jobs[i];
         STIN_REQUIRE(J.n >= 0 && J.limit >= 0, STIN_E_SIZE);
         if (J.n == 0) continue;
-        STIN_REQUIRE(J.in && J.rank && J.out && (J.rank_fine == nullptr || (J.fine_out && J.trace_out)), STIN_E_NULL);
+        STIN_REQUIRE(J.ids && J.rank && J.out && (J.rank_fine == nullptr || (J.fine_out && J.trace_out)), STIN_E_NULL);
         b.j[b.n] = J;
         b.blk[b.n] = blk;
         blk += blocks_for(J.n);

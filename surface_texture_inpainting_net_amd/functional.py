@@ -721,17 +721,21 @@ def _plain_autograd_may_defer():
     return not (dist.is_available() and dist.is_initialized() and dist.get_world_size() > 1)
 
 
-def _wgrad_side_args(dev, keep_alive, params, direct=False, work=0):
-    """-> (wgrad_stream, ev_dagg, ev_dy, ev_done, join) for stin_edgeconv_block_bwd.  The join with the compute stream is
-    deferred to the end of the backward pass when nothing can read the gradients earlier: the TrainStep bucket route
-    (`direct`), or plain single-process autograd with every parameter a leaf whose .grad is None (autograd then adopts
-    the returned tensor without a kernel) and without hooks; otherwise the block stays on one stream."""
-    if not USE_WGRAD_STREAM or work > WGRAD_MAX_WORK or work < WGRAD_MIN_WORK:
-        return 0, 0, 0, 0, 0
-    deferred = WGRAD_DEFER_JOIN and (direct or (_plain_autograd_may_defer() and all(
+def _join_deferrable(params, direct):
+    """The join of the weight-gradient stream may wait until the end of the backward pass when nothing can read these
+    parameters' gradients earlier: the TrainStep bucket route (`direct`), or plain single-process autograd with every
+    parameter a leaf whose .grad is None (autograd then adopts the returned tensor without a kernel) and without hooks."""
+    return WGRAD_DEFER_JOIN and (bool(direct) or (_plain_autograd_may_defer() and all(
         p is None or (p.is_leaf and p.grad is None and not p._backward_hooks and
                       not getattr(p, '_post_accumulate_grad_hooks', None)) for p in params)))
-    if not deferred:
+
+
+def _wgrad_side_args(dev, keep_alive, params, direct=False, work=0):
+    """-> (wgrad_stream, ev_dagg, ev_dy, ev_done, join) for stin_edgeconv_block_bwd.  The join with the compute stream is
+    deferred to the end of the backward pass where _join_deferrable allows it; otherwise the block stays on one stream."""
+    if not USE_WGRAD_STREAM or work > WGRAD_MAX_WORK or work < WGRAD_MIN_WORK:
+        return 0, 0, 0, 0, 0
+    if not _join_deferrable(params, direct):
         # a join inside every call measured SLOWER than one stream (9.70 vs 9.45 ms per step): gradient accumulation,
         # parameter hooks, DDP and non-leaf weights simply keep the whole block on the compute stream
         return 0, 0, 0, 0, 0
@@ -802,6 +806,23 @@ def block_yw(H, Cout, has_shortcut, ti_mode):
     return (H if ti_mode == TI_MODE_COMPACT else 2 * H) + (Cout if has_shortcut else 0)
 
 
+def _pad_rows(x, pad):
+    """x [N, Cin] with its rows padded to a multiple of `pad` channels (the inner dimension of the 16-byte GEMM paths: the
+    10-channel network input -> 12; bf16: 16) in one launch (F.pad: fill + copy), or x itself."""
+    N, Cin = x.shape
+    Cp = (Cin + pad - 1) // pad * pad
+    if Cp == Cin:
+        return x
+    xp = torch.empty(N, Cp, dtype=x.dtype, device=x.device)
+    _call('stin_pad_rows' + _sfx(x), _ptr(x), x.stride(0), N, Cin, Cp, _ptr(xp), _stream(x))
+    return xp
+
+
+def _fresh_grads(params, dev):
+    """Fresh fp32 gradient tensors [dW1, db1, dW2, db2, dWs, dbs] of one block's params (W1, b1, W2, b2, Ws, bs; None stays None)."""
+    return [None if p is None else torch.empty(p.shape, dtype=torch.float32, device=dev) for p in params]
+
+
 BLOCK_PACKED = _C['STIN_BLOCK_PACKED']
 _PACK_JOB = _lib.STRUCTS['stin_pack_job_t']
 USE_PACK_MANY = True
@@ -841,8 +862,9 @@ class PackSet:
             wcat, w2s, bcat = (base + o.value for o in off)
             W1c, W2c = W1.contiguous(), W2.contiguous()
             assert W1c.data_ptr() == W1.data_ptr() and W2c.data_ptr() == W2.data_ptr(), 'pack_many needs contiguous weights'
-            blob += _PACK_JOB.pack(_ptr(W1), _ptr(b1), _ptr(Ws), _ptr(bs), _ptr(W2), wcat, bcat, _ptr(wts),
-                                   _ptr(wts) + 4 * Yw * Cp, w2s if jf else 0, Cin, Cp, H, Cout, int(has_sc), ti, jf, jb)
+            blob += _PACK_JOB.pack(W1=_ptr(W1), b1=_ptr(b1), Ws=_ptr(Ws), bs=_ptr(bs), W2=_ptr(W2), wcat=wcat, bcat=bcat,
+                                   wcatT=_ptr(wts), w2T=_ptr(wts) + 4 * Yw * Cp, w2s=w2s if jf else 0, Cin=Cin, Cp=Cp, H=H,
+                                   Cout=Cout, has_shortcut=int(has_sc), trans_inv=ti, fwd_split=jf, bwd_split=jb)
             self.max_elems = max(self.max_elems, Yw * Cp + H * Cout)
             # (the two backward operands as ready-made views: no tensor views are created inside autograd.Function.forward)
             self.buffers.append((ws, wts, fsp, bsp, wts[:Yw * Cp].view(Cp, Yw), wts[Yw * Cp:].view(H, Cout), bool(b16)))
@@ -853,7 +875,7 @@ class PackSet:
             Nc, K = W.shape
             assert W.is_contiguous() and W.dtype == torch.float32
             wT = torch.empty(K, Nc, dtype=torch.float32, device=dev)
-            blob += _PACK_JOB.pack(0, 0, 0, 0, _ptr(W), 0, 0, 0, _ptr(wT), 0, 0, 0, K, Nc, 0, 0, 0, 0)
+            blob += _PACK_JOB.pack(W2=_ptr(W), w2T=_ptr(wT), H=K, Cout=Nc)
             self.max_elems = max(self.max_elems, K * Nc)
             self.transposed.append(wT)
         self.jobs = torch.frombuffer(bytearray(blob), dtype=torch.uint8).to(dev)
@@ -898,12 +920,8 @@ class EdgeConvBlockFn(torch.autograd.Function):
         Yw = block_yw(H, Cout, has_shortcut, ti)
         oB, oS = (0 if ti == TI_MODE_COMPACT else H), Yw - (Cout if has_shortcut else 0)   # columns of B and of the shortcut in Y / dY
         pad = 8 if b16 else 4
-        Cp = (Cin + pad - 1) // pad * pad                         # inner dimension padded for the 16-byte GEMM paths
-        if Cp != Cin:                                             # (the 10-channel network input -> 12; bf16: 16)
-            xp = torch.empty(x.shape[0], Cp, dtype=x.dtype, device=dev)
-            _call('stin_pad_rows' + ('_bf16' if b16 else '_f32'), _ptr(x), x.stride(0), x.shape[0], Cin, Cp, _ptr(xp), _stream(x))
-        else:
-            xp = x
+        xp = _pad_rows(x, pad)
+        Cp = xp.shape[1]
         # forward / backward weight operands, pre-split once here into the two 16-bit pieces the split GEMMs use
         # (instead of once per GEMM block); plain fp32 for the other precisions and for bf16-storage activations
         fsp, bsp = block_split_modes(prec_fwd, b16, Cout)
@@ -944,8 +962,6 @@ class EdgeConvBlockFn(torch.autograd.Function):
             ctx.mask = mask
             ctx.cin = Cin
             ctx.edges, ctx.groups, ctx.H, ctx.has_shortcut, ctx.trans_inv = edges, groups, H, has_shortcut, ti
-            ctx.has_b1, ctx.has_b2, ctx.has_bs = b1 is not None, b2 is not None, bs is not None
-            ctx.w1_shape = tuple(W1.shape)
             ctx.bsp = bsp
             ctx.params = (W1, b1, W2, b2, Ws, bs)
             return out
@@ -989,8 +1005,7 @@ class EdgeConvBlockFn(torch.autograd.Function):
         ctx.mask = mask
         ctx.cin = Cin
         ctx.edges, ctx.groups, ctx.H, ctx.has_shortcut, ctx.trans_inv = edges, groups, H, has_shortcut, ti
-        ctx.has_b1, ctx.has_b2, ctx.has_bs = b1 is not None, b2 is not None, bs is not None
-        ctx.w1_shape = tuple(W1.shape)
+        ctx.params = (W1, b1, W2, b2, Ws, bs)
         ctx.prec_bwd_nt = (PREC_BWD | GEMM_W_PRESPLIT | GEMM_W_FRAG) if bsp else PREC_BWD
         ctx.bsp = bsp
         return out
@@ -1007,15 +1022,8 @@ class EdgeConvBlockFn(torch.autograd.Function):
             _same(x, g)
             dx = torch.empty(N, Cp, dtype=x.dtype, device=dev) if ctx.needs_input_grad[0] else None
             direct = _direct_grad_views(ctx.params)
-            if direct is not None:            # a TrainStep bucket is accepting: write the gradients where the optimizer reads them
-                dW1, db1, dW2, db2, dWs, dbs = direct
-            else:
-                dW1 = torch.empty(ctx.w1_shape, dtype=torch.float32, device=dev)
-                db1 = torch.empty(H, dtype=torch.float32, device=dev) if ctx.has_b1 else None
-                dWs = torch.empty(Cout, Cin, dtype=torch.float32, device=dev) if ctx.has_shortcut else None
-                dbs = torch.empty(Cout, dtype=torch.float32, device=dev) if ctx.has_bs else None
-                dW2 = torch.empty(Cout, H, dtype=torch.float32, device=dev)
-                db2 = torch.empty(Cout, dtype=torch.float32, device=dev) if ctx.has_b2 else None
+            # a TrainStep bucket is accepting: write the gradients where the optimizer reads them; else fresh tensors for autograd
+            dW1, db1, dW2, db2, dWs, dbs = direct if direct is not None else _fresh_grads(ctx.params, dev)
             ws_bytes = lib.stin_edgeconv_block_bwd_workspace_bytes(N, Cp, H, Cout, int(ctx.has_shortcut), groups.B, int(b16))
             ws = torch.empty(ws_bytes, dtype=torch.uint8, device=dev)
             cs = edges.by_src
@@ -1078,13 +1086,7 @@ class EdgeConvBlockFn(torch.autograd.Function):
             dx = gemm_nt(dY, wcatT, precision=ctx.prec_bwd_nt, residual=None if ctx.has_shortcut else g)
             if Cp != Cin:
                 dx = dx[:, :Cin]
-        dev = x.device
-        dW1 = torch.empty(ctx.w1_shape, dtype=torch.float32, device=dev)
-        db1 = torch.empty(H, dtype=torch.float32, device=dev) if ctx.has_b1 else None
-        dWs = torch.empty(Cout, Cin, dtype=torch.float32, device=dev) if ctx.has_shortcut else None
-        dbs = torch.empty(Cout, dtype=torch.float32, device=dev) if ctx.has_bs else None
-        dW2 = torch.empty(Cout, H, dtype=torch.float32, device=dev)
-        db2 = torch.empty(Cout, dtype=torch.float32, device=dev) if ctx.has_b2 else None
+        dW1, db1, dW2, db2, dWs, dbs = _fresh_grads(ctx.params, x.device)
         _call('stin_edgeconv_unpack_grads_f32', _ptr(dwb), _ptr(dw2b), Cin, Cp, H, Cout, int(ctx.has_shortcut),
               int(ctx.trans_inv), _ptr(dW1), _ptr(db1), _ptr(dWs), _ptr(dbs), _ptr(dW2), _ptr(db2), _stream(x))
         if compact and db1 is not None:
@@ -1092,212 +1094,9 @@ class EdgeConvBlockFn(torch.autograd.Function):
         return dx, dW1, db1, dW2, db2, dWs, dbs, None, None, None, None, None, None
 
 
-# ---- a chain of fused blocks of one level in ONE autograd node ------------------------------------------------------------
-USE_CHAIN = True
-_CHAIN_JOB = _lib.STRUCTS['stin_chain_job_t']
-
-
-def chain_eligible(blocks, x, edges_list, groups):
-    """The n blocks can run as one EdgeConvChainFn: all fused EdgeConv + instance-norm blocks of the same width without
-    shortcut (the bottleneck of the network), operands packed by the network's PackSet, saved-mask path available."""
-    if not (USE_CHAIN and USE_BLOCK_CALL and USE_EDGE_MASK and not KernelTimer.per_kernel_path() and len(blocks) >= 2 and x.is_cuda):
-        return False
-    if x.dim() != 2 or x.shape[0] <= 1 or x.dtype not in (torch.float32, torch.bfloat16):
-        return False
-    C = x.shape[1]
-    pad = 8 if x.dtype == torch.bfloat16 else 4
-    if C % pad != 0:
-        return False
-    if not edge_mask_supported(2 * C):
-        return False
-    b16 = x.dtype == torch.bfloat16
-    fsp, bsp = block_split_modes(PREC_FWD, b16, C)
-    packed = [b._prepacked is not None for b in blocks]
-    if any(packed) != all(packed):                                # all operands packed by the network's PackSet, or none
-        return False
-    for b in blocks:
-        pp = b._prepacked
-        if pp is not None and (len(pp) < 7 or pp[6] != b16 or pp[2] != fsp or pp[3] != bsp):
-            return False
-        if (b.dim_in != C or b.dim_out != C or b.unbounded_input or hasattr(b, 'shortcut')
-                or b.first_norm.eps != blocks[0].first_norm.eps):
-            return False
-    return True
-
-
-class EdgeConvChainFn(torch.autograd.Function):
-    """n consecutive GraphResnetBlocks (EdgeConv(mean) + instance norm + ELU + identity residual) of one level as ONE
-    autograd node and one C call per direction (stin_edgeconv_chain_fwd / _bwd: a loop over the whole-block launch
-    sequences, same kernels in the same order -> bit-identical to n EdgeConvBlockFn nodes).  What it removes is host time:
-    n - 1 autograd nodes, 2 (n - 1) foreign calls and ~12 (n - 1) tensor allocations per step (the 9 bottleneck blocks of
-    the 3-D config).  args: x, meta = (edges_list, groups, eps, prec_fwd, prepacked_list, trans_inv_list), then the flat
-    parameters W1, b1, W2, b2 of every block."""
-
-    calls = 0                    # (tests check that the chain path was actually taken)
-
-    @staticmethod
-    def forward(ctx, x, meta, *params):
-        EdgeConvChainFn.calls += 1
-        edges_list, groups, eps, prec_fwd, prepacked, trans_inv = meta
-        n = len(edges_list)
-        lib = _lib.load()
-        x, _ = _mat(x)
-        N, C = x.shape
-        H = 2 * C
-        dev, dt = x.device, x.dtype
-        b16 = dt == torch.bfloat16
-        pad = 8 if b16 else 4
-        B = groups.B
-        Yw = 2 * H
-        fsp, bsp = block_split_modes(prec_fwd, b16, C)
-        # one arena per tensor kind (no views of them are created in here: block i's slices are addressed by pointer)
-        Y = torch.empty(n, N, Yw, dtype=dt, device=dev)
-        hE = torch.empty(n, N, H + pad, dtype=dt, device=dev)
-        agg = torch.empty(n, N, C, dtype=dt, device=dev)
-        outs = torch.empty(max(n - 1, 1), N, C, dtype=dt, device=dev)         # outputs of blocks 0 .. n - 2
-        out = torch.empty(N, C, dtype=dt, device=dev)                         # the chain's output (block n - 1)
-        stats = torch.empty(n, 2, B, C, dtype=torch.float32, device=dev)
-        words = [max(e.n_edges, 1) * (H // 32) for e in edges_list]
-        mask = torch.empty(sum(words), dtype=torch.int32, device=dev)
-        es = x.element_size()
-        ws_bytes = lib.stin_edgeconv_block_fwd_workspace_bytes(C, C, H, C, 0, B)
-        packed = prepacked[0] is not None
-        wts_n = Yw * C + H * C                                                # backward weight operands wcatT | w2T per block
-        wts = ws = None
-        if not packed:                                                        # the block calls run their own pack: own buffers
-            wts = torch.empty(n, wts_n, dtype=torch.float32, device=dev)
-            ws = torch.empty(n, ws_bytes, dtype=torch.uint8, device=dev)
-        st = _CHAIN_JOB
-        blob, moff = [], 0
-        pY, pH, pA, pO, pS, pM = _ptr(Y), _ptr(hE), _ptr(agg), _ptr(outs), _ptr(stats), _ptr(mask)
-        for i in range(n):
-            W1, b1, W2, b2 = params[4 * i:4 * i + 4]
-            pp = prepacked[i]
-            if packed:
-                if pp[2] != fsp or pp[3] != bsp or pp[0].numel() < ws_bytes:
-                    raise RuntimeError('EdgeConvChainFn: prepacked operands do not match this call (stale PackSet)')
-                p_wcatT, p_w2T, p_ws, flag = _ptr(pp[4]), _ptr(pp[5]), _ptr(pp[0]), fsp | BLOCK_PACKED
-            else:
-                p_wcatT = _ptr(wts) + i * wts_n * 4
-                p_w2T, p_ws, flag = p_wcatT + Yw * C * 4, _ptr(ws) + i * ws_bytes, fsp
-            cd = edges_list[i].by_dst
-            o_i = _ptr(out) if i == n - 1 else pO + i * N * C * es
-            blob.append(st.pack(_ptr(W1.contiguous()), _ptr(b1), _ptr(W2.contiguous()), _ptr(b2), p_wcatT, p_w2T, p_ws,
-                                _ptr(cd.rowptr), _ptr(cd.col), 0, 0, 0, 0,
-                                pY + i * N * Yw * es, pH + i * N * (H + pad) * es, pM + moff * 4, pA + i * N * C * es,
-                                pS + (2 * i) * B * C * 4, pS + (2 * i + 1) * B * C * 4, o_i, 0, 0, 0, 0, 0, 0, 0,
-                                int(trans_inv[i]), flag, bsp, int(prec_fwd)))
-            moff += words[i]
-        import ctypes
-        buf = ctypes.create_string_buffer(b''.join(blob), n * st.size)
-        _call('stin_edgeconv_chain_fwd', int(b16), buf, n, _ptr(x), x.stride(0), N, C, C, H, _ptr(groups.ptr_sum), B, _ptr(groups.gid),
-              _ptr(groups.inv_cnt), int(groups.quirk), float(eps), ws_bytes, _stream(x))
-        ctx.save_for_backward(x, Y, hE, agg, outs, stats, mask)
-        ctx.meta = (edges_list, groups, prepacked, trans_inv, words, bsp, wts)
-        ctx.params = params
-        return out
-
-    @staticmethod
-    def backward(ctx, g):
-        x, Y, hE, agg, outs, stats, mask = ctx.saved_tensors
-        edges_list, groups, prepacked, trans_inv, words, bsp, wts = ctx.meta
-        params = ctx.params
-        n = len(edges_list)
-        lib = _lib.load()
-        N, C = x.shape
-        b16 = x.dtype == torch.bfloat16
-        H, Yw, pad, B = 2 * C, 4 * C, (8 if b16 else 4), groups.B
-        wts_n = Yw * C + H * C
-        dev, dt, es = x.device, x.dtype, x.element_size()
-        g, ldg = _mat(g)
-        _same(x, g)
-        need_dx = ctx.needs_input_grad[0]
-        dx = torch.empty(N, C, dtype=dt, device=dev) if need_dx else None
-        scratch = torch.empty(2, N, C, dtype=dt, device=dev)
-        # gradients: straight into an accepting TrainStep bucket (all blocks or none), else fresh tensors handed to autograd
-        direct = []                                        # (all blocks probed before the bucket's bookkeeping changes, as in NetFn)
-        if all(_direct_grad_views(tuple(params[4 * i:4 * i + 4]) + (None, None), dry_run=True) is not None for i in range(n)):
-            direct = [_direct_grad_views(tuple(params[4 * i:4 * i + 4]) + (None, None)) for i in range(n)]
-        if len(direct) != n:
-            direct = []
-            grads = []
-            for i in range(n):
-                W1, b1, W2, b2 = params[4 * i:4 * i + 4]
-                grads += [torch.empty(W1.shape, dtype=torch.float32, device=dev),
-                          torch.empty(H, dtype=torch.float32, device=dev) if b1 is not None else None,
-                          torch.empty(C, H, dtype=torch.float32, device=dev),
-                          torch.empty(C, dtype=torch.float32, device=dev) if b2 is not None else None]
-        ws_bytes = lib.stin_edgeconv_block_bwd_workspace_bytes(N, C, H, C, 0, B, int(b16))
-        ws = torch.empty(n, ws_bytes, dtype=torch.uint8, device=dev)          # every block its own: the side stream reads it later
-        work = float(N) * Yw * C
-        all_params = [p for p in params]
-        use_side = (USE_WGRAD_STREAM and WGRAD_MIN_WORK <= work <= WGRAD_MAX_WORK and WGRAD_DEFER_JOIN and
-                    (bool(direct) or (_plain_autograd_may_defer() and all(
-                        p is None or (p.is_leaf and p.grad is None and not p._backward_hooks and
-                                      not getattr(p, '_post_accumulate_grad_hooks', None)) for p in all_params))))
-        side_stream, evs = 0, [(0, 0)] * n
-        if use_side:
-            side = _wgrad_side(dev)
-            side.hold.append((ws, x, hE, outs, Y, agg, mask, scratch, wts))
-            side_stream = side.stream.cuda_stream
-            evs = [None] * n
-            for i in reversed(range(n)):          # in BACKWARD order: side.last_done must be the event recorded last (block 0's)
-                tri = side.next_events()
-                evs[i] = (tri[1].cuda_event, tri[2].cuda_event)
-            if not direct:
-                for t in grads:
-                    if t is not None:
-                        t.record_stream(side.stream)
-        st = _CHAIN_JOB
-        blob, moff = [], 0
-        pY, pH, pA, pO, pS, pM, pW = _ptr(Y), _ptr(hE), _ptr(agg), _ptr(outs), _ptr(stats), _ptr(mask), _ptr(ws)
-        for i in range(n):
-            pp = prepacked[i]
-            e = edges_list[i]
-            cs = e.by_src
-            if direct:
-                dW1, db1, dW2, db2 = direct[i][:4]
-            else:
-                dW1, db1, dW2, db2 = grads[4 * i:4 * i + 4]
-            if pp is not None:
-                p_wcatT, p_w2T = _ptr(pp[4]), _ptr(pp[5])
-            else:
-                p_wcatT = _ptr(wts) + i * wts_n * 4
-                p_w2T = p_wcatT + Yw * C * 4
-            blob.append(st.pack(0, 0, 0, 0, p_wcatT, p_w2T, 0,
-                                _ptr(e.by_dst.rowptr), 0, _ptr(cs.rowptr), _ptr(cs.col), _ptr(e.xslot), _ptr(e.w_src),
-                                pY + i * N * Yw * es, pH + i * N * (H + pad) * es, pM + moff * 4, pA + i * N * C * es,
-                                pS + (2 * i) * B * C * 4, pS + (2 * i + 1) * B * C * 4, (pO + i * N * C * es) if i < n - 1 else 0,
-                                _ptr(dW1), _ptr(db1), _ptr(dW2), _ptr(db2), pW + i * ws_bytes, evs[i][0], evs[i][1],
-                                int(trans_inv[i]), 0, bsp, 0))
-            moff += words[i]
-        import ctypes
-        buf = ctypes.create_string_buffer(b''.join(blob), n * st.size)
-        _call('stin_edgeconv_chain_bwd', int(b16), buf, n, _ptr(g), ldg, _ptr(x), x.stride(0), N, C, C, H, _ptr(groups.ptr_true), B,
-              _ptr(groups.gid), _ptr(groups.sid if groups.quirk else None), _ptr(groups.inv_cnt), int(PREC_BWD), _ptr(dx), C,
-              _ptr(scratch[0]), _ptr(scratch[1]), ws_bytes, _stream(x), side_stream)
-        if use_side:
-            _wgrad_deferred_join(dev, all_params if not direct else (), () if direct else grads)
-        if direct:
-            sd = _WGRAD_SIDE.get(dev.index if dev.index is not None else torch.cuda.current_device())
-            params[0]._stin_slot[0].block_done(sd.last_done if (sd is not None and sd.hold) else None)
-            return (dx, None) + (None,) * len(params)
-        return (dx, None) + tuple(grads)
-
-
-def edgeconv_chain(x, blocks, edges_list, groups, eps, prec_fwd):
-    params = []
-    for b in blocks:
-        lin1, lin2 = b.first_filter.nn[0], b.first_filter.nn[2]
-        params += [lin1.weight, lin1.bias, lin2.weight, lin2.bias]
-    b16 = x.dtype == torch.bfloat16
-    meta = (list(edges_list), groups, float(eps), int(prec_fwd), [b._prepacked for b in blocks],
-            [trans_inv_mode(b.first_filter.trans_inv, b16, b.first_filter.nn[0].weight.shape[0]) for b in blocks])
-    return EdgeConvChainFn.apply(x, meta, *params)
-
-
 # ---- the graph part of the network in ONE autograd node ----------------------------------------------------------------------
-USE_NET_CALL = os.environ.get('STIN_NET_CALL', '1') != '0'
+USE_NET_CALL = os.environ.get('STIN_NET_CALL', '1') != '0'     # the WHOLE graph part as one node (the model's forward() asks)
+USE_CHAIN = True        # ... else the bottleneck blocks as one node (tests flip the attribute to get the per-block nodes)
 _NET_OP = _lib.STRUCTS['stin_net_op_t']
 OP_BLOCK, OP_POOL_MAX, OP_UNPOOL = _C['STIN_OP_BLOCK'], _C['STIN_OP_POOL_MAX'], _C['STIN_OP_UNPOOL']
 
@@ -1310,7 +1109,7 @@ def net_eligible(steps, x):
     """steps = [('block', GraphResnetBlock, EdgeSet, NormGroups) | ('pool', PoolMap) | ('unpool', PoolMap)] can run as one
     NetFn: fused EdgeConv + instance-norm blocks on the whole-block path (saved ReLU mask available), max pooling, fp32 or
     bf16 storage; operands of every block packed by the network's PackSet or of none."""
-    if not (USE_NET_CALL and USE_BLOCK_CALL and USE_EDGE_MASK and not KernelTimer.per_kernel_path() and x.is_cuda and x.dim() == 2):
+    if not (USE_BLOCK_CALL and USE_EDGE_MASK and not KernelTimer.per_kernel_path() and x.is_cuda and x.dim() == 2):
         return False
     if x.dtype not in (torch.float32, torch.bfloat16) or x.shape[0] <= 1:
         return False
@@ -1352,12 +1151,7 @@ class NetFn(torch.autograd.Function):
         es = x.element_size()
         pad = 8 if b16 else 4
         N0, Cin0 = x.shape
-        Cp0 = (Cin0 + pad - 1) // pad * pad
-        if Cp0 != Cin0:                                          # (the 10-channel network input -> 12; bf16: 16)
-            xp = torch.empty(N0, Cp0, dtype=x.dtype, device=x.device)
-            _call('stin_pad_rows' + sfx, _ptr(x), x.stride(0), N0, Cin0, Cp0, _ptr(xp), _stream(x))   # one launch (F.pad: fill + copy)
-        else:
-            xp = x
+        xp = _pad_rows(x, pad)
         # ---- pass 1: shapes and arena layout
         plan, off, pi = [], 0, 0
         n_rows, width = N0, Cin0
@@ -1438,7 +1232,8 @@ class NetFn(torch.autograd.Function):
         out = torch.empty(n_rows, width, dtype=dt, device=dev)
         base, p_out = _ptr(arena), _ptr(out)
         assert base % 256 == 0
-        # ---- pass 2: the op table
+        # ---- pass 2: the op table.  d['op'] keeps each op's fields (by the names of stin_net_op_t): backward packs them again
+        # with its own on top (stin_net_bwd and the block backward read no forward-only field)
         stc = _NET_OP
         blob = []
         xin, ldx = _ptr(xp), xp.stride(0)
@@ -1452,35 +1247,26 @@ class NetFn(torch.autograd.Function):
                 else:
                     p_wcatT = base + d['oW']
                     p_w2T, p_ws, flag = p_wcatT + d['Yw'] * d['Cp'] * 4, base + d['oWS'], d['fsp']
-                d['p_wcatT'], d['p_w2T'] = p_wcatT, p_w2T
                 g, cd = d['groups'], d['edges'].by_dst
                 H, Cout, B = d['H'], d['Cout'], d['B']
-                d['x'], d['ldx'], d['out'] = xin, ldx, o
-                blob.append(stc.pack(OP_BLOCK, d['Cin'], d['Cp'], H, Cout, int(d['sc']), int(d['ti']), int(d['prec']), flag, d['bsp'], B,
-                                     int(g.quirk), 0, 0, 0, 0, d['eps'], 0,
-                                     d['N'], d['N'], ldx, Cout, 0, d['Yw'], H + pad, d['ws_bytes'], 0,
-                                     xin, o, 0,
-                                     _ptr(W1.contiguous()), _ptr(b1), _ptr(W2.contiguous()), _ptr(b2), _ptr(Ws), _ptr(bs), p_wcatT, p_w2T, p_ws,
-                                     _ptr(cd.rowptr), _ptr(cd.col), 0, 0, 0, 0,
-                                     _ptr(g.ptr_sum), 0, _ptr(g.gid), 0, _ptr(g.inv_cnt),
-                                     base + d['oY'], base + d['oH'], (base + d['oM']) if need_grad else 0, base + d['oA'], base + d['oS'],
-                                     base + d['oS'] + B * Cout * 4, 0, 0,
-                                     0, 0, 0, 0, 0, 0, 0, 0, 0,
-                                     *KernelTimer.edge_events('stin_edge_relu_mean_fwd' + sfx, (d['N'], d['edges'].n_edges, H))))
+                d['op'] = dict(kind=OP_BLOCK, Cin=d['Cin'], Cp=d['Cp'], H=H, Cout=Cout, has_shortcut=int(d['sc']), trans_inv=int(d['ti']),
+                               prec_fwd=int(d['prec']), fwd_split=flag, bwd_split=d['bsp'], B=B, slice_quirk=int(g.quirk), eps=d['eps'],
+                               n_out=d['N'], n_in=d['N'], ldx=ldx, ldo=Cout, ldy=d['Yw'], ldh=H + pad, fwd_ws_bytes=d['ws_bytes'],
+                               x=xin, out=o, W1=_ptr(W1.contiguous()), b1=_ptr(b1), W2=_ptr(W2.contiguous()), b2=_ptr(b2), Ws=_ptr(Ws),
+                               bs=_ptr(bs), wcatT=p_wcatT, w2T=p_w2T, fwd_ws=p_ws, rowptr_dst=_ptr(cd.rowptr), col_dst=_ptr(cd.col),
+                               ptr_sum=_ptr(g.ptr_sum), gid=_ptr(g.gid), inv_cnt=_ptr(g.inv_cnt), Y=base + d['oY'], hE=base + d['oH'],
+                               mask=(base + d['oM']) if need_grad else 0, agg=base + d['oA'], mean=base + d['oS'],
+                               rstd=base + d['oS'] + B * Cout * 4)
+                ev0, ev1 = KernelTimer.edge_events('stin_edge_relu_mean_fwd' + sfx, (d['N'], d['edges'].n_edges, H))
+                blob.append(stc.pack(**d['op'], ev_edge0=ev0, ev_edge1=ev1))
                 xin, ldx = o, Cout
             else:
                 pool, C = d['pool'], d['C']
-                d['x'], d['ldx'], d['out'] = xin, ldx, o
                 ch = pool.children
-                blob.append(stc.pack(d['kind'], C, C, 0, C, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0.0, 0,
-                                     d['n_out'], d['n_in'], ldx, C, 0, 0, 0, 0, 0,
-                                     xin, o, 0,
-                                     0, 0, 0, 0, 0, 0, 0, 0, 0,
-                                     _ptr(ch.rowptr), _ptr(ch.col), 0, 0, 0, 0,
-                                     0, 0, 0, 0, 0,
-                                     0, 0, 0, 0, 0, 0,
-                                     (base + d['oArg']) if d['kind'] == OP_POOL_MAX else 0, _ptr(pool.trace),
-                                     0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0))
+                d['op'] = dict(kind=d['kind'], Cin=C, Cp=C, Cout=C, n_out=d['n_out'], n_in=d['n_in'], ldx=ldx, ldo=C, x=xin, out=o,
+                               rowptr_dst=_ptr(ch.rowptr), col_dst=_ptr(ch.col),
+                               arg=(base + d['oArg']) if d['kind'] == OP_POOL_MAX else 0, trace=_ptr(pool.trace))
+                blob.append(stc.pack(**d['op']))
                 xin, ldx = o, C
         import ctypes
         buf = ctypes.create_string_buffer(b''.join(blob), len(plan) * stc.size)
@@ -1495,17 +1281,15 @@ class NetFn(torch.autograd.Function):
 
     @staticmethod
     def backward(ctx, g):
-        xp, arena = ctx.saved_tensors
+        xp, arena = ctx.saved_tensors                    # (the ops' pointers go into the arena)
         plan, params = ctx.plan, ctx.params
         lib = _lib.load()
         dev, dt = xp.device, xp.dtype
         b16 = dt == torch.bfloat16
         sfx = '_bf16' if b16 else '_f32'
         es = xp.element_size()
-        pad = 8 if b16 else 4
         g, ldg = _mat(g)
         _same(xp, g)
-        base = _ptr(arena)
         need_dx = ctx.needs_input_grad[0]
         blocks = [d for d in plan if d['kind'] == OP_BLOCK]
         # gradients: straight into an accepting TrainStep bucket (all blocks or none), else fresh tensors handed to autograd
@@ -1517,16 +1301,7 @@ class NetFn(torch.autograd.Function):
         grads = None
         if len(direct) != len(blocks):
             direct = []
-            grads = []
-            for d in blocks:
-                W1, b1, W2, b2, Ws, bs = d['params']
-                H, Cout = d['H'], d['Cout']
-                grads += [torch.empty(W1.shape, dtype=torch.float32, device=dev),
-                          torch.empty(H, dtype=torch.float32, device=dev) if b1 is not None else None,
-                          torch.empty(Cout, H, dtype=torch.float32, device=dev),
-                          torch.empty(Cout, dtype=torch.float32, device=dev) if b2 is not None else None,
-                          torch.empty(Ws.shape, dtype=torch.float32, device=dev) if Ws is not None else None,
-                          torch.empty(Cout, dtype=torch.float32, device=dev) if bs is not None else None]
+            grads = [t for d in blocks for t in _fresh_grads(d['params'], dev)]
         # scratch: input gradients ping-pong between two buffers of the largest size; every block its own backward workspace
         # (the side stream reads it after this call has returned)
         dx_bytes, ws_off, off = 0, [], 0
@@ -1549,10 +1324,7 @@ class NetFn(torch.autograd.Function):
             dx0 = torch.empty(d0['N'] if d0['kind'] == OP_BLOCK else d0['n_in'], d0['Cp'] if d0['kind'] == OP_BLOCK else d0['C'],
                               dtype=dt, device=dev)
         all_params = [p for d in blocks for p in d['params']]
-        side_ok = (USE_WGRAD_STREAM and WGRAD_DEFER_JOIN and
-                   (bool(direct) or (_plain_autograd_may_defer() and all(
-                       p is None or (p.is_leaf and p.grad is None and not p._backward_hooks and
-                                     not getattr(p, '_post_accumulate_grad_hooks', None)) for p in all_params))))
+        side_ok = USE_WGRAD_STREAM and _join_deferrable(all_params, direct)
         use = [side_ok and WGRAD_MIN_WORK <= float(d['N']) * d['Yw'] * d['Cp'] <= WGRAD_MAX_WORK for d in blocks]
         side_stream, any_side = 0, any(use)
         evs = [(0, 0)] * len(blocks)
@@ -1596,35 +1368,18 @@ class NetFn(torch.autograd.Function):
             if d['kind'] == OP_BLOCK:
                 e, gr = d['edges'], d['groups']
                 cs = e.by_src
-                H, Cout, B = d['H'], d['Cout'], d['B']
                 gs = direct[bi] if direct else grads[6 * bi:6 * bi + 6]
                 ev_dy, ev_done = evs[bi]
-                blob.append(stc.pack(OP_BLOCK, d['Cin'], d['Cp'], H, Cout, int(d['sc']), int(d['ti']), 0, 0, d['bsp'], B,
-                                     int(gr.quirk), int(use[bi]), 0, 0, 0, d['eps'], 0,
-                                     d['N'], d['N'], d['ldx'], Cout, d['Cp'], d['Yw'], H + pad, 0, d['bwd_ws_bytes'],
-                                     d['x'], d['out'], p_dx,
-                                     0, 0, 0, 0, 0, 0, d['p_wcatT'], d['p_w2T'], 0,
-                                     _ptr(e.by_dst.rowptr), 0, _ptr(cs.rowptr), _ptr(cs.col), _ptr(e.xslot), _ptr(e.w_src),
-                                     0, _ptr(gr.ptr_true), _ptr(gr.gid), _ptr(gr.sid if gr.quirk else None), _ptr(gr.inv_cnt),
-                                     base + d['oY'], base + d['oH'], base + d['oM'], base + d['oA'], base + d['oS'],
-                                     base + d['oS'] + B * Cout * 4, 0, 0,
-                                     _ptr(gs[0]), _ptr(gs[1]), _ptr(gs[2]), _ptr(gs[3]), _ptr(gs[4]), _ptr(gs[5]),
-                                     p_ws + ws_off[bi], ev_dy, ev_done,
-                                     *KernelTimer.edge_events('stin_edge_relu_mean_bwd_mask' + ('_ti' if d['ti'] == TI_MODE_COMPACT else '') + sfx,
-                                                              (d['N'], e.n_edges, H))))
+                ev0, ev1 = KernelTimer.edge_events('stin_edge_relu_mean_bwd_mask' + ('_ti' if d['ti'] == TI_MODE_COMPACT else '') + sfx,
+                                                   (d['N'], e.n_edges, d['H']))
+                blob.append(stc.pack(**d['op'], use_side=int(use[bi]), lddx=d['Cp'], bwd_ws_bytes=d['bwd_ws_bytes'], dx=p_dx,
+                                     rowptr_src=_ptr(cs.rowptr), col_src=_ptr(cs.col), xslot=_ptr(e.xslot), w_src=_ptr(e.w_src),
+                                     ptr_true=_ptr(gr.ptr_true), sid=_ptr(gr.sid if gr.quirk else None),
+                                     dW1=_ptr(gs[0]), db1=_ptr(gs[1]), dW2=_ptr(gs[2]), db2=_ptr(gs[3]), dWs=_ptr(gs[4]), dbs=_ptr(gs[5]),
+                                     bwd_ws=p_ws + ws_off[bi], ev_dy=ev_dy, ev_done=ev_done, ev_edge0=ev0, ev_edge1=ev1))
                 bi += 1
             else:
-                pool, C = d['pool'], d['C']
-                ch = pool.children
-                blob.append(stc.pack(d['kind'], C, C, 0, C, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0.0, 0,
-                                     d['n_out'], d['n_in'], d['ldx'], C, C, 0, 0, 0, 0,
-                                     d['x'], d['out'], p_dx,
-                                     0, 0, 0, 0, 0, 0, 0, 0, 0,
-                                     _ptr(ch.rowptr), _ptr(ch.col), 0, 0, 0, 0,
-                                     0, 0, 0, 0, 0,
-                                     0, 0, 0, 0, 0, 0,
-                                     (base + d['oArg']) if d['kind'] == OP_POOL_MAX else 0, _ptr(pool.trace),
-                                     0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0))
+                blob.append(stc.pack(**d['op'], lddx=d['C'], dx=p_dx))
         import ctypes
         buf = ctypes.create_string_buffer(b''.join(blob), len(plan) * stc.size)
         _call('stin_net_bwd', int(b16), buf, len(plan), _ptr(g), ldg, int(PREC_BWD), _stream(xp), side_stream)

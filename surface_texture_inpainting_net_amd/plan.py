@@ -136,8 +136,9 @@ class PlanJobs:
 
     def add(self, a, b, E, N, b_limit, pair, rowptr0, col0, perm0, inv_deg0, rowptr1=None, col1=None, xslot=None, w_src=None,
             narrow_out=None):
-        self.blobs.append(_JOB.pack(_ptr(a), _ptr(b), E, N, b_limit, _ptr(rowptr0), _ptr(col0), _ptr(perm0), _ptr(inv_deg0),
-                                    _ptr(rowptr1), _ptr(col1), _ptr(xslot), _ptr(w_src), _ptr(narrow_out), int(pair), 0))
+        self.blobs.append(_JOB.pack(a=_ptr(a), b=_ptr(b), E=E, N=N, b_limit=b_limit, rowptr0=_ptr(rowptr0), col0=_ptr(col0),
+                                    perm0=_ptr(perm0), inv_deg0=_ptr(inv_deg0), rowptr1=_ptr(rowptr1), col1=_ptr(col1),
+                                    xslot=_ptr(xslot), w_src=_ptr(w_src), narrow_out=_ptr(narrow_out), pair=int(pair)))
         self.total_e += E
         self.total_cnt += (2 if pair else 1) * N + 1
         self.keep.append((a, b))                 # contiguous copies of the index rows must outlive the launches
@@ -406,7 +407,7 @@ class GraphPlan:
                 if lvl > 0:
                     tr = s['hierarchy_trace_index_%d' % lvl].contiguous()
                     keep.append(tr)
-                blob.append(st.pack(n, _ptr(tr), _ptr(ranks[lvl]), _ptr(order0) if lvl == 0 else 0))
+                blob.append(st.pack(n=n, trace=_ptr(tr), rank=_ptr(ranks[lvl]), order=_ptr(order0) if lvl == 0 else 0))
             buf = ctypes.create_string_buffer(b''.join(blob), len(blob) * st.size)
             _lib.check(lib.stin_vertex_order_f32(s.x.data_ptr() + 4 * a, s.x.stride(0), buf, len(sizes), _ptr(ws), ws_bytes, _stream(ws)),
                        'stin_vertex_order_f32')
@@ -459,15 +460,15 @@ class GraphPlan:
             rank = self._ranks[level]
             if kind == 'e':
                 out = torch.empty_like(t)
-                blobs.append(st.pack(_ptr(t), t.numel(), _ptr(rank), self.level_sizes[level], _ptr(out), 0, 0, 0))
+                blobs.append(st.pack(ids=_ptr(t), n=t.numel(), rank=_ptr(rank), limit=self.level_sizes[level], out=_ptr(out)))
                 outs.append(out)
             else:
                 nf = t.numel()
                 coarse_new = torch.empty(max(nf, 1), dtype=torch.int64, device=self.device)[:nf]
                 fine_new = torch.empty(max(nf, 1), dtype=torch.int64, device=self.device)[:nf]
                 trace_new = torch.empty(max(nf, 1), dtype=torch.int32, device=self.device)[:nf]
-                blobs.append(st.pack(_ptr(t), nf, _ptr(rank), self.level_sizes[level], _ptr(coarse_new), _ptr(self._ranks[level - 1]),
-                                     _ptr(fine_new), _ptr(trace_new)))
+                blobs.append(st.pack(ids=_ptr(t), n=nf, rank=_ptr(rank), limit=self.level_sizes[level], out=_ptr(coarse_new),
+                                     rank_fine=_ptr(self._ranks[level - 1]), fine_out=_ptr(fine_new), trace_out=_ptr(trace_new)))
                 outs.append((coarse_new, fine_new, trace_new))
         for i in range(0, len(blobs), 16):
             chunk = blobs[i:i + 16]

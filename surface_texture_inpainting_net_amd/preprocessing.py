@@ -264,7 +264,8 @@ def circle_masks(edge_index, num_nodes, radius=16, frac_masked_vertices=0.25, nu
 
 # ------------------------------------------------------------------------------------------------------------- training crops
 MIN_NUM_MAXIMALLY_DECIMATED_VERTS = 50      # preprocessing/crop_training_samples.py:24
-_SEG_WORDS = _lib.STRUCTS['stin_crop_seg_t'].size // 8         # int64 words of a stin_crop_seg_t
+_SEG = _lib.STRUCTS['stin_crop_seg_t']
+_SEG_WORDS = _SEG.size // 8                                      # int64 words of a stin_crop_seg_t
 _SEG_VERTICES, _SEG_EDGES, _SEG_DILATED, _SEG_OCCURS, _SEG_TRACE = (_lib.CONSTANTS[n] for n in (
     'STIN_CROP_VERTICES', 'STIN_CROP_EDGES', 'STIN_CROP_DILATED', 'STIN_CROP_OCCURS', 'STIN_CROP_TRACE'))
 
@@ -385,11 +386,11 @@ def _crop_chunk(saved, boxes, pooled, reference_dilated_labels, min_coarsest):
         raise ValueError('too many crops for one pass')           # (crop_scene splits the crop list before this can happen)
 
     def table():
-        t = np.zeros((n_segs, _SEG_WORDS), dtype=np.int64)
-        for i, r in enumerate(rows):
-            t[i, :8] = (r['kind'], r['level'], r['vseg'], r['aux'], r['n'], r['base'], r['width'], r['ibase'])
-            t[i, 8:13] = [0 if r[k] is None else r[k].data_ptr() for k in ('src', 'out', 'ids', 'p0', 'p1')]
-        return torch.from_numpy(t).to(dev)
+        ptr = lambda t: 0 if t is None else t.data_ptr()
+        blob = b''.join(_SEG.pack(kind=r['kind'], level=r['level'], vseg=r['vseg'], aux=r['aux'], n=r['n'], base=r['base'],
+                                  width=r['width'], ibase=r['ibase'], src=ptr(r['src']), out=ptr(r['out']), ids_out=ptr(r['ids']),
+                                  p0=ptr(r['p0']), p1=ptr(r['p1'])) for r in rows)
+        return torch.from_numpy(np.frombuffer(blob, dtype=np.int64).reshape(n_segs, _SEG_WORDS).copy()).to(dev)
 
     stream = _stream(verts[0])
     boxes_d = torch.from_numpy(np.ascontiguousarray(boxes, dtype=np.float64)).to(dev)

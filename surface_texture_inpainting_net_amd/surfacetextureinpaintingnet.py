@@ -334,10 +334,12 @@ class SurfaceTextureInpaintingNet(nn.Module):
             out = blk(out, plan.edges('hierarchy_edge_index_%d' % level, level), self._norm_arg(plan, level))
         last = num_levels - 1
         bn = list(self.bottleneck_blocks)
-        if (self.norm is M.FastInstanceNorm and bn and all(isinstance(b.first_filter, M.EdgeConv) for b in bn)
-                and SF.chain_eligible(bn, out, bn_edges, None)):
-            # the whole bottleneck as ONE autograd node / one foreign call per direction (functional.EdgeConvChainFn)
-            out = SF.edgeconv_chain(out, bn, bn_edges, self._norm_arg(plan, last), bn[0].first_norm.eps, SF.PREC_FWD)
+        fused = self.norm is M.FastInstanceNorm and all(isinstance(b.first_filter, M.EdgeConv) and
+                                                        isinstance(b.first_norm, M.FastInstanceNorm) for b in bn)
+        bn_steps = [('block', blk, edges, self._norm_arg(plan, last)) for blk, edges in zip(bn, bn_edges)] if fused else []
+        if SF.USE_CHAIN and len(bn_steps) >= 2 and SF.net_eligible(bn_steps, out):
+            # the whole bottleneck as ONE autograd node / one foreign call per direction (functional.NetFn on the block ops alone)
+            out = SF.run_net(out, bn_steps)
         else:
             for blk, edges in zip(bn, bn_edges):
                 out = blk(out, edges, self._norm_arg(plan, last))
@@ -373,7 +375,7 @@ class SurfaceTextureInpaintingNet(nn.Module):
                 key = 'hierarchy_edge_index_{}'.format(last)
             bn_edges.append(e0 if last == 0 and self.dilations[i] <= 1 else plan.edges(key, last))
         steps = self._net_steps(plan, e0, bn_edges, num_levels)
-        if steps is not None and SF.net_eligible(steps, out):
+        if SF.USE_NET_CALL and steps is not None and SF.net_eligible(steps, out):
             # the whole graph part as ONE autograd node / one foreign call per direction (functional.NetFn)
             out = SF.run_net(out, steps)
         else:

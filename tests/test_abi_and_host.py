@@ -64,7 +64,7 @@ def test_longest_prototype_is_read_argument_by_argument():
 def test_struct_layouts_have_the_sizes_the_c_side_asserts():
     """The same literals as the static_asserts of csrc/stin_common.h."""
     sizes = {'stin_plan_job_t': 120, 'stin_order_level_t': 32, 'stin_relabel_job_t': 64, 'stin_pack_job_t': 112,
-             'stin_chain_job_t': 232, 'stin_net_op_t': 480, 'stin_crop_seg_t': 128}
+             'stin_net_op_t': 480, 'stin_crop_seg_t': 128}
     assert {k: v.size for k, v in _lib.STRUCTS.items()} == sizes
     common = open(os.path.join(ROOT, 'surface_texture_inpainting_net_amd', 'csrc', 'stin_common.h')).read()
     for name, size in sizes.items():
@@ -76,7 +76,7 @@ def test_struct_layouts_have_the_sizes_the_c_side_asserts():
 
 def test_constants_come_from_the_header():
     c = _lib.CONSTANTS
-    assert c['STIN_E_WORKSPACE'] == -4 and c['STIN_E_NULL'] == -1 and c['STIN_OK'] == 0 and c['STIN_VERSION'] == 100
+    assert c['STIN_E_WORKSPACE'] == -4 and c['STIN_E_NULL'] == -1 and c['STIN_OK'] == 0 and c['STIN_VERSION'] == 101
     assert c['STIN_GEMM_W_FRAG'] == 0x400 and c['STIN_BLOCK_PACKED'] == 0x800 and c['STIN_GEMM_F16X3'] == 4
     assert c['STIN_SEG_MAX_CLASSES'] == 128 and c['STIN_CROP_TRACE'] == 4 and c['STIN_PLAN_MAX_JOBS'] == 16
     assert all(k.startswith('STIN_') and isinstance(v, int) for k, v in c.items()) and 'STIN_HIP_H' not in c
@@ -135,6 +135,79 @@ def test_header_reader_is_strict():
         _abi.read_header(os.path.join(ROOT, 'include', 'nope.h'))
 
 
+def test_records_pack_by_field_name_only():
+    import struct
+    from surface_texture_inpainting_net_amd import _abi
+    job = _abi.parse_header(_SMALL_HEADER)[1]['stin_job_t']
+    assert job.fields == ('a', 'b', 'n', 'k', 'reserved') and job.size == 40
+    assert job.pack(a=1, n=(2, 3), k=4) == struct.pack('<QQqqii', 1, 0, 2, 3, 4, 0)
+    assert job.pack() == bytes(40)
+    with pytest.raises(_lib.StinLibraryError, match=r'stin_job_t.*\bm\b'):
+        job.pack(a=1, m=2)                                                      # an unknown field: record and field are named
+    with pytest.raises(_lib.StinLibraryError, match='stin_job_t'):
+        job.pack(n=(2, 3, 4))                                                   # an array field takes exactly its length
+    with pytest.raises(_lib.StinLibraryError, match='stin_job_t'):
+        job.pack(n=2)
+    with pytest.raises(TypeError):
+        job.pack(1, 0, 2, 3, 4, 0)                                              # there is no positional pack
+    with pytest.raises(_lib.StinLibraryError, match=r':11: '):
+        _abi.parse_header(_SMALL_HEADER.replace('int32_t k, reserved;', 'int32_t a, reserved;'))      # a second field `a`
+
+
+def test_net_op_field_names_sit_where_the_header_puts_them():
+    """Positions counted by hand in include/stin_hip.h."""
+    import struct
+    op = _lib.STRUCTS['stin_net_op_t']
+    f = op.fields
+    assert len(f) == 69 and f[0] == 'kind' and f[16] == 'eps' and f[18] == 'n_out' and f[27] == 'x' and f[-1] == 'ev_edge1'
+    assert f.index('trace') == 57
+    row = [0] * 69
+    row[0], row[16], row[57] = 2, 0.5, 7
+    assert op.pack(kind=2, eps=0.5, trace=7) == struct.pack(op.format, *row)
+
+
+def test_named_packs_equal_the_positional_argument_lists():
+    """A block op, a pool op and a plan job as the call sites name them, against the argument lists the call sites passed by
+    POSITION before the records were packed by name (every value distinct).  The one place where positions are written down: a
+    reordered header fails here."""
+    import struct
+    op, job = _lib.STRUCTS['stin_net_op_t'], _lib.STRUCTS['stin_plan_job_t']
+    block = (0, 10, 12, 128, 64, 1, 2, 4, 0xC04, 0x402, 3, 1, 1, 0, 0, 0, 1.5e-5, 0,
+             5000, 5001, 13, 65, 14, 321, 132, 4096, 8192,
+             0x1000, 0x1100, 0x1200,
+             0x2000, 0x2100, 0x2200, 0x2300, 0x2400, 0x2500, 0x2600, 0x2700, 0x2800,
+             0x3000, 0x3100, 0x3200, 0x3300, 0x3400, 0x3500,
+             0x4000, 0x4100, 0x4200, 0x4300, 0x4400,
+             0x5000, 0x5100, 0x5200, 0x5300, 0x5400, 0x5500, 0, 0,
+             0x6000, 0x6100, 0x6200, 0x6300, 0x6400, 0x6500, 0x6600, 0x6700, 0x6800, 0x6900, 0x6A00)
+    assert op.pack(kind=0, Cin=10, Cp=12, H=128, Cout=64, has_shortcut=1, trans_inv=2, prec_fwd=4, fwd_split=0xC04, bwd_split=0x402,
+                   B=3, slice_quirk=1, use_side=1, eps=1.5e-5, n_out=5000, n_in=5001, ldx=13, ldo=65, lddx=14, ldy=321, ldh=132,
+                   fwd_ws_bytes=4096, bwd_ws_bytes=8192, x=0x1000, out=0x1100, dx=0x1200, W1=0x2000, b1=0x2100, W2=0x2200,
+                   b2=0x2300, Ws=0x2400, bs=0x2500, wcatT=0x2600, w2T=0x2700, fwd_ws=0x2800, rowptr_dst=0x3000, col_dst=0x3100,
+                   rowptr_src=0x3200, col_src=0x3300, xslot=0x3400, w_src=0x3500, ptr_sum=0x4000, ptr_true=0x4100, gid=0x4200,
+                   sid=0x4300, inv_cnt=0x4400, Y=0x5000, hE=0x5100, mask=0x5200, agg=0x5300, mean=0x5400, rstd=0x5500,
+                   dW1=0x6000, db1=0x6100, dW2=0x6200, db2=0x6300, dWs=0x6400, dbs=0x6500, bwd_ws=0x6600, ev_dy=0x6700,
+                   ev_done=0x6800, ev_edge0=0x6900, ev_edge1=0x6A00) == struct.pack(op.format, *block)
+    pool = (1, 256, 256, 0, 256, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0.0, 0,
+            1250, 5000, 257, 258, 259, 0, 0, 0, 0,
+            0x1000, 0x1100, 0x1200,
+            0, 0, 0, 0, 0, 0, 0, 0, 0,
+            0x3000, 0x3100, 0, 0, 0, 0,
+            0, 0, 0, 0, 0,
+            0, 0, 0, 0, 0, 0,
+            0x5600, 0x5700,
+            0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0)
+    assert op.pack(kind=1, Cin=256, Cp=256, Cout=256, n_out=1250, n_in=5000, ldx=257, ldo=258, lddx=259, x=0x1000, out=0x1100,
+                   dx=0x1200, rowptr_dst=0x3000, col_dst=0x3100, arg=0x5600, trace=0x5700) == struct.pack(op.format, *pool)
+    plan = (0x100, 0x200, 30000, 5000, 4999, 0x300, 0x400, 0x500, 0x600, 0x700, 0x800, 0x900, 0xA00, 0xB00, 1, 0)
+    assert job.pack(a=0x100, b=0x200, E=30000, N=5000, b_limit=4999, rowptr0=0x300, col0=0x400, perm0=0x500, inv_deg0=0x600,
+                    rowptr1=0x700, col1=0x800, xslot=0x900, w_src=0xA00, narrow_out=0xB00, pair=1) == struct.pack(job.format, *plan)
+
+
+def test_the_header_declares_no_chain_entry_point():
+    assert not [n for n in list(_lib.SIGNATURES) + list(_lib.STRUCTS) if 'chain' in n]
+
+
 def test_no_struct_format_is_typed_by_hand():
     """Record layouts come from STRUCTS (the header), never from a format string in the package."""
     pkg = os.path.join(ROOT, 'surface_texture_inpainting_net_amd')
@@ -148,7 +221,7 @@ def test_no_struct_format_is_typed_by_hand():
 
 def test_library_host_only_entry_points():
     lib = _lib.load()                       # no GPU needed for these calls
-    assert lib.stin_version() == 100
+    assert lib.stin_version() == 101
     assert lib.stin_error_string(0) == b'ok'
     assert b'workspace' in lib.stin_error_string(-4)
     assert lib.stin_colreduce_workspace_bytes(64, 1) >= 1024 * 2 * 64 * 8

@@ -1494,7 +1494,7 @@ def test_block_call_equals_per_kernel_path_bitwise(batched, dtype):
 @pytest.mark.parametrize('dtype', ['f32', 'bf16'])
 @pytest.mark.parametrize('batched', [False, True])
 def test_bottleneck_chain_equals_per_block_nodes_bitwise(batched, dtype):
-    """functional.EdgeConvChainFn (the bottleneck blocks as ONE autograd node, stin_edgeconv_chain_fwd / _bwd) only loops
+    """The bottleneck blocks as ONE autograd node (functional.NetFn on the block ops alone, stin_net_fwd / _bwd) only loop
     over the whole-block launch sequences: outputs, input gradient and every parameter gradient equal the per-block
     autograd nodes bit for bit - plain autograd and the TrainStep bucket route, single graph and a batch of unequal crops."""
     from surface_texture_inpainting_net_amd.data import collate
@@ -1528,10 +1528,11 @@ def test_bottleneck_chain_equals_per_block_nodes_bitwise(batched, dtype):
         finally:
             SF.USE_CHAIN, SF.USE_NET_CALL = old, old_net
 
+    before = SF.NetFn.calls
     want = run(False)
-    before = SF.EdgeConvChainFn.calls
+    assert SF.NetFn.calls == before, 'the reference run is made of per-block nodes'
     got = run(True)
-    assert SF.EdgeConvChainFn.calls == before + 4, 'the chain path must have been taken (1 plain + 3 TrainStep forwards)'
+    assert SF.NetFn.calls == before + 4, 'the chain path must have been taken (1 plain + 3 TrainStep forwards)'
     assert len(want) == len(got)
     for i, (a, b) in enumerate(zip(got, want)):
         assert torch.equal(a, b), i
