@@ -33,7 +33,7 @@
 extern "C" {
 #endif
 
-#define STIN_VERSION 101           /* major*10000 + minor*100 + patch */
+#define STIN_VERSION 102           /* major*10000 + minor*100 + patch */
 
 #define STIN_OK 0
 #define STIN_E_NULL (-1)           /* required pointer is NULL */
@@ -43,7 +43,7 @@ extern "C" {
 #define STIN_E_UNSUPPORTED (-5)    /* shape outside what this build supports */
 
 typedef void* stin_stream_t;
-typedef void* stin_event_t;  /* a hipEvent_t owned by the caller (only stin_edgeconv_block_bwd's optional side stream uses events) */
+typedef void* stin_event_t;  /* a hipEvent_t owned by the caller (only stin_net_bwd's optional side stream and timing brackets use events) */
 /* bf16 STORAGE variants (*_bf16): the same operation on row-major bfloat16 matrices (raw 16-bit patterns, the
  * upper half of an fp32).  Every kernel widens to fp32 on load, computes and accumulates in fp32 and rounds to
  * nearest-even on store; statistics, weights, biases, index plans and weight gradients stay fp32.  Halves the HBM
@@ -540,7 +540,7 @@ int stin_concat_unpool_f32(const float* skip, int64_t ld_skip, const float* coar
 /* pack_many: the pack of EVERY block of a network in one launch.  `jobs_device` = n_jobs records in DEVICE memory (the
  * arguments of stin_edgeconv_pack_f32 as a struct; written once per model - the pointers do not change from step to step),
  * max_elems = max over the jobs of Yw * Cp + H * Cout.  The same argument rules as stin_edgeconv_pack_f32 apply per job
- * (not re-checked on the device).  stin_edgeconv_block_fwd then takes STIN_BLOCK_PACKED in fwd_split. */
+ * (not re-checked on the device).  A block op of stin_net_fwd then takes STIN_BLOCK_PACKED in fwd_split. */
 typedef struct stin_pack_job {
     const float *W1, *b1, *Ws, *bs, *W2;
     float *wcat, *bcat, *wcatT, *w2T, *w2s;
@@ -732,73 +732,52 @@ int stin_linear_tanh_bwd_bf16(const float* g, const float* y, const stin_bf16_t*
                               size_t workspace_bytes, stin_stream_t stream);
 
 /* ------------------------------------------------------ whole-block launch sequences --
- * One GraphResnetBlock (EdgeConv(mean) -> instance norm -> ELU -> + residual,
- * models/surfacetextureinpaintingnet.py:507-521) per call: these functions only ENQUEUE the entry points above in the
- * order of the fused block (pack -> Y GEMM -> edge stage -> agg GEMM -> moments -> norm/ELU/residual; and its
- * backward), so the arithmetic is identical to calling them one by one - what they remove is ~9 / ~16 host-side
- * foreign calls per block and direction.  storage: 0 = fp32 rows, 1 = bf16 rows (x, Y, hE, agg, out, g, dx).
- * Fast-path precondition (callers fall back to the individual entry points otherwise): H supports the saved ReLU mask.
- * slice_quirk != 0 (fwd) / sid != NULL (bwd): the reference's linspace-slice statistics for batches of unequal graphs
- * (fastinstancenorm.py:53-82) - sums over the `ptr_sum` slices, centring through gid: two-pass statistics forward, the
- * extra COEF_XC reduction backward; ptr_true are the true per-graph row ranges.
- *   fwd: x [N, Cp] (input zero-padded to Cp columns), reference-layout parameters, destination CSR, norm groups
- *        (ptr_sum/gid may be NULL for one graph; inv_cnt [B]); writes what backward needs - wcatT [Cp, Yw], w2T [H, Cout]
+ * The graph part of the network - or any part of it, down to ONE block - in one call per direction: every fused
+ * EdgeConv + instance-norm block and the pool / unpool steps between them, in network order
+ * (models/surfacetextureinpaintingnet.py:404-455: input blocks, `for` over the encoder levels - `_pooling` :384-386 then a
+ * block -, the bottleneck blocks, `for` over the decoder levels - `_unpooling` :390-391 then a block -, the output blocks).
+ * stin_net_fwd / stin_net_bwd only ENQUEUE the entry points above with the per-op pointers of a HOST op array, so the
+ * arithmetic is identical to calling them one by one (bit-identical to the per-kernel calls) - what they remove is host
+ * time: ~9 / ~16 foreign calls per block and direction and one autograd node per op (the launch-bound sizes: 20 k-vertex
+ * crops, the 8-crop batches).  storage: 0 = fp32 rows, 1 = bf16 rows (x, Y, hE, agg, out, g, dx).
+ *   op i reads `x` (ops[0]: the input padded to Cp channels; else ops[i - 1].out) and writes `out`;
+ *   bwd walks the ops in reverse: the gradient of op i's output is ops[i + 1].dx (the call's `g` for the last op), op i writes
+ *   its input gradient to `dx` (NULL for ops[0] when the input needs none).
+ *   STIN_OP_BLOCK: one GraphResnetBlock (EdgeConv(mean) -> instance norm -> ELU -> + residual,
+ *     models/surfacetextureinpaintingnet.py:507-521) over n_out = n_in = N rows, in the order of the fused block:
+ *     pack -> Y GEMM -> edge stage -> agg GEMM -> moments -> norm / ELU / residual; and its backward.
+ *     Precondition (callers use the individual entry points otherwise): H supports the saved ReLU mask.
+ *     fwd: x [N, Cp] (input zero-padded to Cp columns), reference-layout parameters W1 .. bs, destination CSR, norm groups
+ *        (ptr_sum / gid may be NULL for one graph; inv_cnt [B]); writes what backward needs - wcatT [Cp, Yw], w2T [H, Cout]
  *        (fp32 or pre-split per bwd_split), Y [N, Yw], hE [N, H + pad] (column H = [deg > 0]), mask [E * H / 32],
- *        agg [N, Cout], mean / rstd [B, Cout] - and out [N, Cout].  Yw = 2 H (+ Cout with a shortcut).
+ *        agg [N, Cout], mean / rstd [B, Cout] - and out [N, Cout].  Yw = 2 H (+ Cout with a shortcut); H (+ Cout) when
+ *        trans_inv == STIN_TI_COMPACT.  fwd_ws: stin_edgeconv_block_fwd_workspace_bytes.
  *        mask may be NULL for a forward nobody differentiates (the reference's validation loop,
  *        trainers/inpainting3d_trainer.py:204-263: model(data) under torch.no_grad()): same kernels, same rows bit for
  *        bit, the E * H / 8 mask bytes per block are not written.
- *   bwd: g = dL/dout; dx [N, Cp] may be NULL; parameter gradients in the reference layout (NULL where the parameter
- *        does not exist).  All temporaries live in the caller's workspace.
- *        wgrad_stream (optional, NULL = everything on `stream`): the two weight-gradient GEMMs, their slab reductions
- *        and the unpack are off the dx <- g critical path; given a second stream they are enqueued there, ordered after
- *        `stream` by ev_dagg / ev_dy (recorded on `stream` when their inputs are complete) and followed by ev_done
- *        (recorded on wgrad_stream after the unpack).  join != 0 makes `stream` wait for ev_done before returning to the
- *        caller's next enqueue; with join == 0 the CALLER must order any reader of dW1..dbs after ev_done and keep the
- *        workspace (and x, hE, g) alive until then.  The three events are caller-owned hipEvent_t.
- */
+ *     slice_quirk != 0 (fwd) / sid != NULL (bwd): the reference's linspace-slice statistics for batches of unequal graphs
+ *        (fastinstancenorm.py:53-82) - sums over the `ptr_sum` slices, centring through gid: two-pass statistics forward,
+ *        the extra COEF_XC reduction backward; ptr_true are the true per-graph row ranges.
+ *     bwd: dx [N, Cp]; parameter gradients dW1 .. dbs in the reference layout (NULL where the parameter does not exist).
+ *        All temporaries live in bwd_ws (stin_edgeconv_block_bwd_workspace_bytes).
+ *        Side stream: the weight-gradient products and their finalize launch are off the dx <- g critical path.  With
+ *        use_side != 0 and a `wgrad_stream` other than `stream` they are enqueued there behind ev_dy (recorded on `stream`
+ *        when dY is complete) and followed by ev_done (recorded on wgrad_stream).  Nothing joins the two streams: the
+ *        CALLER must order any reader of dW1 .. dbs after ev_done and keep bwd_ws, x, hE and g alive until then.  Without
+ *        use_side a non-NULL ev_done is recorded on `stream` behind the block's last gradient write.  The events are
+ *        caller-owned hipEvent_t.
+ *   STIN_OP_POOL_MAX: x [n_in, Cout] -> out [n_out, Cout], arg [n_out, Cout]; rowptr_dst / col_dst = the children CSR, trace = the
+ *     fine -> coarse map (backward).  STIN_OP_UNPOOL: out[v] = x[trace[v]] (n_out fine rows); backward = the segment sum
+ *     over the children CSR. */
 #define STIN_TI_COMPACT 2         /* value of `trans_inv`: translation-invariant, compact layout (see the pack documentation above) */
-#define STIN_BLOCK_PACKED 0x800   /* OR-ed into stin_edgeconv_block_fwd's fwd_split: the caller has already run the pack (e.g.
-                                     stin_edgeconv_pack_many_f32) with the same modes into wcatT / w2T and into THIS workspace
+#define STIN_BLOCK_PACKED 0x800   /* OR-ed into a block op's fwd_split: the caller has already run the pack (e.g.
+                                     stin_edgeconv_pack_many_f32) with the same modes into wcatT / w2T and into THIS fwd_ws
                                      at the offsets stin_edgeconv_block_fwd_pack_offsets reports - the call then skips it    */
 size_t stin_edgeconv_block_fwd_workspace_bytes(int Cin, int Cp, int H, int Cout, int has_shortcut, int B);
 /* byte offsets of wcat [Yw, Cp], w2s [Cout, H] and bcat [Yw] from the workspace pointer rounded UP to 256 bytes */
 int stin_edgeconv_block_fwd_pack_offsets(int Cp, int H, int Cout, int has_shortcut, size_t* off_wcat, size_t* off_w2s,
                                          size_t* off_bcat);
-int stin_edgeconv_block_fwd(int storage, const void* x, int64_t ldx, int64_t N, int Cin, int Cp, int H, int Cout,
-                            int has_shortcut, int trans_inv, const float* W1, const float* b1, const float* W2,
-                            const float* b2, const float* Ws, const float* bs, const int32_t* rowptr_dst,
-                            const int32_t* col_dst, const int32_t* ptr_sum, int B, const int32_t* gid, const float* inv_cnt,
-                            int slice_quirk, float eps, int prec_fwd, int fwd_split, int bwd_split, float* wcatT, float* w2T, void* Y,
-                            int64_t ldy, void* hE, int64_t ldh, uint32_t* mask, void* agg, float* mean, float* rstd, void* out,
-                            int64_t ldo, void* workspace, size_t workspace_bytes, stin_stream_t stream);
 size_t stin_edgeconv_block_bwd_workspace_bytes(int64_t N, int Cp, int H, int Cout, int has_shortcut, int B, int storage);
-int stin_edgeconv_block_bwd(int storage, const void* g, int64_t ldg, const void* x, int64_t ldx, int64_t N, int Cin, int Cp,
-                            int H, int Cout, int has_shortcut, int trans_inv, const void* Y, int64_t ldy, const void* hE,
-                            int64_t ldh, const uint32_t* mask, const void* agg, const float* mean, const float* rstd,
-                            const float* wcatT, const float* w2T, const int32_t* rowptr_dst, const int32_t* rowptr_src,
-                            const int32_t* col_src, const int32_t* xslot, const float* w_src, const int32_t* ptr_true, int B,
-                            const int32_t* gid, const int32_t* sid, const float* inv_cnt, int prec_bwd, int bwd_split, void* dx,
-                            int64_t lddx,
-                            float* dW1, float* db1, float* dW2, float* db2, float* dWs, float* dbs, void* workspace,
-                            size_t workspace_bytes, stin_stream_t stream, stin_stream_t wgrad_stream, stin_event_t ev_dagg,
-                            stin_event_t ev_dy, stin_event_t ev_done, int join);
-
-/* The WHOLE graph part of the network in one call per direction (round 3): every fused EdgeConv + instance-norm block and the
- * pool / unpool steps between them, in network order (models/surfacetextureinpaintingnet.py:404-455: input blocks, `for`
- * over the encoder levels - `_pooling` :384-386 then a block -, the bottleneck blocks, `for` over the decoder levels -
- * `_unpooling` :390-391 then a block -, the output blocks).  The calls loop over stin_edgeconv_block_fwd / _bwd,
- * stin_pool_max_{fwd,bwd}_*, stin_gather_rows_* and stin_segment_sum_* with the per-op pointers of a HOST op array: identical
- * kernels in identical order (bit-identical to the per-op calls), ONE foreign call and one autograd node per direction
- * instead of ~20 - what it removes is host time (the launch-bound sizes: 20 k-vertex crops, the 8-crop batches).
- *   op i reads `x` (ops[0]: the network input padded to Cp channels; else ops[i - 1].out) and writes `out`;
- *   bwd walks the ops in reverse: the gradient of op i's output is ops[i + 1].dx (the call's `g` for the last op), op i writes
- *   its input gradient to `dx` (NULL for ops[0] when the network input needs none).
- *   STIN_OP_BLOCK: the arguments of stin_edgeconv_block_fwd / _bwd (n_out = n_in = N rows); use_side != 0 puts the block's
- *     weight-gradient work on `wgrad_stream` behind ev_dy and records ev_done there (as stin_edgeconv_block_bwd).
- *   STIN_OP_POOL_MAX: x [n_in, Cout] -> out [n_out, Cout], arg [n_out, Cout]; rowptr_dst / col_dst = the children CSR, trace = the
- *     fine -> coarse map (backward).  STIN_OP_UNPOOL: out[v] = x[trace[v]] (n_out fine rows); backward = the segment sum
- *     over the children CSR. */
 #define STIN_OP_BLOCK 0
 #define STIN_OP_POOL_MAX 1
 #define STIN_OP_UNPOOL 2
@@ -842,7 +821,7 @@ int stin_net_bwd(int storage, const stin_net_op_t* ops, int n_ops, const void* g
  * as ONE grid of the producer / consumer TN kernel (csrc/stin_wgrad.hip) where both have 128 x 128 tiles and 16-byte rows
  * (otherwise one TN launch each), then ONE kernel that sums the partial slabs in the fixed order of the stand-alone
  * stin_gemm_tn_* reduction and writes the reference-layout gradients directly - bit-identical to
- * stin_gemm_tn_f32 x 2 + stin_edgeconv_unpack_grads_f32, which it replaces inside stin_edgeconv_block_bwd.
+ * stin_gemm_tn_f32 x 2 + stin_edgeconv_unpack_grads_f32, which it replaces inside a block op's backward.
  * Replaces the autograd backward of the two nn.Linear modules of edge_conv_filter.py:46-57 and of the shortcut Linear
  * (models/surfacetextureinpaintingnet.py:489-492) for the gradients w.r.t. their parameters.
  * storage: 0 = fp32 rows, 1 = bf16 rows (dagg, hE, dY, x); hE has at least H + 1 columns; precision as stin_gemm_tn_f32. */

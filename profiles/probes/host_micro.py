@@ -24,6 +24,6 @@ t('x.stride(0)', lambda: x.stride(0))
 t('lib.stin_version()', lambda: lib.stin_version())
 t('workspace_bytes ctypes call', lambda: lib.stin_edgeconv_block_fwd_workspace_bytes(256, 256, 512, 256, 0, 1))
 t('torch.cuda.current_stream().cuda_stream', lambda: torch.cuda.current_stream(dev).cuda_stream)
-t('getattr(lib, name)', lambda: getattr(lib, 'stin_edgeconv_block_fwd'))
+t('getattr(lib, name)', lambda: getattr(lib, 'stin_net_fwd'))
 a, b = torch.empty(20000, 64, device=dev), torch.empty(20000, 64, device=dev)
 t('a.copy_(b) launch', lambda: a.copy_(b), 500)

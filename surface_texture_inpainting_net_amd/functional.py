@@ -6,6 +6,7 @@ Every function here runs on GPU tensors only and calls through the C ABI
 the hand-written MFMA kernels too (gemm_nt / gemm_tn); the library-GEMM A/B aid of round 1 lives in
 profiles/gemm_bench.py, outside the package.
 """
+import collections
 import os
 
 import torch
@@ -312,7 +313,7 @@ def instance_norm_act_bwd(x, gout, mean, rstd, groups, act=True, out=None):
               _ptr(m), _stream(x))
     else:
         # k = -(rstd^3) T1 / n, indexed by the SUM slice (sid): the coefficient kernel's k (its m is overwritten below) - the same
-        # float operations as the four framework launches this replaces, as stin_edgeconv_block_bwd's slice-quirk path does
+        # float operations as the four framework launches this replaces, as the slice-quirk path of stin_net_bwd's block op does
         k = torch.empty_like(rstd)
         m = torch.empty_like(rstd)
         _call('stin_norm_bwd_coef_f32', _ptr(T1), _ptr(S0), _ptr(rstd), _ptr(groups.inv_cnt), rstd.shape[0], C, _ptr(k),
@@ -342,8 +343,9 @@ GEMM_W_BF16 = _C['STIN_GEMM_W_BF16']           # stin_gemm_nt_bf16: the weight o
 # kernel reads.  STIN_NT_STRIP=0 keeps the k-group layout and with it the tiled kernel (A/B aid).
 GEMM_W_FRAG = _C['STIN_GEMM_W_FRAG']           # (a module constant since round 6; tests flip the attribute)
 WEIGHT_PRESPLIT = True
-# one C call per GraphResnetBlock and direction (stin_edgeconv_block_fwd/bwd enqueue the same kernels in the same order
-# as the per-kernel path below): removes ~25 Python-level foreign calls per block.  STIN_BLOCK_CALL=0 = per-kernel path.
+# one C call per direction for a GraphResnetBlock or a run of them (NetFn: stin_net_fwd / _bwd enqueue the same kernels in the
+# same order as the per-kernel path of EdgeConvBlockFn): removes ~25 Python-level foreign calls per block.  STIN_BLOCK_CALL=0 =
+# per-kernel path.
 USE_BLOCK_CALL = os.environ.get('STIN_BLOCK_CALL', '1') != '0'
 
 
@@ -648,8 +650,8 @@ _WGRAD_SIDE = {}
 
 
 class _WgradSide:
-    """Per device: the HIP stream the weight-gradient GEMMs of stin_edgeconv_block_bwd run on and a ring of event
-    triples that order it against the compute stream (a fresh triple per block call, so no event is re-recorded while
+    """Per device: the HIP stream the weight-gradient GEMMs of a block's backward (stin_net_bwd, use_side) run on and a ring
+    of event triples that order it against the compute stream (a fresh triple per block, so no event is re-recorded while
     a wait on its previous record may still be queued)."""
     RING = 64
 
@@ -728,24 +730,6 @@ def _join_deferrable(params, direct):
     return WGRAD_DEFER_JOIN and (bool(direct) or (_plain_autograd_may_defer() and all(
         p is None or (p.is_leaf and p.grad is None and not p._backward_hooks and
                       not getattr(p, '_post_accumulate_grad_hooks', None)) for p in params)))
-
-
-def _wgrad_side_args(dev, keep_alive, params, direct=False, work=0):
-    """-> (wgrad_stream, ev_dagg, ev_dy, ev_done, join) for stin_edgeconv_block_bwd.  The join with the compute stream is
-    deferred to the end of the backward pass where _join_deferrable allows it; otherwise the block stays on one stream."""
-    if not USE_WGRAD_STREAM or work > WGRAD_MAX_WORK or work < WGRAD_MIN_WORK:
-        return 0, 0, 0, 0, 0
-    if not _join_deferrable(params, direct):
-        # a join inside every call measured SLOWER than one stream (9.70 vs 9.45 ms per step): gradient accumulation,
-        # parameter hooks, DDP and non-leaf weights simply keep the whole block on the compute stream
-        return 0, 0, 0, 0, 0
-    side = _wgrad_side(dev)
-    # the side stream reads these after this call has returned: keep them referenced until the join (then they are freed in
-    # compute-stream order AFTER the join - no record_stream: its deferred frees made the caching allocator's pool grow by
-    # ~80 MB per step over hundreds of steps with changing scene sizes)
-    side.hold.append(keep_alive)
-    ev = side.next_events()
-    return side.stream.cuda_stream, ev[0].cuda_event, ev[1].cuda_event, ev[2].cuda_event, 0
 
 
 def wgrad_side_settle(dev):
@@ -851,7 +835,7 @@ class PackSet:
             Yw = block_yw(H, Cout, has_sc, ti)
             fsp, bsp = block_split_modes(prec_fwd, b16, Cout)       # what the block call is handed (bf16 rows: 0, 0)
             # what the pack writes: bf16 rows -> plain bf16 operands where every reduction length is a multiple of 8
-            # (the rule of stin_edgeconv_block_fwd), else the fp32 / split form of the fp32-storage path
+            # (the rule of stin_net_fwd's block op), else the fp32 / split form of the fp32-storage path
             jf, jb = ((GEMM_W_BF16, GEMM_W_BF16) if (Cp % 8 == 0 and Cout % 8 == 0) else (0, 0)) if b16 else (fsp, bsp)
             ws = torch.empty(lib.stin_edgeconv_block_fwd_workspace_bytes(Cin, Cp, H, Cout, int(has_sc), B), dtype=torch.uint8, device=dev)
             wts = torch.empty(Yw * Cp + H * Cout, dtype=torch.float32, device=dev)
@@ -905,10 +889,12 @@ class EdgeConvBlockFn(torch.autograd.Function):
         out = (Y[:, 2H:] or x) + ELU(InstanceNorm(agg))            (HIP epilogue)
 
     Saved for backward: per-vertex tensors plus the E*H-bit ReLU mask (recompute kernels when the hidden width does not
-    support the mask).  Fast path: one C call per direction (stin_edgeconv_block_fwd / _bwd, same kernels, same order)."""
+    support the mask).  This is the per-kernel path: one foreign call per launch.  GraphResnetBlock.forward takes it where
+    net_eligible declines (STIN_BLOCK_CALL=0, STIN_EDGE_MASK=0, a hidden width without a saved mask, N <= 1, the bench's
+    per-kernel brackets); everywhere else the block is a one-op NetFn, which enqueues the same kernels in the same order."""
 
     @staticmethod
-    def forward(ctx, x, W1, b1, W2, b2, Ws, bs, edges, groups, trans_inv, eps=EPS, prec_fwd=None, prepacked=None):
+    def forward(ctx, x, W1, b1, W2, b2, Ws, bs, edges, groups, trans_inv, eps=EPS, prec_fwd=None):
         prec_fwd = PREC_FWD if prec_fwd is None else int(prec_fwd)
         x, _ = _mat(x)
         N, Cin = x.shape
@@ -918,53 +904,13 @@ class EdgeConvBlockFn(torch.autograd.Function):
         b16 = x.dtype == torch.bfloat16
         ti = trans_inv_mode(trans_inv, b16, H)                    # 2 = compact: Y = [B | S], A_i = b1 - B_i formed by the edge stage
         Yw = block_yw(H, Cout, has_shortcut, ti)
-        oB, oS = (0 if ti == TI_MODE_COMPACT else H), Yw - (Cout if has_shortcut else 0)   # columns of B and of the shortcut in Y / dY
+        oS = Yw - (Cout if has_shortcut else 0)                   # column of the shortcut in Y / dY
         pad = 8 if b16 else 4
         xp = _pad_rows(x, pad)
         Cp = xp.shape[1]
         # forward / backward weight operands, pre-split once here into the two 16-bit pieces the split GEMMs use
         # (instead of once per GEMM block); plain fp32 for the other precisions and for bf16-storage activations
         fsp, bsp = block_split_modes(prec_fwd, b16, Cout)
-        fast = (USE_BLOCK_CALL and USE_EDGE_MASK and edge_mask_supported(H) and N > 1
-                and not KernelTimer.per_kernel_path())   # (the bench's per-kernel HIP-event brackets need the per-kernel path)
-        ctx.fast = fast
-        if fast:
-            lib = _lib.load()
-            B = groups.B
-            packed = 0
-            if prepacked is not None and len(prepacked) > 6 and prepacked[6] == b16 and prepacked[2] == fsp and prepacked[3] == bsp:
-                ws, packed = prepacked[0], BLOCK_PACKED                           # operands already packed (PackSet.run)
-                wcatT, w2T = prepacked[4], prepacked[5]
-            else:                                                                 # backward weight operands (no views in here)
-                wcatT = torch.empty(Cp, Yw, dtype=torch.float32, device=dev)
-                w2T = torch.empty(H, Cout, dtype=torch.float32, device=dev)
-            Y = torch.empty(N, Yw, dtype=x.dtype, device=dev)
-            hE = torch.empty(N, H + pad, dtype=x.dtype, device=dev)
-            mask = torch.empty(max(edges.n_edges, 1) * (H // 32), dtype=torch.int32, device=dev)
-            agg = torch.empty(N, Cout, dtype=x.dtype, device=dev)
-            mean = torch.empty(B, Cout, dtype=torch.float32, device=dev)
-            rstd = torch.empty(B, Cout, dtype=torch.float32, device=dev)
-            out = torch.empty(N, Cout, dtype=x.dtype, device=dev)
-            ws_bytes = lib.stin_edgeconv_block_fwd_workspace_bytes(Cin, Cp, H, Cout, int(has_shortcut), B)
-            if not packed:
-                ws = torch.empty(ws_bytes, dtype=torch.uint8, device=dev)
-            elif ws.numel() < ws_bytes:
-                raise RuntimeError('prepacked workspace too small for this batch (PackSet built for another batch size)')
-            W1c, W2c = W1.contiguous(), W2.contiguous()
-            cd = edges.by_dst
-            _call('stin_edgeconv_block_fwd', int(b16), _ptr(xp), xp.stride(0), N, Cin, Cp, H, Cout, int(has_shortcut),
-                  ti, _ptr(W1c), _ptr(b1), _ptr(W2c), _ptr(b2), _ptr(Ws), _ptr(bs), _ptr(cd.rowptr), _ptr(cd.col),
-                  _ptr(groups.ptr_sum), B, _ptr(groups.gid), _ptr(groups.inv_cnt), int(groups.quirk), float(eps), prec_fwd,
-                  fsp | packed, bsp,
-                  _ptr(wcatT), _ptr(w2T), _ptr(Y), Yw, _ptr(hE), H + pad, _ptr(mask), _ptr(agg), _ptr(mean), _ptr(rstd),
-                  _ptr(out), Cout, _ptr(ws), ws_bytes, _stream(x))
-            ctx.save_for_backward(xp, Y, hE, agg, mean, rstd, wcatT, w2T)
-            ctx.mask = mask
-            ctx.cin = Cin
-            ctx.edges, ctx.groups, ctx.H, ctx.has_shortcut, ctx.trans_inv = edges, groups, H, has_shortcut, ti
-            ctx.bsp = bsp
-            ctx.params = (W1, b1, W2, b2, Ws, bs)
-            return out
         pack = torch.empty(Yw * Cp * 2 + 2 * H * Cout + Yw, dtype=torch.float32, device=dev)
         wcat = pack[:Yw * Cp].view(Yw, Cp)
         wcatT = pack[Yw * Cp:2 * Yw * Cp].view(Cp, Yw)
@@ -1007,7 +953,6 @@ class EdgeConvBlockFn(torch.autograd.Function):
         ctx.edges, ctx.groups, ctx.H, ctx.has_shortcut, ctx.trans_inv = edges, groups, H, has_shortcut, ti
         ctx.params = (W1, b1, W2, b2, Ws, bs)
         ctx.prec_bwd_nt = (PREC_BWD | GEMM_W_PRESPLIT | GEMM_W_FRAG) if bsp else PREC_BWD
-        ctx.bsp = bsp
         return out
 
     @staticmethod
@@ -1016,49 +961,6 @@ class EdgeConvBlockFn(torch.autograd.Function):
         edges, groups, H = ctx.edges, ctx.groups, ctx.H
         Cin, Cp, Cout = ctx.cin, x.shape[1], agg.shape[1]
         g, ldg = _mat(g)
-        if ctx.fast:
-            lib = _lib.load()
-            dev, N, b16 = x.device, x.shape[0], x.dtype == torch.bfloat16
-            _same(x, g)
-            dx = torch.empty(N, Cp, dtype=x.dtype, device=dev) if ctx.needs_input_grad[0] else None
-            direct = _direct_grad_views(ctx.params)
-            # a TrainStep bucket is accepting: write the gradients where the optimizer reads them; else fresh tensors for autograd
-            dW1, db1, dW2, db2, dWs, dbs = direct if direct is not None else _fresh_grads(ctx.params, dev)
-            ws_bytes = lib.stin_edgeconv_block_bwd_workspace_bytes(N, Cp, H, Cout, int(ctx.has_shortcut), groups.B, int(b16))
-            ws = torch.empty(ws_bytes, dtype=torch.uint8, device=dev)
-            cs = edges.by_src
-            side = _wgrad_side_args(dev, (ws, x, hE, g), ctx.params, direct is not None, work=float(N) * Y.shape[1] * Cp)
-            if side[0] and direct is None:
-                # the side stream WRITES these fresh tensors after this call has returned.  They must not be referenced from
-                # here (autograd adopts a returned gradient only when it holds the sole reference - otherwise it copies it on
-                # the compute stream, before the join); record_stream makes the allocator wait for the side stream should
-                # an aborted backward free them early (a few MB of weights: no pool growth, unlike the activations)
-                ss = _wgrad_side(dev).stream
-                for t in (dW1, db1, dW2, db2, dWs, dbs):
-                    if t is not None:
-                        t.record_stream(ss)
-            _call('stin_edgeconv_block_bwd', int(b16), _ptr(g), ldg, _ptr(x), x.stride(0), N, Cin, Cp, H, Cout,
-                  int(ctx.has_shortcut), int(ctx.trans_inv), _ptr(Y), Y.stride(0), _ptr(hE), hE.stride(0), _ptr(ctx.mask),
-                  _ptr(agg), _ptr(mean), _ptr(rstd), _ptr(wcatT), _ptr(w2T), _ptr(edges.by_dst.rowptr), _ptr(cs.rowptr),
-                  _ptr(cs.col), _ptr(edges.xslot), _ptr(edges.w_src), _ptr(groups.ptr_true), groups.B, _ptr(groups.gid),
-                  _ptr(groups.sid if groups.quirk else None), _ptr(groups.inv_cnt), int(PREC_BWD), ctx.bsp, _ptr(dx), Cp, _ptr(dW1), _ptr(db1), _ptr(dW2), _ptr(db2),
-                  _ptr(dWs), _ptr(dbs), _ptr(ws), ws_bytes, _stream(x), *side)
-            ctx.mask = None
-            if side[0] and not side[4]:
-                _wgrad_deferred_join(dev, ctx.params, () if direct is not None else (dW1, db1, dW2, db2, dWs, dbs))
-            if direct is not None:
-                # a bucket that reduces in segments hands every completed one to RCCL now (train_step.FlatGradBucket)
-                # behind the side stream's NEWEST event whenever any block of THIS backward pass has put weight-gradient work
-                # there (`hold` is emptied by the end-of-backward join) - not only when this block did: a segment spans
-                # several blocks, and an earlier one may have used the side stream while the block completing it did not
-                sd = _WGRAD_SIDE.get(dev.index if dev.index is not None else torch.cuda.current_device())
-                ctx.params[0]._stin_slot[0].block_done(sd.last_done if (sd is not None and sd.hold) else None)
-                if dx is not None and Cp != Cin:
-                    dx = dx[:, :Cin]
-                return (dx,) + (None,) * 12
-            if dx is not None and Cp != Cin:
-                dx = dx[:, :Cin]
-            return dx, dW1, db1, dW2, db2, dWs, dbs, None, None, None, None, None, None
         dagg = instance_norm_act_bwd(agg, g, mean, rstd, groups, act=True)
         dw2b = gemm_tn(dagg, hE[:, :H], ones_column=True, row_weight=hE[:, H], precision=PREC_BWD)   # [Cout, H + 1] = dW2 | db2
         dhE = gemm_nt(dagg, w2T, precision=ctx.prec_bwd_nt)                                             # [N, H] = dagg W2
@@ -1091,7 +993,7 @@ class EdgeConvBlockFn(torch.autograd.Function):
               int(ctx.trans_inv), _ptr(dW1), _ptr(db1), _ptr(dWs), _ptr(dbs), _ptr(dW2), _ptr(db2), _stream(x))
         if compact and db1 is not None:
             db1 = db1_ti                            # (the packed product's ones column holds sum_i D_i ~ 0, not db1)
-        return dx, dW1, db1, dW2, db2, dWs, dbs, None, None, None, None, None, None
+        return dx, dW1, db1, dW2, db2, dWs, dbs, None, None, None, None, None
 
 
 # ---- the graph part of the network in ONE autograd node ----------------------------------------------------------------------
@@ -1105,10 +1007,20 @@ def _align256(n):
     return (n + 255) & ~255
 
 
+def usable_prepack(blk, b16):
+    """blk._prepacked - the block's operand buffers in the network's PackSet - when it was packed for this storage type and
+    the split modes the block runs with now, else None: the node then packs for itself."""
+    pp = blk._prepacked
+    if pp is None:
+        return None
+    fsp, bsp = block_split_modes(forward_precision(blk.unbounded_input), b16, blk.dim_out)
+    return pp if (len(pp) > 6 and pp[6] == b16 and pp[2] == fsp and pp[3] == bsp) else None
+
+
 def net_eligible(steps, x):
     """steps = [('block', GraphResnetBlock, EdgeSet, NormGroups) | ('pool', PoolMap) | ('unpool', PoolMap)] can run as one
     NetFn: fused EdgeConv + instance-norm blocks on the whole-block path (saved ReLU mask available), max pooling, fp32 or
-    bf16 storage; operands of every block packed by the network's PackSet or of none."""
+    bf16 storage; operands of every block packed by the network's PackSet or of none.  One block alone is a valid list."""
     if not (USE_BLOCK_CALL and USE_EDGE_MASK and not KernelTimer.per_kernel_path() and x.is_cuda and x.dim() == 2):
         return False
     if x.dtype not in (torch.float32, torch.bfloat16) or x.shape[0] <= 1:
@@ -1122,27 +1034,32 @@ def net_eligible(steps, x):
         H = b.first_filter.nn[0].weight.shape[0]
         if not edge_mask_supported(H) or st[2].n <= 1:
             return False
-        pp = b._prepacked
-        if pp is not None:
-            fsp, bsp = block_split_modes(forward_precision(b.unbounded_input), b16, b.dim_out)
-            if len(pp) < 7 or pp[6] != b16 or pp[2] != fsp or pp[3] != bsp:
-                return False
-        packed.append(pp is not None)
+        packed.append(usable_prepack(b, b16) is not None)
     return bool(packed) and any(packed) == all(packed)
 
 
 class NetFn(torch.autograd.Function):
-    """Every fused block and pool / unpool step of the network's graph part as ONE autograd node and one C call per direction
-    (stin_net_fwd / _bwd: loops over the per-op entry points, same kernels in the same order -> bit-identical to the per-op
-    nodes).  All tensors backward needs live in one arena allocation, the op table is packed on the host (480 bytes per op).
-    args: x, meta = (steps, prec list), then the flat parameters (W1, b1, W2, b2, Ws, bs) of every block in step order."""
+    """A run of fused blocks and pool / unpool steps - the network's whole graph part, its bottleneck chain, or one block - as
+    ONE autograd node and one C call per direction (stin_net_fwd / _bwd: loops over the per-op launch sequences, same kernels
+    in the same order -> bit-identical to the per-kernel path).  All tensors backward needs live in one arena allocation, the
+    op table is packed on the host (480 bytes per op).
+    args: x, meta = (steps, need_grad), then the flat parameters (W1, b1, W2, b2, Ws, bs) of every block in step order."""
 
-    calls = 0
+    calls = 0                           # nodes created ...
+    sizes = collections.Counter()       # ... and how many of them per number of ops (1 = a block on its own)
+
+    @staticmethod
+    def _in_arena(rel, base, xp):
+        """The fields of an op that point into the arena (offsets `rel`) as addresses; the first op reads the padded input xp."""
+        ptrs = {k: base + o for k, o in rel.items()}
+        ptrs.setdefault('x', _ptr(xp))
+        return ptrs
 
     @staticmethod
     def forward(ctx, x, meta, *params):
-        NetFn.calls += 1
         steps, need_grad = meta
+        NetFn.calls += 1
+        NetFn.sizes[len(steps)] += 1
         lib = _lib.load()
         x, _ = _mat(x)
         dev, dt = x.device, x.dtype
@@ -1190,7 +1107,7 @@ class NetFn(torch.autograd.Function):
                 B = groups.B
                 prec = forward_precision(blk.unbounded_input)
                 fsp, bsp = block_split_modes(prec, b16, Cout)
-                pp = blk._prepacked
+                pp = usable_prepack(blk, b16)
                 ws_bytes = lib.stin_edgeconv_block_fwd_workspace_bytes(Cin, Cp, H, Cout, int(sc), B)
                 d = dict(kind=OP_BLOCK, N=n_rows, Cin=Cin, Cp=Cp, H=H, Cout=Cout, sc=sc, Yw=Yw, B=B, prec=prec, fsp=fsp, bsp=bsp, pp=pp,
                          ws_bytes=ws_bytes, edges=edges, groups=groups, ti=ti, eps=float(blk.first_norm.eps),
@@ -1232,42 +1149,50 @@ class NetFn(torch.autograd.Function):
         out = torch.empty(n_rows, width, dtype=dt, device=dev)
         base, p_out = _ptr(arena), _ptr(out)
         assert base % 256 == 0
-        # ---- pass 2: the op table.  d['op'] keeps each op's fields (by the names of stin_net_op_t): backward packs them again
-        # with its own on top (stin_net_bwd and the block backward read no forward-only field)
+        # ---- pass 2: the op table.  d['op'] keeps each op's fields (by the names of stin_net_op_t) and d['rel'] those that point
+        # into the arena, as offsets: backward packs both again with its own on top (stin_net_bwd and the block backward read no
+        # forward-only field), on the addresses of the saved tensors IT is handed - under torch.utils.checkpoint(use_reentrant=
+        # False) those are the recomputed ones, not this call's
         stc = _NET_OP
         blob = []
-        xin, ldx = _ptr(xp), xp.stride(0)
+        xin, ldx = None, xp.stride(0)                      # offset of the op's input rows in the arena; None = xp
         for d in plan:
-            o = p_out if d['oO'] is None else base + d['oO']
+            rel = {} if xin is None else {'x': xin}
             if d['kind'] == OP_BLOCK:
                 W1, b1, W2, b2, Ws, bs = d['params']
                 pp = d['pp']
                 if pp is not None:
-                    p_wcatT, p_w2T, p_ws, flag = _ptr(pp[4]), _ptr(pp[5]), _ptr(pp[0]), d['fsp'] | BLOCK_PACKED
+                    packed = dict(wcatT=_ptr(pp[4]), w2T=_ptr(pp[5]), fwd_ws=_ptr(pp[0]), fwd_split=d['fsp'] | BLOCK_PACKED)
                 else:
-                    p_wcatT = base + d['oW']
-                    p_w2T, p_ws, flag = p_wcatT + d['Yw'] * d['Cp'] * 4, base + d['oWS'], d['fsp']
+                    packed = dict(fwd_split=d['fsp'])
+                    rel.update(wcatT=d['oW'], w2T=d['oW'] + d['Yw'] * d['Cp'] * 4, fwd_ws=d['oWS'])
                 g, cd = d['groups'], d['edges'].by_dst
                 H, Cout, B = d['H'], d['Cout'], d['B']
                 d['op'] = dict(kind=OP_BLOCK, Cin=d['Cin'], Cp=d['Cp'], H=H, Cout=Cout, has_shortcut=int(d['sc']), trans_inv=int(d['ti']),
-                               prec_fwd=int(d['prec']), fwd_split=flag, bwd_split=d['bsp'], B=B, slice_quirk=int(g.quirk), eps=d['eps'],
+                               prec_fwd=int(d['prec']), bwd_split=d['bsp'], B=B, slice_quirk=int(g.quirk), eps=d['eps'],
                                n_out=d['N'], n_in=d['N'], ldx=ldx, ldo=Cout, ldy=d['Yw'], ldh=H + pad, fwd_ws_bytes=d['ws_bytes'],
-                               x=xin, out=o, W1=_ptr(W1.contiguous()), b1=_ptr(b1), W2=_ptr(W2.contiguous()), b2=_ptr(b2), Ws=_ptr(Ws),
-                               bs=_ptr(bs), wcatT=p_wcatT, w2T=p_w2T, fwd_ws=p_ws, rowptr_dst=_ptr(cd.rowptr), col_dst=_ptr(cd.col),
-                               ptr_sum=_ptr(g.ptr_sum), gid=_ptr(g.gid), inv_cnt=_ptr(g.inv_cnt), Y=base + d['oY'], hE=base + d['oH'],
-                               mask=(base + d['oM']) if need_grad else 0, agg=base + d['oA'], mean=base + d['oS'],
-                               rstd=base + d['oS'] + B * Cout * 4)
+                               W1=_ptr(W1.contiguous()), b1=_ptr(b1), W2=_ptr(W2.contiguous()), b2=_ptr(b2), Ws=_ptr(Ws),
+                               bs=_ptr(bs), rowptr_dst=_ptr(cd.rowptr), col_dst=_ptr(cd.col),
+                               ptr_sum=_ptr(g.ptr_sum), gid=_ptr(g.gid), inv_cnt=_ptr(g.inv_cnt), **packed)
+                rel.update(Y=d['oY'], hE=d['oH'], agg=d['oA'], mean=d['oS'], rstd=d['oS'] + B * Cout * 4)
+                if need_grad:
+                    rel['mask'] = d['oM']
                 ev0, ev1 = KernelTimer.edge_events('stin_edge_relu_mean_fwd' + sfx, (d['N'], d['edges'].n_edges, H))
-                blob.append(stc.pack(**d['op'], ev_edge0=ev0, ev_edge1=ev1))
-                xin, ldx = o, Cout
+                events = dict(ev_edge0=ev0, ev_edge1=ev1)
+                ldx = Cout
             else:
                 pool, C = d['pool'], d['C']
                 ch = pool.children
-                d['op'] = dict(kind=d['kind'], Cin=C, Cp=C, Cout=C, n_out=d['n_out'], n_in=d['n_in'], ldx=ldx, ldo=C, x=xin, out=o,
-                               rowptr_dst=_ptr(ch.rowptr), col_dst=_ptr(ch.col),
-                               arg=(base + d['oArg']) if d['kind'] == OP_POOL_MAX else 0, trace=_ptr(pool.trace))
-                blob.append(stc.pack(**d['op']))
-                xin, ldx = o, C
+                d['op'] = dict(kind=d['kind'], Cin=C, Cp=C, Cout=C, n_out=d['n_out'], n_in=d['n_in'], ldx=ldx, ldo=C,
+                               rowptr_dst=_ptr(ch.rowptr), col_dst=_ptr(ch.col), trace=_ptr(pool.trace))
+                if d['kind'] == OP_POOL_MAX:
+                    rel['arg'] = d['oArg']
+                events = {}
+                ldx = C
+            d['rel'] = rel
+            blob.append(stc.pack(**d['op'], **NetFn._in_arena(rel, base, xp), **events,
+                                 out=p_out if d['oO'] is None else base + d['oO']))
+            xin = d['oO']
         import ctypes
         buf = ctypes.create_string_buffer(b''.join(blob), len(plan) * stc.size)
         _call('stin_net_fwd', int(b16), buf, len(plan), _stream(x))
@@ -1282,6 +1207,7 @@ class NetFn(torch.autograd.Function):
     @staticmethod
     def backward(ctx, g):
         xp, arena = ctx.saved_tensors                    # (the ops' pointers go into the arena)
+        base = _ptr(arena)
         plan, params = ctx.plan, ctx.params
         lib = _lib.load()
         dev, dt = xp.device, xp.dtype
@@ -1372,14 +1298,15 @@ class NetFn(torch.autograd.Function):
                 ev_dy, ev_done = evs[bi]
                 ev0, ev1 = KernelTimer.edge_events('stin_edge_relu_mean_bwd_mask' + ('_ti' if d['ti'] == TI_MODE_COMPACT else '') + sfx,
                                                    (d['N'], e.n_edges, d['H']))
-                blob.append(stc.pack(**d['op'], use_side=int(use[bi]), lddx=d['Cp'], bwd_ws_bytes=d['bwd_ws_bytes'], dx=p_dx,
+                blob.append(stc.pack(**d['op'], **NetFn._in_arena(d['rel'], base, xp), use_side=int(use[bi]), lddx=d['Cp'],
+                                     bwd_ws_bytes=d['bwd_ws_bytes'], dx=p_dx,
                                      rowptr_src=_ptr(cs.rowptr), col_src=_ptr(cs.col), xslot=_ptr(e.xslot), w_src=_ptr(e.w_src),
                                      ptr_true=_ptr(gr.ptr_true), sid=_ptr(gr.sid if gr.quirk else None),
                                      dW1=_ptr(gs[0]), db1=_ptr(gs[1]), dW2=_ptr(gs[2]), db2=_ptr(gs[3]), dWs=_ptr(gs[4]), dbs=_ptr(gs[5]),
                                      bwd_ws=p_ws + ws_off[bi], ev_dy=ev_dy, ev_done=ev_done, ev_edge0=ev0, ev_edge1=ev1))
                 bi += 1
             else:
-                blob.append(stc.pack(**d['op'], lddx=d['C'], dx=p_dx))
+                blob.append(stc.pack(**d['op'], **NetFn._in_arena(d['rel'], base, xp), lddx=d['C'], dx=p_dx))
         import ctypes
         buf = ctypes.create_string_buffer(b''.join(blob), len(plan) * stc.size)
         _call('stin_net_bwd', int(b16), buf, len(plan), _ptr(g), ldg, int(PREC_BWD), _stream(xp), side_stream)
@@ -1388,16 +1315,12 @@ class NetFn(torch.autograd.Function):
         if dx0 is not None and dx0.shape[1] != ctx.cin0:
             dx0 = dx0[:, :ctx.cin0]
         if direct:
+            # completed segments go to RCCL now, each behind its own blocks' events; one that also holds gradients of another node
+            # waits behind the side stream's NEWEST event whenever any block of THIS backward pass has put weight-gradient work
+            # there (`hold` is emptied by the end-of-backward join), not only when a block of this node did
             sd = _WGRAD_SIDE.get(dev.index if dev.index is not None else torch.cuda.current_device())
-            slot = None
-            for p in all_params:
-                if p is not None:
-                    slot = p._stin_slot[0]
-                    break
-            if seg_events:                   # completed segments go to RCCL now, each behind its own blocks' events
-                slot.blocks_done([([p._stin_slot[1] for p in d['params'] if p is not None], done_ev[bi]) for bi, d in enumerate(blocks)])
-            else:
-                slot.block_done(sd.last_done if (sd is not None and sd.hold) else None)
+            bucket.blocks_done([([p._stin_slot[1] for p in d['params'] if p is not None], done_ev[bi]) for bi, d in enumerate(blocks)],
+                               sd.last_done if (sd is not None and sd.hold) else None)
             return (dx0, None) + (None,) * len(params)
         return (dx0, None) + tuple(grads)
 

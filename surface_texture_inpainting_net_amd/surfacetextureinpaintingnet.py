@@ -27,7 +27,7 @@ class GraphResnetBlock(nn.Module):
         # True where the reference wraps the block in torch.utils.checkpoint (:429, :438, :451, :454): its forward runs a
         # second time inside backward, which numerically only matters for BatchNorm running statistics (norm='batch')
         self.recomputed = False
-        self._prepacked = None        # (workspace, wcatT | w2T, fwd_split, bwd_split) of functional.PackSet, set by the network
+        self._prepacked = None        # this block's entry of functional.PackSet.buffers, set by the network (functional.usable_prepack)
         # True for a block fed by un-normalised data (the network's first block, or any block of a norm-free network):
         # its forward GEMMs take the range-safe matrix-core path (functional.forward_precision)
         self.unbounded_input = False
@@ -59,13 +59,16 @@ class GraphResnetBlock(nn.Module):
         fused = isinstance(self.first_filter, M.EdgeConv) and isinstance(self.first_norm, M.FastInstanceNorm)
         if fused:
             groups = M._as_groups(batch, n, x.device, self.first_norm.linspace_quirk)
+            steps = [('block', self, edges, groups)]
+            if SF.net_eligible(steps, x):                           # a one-op node: one foreign call per direction
+                return SF.run_net(x, steps)
             shortcut = self.shortcut if self.dim_in != self.dim_out else None
             lin1, lin2 = self.first_filter.nn[0], self.first_filter.nn[2]
-            return SF.EdgeConvBlockFn.apply(x, lin1.weight, lin1.bias, lin2.weight, lin2.bias,
+            return SF.EdgeConvBlockFn.apply(x, lin1.weight, lin1.bias, lin2.weight, lin2.bias,      # the per-kernel path
                                             None if shortcut is None else shortcut.weight,
                                             None if shortcut is None else shortcut.bias, edges, groups,
                                             self.first_filter.trans_inv, self.first_norm.eps,
-                                            SF.forward_precision(self.unbounded_input), self._prepacked)
+                                            SF.forward_precision(self.unbounded_input))
         self.first_filter.fwd_precision = SF.forward_precision(self.unbounded_input)
         out = self.first_filter(x, edges)
         res = (SF.linear(x, self.shortcut.weight, self.shortcut.bias, precision=SF.forward_precision(self.unbounded_input))

@@ -55,7 +55,7 @@ class FlatGradBucket:
             p.grad = v
             off += p.numel()
             if dev.type == 'cuda':
-                # the whole-block backward (functional.EdgeConvBlockFn) writes this parameter's gradient straight
+                # the whole-block backward (functional.NetFn) writes this parameter's gradient straight
                 # into its bucket view while the bucket is `accepting`, instead of handing a fresh tensor to autograd
                 p._stin_slot = (self, i)
         self.accepting = False
@@ -159,11 +159,15 @@ class FlatGradBucket:
         completion event per block."""
         return bool(self.segments) and self._seg_next < len(self.segments) and self.accepting and _world(self._group) > 1
 
-    def blocks_done(self, items):
-        """functional.NetFn.backward, after ONE C call has enqueued the backward kernels of every block: items = [(parameter slot
-        indices of a block, the event recorded when that block's gradient writes are complete)].  Each segment whose parameters
-        are all written goes to RCCL on the communication stream behind the events of exactly its blocks - NOT behind the
-        compute stream's current position, which would be the end of the whole backward pass (the round-3 regression)."""
+    def blocks_done(self, items, side_event=None):
+        """functional.NetFn.backward, after ONE C call has enqueued the backward kernels of every block of the node: items =
+        [(parameter slot indices of a block, the event recorded when that block's gradient writes are complete, or None)].
+        Each segment whose parameters are all written goes to RCCL on the communication stream behind the events of exactly its
+        blocks - NOT behind the compute stream's current position, which would be the end of the whole backward pass (the
+        round-3 regression).  A segment that also holds parameters written by an earlier node (every block its own node: a
+        segment spans several) has no event for those: it waits for the compute stream's position AND for `side_event`, the
+        weight-gradient side stream's newest event while any block of this backward pass has work there (else None) - the
+        block completing the segment may have stayed on the compute stream while an earlier one did not."""
         if not self.segments or self._seg_next >= len(self.segments) or _world(self._group) == 1:
             return
         ev_of = {}
@@ -181,30 +185,12 @@ class FlatGradBucket:
                     cs.wait_event(ev)
             else:                                                # a parameter written by some other node: the conservative order
                 cs.wait_stream(torch.cuda.current_stream(dev))
+                if side_event is not None:
+                    cs.wait_event(side_event)
             if self.overlap_log is not None:
                 e = torch.cuda.Event(enable_timing=True)
                 e.record(cs)
                 self.overlap_log.append((self._seg_next, e))
-            with torch.cuda.stream(cs):
-                w = dist.all_reduce(self._seg_slice((lo, hi)), op=dist.ReduceOp.SUM, group=self._group, async_op=True)
-            self._seg_work.append(w)
-            self._seg_next += 1
-
-    def block_done(self, side_event=None):
-        """functional.EdgeConvBlockFn.backward calls this after it has ENQUEUED a block's direct gradient writes: every
-        segment whose parameters are all written is handed to RCCL now - on the communication stream, behind the compute
-        stream's position and the weight-gradient side stream's newest event - while backward continues."""
-        if not self.segments or self._seg_next >= len(self.segments) or _world(self._group) == 1:
-            return
-        while self._seg_next < len(self.segments):
-            lo, hi = self.segments[self._seg_next]
-            if not all(self.written[lo:hi]):
-                break
-            dev = self.flat.device
-            cs = self._comm_stream
-            cs.wait_stream(torch.cuda.current_stream(dev))
-            if side_event is not None:
-                cs.wait_event(side_event)
             with torch.cuda.stream(cs):
                 w = dist.all_reduce(self._seg_slice((lo, hi)), op=dist.ReduceOp.SUM, group=self._group, async_op=True)
             self._seg_work.append(w)

@@ -54,11 +54,19 @@ def test_derived_signatures_match_hand_written_ones(name, want):
 
 
 def test_longest_prototype_is_read_argument_by_argument():
-    res, args = _lib.SIGNATURES['stin_edgeconv_block_bwd']
-    assert res is _I and len(args) == 50 == max(len(a) for _, a in _lib.SIGNATURES.values())
-    other = {0: _I, 2: _L, 4: _L, 5: _L, 6: _I, 7: _I, 8: _I, 9: _I, 10: _I, 11: _I, 13: _L, 15: _L, 28: _I, 32: _I, 33: _I,
-             35: _L, 43: _Z, 49: _I}
-    assert args == [other.get(i, _P) for i in range(50)]
+    res, args = _lib.SIGNATURES['stin_edgeconv_wgrad_ti']
+    assert res is _I and len(args) == 28 == max(len(a) for _, a in _lib.SIGNATURES.values())
+    other = {0: _I, 2: _L, 4: _L, 6: _L, 8: _L, 9: _L, 10: _I, 11: _I, 12: _I, 13: _I, 14: _I, 15: _I, 16: _I, 24: _L, 26: _Z}
+    assert args == [other.get(i, _P) for i in range(28)]
+
+
+def test_a_block_is_reached_through_the_op_record_only():
+    """The positional whole-block entry points are gone: a block's operands are the named fields of stin_net_op_t.  The size
+    and offset helpers its callers lay their buffers out with stay."""
+    assert 'stin_edgeconv_block_fwd' not in _lib.SIGNATURES and 'stin_edgeconv_block_bwd' not in _lib.SIGNATURES
+    for name in ('stin_edgeconv_block_fwd_workspace_bytes', 'stin_edgeconv_block_fwd_pack_offsets',
+                 'stin_edgeconv_block_bwd_workspace_bytes', 'stin_net_fwd', 'stin_net_bwd'):
+        assert name in _lib.SIGNATURES
 
 
 def test_struct_layouts_have_the_sizes_the_c_side_asserts():
@@ -76,7 +84,7 @@ def test_struct_layouts_have_the_sizes_the_c_side_asserts():
 
 def test_constants_come_from_the_header():
     c = _lib.CONSTANTS
-    assert c['STIN_E_WORKSPACE'] == -4 and c['STIN_E_NULL'] == -1 and c['STIN_OK'] == 0 and c['STIN_VERSION'] == 101
+    assert c['STIN_E_WORKSPACE'] == -4 and c['STIN_E_NULL'] == -1 and c['STIN_OK'] == 0 and c['STIN_VERSION'] == 102
     assert c['STIN_GEMM_W_FRAG'] == 0x400 and c['STIN_BLOCK_PACKED'] == 0x800 and c['STIN_GEMM_F16X3'] == 4
     assert c['STIN_SEG_MAX_CLASSES'] == 128 and c['STIN_CROP_TRACE'] == 4 and c['STIN_PLAN_MAX_JOBS'] == 16
     assert all(k.startswith('STIN_') and isinstance(v, int) for k, v in c.items()) and 'STIN_HIP_H' not in c
@@ -221,7 +229,7 @@ def test_no_struct_format_is_typed_by_hand():
 
 def test_library_host_only_entry_points():
     lib = _lib.load()                       # no GPU needed for these calls
-    assert lib.stin_version() == 101
+    assert lib.stin_version() == 102
     assert lib.stin_error_string(0) == b'ok'
     assert b'workspace' in lib.stin_error_string(-4)
     assert lib.stin_colreduce_workspace_bytes(64, 1) >= 1024 * 2 * 64 * 8

@@ -1346,9 +1346,10 @@ def test_norm_backward_coefficients_fused_into_the_reduction_equal_the_separate_
 
 
 def test_weight_gradient_side_stream_is_bit_identical_in_every_autograd_mode():
-    """stin_edgeconv_block_bwd with a wgrad_stream (the default): same bits as the single-stream order for (a) a plain
-    backward into empty .grad (join deferred to the end of the pass), (b) accumulation into existing .grad (joined inside
-    the call), (c) torch.autograd.grad, repeated so that freed workspaces get recycled while side work is queued."""
+    """stin_net_bwd with a wgrad_stream (the default): same bits as the single-stream order for (a) a plain backward into
+    empty .grad (join deferred to the end of the pass), (b) accumulation into existing .grad (no deferred join is possible:
+    the second pass keeps every block on the compute stream), (c) torch.autograd.grad, repeated so that freed workspaces
+    get recycled while side work is queued."""
     cfg = dict(input_nc=10, output_nc=3, ngf=64, filter_type='edgeconvtransinv', norm='instance', n_blocks=3, n_levels=2,
                pooling_type='max', dilations=[1, 2, 4])
     torch.manual_seed(7)
@@ -1452,12 +1453,14 @@ def test_pack_many_equals_the_per_block_pack(batched):
     assert all(torch.equal(a, b) for a, b in zip(got, want))
 
 
-@pytest.mark.parametrize('dtype', ['f32', 'bf16'])
-@pytest.mark.parametrize('batched', [False, True])
-def test_block_call_equals_per_kernel_path_bitwise(batched, dtype):
-    """stin_edgeconv_block_fwd/bwd only enqueue the individual entry points: outputs and gradients must equal the
-    per-kernel host path bit for bit - single graph, and a batch of unequal crops (the reference's linspace-slice
-    statistics, fastinstancenorm.py:53-82, inside the block call)."""
+@pytest.mark.parametrize('batched,dtype,nodes', [      # ('net' keeps the ids the test had before `nodes` existed)
+    pytest.param(b, d, n, id='%s-%s%s' % (b, d, '' if n == 'net' else '-' + n))
+    for n in ('net', 'per-block') for d in ('f32', 'bf16') for b in (False, True)])
+def test_block_call_equals_per_kernel_path_bitwise(batched, dtype, nodes):
+    """stin_net_fwd / _bwd only enqueue the individual entry points: outputs and gradients must equal the per-kernel host
+    path bit for bit - single graph, and a batch of unequal crops (the reference's linspace-slice statistics,
+    fastinstancenorm.py:53-82, inside the block op) - with the graph part as one node ('net') and with every fused block
+    as a one-op node of its own ('per-block')."""
     from surface_texture_inpainting_net_amd.data import collate
     if dtype == 'bf16' and not SF.USE_EDGE_MASK:
         pytest.skip('bf16 storage needs the saved ReLU mask (STIN_EDGE_MASK=0 set)')
@@ -1478,17 +1481,92 @@ def test_block_call_equals_per_kernel_path_bitwise(batched, dtype):
         out.float().square().mean().backward()
         return [out.detach().clone()] + [p.grad.clone() for p in net.parameters()]
 
-    old = SF.USE_BLOCK_CALL
+    old = SF.USE_BLOCK_CALL, SF.USE_NET_CALL, SF.USE_CHAIN
     try:
         SF.USE_BLOCK_CALL = False
         want = run()
         SF.USE_BLOCK_CALL = True
+        if nodes == 'per-block':
+            SF.USE_NET_CALL = SF.USE_CHAIN = False
+        sizes = SF.NetFn.sizes.copy()
         got = run()
+        sizes = SF.NetFn.sizes - sizes
     finally:
-        SF.USE_BLOCK_CALL = old
+        SF.USE_BLOCK_CALL, SF.USE_NET_CALL, SF.USE_CHAIN = old
     if batched:
         assert any(g.quirk for g in s._plan_cache._norms.values()), 'the batch must exercise the linspace-slice path'
+    if nodes == 'per-block':
+        assert set(sizes) == {1} and sizes[1] == 9, 'every one of the 9 fused blocks must have been a one-op node'
     assert all(torch.equal(a, b) for a, b in zip(got, want))
+
+
+_LONE_BLOCK_GRAPHS = {}
+
+
+def _lone_block_graph(batched):
+    """(x10 [N, 10], EdgeSet, NormGroups or None) of one ~700-vertex mesh / of three unequal ones, built once per session."""
+    if batched not in _LONE_BLOCK_GRAPHS:
+        from surface_texture_inpainting_net_amd.data import collate
+        if batched:
+            s = collate([make_synthetic_mesh(n, 1, seed=40 + i, dilations=()) for i, n in enumerate((250, 300, 150))]).to(DEV)
+        else:
+            s = make_synthetic_mesh(700, 1, seed=40, dilations=()).to(DEV)
+        n = s.x.shape[0]
+        groups = M._as_groups(s.batch, n, torch.device(DEV), True) if batched else None
+        _LONE_BLOCK_GRAPHS[batched] = (s.x.float(), M._as_edges(s.edge_index, n), groups)
+    return _LONE_BLOCK_GRAPHS[batched]
+
+
+@pytest.mark.parametrize('dtype', ['f32', 'bf16'])
+@pytest.mark.parametrize('batched', [False, True])
+@pytest.mark.parametrize('trans_inv', [False, True])
+@pytest.mark.parametrize('dim_in', [10, 64])
+def test_lone_block_as_one_op_node_equals_per_kernel_path_bitwise(dim_in, trans_inv, batched, dtype):
+    """A GraphResnetBlock called outside any network (`_prepacked` is None: the node packs for itself) runs as a one-op
+    functional.NetFn.  Output, input gradient and the six parameter gradients equal the per-kernel path
+    (USE_BLOCK_CALL = False) bit for bit: 10 -> 64 channels with a shortcut (rows padded to 12 channels in fp32, 16 in bf16)
+    and 64 -> 64 without one, hidden width 128 (the smallest with a saved mask), EdgeConv and its translation-invariant
+    form, fp32 and bf16 rows, one graph and three unequal ones (the linspace-slice statistics), the input with and without
+    requires_grad; under torch.no_grad() the node keeps nothing for backward and returns the same bits."""
+    if not SF.USE_EDGE_MASK:
+        pytest.skip('the one-op node needs the saved ReLU mask (STIN_EDGE_MASK=0 set)')
+    x10, edges, groups = _lone_block_graph(batched)
+    if batched:
+        assert groups.quirk, 'three unequal graphs must exercise the linspace-slice statistics'
+    dt = torch.bfloat16 if dtype == 'bf16' else torch.float32
+    torch.manual_seed(3 + dim_in)
+    kw = dict(module=M.EdgeConvTransInv, double_input=False) if trans_inv else {}
+    blk = S.GraphResnetBlock(dim_in, 64, M.get_gcn_filter, M.FastInstanceNorm, False, True, **kw).to(DEV)
+    blk.unbounded_input = dim_in == 10                       # raw features, as the network's first block takes them
+    assert blk._prepacked is None and blk.first_filter.hidden() == 128 and hasattr(blk, 'shortcut') == (dim_in == 10)
+    x0 = (x10 if dim_in == 10 else torch.randn(x10.shape[0], 64, generator=torch.Generator().manual_seed(8)).to(DEV)).to(dt)
+    params = list(blk.parameters())
+    assert len(params) == (6 if dim_in == 10 else 4)
+
+    def run(block_call, need_dx):
+        old = SF.USE_BLOCK_CALL
+        SF.USE_BLOCK_CALL = block_call
+        try:
+            blk.zero_grad(set_to_none=True)
+            x = x0.clone().requires_grad_(need_dx)
+            sizes = SF.NetFn.sizes.copy()
+            out = blk(x, edges, groups)
+            assert SF.NetFn.sizes - sizes == ({1: 1} if block_call else {})
+            out.float().square().mean().backward()
+            res = [out.detach().clone()] + ([x.grad.clone()] if need_dx else []) + [p.grad.clone() for p in params]
+            with torch.no_grad():
+                quiet = blk(x, edges, groups)
+            assert quiet.grad_fn is None and not quiet.requires_grad
+            return res + [quiet]
+        finally:
+            SF.USE_BLOCK_CALL = old
+
+    for need_dx in (True, False):
+        want, got = run(False, need_dx), run(True, need_dx)
+        assert len(want) == len(got) == 2 + int(need_dx) + len(params)
+        assert torch.equal(got[-1], got[0]), 'the no-grad forward must return the grad-mode bits'
+        for i, (a, b) in enumerate(zip(got, want)):
+            assert a.dtype == b.dtype and torch.equal(a, b), (need_dx, i)
 
 
 @pytest.mark.parametrize('dtype', ['f32', 'bf16'])
@@ -1528,11 +1606,15 @@ def test_bottleneck_chain_equals_per_block_nodes_bitwise(batched, dtype):
         finally:
             SF.USE_CHAIN, SF.USE_NET_CALL = old, old_net
 
-    before = SF.NetFn.calls
+    sizes = SF.NetFn.sizes.copy()
     want = run(False)
-    assert SF.NetFn.calls == before, 'the reference run is made of per-block nodes'
+    made = SF.NetFn.sizes - sizes
+    assert made and set(made) == {1}, 'the reference run is made of per-block (one-op) nodes'
+    sizes = SF.NetFn.sizes.copy()
     got = run(True)
-    assert SF.NetFn.calls == before + 4, 'the chain path must have been taken (1 plain + 3 TrainStep forwards)'
+    made = SF.NetFn.sizes - sizes
+    assert made[4] == 4 and not [n for n in made if n not in (1, 4)], \
+        'the chain path must have been taken: four 4-op nodes (1 plain + 3 TrainStep forwards)'
     assert len(want) == len(got)
     for i, (a, b) in enumerate(zip(got, want)):
         assert torch.equal(a, b), i
@@ -1970,7 +2052,7 @@ def test_vertex_order_hip_path_equals_the_torch_formulation(monkeypatch):
 @pytest.mark.parametrize('dtype', [torch.float32, torch.bfloat16])
 def test_no_grad_forward_is_bit_identical_to_the_training_forward_and_keeps_no_mask(dtype):
     """Round 6: the reference's validation loop runs model(data) under torch.no_grad() (trainers/inpainting3d_trainer.py:204-263).
-    There the whole-network call stores no ReLU mask (stin_edgeconv_block_fwd: mask NULL), shares one temporaries region between
+    There the whole-network call stores no ReLU mask (stin_net_op_t: mask NULL), shares one temporaries region between
     all blocks and ping-pongs the op outputs - same kernels otherwise: the colours equal the differentiable forward's bit for bit,
     no autograd graph is built, and the pass allocates a fraction of the training forward's arena."""
     cfg = dict(input_nc=10, output_nc=3, ngf=64, filter_type='edgeconvtransinv', norm='instance', n_blocks=3, n_levels=2,

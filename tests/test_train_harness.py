@@ -340,7 +340,7 @@ def test_singleconvmeshnet_data_parallel_step_with_a_loss_hook(tmp_path):
     assert r[0]['loss'][2] < r[0]['loss'][0]          # (three Adam steps on the same scene reduce its loss)
 
 
-def _overlap_worker(rank, world, port, out_dir, min_bytes, mix=False):
+def _overlap_worker(rank, world, port, out_dir, min_bytes, mix=False, per_block=False):
     os.environ.update(MASTER_ADDR='127.0.0.1', MASTER_PORT=str(port), RANK=str(rank), WORLD_SIZE=str(world))
     import torch.distributed as dist
     torch.cuda.set_device(0)
@@ -359,7 +359,10 @@ def _overlap_worker(rank, world, port, out_dir, min_bytes, mix=False):
     s = make_synthetic_mesh(3000 + 500 * rank, 3, seed=rank, dilations=(2,)).to(DEV)
     grads, segs, early = [], [], []
     from surface_texture_inpainting_net_amd import functional as SF2
-    assert SF2.USE_NET_CALL, 'the test is about the whole-network node (functional.NetFn)'
+    if per_block:                         # every fused block outside the bottleneck chain is a one-op node of its own: a segment
+        SF2.USE_NET_CALL = False          # spans several nodes, each of which sees only its own blocks' events
+    else:
+        assert SF2.USE_NET_CALL, 'the test is about the whole-network node (functional.NetFn)'
     for _ in range(3):
         step.bucket.overlap_log = []
         step(s)
@@ -371,7 +374,7 @@ def _overlap_worker(rank, world, port, out_dir, min_bytes, mix=False):
         early.append(sum(1 for _, e in step.bucket.overlap_log if e.elapsed_time(step.bucket.backward_end) > 0.0))
     step.finish()
     torch.save({'grads': grads, 'segs': segs, 'early': early, 'p': torch.cat([p.detach().reshape(-1) for p in net.parameters()]).cpu()},
-               os.path.join(out_dir, 'r%d_%d%s.pt' % (rank, min_bytes, '_mix' if mix else '')))
+               os.path.join(out_dir, 'r%d_%d%s%s.pt' % (rank, min_bytes, '_mix' if mix else '', '_pb' if per_block else '')))
     dist.barrier()
     dist.destroy_process_group()
 
@@ -449,6 +452,15 @@ def test_segmented_allreduce_during_backward_equals_the_single_tail_allreduce(tm
     mp.spawn(_overlap_worker, args=(2, _free_port(), str(tmp_path), 256 << 10, True), nprocs=2, join=True)
     for r in range(2):
         mixed = torch.load(tmp_path / ('r%d_%d_mix.pt' % (r, 256 << 10)))
+        assert mixed['segs'][1] >= 2
+        for a, b in zip(res[0][r]['grads'], mixed['grads']):
+            assert torch.equal(a, b)
+        assert torch.equal(res[0][r]['p'], mixed['p'])
+    # the same mix with every block a node of its own (USE_NET_CALL off): a segment completed by a block that stayed on the
+    # compute stream holds gradients an EARLIER node left on the side stream - its all-reduce must wait for that stream too
+    mp.spawn(_overlap_worker, args=(2, _free_port(), str(tmp_path), 256 << 10, True, True), nprocs=2, join=True)
+    for r in range(2):
+        mixed = torch.load(tmp_path / ('r%d_%d_mix_pb.pt' % (r, 256 << 10)))
         assert mixed['segs'][1] >= 2
         for a, b in zip(res[0][r]['grads'], mixed['grads']):
             assert torch.equal(a, b)
