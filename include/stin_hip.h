@@ -183,6 +183,14 @@ int stin_segment_sum_f32(const float* src, int64_t ld_src, const int32_t* rowptr
 int stin_edge_relu_mean_fwd_f32(const float* A, int64_t lda, const float* B, int64_t ldb,
                                 const int32_t* rowptr, const int32_t* col, int64_t N, int H,
                                 float* out, int64_t ldo, int indicator, uint32_t* mask, stin_stream_t stream);
+/* The same stage through a row map: A, B hold M distinct rows and row i of the N stands for row row_map[i] of them (a decoder
+ * block behind an unpool step: row_map = the unpool trace, A | B = the first product over the COARSE rows):
+ *   out[i,:] = mean_{j in N(i)} ReLU( A[row_map[i],:] + B[row_map[j],:] )
+ * Same arithmetic, indicator column and mask words as stin_edge_relu_mean_fwd_f32 on the gathered rows, bit for bit.  fp32 rows,
+ * H a saved-mask width (128, 256, 512, 1024, 2048), 16-byte rows; every row_map value must lie in [0, M). */
+int stin_edge_relu_mean_fwd_map_f32(const float* A, int64_t lda, const float* B, int64_t ldb, const int32_t* rowptr,
+                                    const int32_t* col, const int32_t* row_map, int64_t N, int H, float* out, int64_t ldo,
+                                    int indicator, uint32_t* mask, stin_stream_t stream);
 /* Backward from the saved mask instead of recomputing it (H % 128 == 0):
  *   bwd_dst_mask: dA[i,:] = inv_deg[i] * G[i,:] * popcount over the in-edge slots of i   (streams H/8 bytes
  *                 per edge instead of gathering a B row)
@@ -318,6 +326,10 @@ int stin_colreduce_f32(int mode, const float* x, int64_t ldx, const float* gout,
 int stin_norm_act_res_fwd_f32(const float* x, int64_t ldx, const float* mean, const float* rstd,
                               const int32_t* gid, const float* res, int64_t ldres, int64_t N, int C, int act,
                               float* y, int64_t ldy, stin_stream_t stream);
+/* ... with the residual read through a row map: y[r] = res[row_map[r]] + ELU(...) (res, row_map not NULL) */
+int stin_norm_act_res_fwd_map_f32(const float* x, int64_t ldx, const float* mean, const float* rstd, const int32_t* gid,
+                                  const float* res, int64_t ldres, const int32_t* row_map, int64_t N, int C, int act, float* y,
+                                  int64_t ldy, stin_stream_t stream);
 /* dx = a[gid] * dY + k[sid] * (x - mean[gid]) + m[sid],  dY = gout * act'((x-mean[gid])*rstd[gid]) */
 int stin_norm_act_bwd_f32(const float* x, int64_t ldx, const float* gout, int64_t ldg, const float* mean,
                           const float* rstd, const float* a, const float* k, const float* m,
@@ -663,6 +675,10 @@ int stin_norm_fold_rows(int64_t N, int C, int64_t groups);
 int stin_norm_act_res_fwd_fold_f32(const double* partial, int64_t groups, const float* x, int64_t ldx, const float* res,
                                    int64_t ldres, const float* inv_cnt, float eps, int64_t N, int C, float* mean, float* rstd,
                                    float* y, int64_t ldy, stin_stream_t stream);
+/* the forward form with the residual read through a row map (y[r] += res[row_map[r]]; res, row_map not NULL) */
+int stin_norm_act_res_fwd_fold_map_f32(const double* partial, int64_t groups, const float* x, int64_t ldx, const float* res,
+                                       int64_t ldres, const int32_t* row_map, const float* inv_cnt, float eps, int64_t N, int C,
+                                       float* mean, float* rstd, float* y, int64_t ldy, stin_stream_t stream);
 int stin_norm_act_bwd_fold_f32(const double* partial, int64_t groups, const float* x, int64_t ldx, const float* gout, int64_t ldg,
                                const float* mean, const float* rstd, const float* inv_cnt, int64_t N, int C, float* dx,
                                int64_t lddx, stin_stream_t stream);
@@ -766,6 +782,14 @@ int stin_linear_tanh_bwd_bf16(const float* g, const float* y, const stin_bf16_t*
  *        CALLER must order any reader of dW1 .. dbs after ev_done and keep bwd_ws, x, hE and g alive until then.  Without
  *        use_side a non-NULL ev_done is recorded on `stream` behind the block's last gradient write.  The events are
  *        caller-owned hipEvent_t.
+ *     y_from_src != 0 (forward, fp32 rows, a shortcut block in the wide layout right behind the STIN_OP_UNPOOL op whose output
+ *        it reads): x_up[v] = x_c[trace[v]] makes every row of Y = x_up Wcat^T + bcat a copy of a row of Yc = x_c Wcat^T + bcat
+ *        (a row of an NT product depends on no other row), so the product runs over the unpool op's n_in COARSE rows - Y is
+ *        [n_in, Yw] - and the edge stage and the residual read Y through the trace (stin_edge_relu_mean_fwd_map_f32,
+ *        stin_norm_act_res_fwd*_map_f32).  hE, mask, agg, mean / rstd and out have the same bits as with 0 (the behaviour of every
+ *        earlier caller); backward is untouched, it reads x and never Y.  The unpool op's gather still runs when it has an `out`
+ *        (x is kept for backward); with out == NULL - a forward nobody differentiates - it is skipped and the block's x is unused.
+ *        A flag on a block where these conditions do not hold is STIN_E_UNSUPPORTED (its Y is sized for the coarse rows).
  *   STIN_OP_POOL_MAX: x [n_in, Cout] -> out [n_out, Cout], arg [n_out, Cout]; rowptr_dst / col_dst = the children CSR, trace = the
  *     fine -> coarse map (backward).  STIN_OP_UNPOOL: out[v] = x[trace[v]] (n_out fine rows); backward = the segment sum
  *     over the children CSR. */
@@ -782,7 +806,7 @@ size_t stin_edgeconv_block_bwd_workspace_bytes(int64_t N, int Cp, int H, int Cou
 #define STIN_OP_POOL_MAX 1
 #define STIN_OP_UNPOOL 2
 typedef struct stin_net_op {
-    int32_t kind, Cin, Cp, H, Cout, has_shortcut, trans_inv, prec_fwd, fwd_split, bwd_split, B, slice_quirk, use_side, reserved0,
+    int32_t kind, Cin, Cp, H, Cout, has_shortcut, trans_inv, prec_fwd, fwd_split, bwd_split, B, slice_quirk, use_side, y_from_src,
         reserved1, reserved2;
     float eps;
     int32_t reserved3;

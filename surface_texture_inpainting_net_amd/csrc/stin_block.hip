@@ -133,13 +133,24 @@ extern "C" size_t stin_edgeconv_block_bwd_workspace_bytes(int64_t N, int Cp, int
     return bwd_layout(N, H, Cout, has_shortcut, B, storage).tn + up256(stin_edgeconv_wgrad_workspace_bytes(N, Cp, H, Cout, has_shortcut)) + 256;
 }
 
+// The unpool op `Un` in front of block `J` commutes with the block's first product (stin_net_op_t::y_from_src): the block reads
+// exactly that op's output, fp32 rows, a shortcut (the residual comes out of Y, not out of x) and A materialised in Y.
+static bool commutes(int storage, const stin_net_op_t& Un, const stin_net_op_t& J) {
+    return storage == 0 && Un.kind == STIN_OP_UNPOOL && J.kind == STIN_OP_BLOCK && J.y_from_src != 0 && J.x == Un.out &&
+           J.n_out == Un.n_out && J.Cin == Un.Cout && J.Cp == J.Cin && J.ldx == Un.ldo && J.has_shortcut != 0 &&
+           J.trans_inv != STIN_TI_COMPACT && Un.trace != nullptr && Un.x != nullptr && Un.n_in > 0;
+}
+
 // Forward of one STIN_OP_BLOCK op (include/stin_hip.h: stin_net_op_t).  storage: 0 = fp32 rows, 1 = bf16 rows (x, Y, hE, agg, out).
-static int block_fwd(int storage, const stin_net_op_t& J, stin_stream_t stream) {
+// Un != NULL (y_from_src, checked by `commutes`): the unpool op in front - the first product runs on ITS input rows and the edge
+// stage and the residual read Y through its trace.
+static int block_fwd(int storage, const stin_net_op_t& J, stin_stream_t stream, const stin_net_op_t* Un = nullptr) {
     const int64_t N = J.n_out;
     const int Cp = J.Cp, H = J.H, Cout = J.Cout;
     STIN_REQUIRE(N >= 0 && J.Cin > 0 && Cp >= J.Cin && H > 0 && Cout > 0 && J.B > 0, STIN_E_SIZE);
     // mask == NULL (round 6): a forward nobody differentiates (torch.no_grad() / evaluation) - the ReLU mask is not stored
-    STIN_REQUIRE(J.x && J.W1 && J.W2 && J.rowptr_dst && J.wcatT && J.w2T && J.Y && J.hE && J.agg && J.mean && J.rstd && J.out && J.fwd_ws,
+    STIN_REQUIRE((J.x || Un) && J.W1 && J.W2 && J.rowptr_dst && J.wcatT && J.w2T && J.Y && J.hE && J.agg && J.mean && J.rstd && J.out &&
+                     J.fwd_ws,
                  STIN_E_NULL);
     STIN_REQUIRE(J.fwd_ws_bytes >= stin_edgeconv_block_fwd_workspace_bytes(J.Cin, Cp, H, Cout, J.has_shortcut, J.B), STIN_E_WORKSPACE);
     // trans_inv == STIN_TI_COMPACT (round 6, fp32 rows): Y = [B | S], the edge stage forms A_i = b1 - B_i (stin_common.h: stin_yw)
@@ -172,9 +183,17 @@ static int block_fwd(int storage, const stin_net_op_t& J, stin_stream_t stream) 
         float* Yf = static_cast<float*>(J.Y);
         float* hf = static_cast<float*>(J.hE);
         float* aggf = static_cast<float*>(J.agg);
-        STIN_TRY(stin_gemm_nt_f32(static_cast<const float*>(J.x), J.ldx, wcat, Cp, bcat, nullptr, 0, nullptr, 0, N, Yw, Cp, Yf, J.ldy, pf,
-                                  stream));
-        if (compact)
+        const int32_t* row_map = Un ? Un->trace : nullptr;
+        if (Un)     // Yc = x_c Wcat^T + bcat over the coarse rows: Y[v] of the unpooled input is Yc[trace[v]], bit for bit
+            STIN_TRY(stin_gemm_nt_f32(static_cast<const float*>(Un->x), Un->ldx, wcat, Cp, bcat, nullptr, 0, nullptr, 0, Un->n_in, Yw, Cp,
+                                      Yf, J.ldy, pf, stream));
+        else
+            STIN_TRY(stin_gemm_nt_f32(static_cast<const float*>(J.x), J.ldx, wcat, Cp, bcat, nullptr, 0, nullptr, 0, N, Yw, Cp, Yf, J.ldy,
+                                      pf, stream));
+        if (Un)
+            STIN_EDGE_BRACKET(stin_edge_relu_mean_fwd_map_f32(Yf, J.ldy, Yf + H, J.ldy, J.rowptr_dst, J.col_dst, row_map, N, H, hf, J.ldh,
+                                                              1, J.mask, stream));
+        else if (compact)
             STIN_EDGE_BRACKET(stin_edge_relu_mean_fwd_ti_f32(J.b1, Yf, J.ldy, J.rowptr_dst, J.col_dst, N, H, hf, J.ldh, 1, J.mask, stream));
         else
             STIN_EDGE_BRACKET(stin_edge_relu_mean_fwd_f32(Yf, J.ldy, Yf + H, J.ldy, J.rowptr_dst, J.col_dst, N, H, hf, J.ldh, 1, J.mask,
@@ -191,8 +210,13 @@ static int block_fwd(int storage, const stin_net_op_t& J, stin_stream_t stream) 
             // partials - no separate fold launch on the critical path; same sums, same order: bit-identical (k_norm_fold)
             int rc_fold = STIN_E_UNSUPPORTED;
             if (N > 0 && stin_norm_fold_rows(N, Cout, stat_groups) > 0)
-                rc_fold = stin_norm_act_res_fwd_fold_f32(partial, stat_groups, aggf, Cout, static_cast<const float*>(res), ld_res, J.inv_cnt,
-                                                         J.eps, N, Cout, J.mean, J.rstd, static_cast<float*>(J.out), J.ldo, stream);
+                rc_fold = row_map
+                              ? stin_norm_act_res_fwd_fold_map_f32(partial, stat_groups, aggf, Cout, static_cast<const float*>(res), ld_res,
+                                                                   row_map, J.inv_cnt, J.eps, N, Cout, J.mean, J.rstd,
+                                                                   static_cast<float*>(J.out), J.ldo, stream)
+                              : stin_norm_act_res_fwd_fold_f32(partial, stat_groups, aggf, Cout, static_cast<const float*>(res), ld_res,
+                                                               J.inv_cnt, J.eps, N, Cout, J.mean, J.rstd, static_cast<float*>(J.out),
+                                                               J.ldo, stream);
             if (rc_fold == STIN_OK) normed = true;
             else if (rc_fold != STIN_E_UNSUPPORTED) return rc_fold;
             else STIN_TRY(stin_moments_final_f32(partial, stat_groups, Cout, J.inv_cnt, J.eps, J.mean, J.rstd, stream));
@@ -200,7 +224,10 @@ static int block_fwd(int storage, const stin_net_op_t& J, stin_stream_t stream) 
             STIN_TRY(stin_gemm_nt_f32(hf, J.ldh, w2_op, H, J.b2, hf + H, J.ldh, nullptr, 0, N, Cout, H, aggf, Cout, pf, stream));
             STIN_TRY(fwd_stats(0, J, red_ws, red_bytes, stream));
         }
-        if (!normed)
+        if (!normed && row_map)
+            STIN_TRY(stin_norm_act_res_fwd_map_f32(aggf, Cout, J.mean, J.rstd, J.gid, static_cast<const float*>(res), ld_res, row_map, N,
+                                                   Cout, 1, static_cast<float*>(J.out), J.ldo, stream));
+        else if (!normed)
             STIN_TRY(stin_norm_act_res_fwd_f32(aggf, Cout, J.mean, J.rstd, J.gid, static_cast<const float*>(res), ld_res, N, Cout, 1,
                                                static_cast<float*>(J.out), J.ldo, stream));
     } else {
@@ -408,7 +435,9 @@ extern "C" int stin_net_fwd(int storage, const stin_net_op_t* ops, int n_ops, st
     for (int i = 0; i < n_ops; ++i) {
         const stin_net_op_t& J = ops[i];
         if (J.kind == STIN_OP_BLOCK) {
-            STIN_TRY(block_fwd(storage, J, stream));
+            const stin_net_op_t* un = (i > 0 && commutes(storage, ops[i - 1], J)) ? &ops[i - 1] : nullptr;
+            STIN_REQUIRE(un != nullptr || J.y_from_src == 0, STIN_E_UNSUPPORTED);     // (its Y holds the coarse rows only)
+            STIN_TRY(block_fwd(storage, J, stream, un));
         } else if (J.kind == STIN_OP_POOL_MAX) {
             if (storage)
                 STIN_TRY(stin_pool_max_fwd_bf16(static_cast<const stin_bf16_t*>(J.x), J.ldx, J.rowptr_dst, J.col_dst, J.n_out, J.Cout,
@@ -417,6 +446,8 @@ extern "C" int stin_net_fwd(int storage, const stin_net_op_t* ops, int n_ops, st
                 STIN_TRY(stin_pool_max_fwd_f32(static_cast<const float*>(J.x), J.ldx, J.rowptr_dst, J.col_dst, J.n_out, J.Cout,
                                                static_cast<float*>(J.out), J.ldo, J.arg, stream));
         } else if (J.kind == STIN_OP_UNPOOL) {
+            // no output: a forward nobody differentiates, whose next block takes its first product from this op's input rows
+            if (J.out == nullptr && i + 1 < n_ops && commutes(storage, J, ops[i + 1])) continue;
             if (storage)
                 STIN_TRY(stin_gather_rows_bf16(static_cast<const stin_bf16_t*>(J.x), J.ldx, J.trace, nullptr, J.n_out, J.Cout,
                                                static_cast<stin_bf16_t*>(J.out), J.ldo, stream));

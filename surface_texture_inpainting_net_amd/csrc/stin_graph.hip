@@ -84,13 +84,18 @@ struct Lane {
 // wrote when it multiplied by [-W1 ; W1] this differs by at most one unit in the last place of the matrix-core accumulator (the
 // MFMA's internal adder is not symmetric under negation: measured 2.4e-7 .. 9.5e-7 absolute on unit-scale rows) - both are fp32
 // evaluations of W1 (x_j - x_i) + b1.
-template <typename T, int G, int VPL, int U, bool EXACT, bool TI = false>
+// MAP (decoder blocks behind an unpool step): A and B hold the COARSE rows of the block's first product and row_map [N] is the
+// unpool trace, so the row's own operand is A[row_map[i]] and neighbour e reads B[row_map[col[e]]] - the rows the product over the
+// unpooled input would hold, bit for bit, without that product's ~3.3 copies of every distinct row.  The composed index costs one
+// dependent 4-byte load per neighbour from a list that stays in L2 (0.8 MB at 200 704 rows).  A coarse A row is read by all of
+// its fine rows, so it goes through plain loads here.
+template <typename T, int G, int VPL, int U, bool EXACT, bool TI = false, bool MAP = false>
 __device__ __forceinline__ void edge_fwd_body(const T* __restrict__ A, int64_t lda,
                                               const T* __restrict__ B, int64_t ldb,
                                               const int32_t* __restrict__ rowptr,
                                               const int32_t* __restrict__ col, int64_t N, int H,
                                               T* __restrict__ out, int64_t ldo, int indicator,
-                                              uint32_t* __restrict__ mask) {
+                                              uint32_t* __restrict__ mask, const int32_t* __restrict__ row_map = nullptr) {
     Lane<G, VPL> L;
     const bool row_ok = L.row < N;
     if (!row_ok) return;
@@ -104,6 +109,8 @@ __device__ __forceinline__ void edge_fwd_body(const T* __restrict__ A, int64_t l
             const float4 bo = ld4(B + L.row * ldb + L.chan(k));
             const float4 bi = A != nullptr ? ld4(A + L.chan(k)) : f4zero();
             a[k] = make_float4(bi.x - bo.x, bi.y - bo.y, bi.z - bo.z, bi.w - bo.w);
+        } else if (MAP) {
+            a[k] = on[k] ? ld4(A + (int64_t)row_map[L.row] * lda + L.chan(k)) : f4zero();
         } else {
             a[k] = on[k] ? ld4_stream(A + L.row * lda + L.chan(k)) : f4zero();
         }
@@ -116,7 +123,7 @@ __device__ __forceinline__ void edge_fwd_body(const T* __restrict__ A, int64_t l
 #pragma unroll
         for (int u = 0; u < U; ++u) {
             const int ee = min(e + u, end - 1);          // clamped: branch-free, always a valid row
-            const int64_t j = col[ee];
+            const int64_t j = MAP ? row_map[col[ee]] : col[ee];
 #pragma unroll
             for (int k = 0; k < VPL; ++k) b[u][k] = on[k] ? ld4(B + j * ldb + L.chan(k)) : f4zero();
         }
@@ -180,6 +187,13 @@ __global__ __launch_bounds__(BLOCK) void k_edge_fwd_exact(const T* __restrict__ 
                                                           int64_t N, int H, T* __restrict__ out, int64_t ldo, int indicator,
                                                           uint32_t* __restrict__ mask) {
     edge_fwd_body<T, G, VPL, U, true>(A, lda, B, ldb, rowptr, col, N, H, out, ldo, indicator, mask);
+}
+template <typename T, int G, int VPL, int U>
+__global__ __launch_bounds__(BLOCK) void k_edge_fwd_map(const T* __restrict__ A, int64_t lda, const T* __restrict__ B, int64_t ldb,
+                                                        const int32_t* __restrict__ rowptr, const int32_t* __restrict__ col,
+                                                        const int32_t* __restrict__ row_map, int64_t N, int H, T* __restrict__ out,
+                                                        int64_t ldo, int indicator, uint32_t* __restrict__ mask) {
+    edge_fwd_body<T, G, VPL, U, true, false, true>(A, lda, B, ldb, rowptr, col, N, H, out, ldo, indicator, mask, row_map);
 }
 
 template <typename T, int G, int VPL, int U>
@@ -1532,6 +1546,19 @@ int edge_fwd_impl(const T* A, int64_t lda, const T* B, int64_t ldb, const int32_
     return stin_launch_status();
 }
 
+// the forward edge stage through a row map (k_edge_fwd_map): fp32 rows at the saved-mask widths only - what a block op runs at
+int edge_fwd_map_impl(const float* A, int64_t lda, const float* B, int64_t ldb, const int32_t* rowptr, const int32_t* col,
+                      const int32_t* row_map, int64_t N, int H, float* out, int64_t ldo, int indicator, uint32_t* mask,
+                      hipStream_t stream) {
+    typedef float T;
+    STIN_REQUIRE(N >= 0 && H > 0 && lda >= H && ldb >= H && ldo >= H + (indicator ? 4 : 0), STIN_E_SIZE);
+    STIN_REQUIRE(mask_shape_ok(H) && vec_ok<T>(H, {A, B, out}, {lda, ldb, ldo}), STIN_E_UNSUPPORTED);
+    if (N == 0) return STIN_OK;
+    STIN_REQUIRE(A && B && rowptr && row_map && out, STIN_E_NULL);
+    STIN_DISPATCH(H, k_edge_fwd_map, 1, A, lda, B, ldb, rowptr, col, row_map, N, H, out, ldo, indicator, mask);
+    return stin_launch_status();
+}
+
 template <typename T>
 int edge_bwd_dst_mask_impl(const T* G, int64_t ldg, const uint32_t* mask, const int32_t* rowptr, int64_t N, int H, T* dA,
                            int64_t ldda, hipStream_t stream) {
@@ -1796,6 +1823,12 @@ extern "C" int stin_edge_relu_mean_fwd_f32(const float* A, int64_t lda, const fl
                                            int64_t ldo, int indicator, uint32_t* mask, stin_stream_t stream) {
     stin_clear_stale_error();
     return edge_fwd_impl<float>(A, lda, B, ldb, rowptr, col, N, H, out, ldo, indicator, mask, (hipStream_t)stream);
+}
+extern "C" int stin_edge_relu_mean_fwd_map_f32(const float* A, int64_t lda, const float* B, int64_t ldb, const int32_t* rowptr,
+                                               const int32_t* col, const int32_t* row_map, int64_t N, int H, float* out, int64_t ldo,
+                                               int indicator, uint32_t* mask, stin_stream_t stream) {
+    stin_clear_stale_error();
+    return edge_fwd_map_impl(A, lda, B, ldb, rowptr, col, row_map, N, H, out, ldo, indicator, mask, (hipStream_t)stream);
 }
 extern "C" int stin_edge_relu_mean_fwd_bf16(const stin_bf16_t* A, int64_t lda, const stin_bf16_t* B, int64_t ldb,
                                             const int32_t* rowptr, const int32_t* col, int64_t N, int H,

@@ -490,12 +490,13 @@ __global__ void k_moments_final(const double* __restrict__ partial, int nch, int
     }
 }
 
-template <typename T, int VW>
-__global__ __launch_bounds__(BLOCK) void k_norm_fwd(const T* __restrict__ x, int64_t ldx,
-                                                    const float* __restrict__ mean, const float* __restrict__ rstd,
-                                                    const int32_t* __restrict__ gid, const T* __restrict__ res,
-                                                    int64_t ldres, int64_t N, int C, int act, T* __restrict__ y,
-                                                    int64_t ldy) {
+// MAP: the residual row of output row r is res[row_map[r]] (a decoder block behind an unpool step, whose shortcut columns exist
+// for the coarse rows only); everything else is the plain kernel
+template <typename T, int VW, bool MAP>
+__device__ __forceinline__ void norm_fwd_body(const T* __restrict__ x, int64_t ldx, const float* __restrict__ mean,
+                                              const float* __restrict__ rstd, const int32_t* __restrict__ gid,
+                                              const T* __restrict__ res, int64_t ldres, const int32_t* __restrict__ row_map, int64_t N,
+                                              int C, int act, T* __restrict__ y, int64_t ldy) {
     crit_prio();
     const int CV = C / VW;
     const int64_t t = (int64_t)blockIdx.x * BLOCK + threadIdx.x;
@@ -514,11 +515,27 @@ __global__ __launch_bounds__(BLOCK) void k_norm_fwd(const T* __restrict__ x, int
         o.v[i] = n;
     }
     if (res != nullptr) {
-        const V<VW> rv = V<VW>::load(res + r * ldres + c);
+        const V<VW> rv = V<VW>::load(res + (MAP ? (int64_t)row_map[r] : r) * ldres + c);
 #pragma unroll
         for (int i = 0; i < VW; ++i) o.v[i] += rv.v[i];
     }
     o.store(y + r * ldy + c);
+}
+template <typename T, int VW>
+__global__ __launch_bounds__(BLOCK) void k_norm_fwd(const T* __restrict__ x, int64_t ldx,
+                                                    const float* __restrict__ mean, const float* __restrict__ rstd,
+                                                    const int32_t* __restrict__ gid, const T* __restrict__ res,
+                                                    int64_t ldres, int64_t N, int C, int act, T* __restrict__ y,
+                                                    int64_t ldy) {
+    norm_fwd_body<T, VW, false>(x, ldx, mean, rstd, gid, res, ldres, nullptr, N, C, act, y, ldy);
+}
+template <typename T, int VW>
+__global__ __launch_bounds__(BLOCK) void k_norm_fwd_map(const T* __restrict__ x, int64_t ldx,
+                                                        const float* __restrict__ mean, const float* __restrict__ rstd,
+                                                        const int32_t* __restrict__ gid, const T* __restrict__ res,
+                                                        int64_t ldres, const int32_t* __restrict__ row_map, int64_t N, int C, int act,
+                                                        T* __restrict__ y, int64_t ldy) {
+    norm_fwd_body<T, VW, true>(x, ldx, mean, rstd, gid, res, ldres, row_map, N, C, act, y, ldy);
 }
 
 template <typename T, int VW>
@@ -627,11 +644,13 @@ __device__ __forceinline__ void fold_lane_moments(const double* __restrict__ p, 
 // BWD = false: y = ELU((x - mean) rstd) + res with (mean, rstd) folded from moment partials; mean_io / rstd_io are OUTPUTS.
 // BWD = true:  dx = rstd dy + k xc + m, dy = g ELU'((x - mean) rstd), (k, m) folded from the (dy xc, dy) partials; mean_io /
 //              rstd_io are INPUTS.  One graph (B = 1), fp32 rows, C % 32 == 0, 16-byte rows.
-template <bool BWD>
-__global__ __launch_bounds__(NF_BLOCK) void k_norm_fold(const double* __restrict__ partial, int nch, const float* __restrict__ x, int64_t ldx,
-                                                        const float* __restrict__ other, int64_t ldo, float* __restrict__ mean_io,
-                                                        float* __restrict__ rstd_io, const float* __restrict__ inv_cnt, float eps,
-                                                        int64_t N, int C, int rows_per_block, float* __restrict__ y, int64_t ldy) {
+// MAP (forward only): the residual row of output row r is other[row_map[r]] (see norm_fwd_body).
+template <bool BWD, bool MAP>
+__device__ __forceinline__ void norm_fold_body(const double* __restrict__ partial, int nch, const float* __restrict__ x, int64_t ldx,
+                                               const float* __restrict__ other, int64_t ldo, const int32_t* __restrict__ row_map,
+                                               float* __restrict__ mean_io, float* __restrict__ rstd_io,
+                                               const float* __restrict__ inv_cnt, float eps, int64_t N, int C, int rows_per_block,
+                                               float* __restrict__ y, int64_t ldy) {
     __shared__ double sm[2][FIN_KL][NF_GC + 1];
     __shared__ __attribute__((aligned(16))) float coef[4][NF_GC];                 // fwd: mean, rstd; bwd: mean, rstd, k, m
     crit_prio();
@@ -695,7 +714,7 @@ __global__ __launch_bounds__(NF_BLOCK) void k_norm_fold(const double* __restrict
         for (int u = 0; u < UR; ++u) {
             const int64_t r = rb + u * NF_RL < r1 ? rb + u * NF_RL : rb;
             xv[u] = ld4(x + r * ldx + c);
-            ov[u] = other != nullptr ? ld4(other + r * ldo + c) : make_float4(0.f, 0.f, 0.f, 0.f);
+            ov[u] = other != nullptr ? ld4(other + (MAP ? (int64_t)row_map[r] : r) * ldo + c) : make_float4(0.f, 0.f, 0.f, 0.f);
         }
 #pragma unroll
         for (int u = 0; u < UR; ++u) {
@@ -718,6 +737,20 @@ __global__ __launch_bounds__(NF_BLOCK) void k_norm_fold(const double* __restrict
             st4(y + r * ldy + c, make_float4(o[0], o[1], o[2], o[3]));
         }
     }
+}
+template <bool BWD>
+__global__ __launch_bounds__(NF_BLOCK) void k_norm_fold(const double* __restrict__ partial, int nch, const float* __restrict__ x, int64_t ldx,
+                                                        const float* __restrict__ other, int64_t ldo, float* __restrict__ mean_io,
+                                                        float* __restrict__ rstd_io, const float* __restrict__ inv_cnt, float eps,
+                                                        int64_t N, int C, int rows_per_block, float* __restrict__ y, int64_t ldy) {
+    norm_fold_body<BWD, false>(partial, nch, x, ldx, other, ldo, nullptr, mean_io, rstd_io, inv_cnt, eps, N, C, rows_per_block, y, ldy);
+}
+__global__ __launch_bounds__(NF_BLOCK) void k_norm_fold_map(const double* __restrict__ partial, int nch, const float* __restrict__ x,
+                                                            int64_t ldx, const float* __restrict__ other, int64_t ldo,
+                                                            const int32_t* __restrict__ row_map, float* __restrict__ mean_io,
+                                                            float* __restrict__ rstd_io, const float* __restrict__ inv_cnt, float eps,
+                                                            int64_t N, int C, int rows_per_block, float* __restrict__ y, int64_t ldy) {
+    norm_fold_body<false, true>(partial, nch, x, ldx, other, ldo, row_map, mean_io, rstd_io, inv_cnt, eps, N, C, rows_per_block, y, ldy);
 }
 
 // BatchNorm1d-with-affine over all rows (+ ReLU): forward and backward elementwise passes (fp32, SingleConvMeshNet)
@@ -947,24 +980,37 @@ int colreduce_impl(int mode, const T* x, int64_t ldx, const T* gout, int64_t ldg
     return stin_launch_status();
 }
 
+// row_map != NULL: the residual rows go through it (k_norm_fwd_map), same launch geometry
 template <typename T>
 int norm_fwd_impl(const T* x, int64_t ldx, const float* mean, const float* rstd, const int32_t* gid, const T* res,
-                  int64_t ldres, int64_t N, int C, int act, T* y, int64_t ldy, hipStream_t stream) {
+                  int64_t ldres, int64_t N, int C, int act, T* y, int64_t ldy, hipStream_t stream, const int32_t* row_map = nullptr) {
     STIN_REQUIRE(N >= 0 && C > 0 && ldx >= C && ldy >= C && (res == nullptr || ldres >= C), STIN_E_SIZE);
     if (N == 0) return STIN_OK;
     STIN_REQUIRE(x && mean && rstd && y, STIN_E_NULL);
     if (vec8_ok<T>(C, {x, res, y}, {mean, rstd}, {ldx, ldy, res ? ldres : 0})) {
         const int64_t n = N * (C / 8);
-        hipLaunchKernelGGL((k_norm_fwd<T, 8>), dim3((unsigned)((n + BLOCK - 1) / BLOCK)), dim3(BLOCK), 0, stream, x, ldx,
-                           mean, rstd, gid, res, ldres, N, C, act, y, ldy);
+        if (row_map != nullptr)
+            hipLaunchKernelGGL((k_norm_fwd_map<T, 8>), dim3((unsigned)((n + BLOCK - 1) / BLOCK)), dim3(BLOCK), 0, stream, x, ldx,
+                               mean, rstd, gid, res, ldres, row_map, N, C, act, y, ldy);
+        else
+            hipLaunchKernelGGL((k_norm_fwd<T, 8>), dim3((unsigned)((n + BLOCK - 1) / BLOCK)), dim3(BLOCK), 0, stream, x, ldx,
+                               mean, rstd, gid, res, ldres, N, C, act, y, ldy);
     } else if (vec4_ok<T>(C, {x, res, y}, {mean, rstd}, {ldx, ldy, res ? ldres : 0})) {
         const int64_t n = N * (C / 4);
-        hipLaunchKernelGGL((k_norm_fwd<T, 4>), dim3((unsigned)((n + BLOCK - 1) / BLOCK)), dim3(BLOCK), 0, stream, x, ldx,
-                           mean, rstd, gid, res, ldres, N, C, act, y, ldy);
+        if (row_map != nullptr)
+            hipLaunchKernelGGL((k_norm_fwd_map<T, 4>), dim3((unsigned)((n + BLOCK - 1) / BLOCK)), dim3(BLOCK), 0, stream, x, ldx,
+                               mean, rstd, gid, res, ldres, row_map, N, C, act, y, ldy);
+        else
+            hipLaunchKernelGGL((k_norm_fwd<T, 4>), dim3((unsigned)((n + BLOCK - 1) / BLOCK)), dim3(BLOCK), 0, stream, x, ldx,
+                               mean, rstd, gid, res, ldres, N, C, act, y, ldy);
     } else if constexpr (is_f32((const T*)nullptr)) {
         const int64_t n = N * C;
-        hipLaunchKernelGGL((k_norm_fwd<T, 1>), dim3((unsigned)((n + BLOCK - 1) / BLOCK)), dim3(BLOCK), 0, stream, x, ldx,
-                           mean, rstd, gid, res, ldres, N, C, act, y, ldy);
+        if (row_map != nullptr)
+            hipLaunchKernelGGL((k_norm_fwd_map<T, 1>), dim3((unsigned)((n + BLOCK - 1) / BLOCK)), dim3(BLOCK), 0, stream, x, ldx,
+                               mean, rstd, gid, res, ldres, row_map, N, C, act, y, ldy);
+        else
+            hipLaunchKernelGGL((k_norm_fwd<T, 1>), dim3((unsigned)((n + BLOCK - 1) / BLOCK)), dim3(BLOCK), 0, stream, x, ldx,
+                               mean, rstd, gid, res, ldres, N, C, act, y, ldy);
     } else {
         return STIN_E_UNSUPPORTED;
     }
@@ -1029,6 +1075,20 @@ extern "C" int stin_norm_act_res_fwd_fold_f32(const double* partial, int64_t gro
     if (rows <= 0 || !vec4_ok<float>(C, {x, res, y}, {}, {ldx, ldy, res ? ldres : 0})) return STIN_E_UNSUPPORTED;
     hipLaunchKernelGGL((k_norm_fold<false>), dim3((unsigned)(C / NF_GC), (unsigned)((N + rows - 1) / rows)), dim3(NF_BLOCK), 0,
                        (hipStream_t)stream, partial, (int)groups, x, ldx, res, ldres, mean, rstd, inv_cnt, eps, N, C, rows, y, ldy);
+    return stin_launch_status();
+}
+
+extern "C" int stin_norm_act_res_fwd_fold_map_f32(const double* partial, int64_t groups, const float* x, int64_t ldx, const float* res,
+                                                  int64_t ldres, const int32_t* row_map, const float* inv_cnt, float eps, int64_t N,
+                                                  int C, float* mean, float* rstd, float* y, int64_t ldy, stin_stream_t stream) {
+    stin_clear_stale_error();
+    STIN_REQUIRE(N > 0 && C > 0 && ldx >= C && ldy >= C && ldres >= C, STIN_E_SIZE);
+    STIN_REQUIRE(partial && x && res && row_map && inv_cnt && mean && rstd && y, STIN_E_NULL);
+    const int rows = norm_fold_rows(N, C, groups);
+    if (rows <= 0 || !vec4_ok<float>(C, {x, res, y}, {}, {ldx, ldy, ldres})) return STIN_E_UNSUPPORTED;
+    hipLaunchKernelGGL(k_norm_fold_map, dim3((unsigned)(C / NF_GC), (unsigned)((N + rows - 1) / rows)), dim3(NF_BLOCK), 0,
+                       (hipStream_t)stream, partial, (int)groups, x, ldx, res, ldres, row_map, mean, rstd, inv_cnt, eps, N, C, rows, y,
+                       ldy);
     return stin_launch_status();
 }
 
@@ -1101,6 +1161,13 @@ extern "C" int stin_norm_act_res_fwd_f32(const float* x, int64_t ldx, const floa
                                          float* y, int64_t ldy, stin_stream_t stream) {
     stin_clear_stale_error();
     return norm_fwd_impl<float>(x, ldx, mean, rstd, gid, res, ldres, N, C, act, y, ldy, (hipStream_t)stream);
+}
+extern "C" int stin_norm_act_res_fwd_map_f32(const float* x, int64_t ldx, const float* mean, const float* rstd, const int32_t* gid,
+                                             const float* res, int64_t ldres, const int32_t* row_map, int64_t N, int C, int act,
+                                             float* y, int64_t ldy, stin_stream_t stream) {
+    stin_clear_stale_error();
+    STIN_REQUIRE(N == 0 || (res && row_map), STIN_E_NULL);
+    return norm_fwd_impl<float>(x, ldx, mean, rstd, gid, res, ldres, N, C, act, y, ldy, (hipStream_t)stream, row_map);
 }
 extern "C" int stin_norm_act_res_fwd_bf16(const stin_bf16_t* x, int64_t ldx, const float* mean, const float* rstd,
                                           const int32_t* gid, const stin_bf16_t* res, int64_t ldres, int64_t N, int C,

@@ -999,6 +999,11 @@ class EdgeConvBlockFn(torch.autograd.Function):
 # ---- the graph part of the network in ONE autograd node ----------------------------------------------------------------------
 USE_NET_CALL = os.environ.get('STIN_NET_CALL', '1') != '0'     # the WHOLE graph part as one node (the model's forward() asks)
 USE_CHAIN = True        # ... else the bottleneck blocks as one node (tests flip the attribute to get the per-block nodes)
+# A decoder block's first product on the COARSE rows in front of its unpool step (stin_net_op_t::y_from_src): x_up[v] = x_c[trace[v]]
+# makes every row of Y = x_up Wcat^T + bcat a copy of a row of Yc = x_c Wcat^T + bcat, so the product, Y and the reads of x_up shrink
+# by the unpooling ratio (~3.3) and the edge stage / the residual read Yc through the trace - same bits (a row of an NT product
+# depends on no other row).  STIN_UNPOOL_COMMUTE=0: the product over the unpooled rows, as before (A/B switch).
+USE_UNPOOL_COMMUTE = os.environ.get('STIN_UNPOOL_COMMUTE', '1') != '0'
 _NET_OP = _lib.STRUCTS['stin_net_op_t']
 OP_BLOCK, OP_POOL_MAX, OP_UNPOOL = _C['STIN_OP_BLOCK'], _C['STIN_OP_POOL_MAX'], _C['STIN_OP_UNPOOL']
 
@@ -1047,13 +1052,25 @@ class NetFn(torch.autograd.Function):
 
     calls = 0                           # nodes created ...
     sizes = collections.Counter()       # ... and how many of them per number of ops (1 = a block on its own)
+    commuted = 0                        # blocks whose first product ran on the coarse rows in front of their unpool step
+    gathers_skipped = 0                 # ... and unpool ops of no-grad forwards that were given no output (no gather launch)
 
     @staticmethod
     def _in_arena(rel, base, xp):
-        """The fields of an op that point into the arena (offsets `rel`) as addresses; the first op reads the padded input xp."""
-        ptrs = {k: base + o for k, o in rel.items()}
+        """The fields of an op that point into the arena (offsets `rel`; None = no buffer) as addresses; the first op reads the
+        padded input xp."""
+        ptrs = {k: 0 if o is None else base + o for k, o in rel.items()}
         ptrs.setdefault('x', _ptr(xp))
         return ptrs
+
+    @staticmethod
+    def _commutes(steps, si, b16, width, Ws, ti):
+        """Block `si` takes its first product from the input rows of the unpool step in front of it (USE_UNPOOL_COMMUTE): fp32
+        storage, a shortcut (the residual comes out of Y), A materialised in Y, no channel padding in between.  Every level takes
+        it; a level whose mapped edge and norm launches lose more than its product saves is to be excluded HERE
+        (profiles/r14_unpool_commute.md: the per-level figures are still open)."""
+        return (USE_UNPOOL_COMMUTE and si > 0 and steps[si - 1][0] == 'unpool' and not b16 and Ws is not None
+                and ti != TI_MODE_COMPACT and width % 4 == 0 and Ws.shape[0] % 4 == 0)
 
     @staticmethod
     def forward(ctx, x, meta, *params):
@@ -1112,7 +1129,9 @@ class NetFn(torch.autograd.Function):
                 d = dict(kind=OP_BLOCK, N=n_rows, Cin=Cin, Cp=Cp, H=H, Cout=Cout, sc=sc, Yw=Yw, B=B, prec=prec, fsp=fsp, bsp=bsp, pp=pp,
                          ws_bytes=ws_bytes, edges=edges, groups=groups, ti=ti, eps=float(blk.first_norm.eps),
                          params=(W1, b1, W2, b2, Ws, bs))
-                d['oY'] = take(n_rows * Yw * es, 'tmp')
+                # the first product on the coarse rows of the unpool step in front: Y holds those rows only
+                d['src'] = plan[-1] if NetFn._commutes(steps, si, b16, width, Ws, ti) else None
+                d['oY'] = take((d['src']['n_in'] if d['src'] else n_rows) * Yw * es, 'tmp')
                 d['oH'] = take(n_rows * (H + pad) * es, 'tmp')
                 # (round 6) a forward nobody differentiates - torch.no_grad(), the reference's validation loop - keeps no ReLU mask
                 d['oM'] = take(max(edges.n_edges, 1) * (H // 32) * 4) if need_grad else None
@@ -1133,7 +1152,12 @@ class NetFn(torch.autograd.Function):
                 else:
                     d = dict(kind=OP_UNPOOL, pool=pool, n_in=pool.n_coarse, n_out=pool.n_fine, C=width)
                 n_rows = d['n_out']
-                d['oO'] = None if last else take(n_rows * width * es, 'out')
+                # a no-grad forward keeps no x for backward: an unpool step whose block commutes writes no rows at all
+                nxt = steps[si + 1] if not last else None
+                d['skip'] = (stp[0] == 'unpool' and not need_grad and nxt is not None and nxt[0] == 'block' and
+                             NetFn._commutes(steps, si + 1, b16, width, params[pi + 4], trans_inv_mode(
+                                 nxt[1].first_filter.trans_inv, b16, params[pi].shape[0])))
+                d['oO'] = None if (last or d['skip']) else take(n_rows * width * es, 'out')
             plan.append(d)
         if not need_grad:                                        # resolve the shared regions: [kept | out 0 | out 1 | temporaries]
             o_base, t_base, flip = off, off + 2 * omax, 0
@@ -1156,8 +1180,10 @@ class NetFn(torch.autograd.Function):
         stc = _NET_OP
         blob = []
         xin, ldx = None, xp.stride(0)                      # offset of the op's input rows in the arena; None = xp
+        first = True
         for d in plan:
-            rel = {} if xin is None else {'x': xin}
+            rel = {} if first else {'x': xin}               # (xin None behind a skipped unpool gather: the block reads no x)
+            first = False
             if d['kind'] == OP_BLOCK:
                 W1, b1, W2, b2, Ws, bs = d['params']
                 pp = d['pp']
@@ -1170,6 +1196,7 @@ class NetFn(torch.autograd.Function):
                 H, Cout, B = d['H'], d['Cout'], d['B']
                 d['op'] = dict(kind=OP_BLOCK, Cin=d['Cin'], Cp=d['Cp'], H=H, Cout=Cout, has_shortcut=int(d['sc']), trans_inv=int(d['ti']),
                                prec_fwd=int(d['prec']), bwd_split=d['bsp'], B=B, slice_quirk=int(g.quirk), eps=d['eps'],
+                               y_from_src=int(d['src'] is not None),
                                n_out=d['N'], n_in=d['N'], ldx=ldx, ldo=Cout, ldy=d['Yw'], ldh=H + pad, fwd_ws_bytes=d['ws_bytes'],
                                W1=_ptr(W1.contiguous()), b1=_ptr(b1), W2=_ptr(W2.contiguous()), b2=_ptr(b2), Ws=_ptr(Ws),
                                bs=_ptr(bs), rowptr_dst=_ptr(cd.rowptr), col_dst=_ptr(cd.col),
@@ -1177,6 +1204,8 @@ class NetFn(torch.autograd.Function):
                 rel.update(Y=d['oY'], hE=d['oH'], agg=d['oA'], mean=d['oS'], rstd=d['oS'] + B * Cout * 4)
                 if need_grad:
                     rel['mask'] = d['oM']
+                NetFn.commuted += int(d['src'] is not None)
+                # (the mapped launch of a commuted block is bracketed under the plain kernel's name and tag: same rows, edges, width)
                 ev0, ev1 = KernelTimer.edge_events('stin_edge_relu_mean_fwd' + sfx, (d['N'], d['edges'].n_edges, H))
                 events = dict(ev_edge0=ev0, ev_edge1=ev1)
                 ldx = Cout
@@ -1190,8 +1219,10 @@ class NetFn(torch.autograd.Function):
                 events = {}
                 ldx = C
             d['rel'] = rel
+            skip = d.get('skip', False)
+            NetFn.gathers_skipped += int(skip)
             blob.append(stc.pack(**d['op'], **NetFn._in_arena(rel, base, xp), **events,
-                                 out=p_out if d['oO'] is None else base + d['oO']))
+                                 out=0 if skip else p_out if d['oO'] is None else base + d['oO']))
             xin = d['oO']
         import ctypes
         buf = ctypes.create_string_buffer(b''.join(blob), len(plan) * stc.size)
