@@ -787,9 +787,21 @@ int stin_linear_tanh_bwd_bf16(const float* g, const float* y, const stin_bf16_t*
  *        (a row of an NT product depends on no other row), so the product runs over the unpool op's n_in COARSE rows - Y is
  *        [n_in, Yw] - and the edge stage and the residual read Y through the trace (stin_edge_relu_mean_fwd_map_f32,
  *        stin_norm_act_res_fwd*_map_f32).  hE, mask, agg, mean / rstd and out have the same bits as with 0 (the behaviour of every
- *        earlier caller); backward is untouched, it reads x and never Y.  The unpool op's gather still runs when it has an `out`
- *        (x is kept for backward); with out == NULL - a forward nobody differentiates - it is skipped and the block's x is unused.
+ *        earlier caller); backward reads x and never Y.  The unpool op's gather still runs when it has an `out`
+ *        (x is kept for backward); with out == NULL - a forward nobody differentiates, or x_from_src - it is skipped and the
+ *        block's x is unused.
  *        A flag on a block where these conditions do not hold is STIN_E_UNSUPPORTED (its Y is sized for the coarse rows).
+ *     x_from_src != 0 (both directions, only together with y_from_src and where stin_edgeconv_wgrad_map_supported says 1): the
+ *        block's x is never materialised.  The one backward reader of x, the packed weight-gradient product dY^T [x | 1], reads
+ *        row v at x_c[trace[v]] through the unpool op in front (stin_edgeconv_wgrad_map: the same slabs bit for bit), so that op
+ *        takes out == NULL in a training forward as well, the block's x is NULL in both calls and the unpooled rows are neither
+ *        written nor kept.  0 = the behaviour of every earlier caller.
+ *     g_in_dy != 0 (backward, fp32 rows, a shortcut block with its own bwd_ws): a PERMISSION for stin_net_bwd to let the op
+ *        behind this block write its input gradient - this block's g - straight into the shortcut columns of this block's
+ *        dY = [dA | dB | g] inside bwd_ws (leading dimension Yw) instead of into its `dx`, which is then not written; the block
+ *        reads g there and the copy of g into dY goes away.  Taken where stin_net_bwd_g_in_dy says 1 (same rows and width, no
+ *        channel padding in between, 16-byte aligned columns), ignored elsewhere; never for ops[0].dx.  Same values, same
+ *        order of every sum: bit-identical gradients.  0 = the behaviour of every earlier caller.
  *   STIN_OP_POOL_MAX: x [n_in, Cout] -> out [n_out, Cout], arg [n_out, Cout]; rowptr_dst / col_dst = the children CSR, trace = the
  *     fine -> coarse map (backward).  STIN_OP_UNPOOL: out[v] = x[trace[v]] (n_out fine rows); backward = the segment sum
  *     over the children CSR. */
@@ -807,7 +819,7 @@ size_t stin_edgeconv_block_bwd_workspace_bytes(int64_t N, int Cp, int H, int Cou
 #define STIN_OP_UNPOOL 2
 typedef struct stin_net_op {
     int32_t kind, Cin, Cp, H, Cout, has_shortcut, trans_inv, prec_fwd, fwd_split, bwd_split, B, slice_quirk, use_side, y_from_src,
-        reserved1, reserved2;
+        x_from_src, g_in_dy;
     float eps;
     int32_t reserved3;
     int64_t n_out, n_in, ldx, ldo, lddx, ldy, ldh;
@@ -838,6 +850,8 @@ typedef struct stin_net_op {
 int stin_net_fwd(int storage, const stin_net_op_t* ops, int n_ops, stin_stream_t stream);
 int stin_net_bwd(int storage, const stin_net_op_t* ops, int n_ops, const void* g, int64_t ldg, int prec_bwd, stin_stream_t stream,
                  stin_stream_t wgrad_stream);
+/* 1 when stin_net_bwd writes ops[i].dx into the dY of ops[i - 1] (g_in_dy above), else 0.  Host only: reads the records, no pointer. */
+int stin_net_bwd_g_in_dy(int storage, const stin_net_op_t* ops, int n_ops, int i);
 
 /* All weight gradients of one fused block in two launches (round 3): BOTH transposed products
  *   dW2 | db2 = dagg^T [hE[:, :H] | hE[:, H]]        (second Linear; db2 weighted by the [deg > 0] column of hE)
@@ -862,6 +876,18 @@ int stin_edgeconv_wgrad_ti(int storage, const void* dagg, int64_t ld_dagg, const
                            int has_shortcut, int trans_inv, int precision, float* dW1, float* db1, float* dW2, float* db2,
                            float* dWs, float* dbs, const float* ti_colsum, int64_t ti_rows, void* workspace,
                            size_t workspace_bytes, stin_stream_t stream);
+/* stin_edgeconv_wgrad with the rows of x read through a map: x is [x_rows, ldx] and row m of the packed product's operand is
+ * x[x_row_map[m]] (x_row_map [N], 16-byte aligned, values in [0, x_rows)) - the unpooled rows x_up = x_c[trace] of a decoder block
+ * without the gather that writes them.  Only the row addresses of the producer / consumer kernel's X loads change: the same slabs,
+ * the same gradients bit for bit as stin_edgeconv_wgrad on x[x_row_map].  fp32 rows, not the compact layout, and only where
+ * stin_edgeconv_wgrad_map_supported (host only; STIN_TN_WS honoured) says 1 - the shapes whose packed product runs on that kernel;
+ * STIN_E_UNSUPPORTED elsewhere (those shapes keep the gather).  x_row_map == NULL: stin_edgeconv_wgrad. */
+int stin_edgeconv_wgrad_map_supported(int64_t N, int Cp, int H, int Cout, int has_shortcut, int precision);
+int stin_edgeconv_wgrad_map(int storage, const void* dagg, int64_t ld_dagg, const void* hE, int64_t ldh, const void* dY,
+                            int64_t ldy, const void* x, int64_t ldx, int64_t N, int Cin, int Cp, int H, int Cout,
+                            int has_shortcut, int trans_inv, int precision, float* dW1, float* db1, float* dW2, float* db2,
+                            float* dWs, float* dbs, const int32_t* x_row_map, int64_t x_rows, void* workspace,
+                            size_t workspace_bytes, stin_stream_t stream);
 
 /* ------------------------------------------------- offline preprocessing on the GPU --
  * The dilated-edge walk of preprocessing/graph_dilation.py:85-137 (`compute_dilated_edges`), one thread per

@@ -266,12 +266,15 @@ struct BwdLink {
 // Backward of one STIN_OP_BLOCK op.  g = dL/dout [N, Cout]; J.dx may be NULL (block input needs no gradient).  Gradients of the
 // reference-layout parameters are written to dW1 [H, Cin or 2 Cin], db1 [H], dW2 [Cout, H], db2 [Cout], dWs [Cout, Cin],
 // dbs [Cout] (bias / shortcut outputs may be NULL when the parameter does not exist).
+// Un != NULL (x_from_src, checked by `commutes`): the unpool op in front, whose output was never written - the one reader of x, the
+// packed weight-gradient product, reads Un's input rows through its trace.
+// g may already BE the shortcut columns of this block's dY (g_in_dy: the op behind wrote its dx there) - then nothing copies it.
 static int block_bwd(int storage, const stin_net_op_t& J, const void* g, int64_t ldg, int prec_bwd, stin_stream_t stream,
-                     stin_stream_t wgrad_stream, BwdLink* link) {
+                     stin_stream_t wgrad_stream, BwdLink* link, const stin_net_op_t* Un = nullptr) {
     const int64_t N = J.n_out;
     const int Cp = J.Cp, H = J.H, Cout = J.Cout, has_shortcut = J.has_shortcut;
     STIN_REQUIRE(N >= 0 && J.Cin > 0 && Cp >= J.Cin && H > 0 && Cout > 0 && J.B > 0, STIN_E_SIZE);
-    STIN_REQUIRE(g && J.x && J.hE && J.mask && J.agg && J.mean && J.rstd && J.wcatT && J.w2T && J.rowptr_dst && J.rowptr_src && J.col_src &&
+    STIN_REQUIRE(g && (J.x || Un) && J.hE && J.mask && J.agg && J.mean && J.rstd && J.wcatT && J.w2T && J.rowptr_dst && J.rowptr_src && J.col_src &&
                      J.xslot && J.w_src && J.inv_cnt && J.dW1 && J.dW2 && J.bwd_ws && (!has_shortcut || J.dWs),
                  STIN_E_NULL);
     STIN_REQUIRE(J.bwd_ws_bytes >= stin_edgeconv_block_bwd_workspace_bytes(N, Cp, H, Cout, has_shortcut, J.B, storage), STIN_E_WORKSPACE);
@@ -346,9 +349,10 @@ static int block_bwd(int storage, const stin_net_op_t& J, const void* g, int64_t
         // edge stage backward from the saved ReLU mask -> dY = [dA | dB | g]
         // (a shortcut block's dY[:, 2H:] = g rides on the same launch when the rows allow 16-byte copies, else one 2-D memcpy)
         float* dYs = dYf + (Yw - Cout);                             // the shortcut columns of dY (has_shortcut)
-        const bool ride = has_shortcut && N > 0 && Cout % 4 == 0 && ldg % 4 == 0 && Yw % 4 == 0 && stin_aligned16(gf) &&
+        const bool placed = has_shortcut && gf == dYs && ldg == Yw;  // g_in_dy: the producer of g wrote it here
+        const bool ride = has_shortcut && !placed && N > 0 && Cout % 4 == 0 && ldg % 4 == 0 && Yw % 4 == 0 && stin_aligned16(gf) &&
                           stin_aligned16(dYs) && Cout <= H;
-        const bool bind = bind_on && (!has_shortcut || ride);
+        const bool bind = bind_on && (!has_shortcut || ride || placed);     // (no copy follows the edge launch)
         if (bind) stin_tl_stop_event = (hipEvent_t)J.ev_dy;
         if (compact)     // D = dB - dA in ONE row of H columns, + the column partials of dA for db1 (stin_graph.hip: k_edge_bwd_mask_ti)
             STIN_EDGE_BRACKET(stin_edge_relu_mean_bwd_mask_ti_f32(static_cast<const float*>(dhE), H, J.mask, J.rowptr_dst, J.w_src,
@@ -358,7 +362,7 @@ static int block_bwd(int storage, const stin_net_op_t& J, const void* g, int64_t
             STIN_EDGE_BRACKET(stin_edge_relu_mean_bwd_mask_f32(static_cast<const float*>(dhE), H, J.mask, J.rowptr_dst, J.w_src, J.rowptr_src,
                                                               J.col_src, J.xslot, N, H, dYf, Yw, dYf + H, Yw, ride ? gf : nullptr, ldg,
                                                               ride ? dYs : nullptr, Yw, ride ? Cout : 0, stream));
-        if (has_shortcut && N > 0 && !ride) {
+        if (has_shortcut && N > 0 && !ride && !placed) {
             hipError_t e = hipMemcpy2DAsync(dYs, (size_t)Yw * 4, gf, (size_t)ldg * 4, (size_t)Cout * 4, (size_t)N,
                                             hipMemcpyDeviceToDevice, hs);
             if (e != hipSuccess) return (int)e;
@@ -369,8 +373,13 @@ static int block_bwd(int storage, const stin_net_op_t& J, const void* g, int64_t
         bound = bind && stin_tl_stop_event == nullptr;              // (the launch that took the event cleared it)
         stin_tl_stop_event = nullptr;
         STIN_TRY(fork());
-        STIN_TRY(stin_edgeconv_wgrad_ti(0, dagg, Cout, hf, J.ldh, dYf, Yw, J.x, J.ldx, N, J.Cin, Cp, H, Cout, has_shortcut, J.trans_inv,
-                                        prec_bwd, J.dW1, J.db1, J.dW2, J.db2, J.dWs, J.dbs, ti_colsum, ti_rows, tn_ws, tn_bytes, ws_));
+        if (Un)     // x_up[v] = x_c[trace[v]] read where it is (the same slabs bit for bit; never the compact layout: `commutes`)
+            STIN_TRY(stin_edgeconv_wgrad_map(0, dagg, Cout, hf, J.ldh, dYf, Yw, Un->x, Un->ldx, N, J.Cin, Cp, H, Cout, has_shortcut,
+                                             J.trans_inv, prec_bwd, J.dW1, J.db1, J.dW2, J.db2, J.dWs, J.dbs, Un->trace, Un->n_in, tn_ws,
+                                             tn_bytes, ws_));
+        else
+            STIN_TRY(stin_edgeconv_wgrad_ti(0, dagg, Cout, hf, J.ldh, dYf, Yw, J.x, J.ldx, N, J.Cin, Cp, H, Cout, has_shortcut, J.trans_inv,
+                                            prec_bwd, J.dW1, J.db1, J.dW2, J.db2, J.dWs, J.dbs, ti_colsum, ti_rows, tn_ws, tn_bytes, ws_));
         if (J.dx != nullptr) {
             const bool link_ok = link != nullptr && link->next_agg != nullptr && link->next_ld % 4 == 0 && stin_aligned16(link->next_agg) &&
                                  stin_aligned16(link->next_mean) && stin_aligned16(link->next_rstd) && link->next_partial != nullptr;
@@ -386,6 +395,7 @@ static int block_bwd(int storage, const stin_net_op_t& J, const void* g, int64_t
             }
         }
     } else {
+        STIN_REQUIRE(Un == nullptr, STIN_E_UNSUPPORTED);
         const stin_bf16_t* gh = static_cast<const stin_bf16_t*>(g);
         const stin_bf16_t* hh = static_cast<const stin_bf16_t*>(J.hE);
         stin_bf16_t* dYh = static_cast<stin_bf16_t*>(dY);
@@ -436,7 +446,7 @@ extern "C" int stin_net_fwd(int storage, const stin_net_op_t* ops, int n_ops, st
         const stin_net_op_t& J = ops[i];
         if (J.kind == STIN_OP_BLOCK) {
             const stin_net_op_t* un = (i > 0 && commutes(storage, ops[i - 1], J)) ? &ops[i - 1] : nullptr;
-            STIN_REQUIRE(un != nullptr || J.y_from_src == 0, STIN_E_UNSUPPORTED);     // (its Y holds the coarse rows only)
+            STIN_REQUIRE(un != nullptr || (J.y_from_src == 0 && J.x_from_src == 0), STIN_E_UNSUPPORTED);   // (its Y holds the coarse rows only)
             STIN_TRY(block_fwd(storage, J, stream, un));
         } else if (J.kind == STIN_OP_POOL_MAX) {
             if (storage)
@@ -461,6 +471,37 @@ extern "C" int stin_net_fwd(int storage, const stin_net_op_t* ops, int n_ops, st
     return STIN_OK;
 }
 
+// g_in_dy: op i's input gradient IS the output gradient g of the shortcut block ops[i - 1], which needs it as the last Cout columns of
+// its dY = [dA | dB | g] - so op i writes it there (every producer takes a leading dimension) and the block copies nothing.
+// True where that block permits it and the two agree in rows and width without channel padding; *dx / *lddx = the target.
+static bool g_in_dy(int storage, const stin_net_op_t* ops, int n_ops, int i, void** dx, int64_t* lddx) {
+    if (storage != 0 || ops == nullptr || i < 1 || i >= n_ops) return false;
+    const stin_net_op_t &J = ops[i], &Pn = ops[i - 1];
+    if (Pn.kind != STIN_OP_BLOCK || Pn.g_in_dy == 0 || Pn.has_shortcut == 0 || Pn.bwd_ws == nullptr || J.dx == nullptr) return false;
+    if (Pn.n_out <= 0 || Pn.Cp <= 0 || Pn.H <= 0 || Pn.Cout <= 0 || Pn.B <= 0) return false;
+    int64_t rows, width;
+    if (J.kind == STIN_OP_BLOCK) {
+        if (J.Cin != J.Cp) return false;
+        rows = J.n_out, width = J.Cp;
+    } else if (J.kind == STIN_OP_POOL_MAX || J.kind == STIN_OP_UNPOOL) {
+        rows = J.n_in, width = J.Cout;
+    } else {
+        return false;
+    }
+    const int Yw = stin_yw(Pn.H, Pn.Cout, Pn.has_shortcut, Pn.trans_inv);
+    if (rows != Pn.n_out || width != Pn.Cout || Pn.Cout % 4 != 0 || Yw % 4 != 0) return false;
+    if (Pn.bwd_ws_bytes < stin_edgeconv_block_bwd_workspace_bytes(Pn.n_out, Pn.Cp, Pn.H, Pn.Cout, Pn.has_shortcut, Pn.B, storage)) return false;
+    char* t = align256(Pn.bwd_ws) + bwd_layout(Pn.n_out, Pn.H, Pn.Cout, Pn.has_shortcut, Pn.B, storage).dY + (size_t)(Yw - Pn.Cout) * 4;
+    if (!stin_aligned16(t)) return false;
+    if (dx) *dx = t;
+    if (lddx) *lddx = Yw;
+    return true;
+}
+
+extern "C" int stin_net_bwd_g_in_dy(int storage, const stin_net_op_t* ops, int n_ops, int i) {
+    return g_in_dy(storage, ops, n_ops, i, nullptr, nullptr) ? 1 : 0;
+}
+
 extern "C" int stin_net_bwd(int storage, const stin_net_op_t* ops, int n_ops, const void* g, int64_t ldg, int prec_bwd,
                             stin_stream_t stream, stin_stream_t wgrad_stream) {
     STIN_REQUIRE(n_ops >= 0 && (n_ops == 0 || ops != nullptr), STIN_E_NULL);
@@ -470,9 +511,21 @@ extern "C" int stin_net_bwd(int storage, const stin_net_op_t* ops, int n_ops, co
     const double* pre_partial = nullptr;       // statistics of op i computed by op i + 1's dx product (BwdLink)
     int64_t pre_groups = 0;
     for (int i = n_ops - 1; i >= 0; --i) {
-        const stin_net_op_t& J = ops[i];
+        stin_net_op_t Jr;                       // op i on a copy of its record when its dx goes into the dY of the block in front
+        void* dx_in_dy = nullptr;
+        int64_t ld_in_dy = 0;
+        const bool redirect = g_in_dy(storage, ops, n_ops, i, &dx_in_dy, &ld_in_dy);
+        if (redirect) {
+            Jr = ops[i];
+            Jr.dx = dx_in_dy;
+            Jr.lddx = ld_in_dy;
+        }
+        const stin_net_op_t& J = redirect ? Jr : ops[i];
         STIN_REQUIRE(J.dx != nullptr || i == 0, STIN_E_NULL);
         if (J.kind == STIN_OP_BLOCK) {
+            // x_from_src: the unpool op in front never wrote this block's x (found the way stin_net_fwd finds it)
+            const stin_net_op_t* un = (J.x_from_src != 0 && i > 0 && commutes(storage, ops[i - 1], J)) ? &ops[i - 1] : nullptr;
+            STIN_REQUIRE(un != nullptr || J.x_from_src == 0, STIN_E_UNSUPPORTED);
             BwdLink link;
             link.pre_partial = pre_partial;
             link.pre_groups = pre_groups;
@@ -493,7 +546,7 @@ extern "C" int stin_net_bwd(int storage, const stin_net_op_t* ops, int n_ops, co
                     link.next_partial_bytes = Ln.red_bytes > 256 ? Ln.red_bytes - 256 : 0;
                 }
             }
-            STIN_TRY(block_bwd(storage, J, gi, ldgi, prec_bwd, stream, wgrad_stream, &link));
+            STIN_TRY(block_bwd(storage, J, gi, ldgi, prec_bwd, stream, wgrad_stream, &link, un));
             if (link.produced_groups > 0) {
                 pre_partial = link.next_partial;
                 pre_groups = link.produced_groups;

@@ -192,9 +192,12 @@ struct stin_tn_problem {
     const float *G, *X, *row_w;
     float* slab;                       // [chunks][Nc * Kq + roundup4(Nc)] partial results
     int64_t ldg, ldx, ld_w, M, chunks;
-    int Nc, K, Kq, has_bias, rows_per_chunk, tiles_i, tiles_j, TI, TJ, vec;
+    int Nc, K, Kq, has_bias, rows_per_chunk, tiles_i, tiles_j, vec;
+    short TI, TJ;                      // tile (0, 64, 128, 256; host side only) - 16 bits each so that the record keeps its 152 bytes
     unsigned block0;                   // first block of the problem in a merged grid (set by stin_tn_ws_launch)
+    const int32_t* x_row_map;          // optional, k_gemm_tn_ws<true> only: row m of the X operand is X[x_row_map[m]] (NULL: X[m])
 };
+static_assert(sizeof(stin_tn_problem) == 152, "stin_tn_problem is a kernel argument: k_gemm_tn_ws indexes batch.p[] by this stride");
 struct stin_tn_batch {
     stin_tn_problem p[2];
     int n;

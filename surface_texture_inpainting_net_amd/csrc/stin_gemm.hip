@@ -564,6 +564,7 @@ int stin_tn_problem_init(stin_tn_problem* p, int storage, const void* G, int64_t
     p->G = static_cast<const float*>(G);
     p->X = static_cast<const float*>(X);
     p->row_w = static_cast<const float*>(row_w);
+    p->x_row_map = nullptr;                                        // (set by the caller after init: stin_edgeconv_wgrad_map)
     p->slab = slab;
     p->ldg = ldg;
     p->ldx = ldx;

@@ -73,6 +73,10 @@ struct WsSlab {
     bool pv[4];
 };
 
+// MAPPED (k_gemm_tn_ws<true>): a problem with an x_row_map reads row m of its X operand at X[x_row_map[m]] - the weight gradient of a
+// block behind an unpool step takes x_up[m] = x_c[trace[m]] straight from the coarse rows (stin_edgeconv_wgrad_map).  Only the
+// producers' X row addresses differ; MAPPED = false is the kernel as it was, instruction for instruction.
+template <bool MAPPED>
 __global__ __launch_bounds__(WS_THREADS) void k_gemm_tn_ws(const stin_tn_batch batch, const int prio) {
     __shared__ __attribute__((aligned(16))) __bf16 Gt[2][2][WS_PLANE];            // [buffer][piece][ws_lds(column, m / 4)]
     __shared__ __attribute__((aligned(16))) __bf16 Xt[2][2][WS_PLANE];
@@ -113,7 +117,11 @@ __global__ __launch_bounds__(WS_THREADS) void k_gemm_tn_ws(const stin_tn_batch b
     // Pipeline: slab s is multiplied out of buffer s & 1 while the producers split slab s + 1 into the other buffer and
     // request slab s + 3 into the register set that has just been stored (loads two slabs = two barriers ahead).  Rows past
     // the chunk load zeros, so the slab count is rounded up to an even number as in the four-wave kernel.
-    if (producer) {
+    // the producer role as a generic lambda: USE_MAP = this block's problem reads its X rows through x_row_map (MAPPED kernels only;
+    // block-uniform).  Two instantiations behind one scalar branch instead of a test per slab: the index registers of the mapped
+    // form are then plain loop-carried values and the compiler counts the loads in flight as in the plain form.
+    auto produce = [&](auto USE_MAP) {
+        constexpr bool UM = decltype(USE_MAP)::value;
         // ---- producer: patch (row group rg, column group c4) of G and of X per slab
         const int ptid = tid & 255;
         // lane = column group: one wave-wide load instruction covers 2 rows x 512 contiguous bytes.  (The four-wave kernel's
@@ -127,6 +135,23 @@ __global__ __launch_bounds__(WS_THREADS) void k_gemm_tn_ws(const stin_tn_batch b
         const float* gp = G + (i0 + c4 * 4 < Nc ? i0 + c4 * 4 : 0) + (mb + rg * 4) * ldg;     // row rg * 4 of the NEXT slab to load
         const int xcol = j0 + c4 * 4 < K ? j0 + c4 * 4 : 0;
         const float* xp = X + xcol + (mb + rg * 4) * ldx;
+        // mapped X rows: the four row indices of a thread's patch are ONE 16-byte load (m_next is a multiple of 4) where the slab is
+        // known to be whole, else four loads at positions clamped to the map's last entry (rows past the chunk are never loaded
+        // through them) - requested one slab ahead of the rows they address and free of branches, so that the compiler can count
+        // the loads in flight: the row loads stay two slabs ahead.  The map is never read past its M entries.
+        const int32_t* __restrict__ xmap = nullptr;
+        if constexpr (UM) xmap = batch.p[pi].x_row_map;
+        const float* xb = X + xcol;
+        int4 xi = make_int4(0, 0, 0, 0);                           // X rows of the NEXT slab to load
+        auto load_map = [&](int64_t m, auto WHOLE) {
+            if constexpr (decltype(WHOLE)::value) {
+                return *reinterpret_cast<const int4*>(xmap + m);
+            } else {
+                const int64_t last = M - 1;
+                return make_int4(xmap[m < last ? m : last], xmap[m + 1 < last ? m + 1 : last], xmap[m + 2 < last ? m + 2 : last],
+                                 xmap[m + 3 < last ? m + 3 : last]);
+            }
+        };
         const stin_bn_tf xtf = batch.p[pi].xtf;                   // (round 5) X rows read as relu(bn(.)) per column: block-uniform
         stin_bn_coef4 xq;                                           // this thread's four X columns are fixed: (s, t) once
         xq.s = xq.t = make_float4(0.f, 0.f, 0.f, 0.f);
@@ -135,13 +160,27 @@ __global__ __launch_bounds__(WS_THREADS) void k_gemm_tn_ws(const stin_tn_batch b
         int64_t m_next = mb + rg * 4;                                                          // its row index
         float4 bs = make_float4(0.f, 0.f, 0.f, 0.f);
         // FULL = every row of the slab is inside the chunk (all but the last one or two slabs): no row test, no zero fill
-        auto load_slab = [&](WsSlab& S, auto FULL) {
+        // NEXT_WHOLE = the slab after this one is inside the chunk as well (mapped rows: its indices are requested here)
+        auto load_slab = [&](WsSlab& S, auto FULL, auto NEXT_WHOLE) {
             if (WS_ABL(4)) return;
+            const float* xm[4] = {nullptr, nullptr, nullptr, nullptr};
+            if constexpr (UM) {                                     // (this form keeps no running X pointer)
+                const int4 id = xi;
+                xi = load_map(m_next + WS_R, NEXT_WHOLE);
+                xm[0] = xb + (int64_t)id.x * ldx;
+                xm[1] = xb + (int64_t)id.y * ldx;
+                xm[2] = xb + (int64_t)id.z * ldx;
+                xm[3] = xb + (int64_t)id.w * ldx;
+            }
+            auto xrow = [&](int r) -> const float* {
+                if constexpr (UM) return xm[r];
+                else return xp + r * ldx;
+            };
 #pragma unroll
             for (int r = 0; r < 4; ++r) {
                 if (decltype(FULL)::value) {
                     S.g[r] = ld4(gp + r * ldg);
-                    S.x[r] = ld4(xp + r * ldx);
+                    S.x[r] = ld4(xrow(r));
                     if (wp != nullptr) S.pw[r] = wp[r * ld_w];
                     S.pv[r] = true;
                 } else {
@@ -149,7 +188,7 @@ __global__ __launch_bounds__(WS_THREADS) void k_gemm_tn_ws(const stin_tn_batch b
                     float4 vg = make_float4(0.f, 0.f, 0.f, 0.f), vx = vg;
                     if (in) {
                         vg = ld4(gp + r * ldg);
-                        vx = ld4(xp + r * ldx);
+                        vx = ld4(xrow(r));
                     }
                     S.g[r] = vg;
                     S.x[r] = vx;
@@ -158,7 +197,7 @@ __global__ __launch_bounds__(WS_THREADS) void k_gemm_tn_ws(const stin_tn_batch b
                 }
             }
             gp += WS_R * ldg;
-            xp += WS_R * ldx;
+            if constexpr (!UM) xp += WS_R * ldx;
             if (wp != nullptr) wp += WS_R * ld_w;
             m_next += WS_R;
         };
@@ -202,11 +241,12 @@ __global__ __launch_bounds__(WS_THREADS) void k_gemm_tn_ws(const stin_tn_batch b
         };
         WsSlab S0, S1;
         WS_STAMP(0);
-        load_slab(S0, std::false_type());
-        load_slab(S1, std::false_type());
+        if constexpr (UM) xi = load_map(m_next, std::false_type());
+        load_slab(S0, std::false_type(), std::false_type());
+        load_slab(S1, std::false_type(), std::false_type());
         store_slab(S0, 0);
         WS_STAMP(1);
-        load_slab(S0, std::false_type());
+        load_slab(S0, std::false_type(), std::false_type());
         __syncthreads();
         WS_STAMP(2);
         int64_t m0 = mb;
@@ -215,25 +255,33 @@ __global__ __launch_bounds__(WS_THREADS) void k_gemm_tn_ws(const stin_tn_batch b
         for (; m0 + 5 * WS_R <= me; m0 += 2 * WS_R) {             // the slabs requested here (m0 + 96, m0 + 128) are whole
             store_slab(S1, 1);
             WS_STAMP(st);
-            load_slab(S1, std::true_type());
+            load_slab(S1, std::true_type(), std::true_type());
             __syncthreads();
             WS_STAMP(st + 1);
             store_slab(S0, 0);
-            load_slab(S0, std::true_type());
+            load_slab(S0, std::true_type(), std::false_type());
             __syncthreads();
             st += 2;
         }
         WS_STAMP(62);
         for (; m0 < me; m0 += 2 * WS_R) {
             store_slab(S1, 1);
-            load_slab(S1, std::false_type());
+            load_slab(S1, std::false_type(), std::false_type());
             __syncthreads();
             store_slab(S0, 0);
-            load_slab(S0, std::false_type());
+            load_slab(S0, std::false_type(), std::false_type());
             __syncthreads();
         }
         WS_STAMP(63);
         if (want_bias) st4(&bsum[rg][c4 * 4], bs);
+    };
+    if (producer) {
+        if constexpr (MAPPED) {
+            if (batch.p[pi].x_row_map != nullptr) produce(std::true_type());
+            else produce(std::false_type());
+        } else {
+            produce(std::false_type());
+        }
     } else {
         // ---- consumer: wave (wi, wj) owns a 64 x 64 quarter of the tile
         const int wi = (wave >> 1) & 1, wj = wave & 1;
@@ -475,14 +523,17 @@ bool stin_tn_ws_enabled() {
 int stin_tn_ws_launch(stin_tn_batch batch, stin_stream_t stream) {
     const int prio = 1;                                            // consumers (the MFMA-issuing waves) at raised priority
     unsigned blocks = 0;
+    bool mapped = false;
     for (int i = 0; i < batch.n; ++i) {
         stin_tn_problem& p = batch.p[i];
+        mapped = mapped || p.x_row_map != nullptr;
         blocks = (blocks + 7u) & ~7u;                              // every problem starts on an XCD round (blockIdx % 8 == XCD)
         p.block0 = blocks;
         blocks += (unsigned)((p.chunks >= 8 ? ((p.chunks + 7) / 8) * 8 : p.chunks) * (int64_t)p.tiles_i * p.tiles_j);
     }
     if (blocks == 0) return STIN_OK;
-    hipLaunchKernelGGL(k_gemm_tn_ws, dim3(blocks), dim3(WS_THREADS), 0, (hipStream_t)stream, batch, prio);
+    if (mapped) hipLaunchKernelGGL(k_gemm_tn_ws<true>, dim3(blocks), dim3(WS_THREADS), 0, (hipStream_t)stream, batch, prio);
+    else hipLaunchKernelGGL(k_gemm_tn_ws<false>, dim3(blocks), dim3(WS_THREADS), 0, (hipStream_t)stream, batch, prio);
     return stin_launch_status();
 }
 
@@ -501,11 +552,11 @@ extern "C" int stin_edgeconv_wgrad(int storage, const void* dagg, int64_t ld_dag
                                   dW1, db1, dW2, db2, dWs, dbs, nullptr, 0, workspace, workspace_bytes, stream);
 }
 
-extern "C" int stin_edgeconv_wgrad_ti(int storage, const void* dagg, int64_t ld_dagg, const void* hE, int64_t ldh, const void* dY,
-                                      int64_t ldy, const void* x, int64_t ldx, int64_t N, int Cin, int Cp, int H, int Cout,
-                                      int has_shortcut, int trans_inv, int precision, float* dW1, float* db1, float* dW2, float* db2,
-                                      float* dWs, float* dbs, const float* ti_colsum, int64_t ti_rows, void* workspace,
-                                      size_t workspace_bytes, stin_stream_t stream) {
+// x_row_map != NULL: x is [x_rows, ldx] and row m of the packed product's operand is x[x_row_map[m]] (stin_edgeconv_wgrad_map)
+static int wgrad_impl(int storage, const void* dagg, int64_t ld_dagg, const void* hE, int64_t ldh, const void* dY, int64_t ldy, const void* x,
+                      int64_t ldx, int64_t N, int Cin, int Cp, int H, int Cout, int has_shortcut, int trans_inv, int precision, float* dW1,
+                      float* db1, float* dW2, float* db2, float* dWs, float* dbs, const float* ti_colsum, int64_t ti_rows,
+                      const int32_t* x_row_map, int64_t x_rows, void* workspace, size_t workspace_bytes, stin_stream_t stream) {
     stin_clear_stale_error();
     STIN_REQUIRE(storage == 0 || storage == 1, STIN_E_UNSUPPORTED);
     STIN_REQUIRE(N >= 0 && Cin > 0 && Cp >= Cin && H > 0 && Cout > 0, STIN_E_SIZE);
@@ -516,6 +567,8 @@ extern "C" int stin_edgeconv_wgrad_ti(int storage, const void* dagg, int64_t ld_
     STIN_REQUIRE(ld_dagg >= Cout && ldh >= H + 1 && ldy >= Yw && ldx >= Cp, STIN_E_SIZE);
     STIN_REQUIRE(dW1 && dW2 && workspace && (!has_shortcut || dWs) && (N == 0 || (dagg && hE && dY && x)), STIN_E_NULL);
     STIN_REQUIRE(workspace_bytes >= stin_edgeconv_wgrad_workspace_bytes(N, Cp, H, Cout, has_shortcut), STIN_E_WORKSPACE);
+    STIN_REQUIRE(x_row_map == nullptr || (storage == 0 && !compact), STIN_E_UNSUPPORTED);
+    STIN_REQUIRE(x_row_map == nullptr || (x_rows > 0 && stin_aligned16(x_row_map)), STIN_E_SIZE);
     char* p = reinterpret_cast<char*>((reinterpret_cast<uintptr_t>(workspace) + 255) & ~(uintptr_t)255);
     float* slabA = reinterpret_cast<float*>(p);
     float* slabB = reinterpret_cast<float*>(p + up256(stin_gemm_tn_workspace_bytes(N, Cout, H, 1)));
@@ -527,6 +580,10 @@ extern "C" int stin_edgeconv_wgrad_ti(int storage, const void* dagg, int64_t ld_
     if (rc != STIN_OK) return rc;
     rc = stin_tn_problem_init(&pb, storage, dY, ldy, x, ldx, N, Yw, Cp, 1, nullptr, 0, precision, slabB, &wsb);
     if (rc != STIN_OK) return rc;
+    if (x_row_map != nullptr && N > 0) {                          // only the producer / consumer kernel reads X through a map
+        STIN_REQUIRE(wsb, STIN_E_UNSUPPORTED);
+        pb.x_row_map = x_row_map;
+    }
     if (wsa && wsb) {                                             // both products on the producer / consumer kernel: ONE grid
         stin_tn_batch batch;
         batch.p[0] = pa;
@@ -563,6 +620,37 @@ extern "C" int stin_edgeconv_wgrad_ti(int storage, const void* dagg, int64_t ld_
                            (has_shortcut ? (int64_t)Cout * pb.Kq / 4 : 0) + (Yw + 3) / 4 + ((compact && db1 != nullptr) ? H / 4 : 0);
     hipLaunchKernelGGL(k_wgrad_finalize, dim3((unsigned)((groups + FN_COLS - 1) / FN_COLS)), dim3(FN_BLOCK), 0, (hipStream_t)stream, f);
     return stin_launch_status();
+}
+
+extern "C" int stin_edgeconv_wgrad_ti(int storage, const void* dagg, int64_t ld_dagg, const void* hE, int64_t ldh, const void* dY,
+                                      int64_t ldy, const void* x, int64_t ldx, int64_t N, int Cin, int Cp, int H, int Cout,
+                                      int has_shortcut, int trans_inv, int precision, float* dW1, float* db1, float* dW2, float* db2,
+                                      float* dWs, float* dbs, const float* ti_colsum, int64_t ti_rows, void* workspace,
+                                      size_t workspace_bytes, stin_stream_t stream) {
+    return wgrad_impl(storage, dagg, ld_dagg, hE, ldh, dY, ldy, x, ldx, N, Cin, Cp, H, Cout, has_shortcut, trans_inv, precision, dW1, db1, dW2,
+                      db2, dWs, dbs, ti_colsum, ti_rows, nullptr, 0, workspace, workspace_bytes, stream);
+}
+
+extern "C" int stin_edgeconv_wgrad_map(int storage, const void* dagg, int64_t ld_dagg, const void* hE, int64_t ldh, const void* dY,
+                                       int64_t ldy, const void* x, int64_t ldx, int64_t N, int Cin, int Cp, int H, int Cout,
+                                       int has_shortcut, int trans_inv, int precision, float* dW1, float* db1, float* dW2, float* db2,
+                                       float* dWs, float* dbs, const int32_t* x_row_map, int64_t x_rows, void* workspace,
+                                       size_t workspace_bytes, stin_stream_t stream) {
+    return wgrad_impl(storage, dagg, ld_dagg, hE, ldh, dY, ldy, x, ldx, N, Cin, Cp, H, Cout, has_shortcut, trans_inv, precision, dW1, db1, dW2,
+                      db2, dWs, dbs, nullptr, 0, x_row_map, x_rows, workspace, workspace_bytes, stream);
+}
+
+// 1 exactly where the packed product [dW1 ; dWs | db] = dY^T [x | 1] of such a block runs on the producer / consumer kernel (wide
+// layout, 16-byte aligned rows of Yw and Cp floats): ws_eligible of its stin_tn_problem_init, STIN_TN_WS honoured.  Host only.
+extern "C" int stin_edgeconv_wgrad_map_supported(int64_t N, int Cp, int H, int Cout, int has_shortcut, int precision) {
+    if (N <= 0 || Cp <= 0 || H <= 0 || Cout <= 0) return 0;
+    const int Yw = stin_yw(H, Cout, has_shortcut, 0);
+    stin_tn_problem pb;
+    int wsb = 0;
+    void* const some = reinterpret_cast<void*>(uintptr_t(256));   // (geometry only: nothing is read through it)
+    if (stin_tn_problem_init(&pb, 0, some, Yw, some, Cp, N, Yw, Cp, 1, nullptr, 0, precision, static_cast<float*>(some), &wsb) != STIN_OK)
+        return 0;
+    return wsb;
 }
 
 extern "C" int stin_edge_bwd_ti_colsum_fold_f32(const float* colsum, int64_t rows, int H, float* db1, stin_stream_t stream) {

@@ -1004,6 +1004,13 @@ USE_CHAIN = True        # ... else the bottleneck blocks as one node (tests flip
 # by the unpooling ratio (~3.3) and the edge stage / the residual read Yc through the trace - same bits (a row of an NT product
 # depends on no other row).  STIN_UNPOOL_COMMUTE=0: the product over the unpooled rows, as before (A/B switch).
 USE_UNPOOL_COMMUTE = os.environ.get('STIN_UNPOOL_COMMUTE', '1') != '0'
+# ... and its backward without the unpooled rows (stin_net_op_t::x_from_src): their one reader, the packed weight-gradient product,
+# reads x_c through the trace (stin_edgeconv_wgrad_map), so a TRAINING forward launches no gather either and the arena does not hold
+# x_up.  Only where stin_edgeconv_wgrad_map_supported says so; other shapes keep the gather.  Off with STIN_UNPOOL_COMMUTE=0.
+USE_WGRAD_MAP = True
+# The op behind a shortcut block writes its input gradient - that block's g - straight into the shortcut columns of the block's
+# dY = [dA | dB | g] (stin_net_op_t::g_in_dy): no copy of g.  fp32 rows.
+USE_G_IN_DY = True
 _NET_OP = _lib.STRUCTS['stin_net_op_t']
 OP_BLOCK, OP_POOL_MAX, OP_UNPOOL = _C['STIN_OP_BLOCK'], _C['STIN_OP_POOL_MAX'], _C['STIN_OP_UNPOOL']
 
@@ -1053,7 +1060,8 @@ class NetFn(torch.autograd.Function):
     calls = 0                           # nodes created ...
     sizes = collections.Counter()       # ... and how many of them per number of ops (1 = a block on its own)
     commuted = 0                        # blocks whose first product ran on the coarse rows in front of their unpool step
-    gathers_skipped = 0                 # ... and unpool ops of no-grad forwards that were given no output (no gather launch)
+    gathers_skipped = 0                 # ... and unpool ops that were given no output (no gather launch): those of no-grad forwards and,
+                                        # in training, those whose block reads x through the trace in backward (USE_WGRAD_MAP)
 
     @staticmethod
     def _in_arena(rel, base, xp):
@@ -1071,6 +1079,13 @@ class NetFn(torch.autograd.Function):
         (profiles/r14_unpool_commute.md: the per-level figures are still open)."""
         return (USE_UNPOOL_COMMUTE and si > 0 and steps[si - 1][0] == 'unpool' and not b16 and Ws is not None
                 and ti != TI_MODE_COMPACT and width % 4 == 0 and Ws.shape[0] % 4 == 0)
+
+    @staticmethod
+    def _wgrad_mapped(n_rows, width, H, Cout):
+        """The backward of a commuted block over `n_rows` rows reads its x through the trace (USE_WGRAD_MAP): the shapes whose
+        packed weight-gradient product runs on the producer / consumer kernel."""
+        return bool(USE_WGRAD_MAP and _lib.load().stin_edgeconv_wgrad_map_supported(int(n_rows), int(width), int(H), int(Cout), 1,
+                                                                                   int(PREC_BWD)))
 
     @staticmethod
     def forward(ctx, x, meta, *params):
@@ -1131,6 +1146,8 @@ class NetFn(torch.autograd.Function):
                          params=(W1, b1, W2, b2, Ws, bs))
                 # the first product on the coarse rows of the unpool step in front: Y holds those rows only
                 d['src'] = plan[-1] if NetFn._commutes(steps, si, b16, width, Ws, ti) else None
+                # ... and in a training pass that step wrote no rows: backward reads x through its trace (x_from_src)
+                d['xsrc'] = bool(need_grad and d['src'] is not None and d['src']['skip'])
                 d['oY'] = take((d['src']['n_in'] if d['src'] else n_rows) * Yw * es, 'tmp')
                 d['oH'] = take(n_rows * (H + pad) * es, 'tmp')
                 # (round 6) a forward nobody differentiates - torch.no_grad(), the reference's validation loop - keeps no ReLU mask
@@ -1152,11 +1169,13 @@ class NetFn(torch.autograd.Function):
                 else:
                     d = dict(kind=OP_UNPOOL, pool=pool, n_in=pool.n_coarse, n_out=pool.n_fine, C=width)
                 n_rows = d['n_out']
-                # a no-grad forward keeps no x for backward: an unpool step whose block commutes writes no rows at all
+                # a no-grad forward keeps no x for backward: an unpool step whose block commutes writes no rows at all - nor does
+                # it in a training forward when the block's weight gradient reads x through the trace
                 nxt = steps[si + 1] if not last else None
-                d['skip'] = (stp[0] == 'unpool' and not need_grad and nxt is not None and nxt[0] == 'block' and
+                d['skip'] = (stp[0] == 'unpool' and nxt is not None and nxt[0] == 'block' and
                              NetFn._commutes(steps, si + 1, b16, width, params[pi + 4], trans_inv_mode(
-                                 nxt[1].first_filter.trans_inv, b16, params[pi].shape[0])))
+                                 nxt[1].first_filter.trans_inv, b16, params[pi].shape[0])) and
+                             (not need_grad or NetFn._wgrad_mapped(n_rows, width, params[pi].shape[0], params[pi + 2].shape[0])))
                 d['oO'] = None if (last or d['skip']) else take(n_rows * width * es, 'out')
             plan.append(d)
         if not need_grad:                                        # resolve the shared regions: [kept | out 0 | out 1 | temporaries]
@@ -1196,7 +1215,7 @@ class NetFn(torch.autograd.Function):
                 H, Cout, B = d['H'], d['Cout'], d['B']
                 d['op'] = dict(kind=OP_BLOCK, Cin=d['Cin'], Cp=d['Cp'], H=H, Cout=Cout, has_shortcut=int(d['sc']), trans_inv=int(d['ti']),
                                prec_fwd=int(d['prec']), bwd_split=d['bsp'], B=B, slice_quirk=int(g.quirk), eps=d['eps'],
-                               y_from_src=int(d['src'] is not None),
+                               y_from_src=int(d['src'] is not None), x_from_src=int(d['xsrc']),
                                n_out=d['N'], n_in=d['N'], ldx=ldx, ldo=Cout, ldy=d['Yw'], ldh=H + pad, fwd_ws_bytes=d['ws_bytes'],
                                W1=_ptr(W1.contiguous()), b1=_ptr(b1), W2=_ptr(W2.contiguous()), b2=_ptr(b2), Ws=_ptr(Ws),
                                bs=_ptr(bs), rowptr_dst=_ptr(cd.rowptr), col_dst=_ptr(cd.col),
@@ -1330,6 +1349,7 @@ class NetFn(torch.autograd.Function):
                 ev0, ev1 = KernelTimer.edge_events('stin_edge_relu_mean_bwd_mask' + ('_ti' if d['ti'] == TI_MODE_COMPACT else '') + sfx,
                                                    (d['N'], e.n_edges, d['H']))
                 blob.append(stc.pack(**d['op'], **NetFn._in_arena(d['rel'], base, xp), use_side=int(use[bi]), lddx=d['Cp'],
+                                     g_in_dy=int(USE_G_IN_DY and not b16 and d['sc']),
                                      bwd_ws_bytes=d['bwd_ws_bytes'], dx=p_dx,
                                      rowptr_src=_ptr(cs.rowptr), col_src=_ptr(cs.col), xslot=_ptr(e.xslot), w_src=_ptr(e.w_src),
                                      ptr_true=_ptr(gr.ptr_true), sid=_ptr(gr.sid if gr.quirk else None),
