@@ -7,6 +7,8 @@ the hand-written MFMA kernels too (gemm_nt / gemm_tn); the library-GEMM A/B aid 
 profiles/gemm_bench.py, outside the package.
 """
 import collections
+import ctypes
+import dataclasses
 import os
 
 import torch
@@ -807,6 +809,31 @@ def _fresh_grads(params, dev):
     return [None if p is None else torch.empty(p.shape, dtype=torch.float32, device=dev) for p in params]
 
 
+# Everything one fused block's parameter shapes, filter kind, input range and storage type decide, derived in block_shape() and
+# nowhere else: PackSet, EdgeConvBlockFn, net_eligible, usable_prepack and the NetFn planner read it.  Cp: Cin padded to the inner
+# dimension of the 16-byte GEMM paths (_pad_rows); ti: trans_inv_mode(); Yw: block_yw(); prec_fwd: forward_precision(); fwd_split,
+# bwd_split: block_split_modes().
+BlockShape = collections.namedtuple('BlockShape', 'Cin Cp H Cout has_shortcut ti Yw prec_fwd fwd_split bwd_split')
+
+
+def block_shape(w1_shape, w2_shape, has_shortcut, trans_inv, unbounded_input, b16, width=None):
+    """The BlockShape of a block with first / second Linear weights of these shapes.  Cin comes from W1; `width`, the width of
+    the rows the caller is about to feed the block, must agree with it."""
+    H, Cout = w1_shape[0], w2_shape[0]
+    Cin = w1_shape[1] if trans_inv else w1_shape[1] // 2
+    assert width is None or width == Cin, 'block input has %s channels, its first Linear takes %d' % (width, Cin)
+    pad = 8 if b16 else 4
+    ti = trans_inv_mode(trans_inv, b16, H)
+    prec = forward_precision(unbounded_input)
+    return BlockShape(Cin, (Cin + pad - 1) // pad * pad, H, Cout, bool(has_shortcut), ti, block_yw(H, Cout, has_shortcut, ti), prec,
+                      *block_split_modes(prec, b16, Cout))
+
+
+# One block's entry of PackSet.buffers: the block call's forward workspace `ws`, the backward operands (wcatT | w2T in `wts`, and as
+# ready-made views) and what they were packed for.
+Prepack = collections.namedtuple('Prepack', 'ws wts fwd_split bwd_split wcatT w2T b16')
+
+
 BLOCK_PACKED = _C['STIN_BLOCK_PACKED']
 _PACK_JOB = _lib.STRUCTS['stin_pack_job_t']
 USE_PACK_MANY = True
@@ -815,25 +842,18 @@ USE_PACK_MANY = True
 class PackSet:
     """The weight packs of ALL fused blocks of a network in one launch per step (stin_edgeconv_pack_many_f32) instead of
     one tiny launch at the head of every block: persistent per-block operand buffers (the block call's forward workspace
-    and wcatT | w2T), a job table in device memory written once.  specs: [(W1, b1, W2, b2, Ws, bs, trans_inv, prec_fwd, B)]
-    in block order, fp32 storage.  Valid while the parameters stay where they are (`matches`)."""
+    and wcatT | w2T), a job table in device memory written once.  specs: [(W1, b1, W2, b2, Ws, bs, trans_inv, unbounded_input,
+    B)] in block order (GraphResnetBlock.pack_spec), fp32 storage.  Valid while the parameters stay where they are (`matches`)."""
 
     def __init__(self, specs, dev, b16=False, transposes=()):
-        import ctypes
         lib = _lib.load()
         self.key = self.key_of(specs) + (bool(b16),) + tuple((_ptr(W), tuple(W.shape)) for W in transposes)
         self.b16 = bool(b16)
-        self.buffers = []                      # per block: (ws, wts, fwd_split, bwd_split, wcatT view, w2T view, b16)
+        self.buffers = []                      # per block: a Prepack
         blob, self.max_elems = b'', 0
-        pad = 8 if b16 else 4
-        for (W1, b1, W2, b2, Ws, bs, trans_inv, prec_fwd, B) in specs:
-            H, Cout = W1.shape[0], W2.shape[0]
-            Cin = W1.shape[1] if trans_inv else W1.shape[1] // 2
-            Cp = (Cin + pad - 1) // pad * pad
-            has_sc = Ws is not None
-            ti = trans_inv_mode(trans_inv, b16, H)
-            Yw = block_yw(H, Cout, has_sc, ti)
-            fsp, bsp = block_split_modes(prec_fwd, b16, Cout)       # what the block call is handed (bf16 rows: 0, 0)
+        for (W1, b1, W2, b2, Ws, bs, trans_inv, unbounded_input, B) in specs:
+            # (fsp, bsp: what the block call is handed - bf16 rows: 0, 0)
+            Cin, Cp, H, Cout, has_sc, ti, Yw, _, fsp, bsp = block_shape(W1.shape, W2.shape, Ws is not None, trans_inv, unbounded_input, b16)
             # what the pack writes: bf16 rows -> plain bf16 operands where every reduction length is a multiple of 8
             # (the rule of stin_net_fwd's block op), else the fp32 / split form of the fp32-storage path
             jf, jb = ((GEMM_W_BF16, GEMM_W_BF16) if (Cp % 8 == 0 and Cout % 8 == 0) else (0, 0)) if b16 else (fsp, bsp)
@@ -851,7 +871,7 @@ class PackSet:
                                    Cout=Cout, has_shortcut=int(has_sc), trans_inv=ti, fwd_split=jf, bwd_split=jb)
             self.max_elems = max(self.max_elems, Yw * Cp + H * Cout)
             # (the two backward operands as ready-made views: no tensor views are created inside autograd.Function.forward)
-            self.buffers.append((ws, wts, fsp, bsp, wts[:Yw * Cp].view(Cp, Yw), wts[Yw * Cp:].view(H, Cout), bool(b16)))
+            self.buffers.append(Prepack(ws, wts, fsp, bsp, wts[:Yw * Cp].view(Cp, Yw), wts[Yw * Cp:].view(H, Cout), bool(b16)))
         # plain transposes riding on the same launch (the tail Linear's backward operand W^T): a job whose first operand is
         # empty (Cin = Cp = 0) and whose "second Linear" is the weight - the pack writes w2T [K, Nc] = W^T in plain fp32
         self.transposed = []
@@ -867,8 +887,8 @@ class PackSet:
 
     @staticmethod
     def key_of(specs):
-        return tuple((_ptr(W1), _ptr(b1), _ptr(W2), _ptr(Ws), _ptr(bs), tuple(W1.shape), tuple(W2.shape), bool(t), int(pf), int(B),
-                      PREC_BWD, WEIGHT_PRESPLIT, GEMM_W_FRAG, TI_COMPACT, USE_EDGE_MASK) for (W1, b1, W2, b2, Ws, bs, t, pf, B) in specs)
+        return tuple((_ptr(W1), _ptr(b1), _ptr(W2), _ptr(Ws), _ptr(bs), tuple(W1.shape), tuple(W2.shape), bool(t), forward_precision(u),
+                      int(B), PREC_BWD, WEIGHT_PRESPLIT, GEMM_W_FRAG, TI_COMPACT, USE_EDGE_MASK) for (W1, b1, W2, b2, Ws, bs, t, u, B) in specs)
 
     def matches(self, specs, b16=False, transposes=()):
         return self.key == self.key_of(specs) + (bool(b16),) + tuple((_ptr(W), tuple(W.shape)) for W in transposes)
@@ -894,23 +914,19 @@ class EdgeConvBlockFn(torch.autograd.Function):
     per-kernel brackets); everywhere else the block is a one-op NetFn, which enqueues the same kernels in the same order."""
 
     @staticmethod
-    def forward(ctx, x, W1, b1, W2, b2, Ws, bs, edges, groups, trans_inv, eps=EPS, prec_fwd=None):
-        prec_fwd = PREC_FWD if prec_fwd is None else int(prec_fwd)
+    def forward(ctx, x, W1, b1, W2, b2, Ws, bs, edges, groups, trans_inv, eps=EPS, unbounded_input=False):
         x, _ = _mat(x)
-        N, Cin = x.shape
-        H, Cout = W1.shape[0], W2.shape[0]
-        has_shortcut = Ws is not None
+        N = x.shape[0]
         dev = x.device
         b16 = x.dtype == torch.bfloat16
-        ti = trans_inv_mode(trans_inv, b16, H)                    # 2 = compact: Y = [B | S], A_i = b1 - B_i formed by the edge stage
-        Yw = block_yw(H, Cout, has_shortcut, ti)
+        # ti: 2 = compact: Y = [B | S], A_i = b1 - B_i formed by the edge stage.  fsp / bsp: the forward / backward weight operands,
+        # pre-split once here into the two 16-bit pieces the split GEMMs use (instead of once per GEMM block); plain fp32 for the
+        # other precisions and for bf16-storage activations
+        Cin, Cp, H, Cout, has_shortcut, ti, Yw, prec_fwd, fsp, bsp = block_shape(W1.shape, W2.shape, Ws is not None, trans_inv,
+                                                                                 unbounded_input, b16, x.shape[1])
         oS = Yw - (Cout if has_shortcut else 0)                   # column of the shortcut in Y / dY
         pad = 8 if b16 else 4
         xp = _pad_rows(x, pad)
-        Cp = xp.shape[1]
-        # forward / backward weight operands, pre-split once here into the two 16-bit pieces the split GEMMs use
-        # (instead of once per GEMM block); plain fp32 for the other precisions and for bf16-storage activations
-        fsp, bsp = block_split_modes(prec_fwd, b16, Cout)
         pack = torch.empty(Yw * Cp * 2 + 2 * H * Cout + Yw, dtype=torch.float32, device=dev)
         wcat = pack[:Yw * Cp].view(Yw, Cp)
         wcatT = pack[Yw * Cp:2 * Yw * Cp].view(Cp, Yw)
@@ -1019,14 +1035,17 @@ def _align256(n):
     return (n + 255) & ~255
 
 
-def usable_prepack(blk, b16):
+def _block_shape_of(blk, params, b16, width=None):
+    """BlockShape of a fused GraphResnetBlock with the parameters `params` (blk.fused_params()), fed rows of `width` channels."""
+    return block_shape(params[0].shape, params[2].shape, params[4] is not None, blk.first_filter.trans_inv, blk.unbounded_input,
+                       b16, width)
+
+
+def usable_prepack(blk, b16, shape):
     """blk._prepacked - the block's operand buffers in the network's PackSet - when it was packed for this storage type and
-    the split modes the block runs with now, else None: the node then packs for itself."""
+    the split modes the block runs with now (`shape`), else None: the node then packs for itself."""
     pp = blk._prepacked
-    if pp is None:
-        return None
-    fsp, bsp = block_split_modes(forward_precision(blk.unbounded_input), b16, blk.dim_out)
-    return pp if (len(pp) > 6 and pp[6] == b16 and pp[2] == fsp and pp[3] == bsp) else None
+    return pp if (pp is not None and pp.b16 == b16 and pp.fwd_split == shape.fwd_split and pp.bwd_split == shape.bwd_split) else None
 
 
 def net_eligible(steps, x):
@@ -1042,19 +1061,288 @@ def net_eligible(steps, x):
     for st in steps:
         if st[0] != 'block':
             continue
-        b = st[1]
-        H = b.first_filter.nn[0].weight.shape[0]
-        if not edge_mask_supported(H) or st[2].n <= 1:
+        shape = _block_shape_of(st[1], st[1].fused_params(), b16)
+        if not edge_mask_supported(shape.H) or st[2].n <= 1:
             return False
-        packed.append(usable_prepack(b, b16) is not None)
+        packed.append(usable_prepack(st[1], b16, shape) is not None)
     return bool(packed) and any(packed) == all(packed)
+
+
+# ---- the plan of a NetFn (plan_net): what the op table and the arena look like, from shapes and integer attributes alone - no data
+# pointer is read, so it runs without a GPU (tests/test_net_plan.py).
+class Slot:
+    """`nbytes` of the arena; `offset` is set when the layout is closed (Arena.close)."""
+    __slots__ = ('kind', 'nbytes', 'at', 'offset')
+
+    def __init__(self, kind, nbytes, at):
+        self.kind, self.nbytes, self.at, self.offset = kind, nbytes, at, None
+
+
+# A training forward keeps everything for backward: all three kinds bump one offset.  (round 6) A forward nobody differentiates
+# (shared) keeps nothing, so every op's temporaries (Y, hE, agg, statistics, unpacked weights) restart in ONE region and the op
+# outputs ping-pong between two regions of the largest output - [kept | out 0 | out 1 | temporaries]: the arena of an evaluation
+# pass is the largest block's working set instead of the sum over blocks (200 704 vertices: 0.5 GB instead of 3 GB), and it
+# stays cache-warm.
+class Arena:
+    """Byte layout of a NetFn's one allocation in 256-byte aligned slots: KEPT until backward, an op's temporaries, an op's output."""
+    KEPT, TMP, OUT = range(3)
+
+    def __init__(self, shared):
+        self.shared, self.slots, self.nbytes = shared, [], None
+        self.top = [0, 0]                       # where the next KEPT / TMP slot starts inside its region
+        self.tmp_max = self.out_max = self.n_out = 0
+
+    def next_op(self):
+        self.top[Arena.TMP] = 0
+
+    def take(self, nbytes, kind=KEPT):
+        kind = kind if self.shared else Arena.KEPT
+        if kind == Arena.OUT:
+            slot = Slot(kind, nbytes, self.n_out & 1)           # which of the two output regions
+            self.n_out += 1
+            self.out_max = max(self.out_max, _align256(nbytes))
+        else:
+            slot = Slot(kind, nbytes, self.top[kind])
+            self.top[kind] = _align256(self.top[kind] + nbytes)
+            self.tmp_max = max(self.tmp_max, self.top[Arena.TMP])
+        self.slots.append(slot)
+        return slot
+
+    def close(self):
+        """Resolve every slot's offset; `nbytes` is the arena's size."""
+        kept = self.top[Arena.KEPT]
+        for s in self.slots:
+            s.offset = {Arena.KEPT: s.at, Arena.OUT: kept + s.at * self.out_max, Arena.TMP: kept + 2 * self.out_max + s.at}[s.kind]
+        self.nbytes = kept + 2 * self.out_max + self.tmp_max
+
+
+# The descriptors of a plan's ops.  `rel`: the fields of stin_net_op_t that point into the arena, name -> (Slot, byte offset inside
+# it); a Slot of None is a buffer the op does not have (no mask in a plan without backward, no x behind an unpool step that wrote
+# no rows).  `out`: the Slot of the output rows; None for the last op, which writes the node's output tensor.
+@dataclasses.dataclass(eq=False)
+class BlockOp:
+    """One fused block of a plan."""
+    params: tuple           # (W1, b1, W2, b2, Ws, bs)
+    edges: object
+    groups: object
+    shape: BlockShape
+    N: int
+    B: int
+    eps: float
+    pp: object              # usable_prepack()
+    fwd_ws_bytes: int
+    bwd_ws_bytes: int       # (0 in a plan without backward)
+    kind: int = OP_BLOCK
+    src: object = None      # the unpool op in front when the first product runs on ITS input rows (y_from_src): Y holds those rows only
+    x_from_src: bool = False        # ... and that op wrote no rows: backward reads x through its trace
+    rel: dict = None
+    out: Slot = None
+
+
+@dataclasses.dataclass(eq=False)
+class PoolOp:
+    """One max-pool (OP_POOL_MAX) or unpool (OP_UNPOOL) step of a plan, C channels wide."""
+    kind: int
+    pool: object
+    n_in: int
+    n_out: int
+    C: int
+    writes_no_rows: bool = False    # an unpool step whose block reads the coarse rows through the trace: no gather, no output
+    rel: dict = None
+    out: Slot = None
+
+
+NetPlan = collections.namedtuple('NetPlan', 'ops arena n_rows width')        # (n_rows, width: shape of the node's output)
+
+
+def _commutes(shape, b16):
+    """A block behind an unpool step takes its first product from that step's input rows (USE_UNPOOL_COMMUTE): fp32 storage, a shortcut
+    (the residual comes out of Y), A materialised in Y, no channel padding in between.  Every level takes it; a level whose mapped edge and
+    norm launches lose more than its product saves is to be excluded HERE (profiles/r14_unpool_commute.md: the per-level figures are open)."""
+    return (USE_UNPOOL_COMMUTE and not b16 and shape.has_shortcut and shape.ti != TI_MODE_COMPACT and shape.Cin % 4 == 0
+            and shape.Cout % 4 == 0)
+
+
+def plan_net(steps, params, n_rows, width, b16, need_grad):
+    """The NetPlan of `steps` (see net_eligible) with the flat parameters `params` (see run_net) over [n_rows, width] input rows, in
+    three passes: shapes, decisions, arena layout."""
+    lib = _lib.load()
+    es, pad = (2, 8) if b16 else (4, 4)
+    # ---- pass 1, shapes: (rows, width) through the steps -> one BlockOp / PoolOp each
+    ops = []
+    for stp in steps:
+        if stp[0] == 'block':
+            _, blk, edges, groups = stp
+            p, params = tuple(params[:6]), params[6:]
+            sh = _block_shape_of(blk, p, b16, width)
+            ops.append(BlockOp(p, edges, groups, sh, n_rows, groups.B, float(blk.first_norm.eps), usable_prepack(blk, b16, sh),
+                               lib.stin_edgeconv_block_fwd_workspace_bytes(sh.Cin, sh.Cp, sh.H, sh.Cout, int(sh.has_shortcut), groups.B),
+                               lib.stin_edgeconv_block_bwd_workspace_bytes(n_rows, sh.Cp, sh.H, sh.Cout, int(sh.has_shortcut), groups.B,
+                                                                           int(b16)) if need_grad else 0))
+            width = sh.Cout
+        else:
+            pool = stp[1]
+            n_in, n_rows = (pool.n_fine, pool.n_coarse) if stp[0] == 'pool' else (pool.n_coarse, pool.n_fine)
+            ops.append(PoolOp(OP_POOL_MAX if stp[0] == 'pool' else OP_UNPOOL, pool, n_in, n_rows, width))
+    # ---- pass 2, decisions: for every block behind an unpool step, once: does its first product run on the coarse rows (src), and
+    # does the unpool step then write rows at all
+    for prev, op in zip(ops, ops[1:]):
+        if op.kind == OP_BLOCK and prev.kind == OP_UNPOOL and _commutes(op.shape, b16):
+            sh = op.shape
+            op.src = prev
+            # a no-grad forward keeps no x for backward: the unpool step writes no rows at all - nor does it in a training forward
+            # when the block's backward reads x through the trace (USE_WGRAD_MAP): the shapes whose packed weight-gradient product
+            # runs on the producer / consumer kernel
+            prev.writes_no_rows = not need_grad or bool(USE_WGRAD_MAP and lib.stin_edgeconv_wgrad_map_supported(
+                int(op.N), int(sh.Cin), int(sh.H), int(sh.Cout), 1, int(PREC_BWD)))
+            op.x_from_src = need_grad and prev.writes_no_rows
+    # ---- pass 3, layout: the arena slots, in the order  block: Y, hE, mask, agg, stats, [unpacked weights, forward workspace], out;
+    # pool: arg, out;  unpool: out
+    arena = Arena(shared=not need_grad)
+    x, tmp = None, Arena.TMP
+    for op in ops:
+        arena.next_op()
+        last = op is ops[-1]
+        if op.kind == OP_BLOCK:
+            sh, N = op.shape, op.N
+            Y = arena.take((op.src.n_in if op.src else N) * sh.Yw * es, tmp)
+            hE = arena.take(N * (sh.H + pad) * es, tmp)
+            # (round 6) a forward nobody differentiates - torch.no_grad(), the reference's validation loop - keeps no ReLU mask
+            mask = arena.take(max(op.edges.n_edges, 1) * (sh.H // 32) * 4) if need_grad else None
+            agg = arena.take(N * sh.Cout * es, tmp)
+            stats = arena.take(2 * op.B * sh.Cout * 4, tmp)
+            op.rel = dict(x=(x, 0), Y=(Y, 0), hE=(hE, 0), mask=(mask, 0), agg=(agg, 0), mean=(stats, 0), rstd=(stats, op.B * sh.Cout * 4))
+            if op.pp is None:
+                W = arena.take((sh.Yw * sh.Cp + sh.H * sh.Cout) * 4, tmp)
+                op.rel.update(wcatT=(W, 0), w2T=(W, sh.Yw * sh.Cp * 4), fwd_ws=(arena.take(op.fwd_ws_bytes, tmp), 0))
+            elif op.pp.ws.numel() < op.fwd_ws_bytes:
+                raise RuntimeError('NetFn: prepacked workspace too small for this batch (PackSet built for another batch size)')
+            if not last:
+                op.out = arena.take(N * sh.Cout * es, Arena.OUT)
+        else:
+            op.rel = dict(x=(x, 0), arg=(arena.take(op.n_out * op.C * 4, tmp) if op.kind == OP_POOL_MAX else None, 0))
+            if not (last or op.writes_no_rows):
+                op.out = arena.take(op.n_out * op.C * es, Arena.OUT)
+        x = op.out
+    arena.close()
+    return NetPlan(ops, arena, n_rows, width)
+
+
+def _static_fields(plan, ldx, pad):
+    """Per op, the stin_net_op_t fields both directions share and that do not point into the arena; ldx: the input's row pitch."""
+    out = []
+    for op in plan.ops:
+        if op.kind == OP_BLOCK:
+            sh, g, cd, pp = op.shape, op.groups, op.edges.by_dst, op.pp
+            W1, b1, W2, b2, Ws, bs = op.params
+            packed = {} if pp is None else dict(wcatT=_ptr(pp.wcatT), w2T=_ptr(pp.w2T), fwd_ws=_ptr(pp.ws))
+            out.append(dict(kind=OP_BLOCK, Cin=sh.Cin, Cp=sh.Cp, H=sh.H, Cout=sh.Cout, has_shortcut=int(sh.has_shortcut),
+                            trans_inv=int(sh.ti), prec_fwd=int(sh.prec_fwd), bwd_split=sh.bwd_split, B=op.B, slice_quirk=int(g.quirk),
+                            eps=op.eps, y_from_src=int(op.src is not None), x_from_src=int(op.x_from_src),
+                            n_out=op.N, n_in=op.N, ldx=ldx, ldo=sh.Cout, ldy=sh.Yw, ldh=sh.H + pad, fwd_ws_bytes=op.fwd_ws_bytes,
+                            fwd_split=sh.fwd_split | (BLOCK_PACKED if pp is not None else 0),
+                            W1=_ptr(W1.contiguous()), b1=_ptr(b1), W2=_ptr(W2.contiguous()), b2=_ptr(b2), Ws=_ptr(Ws),
+                            bs=_ptr(bs), rowptr_dst=_ptr(cd.rowptr), col_dst=_ptr(cd.col),
+                            ptr_sum=_ptr(g.ptr_sum), gid=_ptr(g.gid), inv_cnt=_ptr(g.inv_cnt), **packed))
+            ldx = sh.Cout
+        else:
+            ch, C = op.pool.children, op.C
+            out.append(dict(kind=op.kind, Cin=C, Cp=C, Cout=C, n_out=op.n_out, n_in=op.n_in, ldx=ldx, ldo=C,
+                            rowptr_dst=_ptr(ch.rowptr), col_dst=_ptr(ch.col), trace=_ptr(op.pool.trace)))
+            ldx = C
+    return out
+
+
+# The arena fields are resolved on the arena of the saved tensors the DIRECTION is handed: under torch.utils.checkpoint(
+# use_reentrant=False) backward gets the recomputed ones, not the forward call's.  (stin_net_bwd and the block backward read no
+# forward-only field, so backward packs the forward's static fields again with its own on top.)
+def _pack_table(plan, static, base, xp, own):
+    """The op table of one direction: per op its static fields, its arena fields as addresses above `base` (the first op reads
+    the padded input xp instead) and the direction's own fields, own(i, op)."""
+    blob = []
+    for i, (op, fields) in enumerate(zip(plan.ops, static)):
+        ptrs = {k: 0 if s is None else base + s.offset + o for k, (s, o) in op.rel.items()}
+        if i == 0:
+            ptrs['x'] = _ptr(xp)
+        blob.append(_NET_OP.pack(**fields, **ptrs, **own(i, op)))
+    return ctypes.create_string_buffer(b''.join(blob), len(blob) * _NET_OP.size)
+
+
+def _grad_targets(plan, blocks, xp, arena, g, need_dx):
+    """Gradient tensors, scratch memory, the weight-gradient stream and the events of one backward pass over `plan`."""
+    dev, dt, es = xp.device, xp.dtype, xp.element_size()
+    # gradients: straight into an accepting TrainStep bucket (all blocks or none), else fresh tensors handed to autograd
+    # (probe every block BEFORE any bucket bookkeeping changes: with a frozen or unslotted parameter in one block - a frozen
+    # decoder, say - the whole node hands fresh tensors to autograd instead of leaving `written` half set and raising)
+    direct = []
+    if all(_direct_grad_views(d.params, dry_run=True) is not None for d in blocks):
+        direct = [_direct_grad_views(d.params) for d in blocks]
+    grads = None
+    if len(direct) != len(blocks):
+        direct = []
+        grads = [t for d in blocks for t in _fresh_grads(d.params, dev)]
+    # scratch: input gradients ping-pong between two buffers of the largest size; every block its own backward workspace
+    # (the side stream reads it after this call has returned)
+    dx_bytes, ws_off, off = 0, [], 0
+    for i, d in enumerate(plan.ops):
+        if d.kind == OP_BLOCK:
+            if i > 0 or need_dx:
+                dx_bytes = max(dx_bytes, d.N * d.shape.Cp * es)
+            ws_off.append(off)
+            off = _align256(off + d.bwd_ws_bytes)
+        else:
+            dx_bytes = max(dx_bytes, d.n_in * d.C * es)
+    dx_bytes = _align256(dx_bytes)
+    scratch = torch.empty(2 * dx_bytes + off, dtype=torch.uint8, device=dev)
+    dx0 = None
+    d0 = plan.ops[0]
+    if need_dx:
+        dx0 = torch.empty(d0.N if d0.kind == OP_BLOCK else d0.n_in, d0.shape.Cp if d0.kind == OP_BLOCK else d0.C,
+                          dtype=dt, device=dev)
+    all_params = [p for d in blocks for p in d.params]
+    side_ok = USE_WGRAD_STREAM and _join_deferrable(all_params, direct)
+    use = [side_ok and WGRAD_MIN_WORK <= float(d.N) * d.shape.Yw * d.shape.Cp <= WGRAD_MAX_WORK for d in blocks]
+    side_stream, any_side = 0, any(use)
+    evs = [(0, 0)] * len(blocks)
+    # Overlapped gradient all-reduce (train_step.FlatGradBucket.enable_overlap, round 4): every block records its ev_done when
+    # its parameter gradients are written - on the weight-gradient stream, or on the compute stream for a block that does
+    # not use it - INSIDE the C call's kernel sequence, and the bucket hands each completed segment to RCCL behind exactly
+    # those events: the reduction of the decoder's gradients runs while the encoder's backward kernels are still queued.
+    bucket = None
+    if direct:
+        for p in all_params:
+            if p is not None:
+                bucket = p._stin_slot[0]
+                break
+    seg_events = bucket is not None and bucket.wants_block_events()
+    done_ev = [None] * len(blocks)
+    if any_side or seg_events:
+        side = _wgrad_side(dev)
+    if any_side:
+        side.hold.append((scratch, xp, arena, g))
+        side_stream = side.stream.cuda_stream
+    if any_side or seg_events:
+        for bi in reversed(range(len(blocks))):      # in BACKWARD order: side.last_done = the event recorded last
+            if use[bi]:
+                tri = side.next_events()
+                evs[bi] = (tri[1].cuda_event, tri[2].cuda_event)
+                done_ev[bi] = tri[2]
+            elif seg_events:
+                tri = side.next_events(track=False)
+                evs[bi] = (0, tri[2].cuda_event)
+                done_ev[bi] = tri[2]
+        if grads is not None:
+            for t in grads:
+                if t is not None:
+                    t.record_stream(side.stream)
+    return direct, grads, scratch, dx_bytes, ws_off, dx0, all_params, use, side_stream, any_side, evs, bucket, done_ev
 
 
 class NetFn(torch.autograd.Function):
     """A run of fused blocks and pool / unpool steps - the network's whole graph part, its bottleneck chain, or one block - as
     ONE autograd node and one C call per direction (stin_net_fwd / _bwd: loops over the per-op launch sequences, same kernels
-    in the same order -> bit-identical to the per-kernel path).  All tensors backward needs live in one arena allocation, the
-    op table is packed on the host (480 bytes per op).
+    in the same order -> bit-identical to the per-kernel path).  All tensors backward needs live in one arena allocation, laid
+    out by plan_net; the op table is packed on the host (480 bytes per op, _pack_table).
     args: x, meta = (steps, need_grad), then the flat parameters (W1, b1, W2, b2, Ws, bs) of every block in step order."""
 
     calls = 0                           # nodes created ...
@@ -1064,303 +1352,71 @@ class NetFn(torch.autograd.Function):
                                         # in training, those whose block reads x through the trace in backward (USE_WGRAD_MAP)
 
     @staticmethod
-    def _in_arena(rel, base, xp):
-        """The fields of an op that point into the arena (offsets `rel`; None = no buffer) as addresses; the first op reads the
-        padded input xp."""
-        ptrs = {k: 0 if o is None else base + o for k, o in rel.items()}
-        ptrs.setdefault('x', _ptr(xp))
-        return ptrs
-
-    @staticmethod
-    def _commutes(steps, si, b16, width, Ws, ti):
-        """Block `si` takes its first product from the input rows of the unpool step in front of it (USE_UNPOOL_COMMUTE): fp32
-        storage, a shortcut (the residual comes out of Y), A materialised in Y, no channel padding in between.  Every level takes
-        it; a level whose mapped edge and norm launches lose more than its product saves is to be excluded HERE
-        (profiles/r14_unpool_commute.md: the per-level figures are still open)."""
-        return (USE_UNPOOL_COMMUTE and si > 0 and steps[si - 1][0] == 'unpool' and not b16 and Ws is not None
-                and ti != TI_MODE_COMPACT and width % 4 == 0 and Ws.shape[0] % 4 == 0)
-
-    @staticmethod
-    def _wgrad_mapped(n_rows, width, H, Cout):
-        """The backward of a commuted block over `n_rows` rows reads its x through the trace (USE_WGRAD_MAP): the shapes whose
-        packed weight-gradient product runs on the producer / consumer kernel."""
-        return bool(USE_WGRAD_MAP and _lib.load().stin_edgeconv_wgrad_map_supported(int(n_rows), int(width), int(H), int(Cout), 1,
-                                                                                   int(PREC_BWD)))
-
-    @staticmethod
     def forward(ctx, x, meta, *params):
         steps, need_grad = meta
         NetFn.calls += 1
         NetFn.sizes[len(steps)] += 1
-        lib = _lib.load()
         x, _ = _mat(x)
-        dev, dt = x.device, x.dtype
-        b16 = dt == torch.bfloat16
+        b16 = x.dtype == torch.bfloat16
         sfx = '_bf16' if b16 else '_f32'
-        es = x.element_size()
         pad = 8 if b16 else 4
-        N0, Cin0 = x.shape
         xp = _pad_rows(x, pad)
-        # ---- pass 1: shapes and arena layout
-        plan, off, pi = [], 0, 0
-        n_rows, width = N0, Cin0
-
-        # (round 6) no-grad forward: nothing is kept for a backward pass, so every block's temporaries (Y, hE, agg, statistics, unpacked
-        # weights) share ONE region and the op outputs ping-pong between two - the arena of an evaluation pass is the largest block's
-        # working set instead of the sum over blocks (200 704 vertices: 0.5 GB instead of 3 GB), and it stays cache-warm
-        toff, tmax, omax = 0, 0, 0
-
-        def take(nbytes, kind='keep'):
-            nonlocal off, toff, tmax, omax
-            if not need_grad and kind == 'tmp':
-                o = toff
-                toff = _align256(toff + nbytes)
-                tmax = max(tmax, toff)
-                return ('tmp', o)
-            if not need_grad and kind == 'out':
-                omax = max(omax, _align256(nbytes))
-                return ('out', 0)
-            o = off
-            off = _align256(off + nbytes)
-            return o
-        for si, stp in enumerate(steps):
-            toff = 0
-            last = si == len(steps) - 1
-            if stp[0] == 'block':
-                blk, edges, groups = stp[1], stp[2], stp[3]
-                W1, b1, W2, b2, Ws, bs = params[pi:pi + 6]
-                pi += 6
-                H, Cout = W1.shape[0], W2.shape[0]
-                Cin = width
-                Cp = (Cin + pad - 1) // pad * pad
-                sc = Ws is not None
-                ti = trans_inv_mode(blk.first_filter.trans_inv, b16, H)
-                Yw = block_yw(H, Cout, sc, ti)
-                B = groups.B
-                prec = forward_precision(blk.unbounded_input)
-                fsp, bsp = block_split_modes(prec, b16, Cout)
-                pp = usable_prepack(blk, b16)
-                ws_bytes = lib.stin_edgeconv_block_fwd_workspace_bytes(Cin, Cp, H, Cout, int(sc), B)
-                d = dict(kind=OP_BLOCK, N=n_rows, Cin=Cin, Cp=Cp, H=H, Cout=Cout, sc=sc, Yw=Yw, B=B, prec=prec, fsp=fsp, bsp=bsp, pp=pp,
-                         ws_bytes=ws_bytes, edges=edges, groups=groups, ti=ti, eps=float(blk.first_norm.eps),
-                         params=(W1, b1, W2, b2, Ws, bs))
-                # the first product on the coarse rows of the unpool step in front: Y holds those rows only
-                d['src'] = plan[-1] if NetFn._commutes(steps, si, b16, width, Ws, ti) else None
-                # ... and in a training pass that step wrote no rows: backward reads x through its trace (x_from_src)
-                d['xsrc'] = bool(need_grad and d['src'] is not None and d['src']['skip'])
-                d['oY'] = take((d['src']['n_in'] if d['src'] else n_rows) * Yw * es, 'tmp')
-                d['oH'] = take(n_rows * (H + pad) * es, 'tmp')
-                # (round 6) a forward nobody differentiates - torch.no_grad(), the reference's validation loop - keeps no ReLU mask
-                d['oM'] = take(max(edges.n_edges, 1) * (H // 32) * 4) if need_grad else None
-                d['oA'] = take(n_rows * Cout * es, 'tmp')
-                d['oS'] = take(2 * B * Cout * 4, 'tmp')
-                if pp is None:
-                    d['oW'] = take((Yw * Cp + H * Cout) * 4, 'tmp')
-                    d['oWS'] = take(ws_bytes, 'tmp')
-                elif pp[0].numel() < ws_bytes:
-                    raise RuntimeError('NetFn: prepacked workspace too small for this batch (PackSet built for another batch size)')
-                d['oO'] = None if last else take(n_rows * Cout * es, 'out')
-                width = Cout
-            else:
-                pool = stp[1]
-                if stp[0] == 'pool':
-                    d = dict(kind=OP_POOL_MAX, pool=pool, n_in=pool.n_fine, n_out=pool.n_coarse, C=width)
-                    d['oArg'] = take(pool.n_coarse * width * 4, 'tmp')
-                else:
-                    d = dict(kind=OP_UNPOOL, pool=pool, n_in=pool.n_coarse, n_out=pool.n_fine, C=width)
-                n_rows = d['n_out']
-                # a no-grad forward keeps no x for backward: an unpool step whose block commutes writes no rows at all - nor does
-                # it in a training forward when the block's weight gradient reads x through the trace
-                nxt = steps[si + 1] if not last else None
-                d['skip'] = (stp[0] == 'unpool' and nxt is not None and nxt[0] == 'block' and
-                             NetFn._commutes(steps, si + 1, b16, width, params[pi + 4], trans_inv_mode(
-                                 nxt[1].first_filter.trans_inv, b16, params[pi].shape[0])) and
-                             (not need_grad or NetFn._wgrad_mapped(n_rows, width, params[pi].shape[0], params[pi + 2].shape[0])))
-                d['oO'] = None if (last or d['skip']) else take(n_rows * width * es, 'out')
-            plan.append(d)
-        if not need_grad:                                        # resolve the shared regions: [kept | out 0 | out 1 | temporaries]
-            o_base, t_base, flip = off, off + 2 * omax, 0
-            for d in plan:
-                for k, v in d.items():
-                    if isinstance(v, tuple) and len(v) == 2 and v[0] == 'tmp':
-                        d[k] = t_base + v[1]
-                    elif isinstance(v, tuple) and len(v) == 2 and v[0] == 'out':
-                        d[k] = o_base + flip * omax
-                        flip ^= 1
-            off = t_base + tmax
-        arena = torch.empty(off, dtype=torch.uint8, device=dev)
-        out = torch.empty(n_rows, width, dtype=dt, device=dev)
+        plan = plan_net(steps, params, x.shape[0], x.shape[1], b16, need_grad)
+        arena = torch.empty(plan.arena.nbytes, dtype=torch.uint8, device=x.device)
+        out = torch.empty(plan.n_rows, plan.width, dtype=x.dtype, device=x.device)
         base, p_out = _ptr(arena), _ptr(out)
         assert base % 256 == 0
-        # ---- pass 2: the op table.  d['op'] keeps each op's fields (by the names of stin_net_op_t) and d['rel'] those that point
-        # into the arena, as offsets: backward packs both again with its own on top (stin_net_bwd and the block backward read no
-        # forward-only field), on the addresses of the saved tensors IT is handed - under torch.utils.checkpoint(use_reentrant=
-        # False) those are the recomputed ones, not this call's
-        stc = _NET_OP
-        blob = []
-        xin, ldx = None, xp.stride(0)                      # offset of the op's input rows in the arena; None = xp
-        first = True
-        for d in plan:
-            rel = {} if first else {'x': xin}               # (xin None behind a skipped unpool gather: the block reads no x)
-            first = False
-            if d['kind'] == OP_BLOCK:
-                W1, b1, W2, b2, Ws, bs = d['params']
-                pp = d['pp']
-                if pp is not None:
-                    packed = dict(wcatT=_ptr(pp[4]), w2T=_ptr(pp[5]), fwd_ws=_ptr(pp[0]), fwd_split=d['fsp'] | BLOCK_PACKED)
-                else:
-                    packed = dict(fwd_split=d['fsp'])
-                    rel.update(wcatT=d['oW'], w2T=d['oW'] + d['Yw'] * d['Cp'] * 4, fwd_ws=d['oWS'])
-                g, cd = d['groups'], d['edges'].by_dst
-                H, Cout, B = d['H'], d['Cout'], d['B']
-                d['op'] = dict(kind=OP_BLOCK, Cin=d['Cin'], Cp=d['Cp'], H=H, Cout=Cout, has_shortcut=int(d['sc']), trans_inv=int(d['ti']),
-                               prec_fwd=int(d['prec']), bwd_split=d['bsp'], B=B, slice_quirk=int(g.quirk), eps=d['eps'],
-                               y_from_src=int(d['src'] is not None), x_from_src=int(d['xsrc']),
-                               n_out=d['N'], n_in=d['N'], ldx=ldx, ldo=Cout, ldy=d['Yw'], ldh=H + pad, fwd_ws_bytes=d['ws_bytes'],
-                               W1=_ptr(W1.contiguous()), b1=_ptr(b1), W2=_ptr(W2.contiguous()), b2=_ptr(b2), Ws=_ptr(Ws),
-                               bs=_ptr(bs), rowptr_dst=_ptr(cd.rowptr), col_dst=_ptr(cd.col),
-                               ptr_sum=_ptr(g.ptr_sum), gid=_ptr(g.gid), inv_cnt=_ptr(g.inv_cnt), **packed)
-                rel.update(Y=d['oY'], hE=d['oH'], agg=d['oA'], mean=d['oS'], rstd=d['oS'] + B * Cout * 4)
-                if need_grad:
-                    rel['mask'] = d['oM']
-                NetFn.commuted += int(d['src'] is not None)
-                # (the mapped launch of a commuted block is bracketed under the plain kernel's name and tag: same rows, edges, width)
-                ev0, ev1 = KernelTimer.edge_events('stin_edge_relu_mean_fwd' + sfx, (d['N'], d['edges'].n_edges, H))
-                events = dict(ev_edge0=ev0, ev_edge1=ev1)
-                ldx = Cout
-            else:
-                pool, C = d['pool'], d['C']
-                ch = pool.children
-                d['op'] = dict(kind=d['kind'], Cin=C, Cp=C, Cout=C, n_out=d['n_out'], n_in=d['n_in'], ldx=ldx, ldo=C,
-                               rowptr_dst=_ptr(ch.rowptr), col_dst=_ptr(ch.col), trace=_ptr(pool.trace))
-                if d['kind'] == OP_POOL_MAX:
-                    rel['arg'] = d['oArg']
-                events = {}
-                ldx = C
-            d['rel'] = rel
-            skip = d.get('skip', False)
-            NetFn.gathers_skipped += int(skip)
-            blob.append(stc.pack(**d['op'], **NetFn._in_arena(rel, base, xp), **events,
-                                 out=0 if skip else p_out if d['oO'] is None else base + d['oO']))
-            xin = d['oO']
-        import ctypes
-        buf = ctypes.create_string_buffer(b''.join(blob), len(plan) * stc.size)
-        _call('stin_net_fwd', int(b16), buf, len(plan), _stream(x))
-        if not need_grad:
-            return out
-        ctx.save_for_backward(xp, arena)
-        ctx.plan = plan
-        ctx.cin0 = Cin0
-        ctx.params = params
+        static = _static_fields(plan, xp.stride(0), pad)
+
+        def own(i, op):
+            if op.kind != OP_BLOCK:
+                NetFn.gathers_skipped += int(op.writes_no_rows)
+                return dict(out=0 if op.writes_no_rows else p_out if op.out is None else base + op.out.offset)
+            NetFn.commuted += int(op.src is not None)
+            # (the mapped launch of a commuted block is bracketed under the plain kernel's name and tag: same rows, edges, width)
+            ev0, ev1 = KernelTimer.edge_events('stin_edge_relu_mean_fwd' + sfx, (op.N, op.edges.n_edges, op.shape.H))
+            return dict(ev_edge0=ev0, ev_edge1=ev1, out=p_out if op.out is None else base + op.out.offset)
+        buf = _pack_table(plan, static, base, xp, own)
+        _call('stin_net_fwd', int(b16), buf, len(plan.ops), _stream(x))
+        if need_grad:
+            ctx.save_for_backward(xp, arena)
+            ctx.plan, ctx.static = plan, static
+            ctx.cin0 = x.shape[1]
+            ctx.params = params
         return out
 
     @staticmethod
     def backward(ctx, g):
         xp, arena = ctx.saved_tensors                    # (the ops' pointers go into the arena)
-        base = _ptr(arena)
         plan, params = ctx.plan, ctx.params
-        lib = _lib.load()
-        dev, dt = xp.device, xp.dtype
-        b16 = dt == torch.bfloat16
+        dev = xp.device
+        b16 = xp.dtype == torch.bfloat16
         sfx = '_bf16' if b16 else '_f32'
-        es = xp.element_size()
         g, ldg = _mat(g)
         _same(xp, g)
-        need_dx = ctx.needs_input_grad[0]
-        blocks = [d for d in plan if d['kind'] == OP_BLOCK]
-        # gradients: straight into an accepting TrainStep bucket (all blocks or none), else fresh tensors handed to autograd
-        # (probe every block BEFORE any bucket bookkeeping changes: with a frozen or unslotted parameter in one block - a frozen
-        # decoder, say - the whole node hands fresh tensors to autograd instead of leaving `written` half set and raising)
-        direct = []
-        if all(_direct_grad_views(d['params'], dry_run=True) is not None for d in blocks):
-            direct = [_direct_grad_views(d['params']) for d in blocks]
-        grads = None
-        if len(direct) != len(blocks):
-            direct = []
-            grads = [t for d in blocks for t in _fresh_grads(d['params'], dev)]
-        # scratch: input gradients ping-pong between two buffers of the largest size; every block its own backward workspace
-        # (the side stream reads it after this call has returned)
-        dx_bytes, ws_off, off = 0, [], 0
-        for i, d in enumerate(plan):
-            if d['kind'] == OP_BLOCK:
-                if i > 0 or need_dx:
-                    dx_bytes = max(dx_bytes, d['N'] * d['Cp'] * es)
-                d['bwd_ws_bytes'] = lib.stin_edgeconv_block_bwd_workspace_bytes(d['N'], d['Cp'], d['H'], d['Cout'], int(d['sc']), d['B'], int(b16))
-                ws_off.append(off)
-                off = _align256(off + d['bwd_ws_bytes'])
-            else:
-                dx_bytes = max(dx_bytes, d['n_in'] * d['C'] * es)
-        dx_bytes = _align256(dx_bytes)
-        scratch = torch.empty(2 * dx_bytes + off, dtype=torch.uint8, device=dev)
+        blocks = [d for d in plan.ops if d.kind == OP_BLOCK]
+        direct, grads, scratch, dx_bytes, ws_off, dx0, all_params, use, side_stream, any_side, evs, bucket, done_ev = _grad_targets(
+            plan, blocks, xp, arena, g, ctx.needs_input_grad[0])
         p_scr = _ptr(scratch)
         p_ws = p_scr + 2 * dx_bytes
-        dx0 = None
-        d0 = plan[0]
-        if need_dx:
-            dx0 = torch.empty(d0['N'] if d0['kind'] == OP_BLOCK else d0['n_in'], d0['Cp'] if d0['kind'] == OP_BLOCK else d0['C'],
-                              dtype=dt, device=dev)
-        all_params = [p for d in blocks for p in d['params']]
-        side_ok = USE_WGRAD_STREAM and _join_deferrable(all_params, direct)
-        use = [side_ok and WGRAD_MIN_WORK <= float(d['N']) * d['Yw'] * d['Cp'] <= WGRAD_MAX_WORK for d in blocks]
-        side_stream, any_side = 0, any(use)
-        evs = [(0, 0)] * len(blocks)
-        # Overlapped gradient all-reduce (train_step.FlatGradBucket.enable_overlap, round 4): every block records its ev_done when
-        # its parameter gradients are written - on the weight-gradient stream, or on the compute stream for a block that does
-        # not use it - INSIDE the C call's kernel sequence, and the bucket hands each completed segment to RCCL behind exactly
-        # those events: the reduction of the decoder's gradients runs while the encoder's backward kernels are still queued.
-        bucket = None
-        if direct:
-            for p in all_params:
-                if p is not None:
-                    bucket = p._stin_slot[0]
-                    break
-        seg_events = bucket is not None and bucket.wants_block_events()
-        done_ev = [None] * len(blocks)
-        if any_side or seg_events:
-            side = _wgrad_side(dev)
-        if any_side:
-            side.hold.append((scratch, xp, arena, g))
-            side_stream = side.stream.cuda_stream
-        if any_side or seg_events:
-            for bi in reversed(range(len(blocks))):      # in BACKWARD order: side.last_done = the event recorded last
-                if use[bi]:
-                    tri = side.next_events()
-                    evs[bi] = (tri[1].cuda_event, tri[2].cuda_event)
-                    done_ev[bi] = tri[2]
-                elif seg_events:
-                    tri = side.next_events(track=False)
-                    evs[bi] = (0, tri[2].cuda_event)
-                    done_ev[bi] = tri[2]
-            if grads is not None:
-                for t in grads:
-                    if t is not None:
-                        t.record_stream(side.stream)
-        stc = _NET_OP
-        blob, bi = [], 0
-        for i, d in enumerate(plan):
-            p_dx = (_ptr(dx0) if i == 0 else p_scr + (i & 1) * dx_bytes)
-            if i == 0 and not need_dx:
-                p_dx = 0
-            if d['kind'] == OP_BLOCK:
-                e, gr = d['edges'], d['groups']
-                cs = e.by_src
-                gs = direct[bi] if direct else grads[6 * bi:6 * bi + 6]
-                ev_dy, ev_done = evs[bi]
-                ev0, ev1 = KernelTimer.edge_events('stin_edge_relu_mean_bwd_mask' + ('_ti' if d['ti'] == TI_MODE_COMPACT else '') + sfx,
-                                                   (d['N'], e.n_edges, d['H']))
-                blob.append(stc.pack(**d['op'], **NetFn._in_arena(d['rel'], base, xp), use_side=int(use[bi]), lddx=d['Cp'],
-                                     g_in_dy=int(USE_G_IN_DY and not b16 and d['sc']),
-                                     bwd_ws_bytes=d['bwd_ws_bytes'], dx=p_dx,
-                                     rowptr_src=_ptr(cs.rowptr), col_src=_ptr(cs.col), xslot=_ptr(e.xslot), w_src=_ptr(e.w_src),
-                                     ptr_true=_ptr(gr.ptr_true), sid=_ptr(gr.sid if gr.quirk else None),
-                                     dW1=_ptr(gs[0]), db1=_ptr(gs[1]), dW2=_ptr(gs[2]), db2=_ptr(gs[3]), dWs=_ptr(gs[4]), dbs=_ptr(gs[5]),
-                                     bwd_ws=p_ws + ws_off[bi], ev_dy=ev_dy, ev_done=ev_done, ev_edge0=ev0, ev_edge1=ev1))
-                bi += 1
-            else:
-                blob.append(stc.pack(**d['op'], **NetFn._in_arena(d['rel'], base, xp), lddx=d['C'], dx=p_dx))
-        import ctypes
-        buf = ctypes.create_string_buffer(b''.join(blob), len(plan) * stc.size)
-        _call('stin_net_bwd', int(b16), buf, len(plan), _ptr(g), ldg, int(PREC_BWD), _stream(xp), side_stream)
+
+        def own(i, d):
+            p_dx = _ptr(dx0) if i == 0 else p_scr + (i & 1) * dx_bytes            # (dx0 is None, p_dx 0, when x needs no gradient)
+            if d.kind != OP_BLOCK:
+                return dict(lddx=d.C, dx=p_dx)
+            bi, sh = blocks.index(d), d.shape
+            e, gr, cs = d.edges, d.groups, d.edges.by_src
+            gs = direct[bi] if direct else grads[6 * bi:6 * bi + 6]
+            ev0, ev1 = KernelTimer.edge_events('stin_edge_relu_mean_bwd_mask' + ('_ti' if sh.ti == TI_MODE_COMPACT else '') + sfx,
+                                               (d.N, e.n_edges, sh.H))
+            return dict(use_side=int(use[bi]), lddx=sh.Cp, g_in_dy=int(USE_G_IN_DY and not b16 and sh.has_shortcut),
+                        bwd_ws_bytes=d.bwd_ws_bytes, dx=p_dx,
+                        rowptr_src=_ptr(cs.rowptr), col_src=_ptr(cs.col), xslot=_ptr(e.xslot), w_src=_ptr(e.w_src),
+                        ptr_true=_ptr(gr.ptr_true), sid=_ptr(gr.sid if gr.quirk else None),
+                        dW1=_ptr(gs[0]), db1=_ptr(gs[1]), dW2=_ptr(gs[2]), db2=_ptr(gs[3]), dWs=_ptr(gs[4]), dbs=_ptr(gs[5]),
+                        bwd_ws=p_ws + ws_off[bi], ev_dy=evs[bi][0], ev_done=evs[bi][1], ev_edge0=ev0, ev_edge1=ev1)
+        buf = _pack_table(plan, ctx.static, _ptr(arena), xp, own)
+        _call('stin_net_bwd', int(b16), buf, len(plan.ops), _ptr(g), ldg, int(PREC_BWD), _stream(xp), side_stream)
         if any_side:
             _wgrad_deferred_join(dev, all_params if not direct else (), () if direct else grads)
         if dx0 is not None and dx0.shape[1] != ctx.cin0:
@@ -1370,21 +1426,15 @@ class NetFn(torch.autograd.Function):
             # waits behind the side stream's NEWEST event whenever any block of THIS backward pass has put weight-gradient work
             # there (`hold` is emptied by the end-of-backward join), not only when a block of this node did
             sd = _WGRAD_SIDE.get(dev.index if dev.index is not None else torch.cuda.current_device())
-            bucket.blocks_done([([p._stin_slot[1] for p in d['params'] if p is not None], done_ev[bi]) for bi, d in enumerate(blocks)],
-                               sd.last_done if (sd is not None and sd.hold) else None)
+            bucket.blocks_done([([p._stin_slot[1] for p in d.params if p is not None], done_ev[bi]) for bi, d in enumerate(blocks)],
+                                 sd.last_done if (sd is not None and sd.hold) else None)
             return (dx0, None) + (None,) * len(params)
         return (dx0, None) + tuple(grads)
 
 
 def run_net(x, steps):
     """x through `steps` (see net_eligible) as one NetFn node."""
-    params = []
-    for st in steps:
-        if st[0] == 'block':
-            b = st[1]
-            lin1, lin2 = b.first_filter.nn[0], b.first_filter.nn[2]
-            sc = b.shortcut if b.dim_in != b.dim_out else None
-            params += [lin1.weight, lin1.bias, lin2.weight, lin2.bias, None if sc is None else sc.weight, None if sc is None else sc.bias]
+    params = [p for st in steps if st[0] == 'block' for p in st[1].fused_params()]
     # need_grad is decided HERE: inside an autograd.Function's forward the grad mode is always off
     need_grad = torch.is_grad_enabled() and (x.requires_grad or any(p is not None and p.requires_grad for p in params))
     return NetFn.apply(x, (steps, need_grad), *params)

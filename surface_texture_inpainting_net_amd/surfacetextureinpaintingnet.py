@@ -43,15 +43,19 @@ class GraphResnetBlock(nn.Module):
         if dim_in != dim_out:
             self.shortcut = nn.Linear(dim_in, dim_out)
 
+    def fused_params(self):
+        """(W1, b1, W2, b2, Ws, bs) of the fused kind of block: the edge MLP's two Linears and the shortcut (None, None without one)."""
+        # (every forward asks for them, so they are read from the module dictionaries: nn.Module.__getattr__ costs a microsecond a name)
+        seq = self._modules['first_filter']._modules['nn']._modules
+        lin1, lin2 = seq['0']._parameters, seq['2']._parameters
+        shortcut = self._modules['shortcut']._parameters if self.dim_in != self.dim_out else {}
+        return (lin1['weight'], lin1['bias'], lin2['weight'], lin2['bias'], shortcut.get('weight'), shortcut.get('bias'))
+
     def pack_spec(self, B):
         """The arguments of this block's weight pack (functional.PackSet), or None when the block is not the fused kind."""
         if not (isinstance(self.first_filter, M.EdgeConv) and isinstance(self.first_norm, M.FastInstanceNorm)):
             return None
-        shortcut = self.shortcut if self.dim_in != self.dim_out else None
-        lin1, lin2 = self.first_filter.nn[0], self.first_filter.nn[2]
-        return (lin1.weight, lin1.bias, lin2.weight, lin2.bias, None if shortcut is None else shortcut.weight,
-                None if shortcut is None else shortcut.bias, self.first_filter.trans_inv,
-                SF.forward_precision(self.unbounded_input), int(B))
+        return self.fused_params() + (self.first_filter.trans_inv, self.unbounded_input, int(B))
 
     def forward(self, x, edges, batch=None):
         n = x.shape[0]
@@ -62,13 +66,8 @@ class GraphResnetBlock(nn.Module):
             steps = [('block', self, edges, groups)]
             if SF.net_eligible(steps, x):                           # a one-op node: one foreign call per direction
                 return SF.run_net(x, steps)
-            shortcut = self.shortcut if self.dim_in != self.dim_out else None
-            lin1, lin2 = self.first_filter.nn[0], self.first_filter.nn[2]
-            return SF.EdgeConvBlockFn.apply(x, lin1.weight, lin1.bias, lin2.weight, lin2.bias,      # the per-kernel path
-                                            None if shortcut is None else shortcut.weight,
-                                            None if shortcut is None else shortcut.bias, edges, groups,
-                                            self.first_filter.trans_inv, self.first_norm.eps,
-                                            SF.forward_precision(self.unbounded_input))
+            return SF.EdgeConvBlockFn.apply(x, *self.fused_params(), edges, groups, self.first_filter.trans_inv,       # the per-kernel path
+                                            self.first_norm.eps, self.unbounded_input)
         self.first_filter.fwd_precision = SF.forward_precision(self.unbounded_input)
         out = self.first_filter(x, edges)
         res = (SF.linear(x, self.shortcut.weight, self.shortcut.bias, precision=SF.forward_precision(self.unbounded_input))
