@@ -1063,6 +1063,50 @@ int stin_trace_check_i64(const int64_t* trace, int64_t n_old, const int64_t* row
 int stin_cluster_mean_f32(const float* coords, int64_t n, const int64_t* order, const int64_t* seg_ptr, int64_t n_seg, float* out,
                           stin_stream_t stream);
 
+/* ------------------------------------------------- 2-D image-graph inpainting experiment --
+ * What the reference's ImageGraphTextureDataSet builds per item on CPU workers (datasets/imagegraph_dataloader.py:46-160) and what
+ * the graph branch of its 2-D trainer reads back per step (trainers/inpainting2d_trainer.py:382-398, without lpips), stin_image.hip.
+ *
+ * stin_grid_levels_i64: the grid graph and the "fake traces" of B images of side S over L levels (side of level l: S >> l; S must be
+ *     divisible by 2^(L-1), L <= STIN_GRID_MAX_LEVELS, B S S < 2^31), one launch.  `out` (int64, out_elems >=
+ *     stin_grid_levels_elems(B, S, L); that query returns 0 for an unsupported shape) holds, in this order:
+ *       for l = 0 .. L-1:  edges of level l [2][B E_l], E_l = 4 s (s - 1), row 0 = source; then, for l >= 1, the trace of level l
+ *                          [B sf sf], sf = side of level l - 1: trace[b sf sf + r sf + c] = b sc sc + (r / 2) sc + (c / 2);
+ *       batch [B S S] (image of every level-0 vertex).
+ *     Edge order (the reference iterates a Python set: its order means nothing): image-major, then the source vertex in row-major
+ *     order, then its neighbours up, left, right, down (those that exist); image b's ids are offset by b s s (the increments of
+ *     HierarchicalData.__inc__).  num_vertices: int32 [B][L] = s_l^2.
+ * stin_image_samples_u8: one launch builds B samples from resident raw H x W x 3 uint8 images (pool: device bytes, any alignment).
+ *     records: int64 [B][STIN_IMAGE_RECORD_HEAD + 2 num_circles] on the device = pool byte offset, h, w, k (rotation, 0..3), flip
+ *     (0 / 1), then (row_start, col_start) of every circle window.  Pixel pipeline of the training recipe: v = fl32(u8) fl32(1 / 255),
+ *     v 2 - 1 in fp32 (Normalize); centre crop at h0 = (h - S) / 2, w0 = (w - S) / 2 (CenterCrop); np.rot90(img, k) (RandomRotation:
+ *     ndimage.rotate by 90 k degrees is that, bit for bit, on a square image); flip along axis 1 (RandomFlip).  mask = OR over the
+ *     windows of the template (r - R)^2 + (c - R)^2 <= R^2 on [0, 2R)^2.  Outputs: color [B S S][3] f32, mask [B S S] bytes (0 / 1),
+ *     x [B S S][4] f32 = (color * !mask, mask), 16-byte aligned.  Rescale (cv2.INTER_AREA) is NOT part of this call: the caller
+ *     guarantees min(h, w) == S, every window inside the image and every image inside the pool (the host wrapper raises
+ *     otherwise); a pixel whose source bytes fall outside [0, pool_bytes) is written as 0, never read.
+ * stin_image_metrics_f32: the 2-D trainer's step metrics as ONE row of 8 floats of a caller-owned device table.  N = num_images
+ *     n rows, image b = rows [b n, (b + 1) n).  P = composite ? where(mask, out, color) : out, d = P - color in fp32:
+ *       row_out[0] loss  loss[0] when loss != NULL, else row_out[1]
+ *       row_out[1] l1    sum |d| / (N C)
+ *       row_out[2] mse   sum d^2 / (N C)
+ *       row_out[3] psnr  piq's: the MEAN over the images of -10 log10(mse_b / data_range^2 + 1e-8) (not the whole-batch value of
+ *                        stin_inpaint_metrics_f32)
+ *       row_out[4] number of rows with mask != 0 (exact: N <= 2^24);  row_out[5..7] = 0
+ *     out [N, C] fp32 with leading dimension ldo, color [N, C] contiguous, mask bytes [N] (a bool tensor's storage), C = 1 .. 4.
+ *     fp64 block partials per image, folded in a fixed order by the finaliser: same bits on every run, no float atomics.
+ *     Workspace: stin_image_metrics_workspace_bytes(N, num_images).  Nothing allocates or synchronises. */
+#define STIN_GRID_MAX_LEVELS 8
+#define STIN_IMAGE_RECORD_HEAD 5
+int64_t stin_grid_levels_elems(int B, int S, int L);
+int stin_grid_levels_i64(int B, int S, int L, int64_t* out, int64_t out_elems, int32_t* num_vertices, stin_stream_t stream);
+int stin_image_samples_u8(const uint8_t* pool, int64_t pool_bytes, const int64_t* records, int B, int S, int R, int num_circles,
+                          float* x, float* color, uint8_t* mask, stin_stream_t stream);
+size_t stin_image_metrics_workspace_bytes(int64_t N, int num_images);
+int stin_image_metrics_f32(const float* out, int64_t ldo, const float* color, const uint8_t* mask, int64_t N, int num_images, int C,
+                           int composite, float data_range, const float* loss, float* row_out, void* workspace,
+                           size_t workspace_bytes, stin_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

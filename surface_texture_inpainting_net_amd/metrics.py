@@ -191,6 +191,79 @@ class StepMetrics:
         return {k: (float(r[:, i].sum() / r.shape[0]) if r.shape[0] else 0.0) for i, k in enumerate(self.KEYS)}
 
 
+def _image_row_torch(out, color, mask, num_images, composite, data_range, loss):
+    """The row stin_image_metrics_f32 writes, through torch (CPU tensors): fp32 terms, sums in double, one final cast.
+    -> float32 [8]."""
+    inside = mask.reshape(-1) != 0
+    out = out.float()
+    P = torch.where(inside[:, None], out, color) if composite else out
+    n, C = P.shape
+    d = P - color
+    sq = (d * d).double().reshape(num_images, -1).sum(dim=1)
+    mse_b = sq / (n // num_images * C)
+    psnr = (-10 * torch.log10(mse_b / float(data_range) ** 2 + 1e-8)).sum() / num_images
+    l1 = d.abs().double().sum() / (n * C)
+    zero = torch.zeros((), dtype=torch.float64)
+    row = torch.stack([l1, l1, sq.sum() / (n * C), psnr, inside.sum().double(), zero, zero, zero]).float()
+    if loss is not None:
+        row[0] = torch.as_tensor(loss, dtype=torch.float32).reshape(())
+    return row
+
+
+class ImageStepMetrics(StepMetrics):
+    """StepMetrics' sibling for the 2-D image-graph experiment: the graph branch of Inpainting2DTrainer logs l1, mse and piq's psnr
+    of every step with one .item() each (trainers/inpainting2d_trainer.py:382-398; lpips needs a VGG and is out of scope).  ``update``
+    is one HIP call (stin_image_metrics_f32, no host synchronisation) that writes a row of the ``[capacity, 8]`` device table:
+    loss, l1, mse, psnr, then the number of masked pixels.  psnr has piq's semantics - the MEAN over the images of the batch of
+    -10 log10(mse_b / data_range^2 + 1e-8) - not the whole-batch value of StepMetrics.  The mask is read as it is stored (bool or
+    uint8): no int64 copy.  The images of a batch have equal sizes (sample.num_graphs of them).  Same update / rows / result
+    surface, so TrainStep(metrics=ImageStepMetrics(...), use_mask_weighted_loss=False) records it."""
+
+    KEYS = ('loss', 'l1', 'mse', 'psnr')
+
+    def __init__(self, device, capacity=1024, data_range=2.0):
+        super().__init__(device, capacity, use_mask_weighted_loss=False, data_range=data_range)
+
+    def update(self, out, sample, loss=None, composite=True):
+        """One step: ``out`` = the network output [N, C] (composite=True forms where(mask, out, color) itself), ``sample`` supplies
+        color, mask and the number of images; ``loss`` = a loss computed elsewhere (0-dim tensor), else column l1 is copied.
+        -> the row, a device view [8]."""
+        out = out.detach()
+        if out.dtype != torch.float32:
+            out = out.float()
+        color, mask = sample.color, sample.mask.reshape(-1)
+        n, B = out.shape[0], int(sample.num_graphs)
+        if n % B != 0:
+            raise ValueError('%d rows are not %d images of equal size' % (n, B))
+        if loss is not None and torch.is_tensor(loss):
+            loss = loss.detach()
+        if not out.is_cuda:
+            row = self._row()
+            row.copy_(_image_row_torch(out, color, mask, B, composite, self.data_range, loss))
+            return row
+        from . import _lib
+        from .plan import _ptr, _stream
+        out, ldo = SF._mat(out)
+        color, _ = SF._mat(color if color.is_contiguous() else color.contiguous())
+        if mask.dtype == torch.bool:
+            mask = mask.view(torch.uint8)
+        elif mask.dtype != torch.uint8:
+            mask = (mask != 0).view(torch.uint8)
+        if not mask.is_contiguous():
+            mask = mask.contiguous()
+        if loss is not None:
+            loss = torch.as_tensor(loss)
+            if loss.dtype != torch.float32 or loss.device != out.device:
+                loss = loss.to(out.device, torch.float32)
+        ws_bytes = _lib.load().stin_image_metrics_workspace_bytes(n, B)
+        if self._ws is None or self._ws.numel() < ws_bytes:
+            self._ws = torch.empty(ws_bytes, dtype=torch.uint8, device=out.device)
+        row = self._row()
+        SF._call('stin_image_metrics_f32', _ptr(out), ldo, _ptr(color), _ptr(mask), n, B, out.shape[1], int(bool(composite)),
+                 self.data_range, _ptr(loss), _ptr(row), _ptr(self._ws), self._ws.numel(), _stream(out))
+        return row
+
+
 def evaluate(model, samples, tracker=None, **tracker_kw):
     """The body of the trainer's _valid_epoch / _eval (:204-252, :89-125): eval mode, no_grad, one tracker row per sample;
     the previous train / eval mode is restored.  -> the tracker (per-scene losses: ``tracker.rows()[:, 0]``)."""
