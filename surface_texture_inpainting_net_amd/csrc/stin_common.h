@@ -116,6 +116,13 @@ static inline int stin_group_lanes(int c4) {
     return g;
 }
 
+// fp64 sum over the 64 lanes of a wave (lane 0 holds it): shuffle-down by 32, 16, ... 1
+__device__ __forceinline__ double stin_wave_sum(double v) {
+#pragma unroll
+    for (int o = STIN_WAVE / 2; o > 0; o >>= 1) v += __shfl_down(v, o, STIN_WAVE);
+    return v;
+}
+
 __device__ __forceinline__ float4 ld4(const float* p) { return *reinterpret_cast<const float4*>(p); }
 __device__ __forceinline__ void st4(float* p, float4 v) { *reinterpret_cast<float4*>(p) = v; }
 

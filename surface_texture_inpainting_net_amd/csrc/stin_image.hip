@@ -163,12 +163,6 @@ __global__ __launch_bounds__(TB) void k_image_samples(const uint8_t* __restrict_
 // ------------------------------------------------------------------------------------------------------------------- metrics
 enum { Q_ABS, Q_SQ, Q_CNT, NQ };
 
-__device__ __forceinline__ double wave_sum(double v) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_down(v, o, 64);
-    return v;
-}
-
 // block (x, b) covers rows [x * TB, (x + 1) * TB) of image b; partial[(q * B + b) * bpi + x]
 __global__ __launch_bounds__(TB) void k_image_metrics_rows(const float* __restrict__ out, int64_t ldo, const float* __restrict__ color,
                                                            const uint8_t* __restrict__ mask, int64_t n_img, int C, int composite,
@@ -192,7 +186,7 @@ __global__ __launch_bounds__(TB) void k_image_metrics_rows(const float* __restri
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
 #pragma unroll
     for (int q = 0; q < NQ; ++q) {
-        const double s = wave_sum(acc[q]);
+        const double s = stin_wave_sum(acc[q]);
         if (lane == 0) sm[q][wave] = s;
     }
     __syncthreads();
@@ -215,7 +209,7 @@ __global__ __launch_bounds__(64 * NQ) void k_image_metrics_final(const double* _
     for (int b = 0; b < B; ++b) {
         double s = 0.0;
         for (int64_t i = lane; i < bpi; i += 64) s += partial[((int64_t)q * B + b) * bpi + i];
-        s = wave_sum(s);
+        s = stin_wave_sum(s);
         total += s;                                                  // (lane 0 holds the sum)
         if (q == Q_SQ) psnr += -10.0 * log10(s / per_image / r2 + 1e-8);
     }

@@ -19,12 +19,6 @@ namespace {
 constexpr int MB = 256;                   // threads per block = rows per block
 enum { Q_ABS, Q_WABS, Q_SQ, Q_SQ_IN, Q_CNT_IN, Q_TV, Q_LAP, Q_LAP2, NQ };
 
-__device__ __forceinline__ double wave_sum(double v) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_down(v, o, 64);
-    return v;
-}
-
 // partial[(q0 + k) * blocks + blockIdx.x] = sum over the block of acc[k]: lanes by shuffle, the four waves in a fixed order
 template <int K>
 __device__ __forceinline__ void block_partials(const double (&acc)[K], int q0, double* __restrict__ partial, int64_t blocks) {
@@ -32,7 +26,7 @@ __device__ __forceinline__ void block_partials(const double (&acc)[K], int q0, d
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
 #pragma unroll
     for (int k = 0; k < K; ++k) {
-        const double s = wave_sum(acc[k]);
+        const double s = stin_wave_sum(acc[k]);
         if (lane == 0) sm[k][wave] = s;
     }
     __syncthreads();
@@ -149,7 +143,7 @@ __global__ __launch_bounds__(64 * NQ) void k_metrics_final(const double* __restr
     const int lane = threadIdx.x & 63, q = threadIdx.x >> 6;
     double s = 0.0;
     for (int64_t i = lane; i < blocks; i += 64) s += partial[(int64_t)q * blocks + i];
-    s = wave_sum(s);
+    s = stin_wave_sum(s);
     if (lane == 0) sums[q] = s;
     __syncthreads();
     if (threadIdx.x == 0) {

@@ -5,6 +5,7 @@
 #include "stin_common.h"
 #include <atomic>
 #include <cstdlib>
+#include <type_traits>
 
 namespace {
 
@@ -64,6 +65,192 @@ __device__ __forceinline__ void crit_prio() {
 
 __device__ __forceinline__ float elu_grad_from_pre(float n) { return n > 0.f ? 1.f : __expf(n); }
 
+// The row loop of a column reduction (k_colreduce, k_colreduce_t): rows first, first + step, ... below r1 of columns [c, c + VW)
+// added to out0 (/ out1, the modes with two outputs: the caller's acc0 / acc1), rows ascending per thread, fp64.
+// UR rows per trip with every load issued before the first use (round 3: the one-row-per-trip loop waited a full memory round
+// trip per row - 22.6 us for the 18 k-row DOT_ELU reduction whose bytes take 6 us); the accumulation order per thread is that of
+// the one-row loop (rows ascending): bit-identical sums.  A slot past r1 loads row rb (clamped: a valid row) and adds nothing.
+template <typename T, int MODE, int VW>
+__device__ __forceinline__ void colreduce_rows(int64_t first, int64_t step, int64_t r1, int c, const T* x, int64_t ldx, const T* gout,
+                                               int64_t ldg, int C, const int32_t* gid, const int32_t* sid, const float* mean,
+                                               const float* rstd, const float* coef, double (&out0)[VW], double (&out1)[VW]) {
+    constexpr bool DOT_BN = (MODE == STIN_RED_DOT_BN || MODE == STIN_RED_DOT_BN_RELU);
+    // the sums run in locals (from out0 / out1 and back): the compiler then orders the loop's values as it did when the loop stood
+    // in the kernels, and allocates the same registers; accumulating through the references costs two k_colreduce instances a wave
+    // of occupancy (profiles/r18_norm_once.md)
+    double acc0[VW], acc1[VW];
+#pragma unroll
+    for (int i = 0; i < VW; ++i) { acc0[i] = out0[i]; acc1[i] = out1[i]; }
+    constexpr int UR = 4;                                                          // rows in flight per thread
+    for (int64_t rb = first; rb < r1; rb += UR * step) {
+        V<VW> xv[UR], go[UR];
+        int gq[UR], sq[UR];
+        bool ok[UR];
+#pragma unroll
+        for (int u = 0; u < UR; ++u) {
+            const int64_t r = rb + u * step;
+            ok[u] = r < r1;
+            const int64_t rc = ok[u] ? r : rb;
+            xv[u] = V<VW>::load(x + rc * ldx + c);
+            if (MODE == STIN_RED_DOT_ELU || DOT_BN) go[u] = V<VW>::load(gout + rc * ldg + c);
+            gq[u] = (MODE != STIN_RED_SUM && MODE != STIN_RED_MOMENTS && gid != nullptr) ? gid[rc] : 0;
+            sq[u] = (MODE == STIN_RED_COEF_XC && sid != nullptr) ? sid[rc] : 0;
+        }
+#pragma unroll
+        for (int u = 0; u < UR; ++u) {
+            if (!ok[u]) continue;
+            if (MODE == STIN_RED_SUM) {
+#pragma unroll
+                for (int i = 0; i < VW; ++i) acc0[i] += (double)xv[u].v[i];
+            } else if (MODE == STIN_RED_MOMENTS) {
+#pragma unroll
+                for (int i = 0; i < VW; ++i) {
+                    const double d = (double)xv[u].v[i];
+                    acc0[i] += d;
+                    acc1[i] += d * d;
+                }
+            } else {
+                const int g = gq[u];
+                const V<VW> mu = V<VW>::load(mean + (int64_t)g * C + c);
+                if (DOT_BN) {
+                    const V<VW> rs = V<VW>::load(rstd + c);
+                    const V<VW> ga = V<VW>::load(coef + c);
+                    const V<VW> be = V<VW>::load(coef + C + c);
+#pragma unroll
+                    for (int i = 0; i < VW; ++i) {
+                        const float n = (xv[u].v[i] - mu.v[i]) * rs.v[i];
+                        const float d = (MODE == STIN_RED_DOT_BN_RELU && !(ga.v[i] * n + be.v[i] > 0.f)) ? 0.f : go[u].v[i];
+                        acc0[i] += (double)(d * n);
+                        acc1[i] += (double)d;
+                    }
+                } else if (MODE == STIN_RED_CSQ) {
+#pragma unroll
+                    for (int i = 0; i < VW; ++i) { const float d = xv[u].v[i] - mu.v[i]; acc0[i] += (double)(d * d); }
+                } else if (MODE == STIN_RED_DOT_ELU) {
+                    const V<VW> rs = V<VW>::load(rstd + (int64_t)g * C + c);
+#pragma unroll
+                    for (int i = 0; i < VW; ++i) {
+                        const float xc = xv[u].v[i] - mu.v[i];
+                        const float dy = go[u].v[i] * elu_grad_from_pre(xc * rs.v[i]);
+                        acc0[i] += (double)(dy * xc);
+                        acc1[i] += (double)dy;
+                    }
+                } else {  // STIN_RED_COEF_XC
+                    const V<VW> cf = V<VW>::load(coef + (int64_t)sq[u] * C + c);
+#pragma unroll
+                    for (int i = 0; i < VW; ++i) acc0[i] += (double)(cf.v[i] * (xv[u].v[i] - mu.v[i]));
+                }
+            }
+        }
+    }
+#pragma unroll
+    for (int i = 0; i < VW; ++i) { out0[i] = acc0[i]; out1[i] = acc1[i]; }
+}
+
+// Folds of a column's chunk list [nch] of fp64 partials (k_colreduce_final, k_moments_final, k_norm_fold): FIN_KL k-lanes per
+// column, each walks the list with stride FIN_KL (16 columns side by side: coalesced 128-byte reads), then a fixed-order LDS
+// reduction across the k-lanes -> deterministic.
+constexpr int FIN_COLS = 16, FIN_KL = 16;
+
+// k-lane ty's share of one sum.  Every load of the lane's list in flight before the first add, 32 at a time (round 3).  The
+// partials were written by the previous kernel on other XCDs, so each dependent batch of loads is a trip to the fabric (~2 us
+// under load): with 4 in flight the 564-chunk list of the bottleneck level took nine trips (9.4 us for 2 MB), now two.  The adds
+// keep the order of the original loop - groups of four strides round-robin into s0..s3 while a whole group is in range, the
+// ragged tail into s0 - so the sums are bit-identical; out-of-range slots load a clamped address and add nothing.
+__device__ __forceinline__ double fold_lane_sum(const double* __restrict__ p, int64_t stride, int nch, int ty) {
+    double s0 = 0.0, s1 = 0.0, s2 = 0.0, s3 = 0.0;
+    for (int k = ty; k < nch; k += 32 * FIN_KL) {
+        double v[32];
+#pragma unroll
+        for (int u = 0; u < 32; ++u) {
+            const int ku = k + u * FIN_KL;
+            v[u] = p[(int64_t)(ku < nch ? ku : ty) * stride];
+        }
+#pragma unroll
+        for (int q = 0; q < 8; ++q) {
+            const int k0 = k + 4 * q * FIN_KL;
+            if (k0 + 3 * FIN_KL < nch) {
+                s0 += v[4 * q];
+                s1 += v[4 * q + 1];
+                s2 += v[4 * q + 2];
+                s3 += v[4 * q + 3];
+            } else {
+#pragma unroll
+                for (int j = 0; j < 4; ++j)
+                    if (k0 + j * FIN_KL < nch) s0 += v[4 * q + j];
+            }
+        }
+    }
+    return (s0 + s1) + (s2 + s3);
+}
+// k-lane ty's share of the two sums of a moments list (sum at p, sum of squares at p + C).  All loads of the lane's list in
+// flight, 16 groups at a time; adds in the order of the original two-accumulator loop: pairs of strides alternate (s1, s2) /
+// (t1, t2) while a whole pair is in range, a ragged last stride goes to (s1, s2).
+__device__ __forceinline__ void fold_lane_moments(const double* __restrict__ p, int64_t st, int C, int nch, int ty, double& o1, double& o2) {
+    double s1 = 0.0, s2 = 0.0, t1 = 0.0, t2 = 0.0;
+    for (int k = ty; k < nch; k += 16 * FIN_KL) {
+        double a[16], q[16];
+#pragma unroll
+        for (int u = 0; u < 16; ++u) {
+            const int ku = k + u * FIN_KL;
+            const int kc = ku < nch ? ku : ty;
+            a[u] = p[kc * st];
+            q[u] = p[kc * st + C];
+        }
+#pragma unroll
+        for (int h = 0; h < 8; ++h) {
+            const int k0 = k + 2 * h * FIN_KL;
+            if (k0 + FIN_KL < nch) {
+                s1 += a[2 * h];
+                s2 += q[2 * h];
+                t1 += a[2 * h + 1];
+                t2 += q[2 * h + 1];
+            } else if (k0 < nch) {
+                s1 += a[2 * h];
+                s2 += q[2 * h];
+            }
+        }
+    }
+    o1 = s1 + t1;
+    o2 = s2 + t2;
+}
+
+// (sum x, sum x^2) in fp64 and ic = 1 / rows -> mean and 1/sqrt(biased var + eps).  Exact to fp32 rounding: the fp64 sums carry
+// ~1e-16 relative error, so E[x^2] - mean^2 loses nothing visible unless mean^2/var exceeds ~1e8.
+__device__ __forceinline__ void moments_post(double a, double q, double ic, float eps, float& mean, float& rstd) {
+    const double mu = a * ic;
+    double var = q * ic - mu * mu;
+    if (var < 0.0) var = 0.0;
+    mean = (float)mu;
+    rstd = (float)(1.0 / sqrt(var + (double)eps));
+}
+
+// Post-op of output o of a column sum, column i = b * C + c of range b.  NORM_COEF: the same float operations as k_norm_coef
+// (stin_pack.hip).  inv_cnt / rstd are read only by the posts that need them.
+__device__ __forceinline__ float colreduce_post(int post, int o, double sum, const float* __restrict__ rstd, int64_t i,
+                                                const float* __restrict__ inv_cnt, int b, float eps) {
+    float r = (float)sum;
+    if (post == STIN_POST_SCALE) r = r * inv_cnt[b];
+    else if (post == STIN_POST_RSTD) r = 1.0f / sqrtf(r * inv_cnt[b] + eps);
+    else if (post == STIN_POST_NORM_COEF) {
+        const float rs = rstd[i], ic = inv_cnt[b];
+        r = (o == 0) ? -(rs * rs * rs) * r * ic : -(rs * r) * ic;
+    }
+    return r;
+}
+
+// One element of the normalise (+ ELU) pass and of its backward, dx = a dy + k xc + m with dy = g ELU'(xc rs)
+__device__ __forceinline__ float norm_fwd_elem(float x, float mu, float rs, int act) {
+    float n = (x - mu) * rs;
+    if (act) n = n > 0.f ? n : expm1f(n);
+    return n;
+}
+__device__ __forceinline__ float norm_bwd_elem(float x, float g, float mu, float rs, float a, float k, float m, int act) {
+    const float xc = x - mu;
+    const float dy = act ? g * elu_grad_from_pre(xc * rs) : g;
+    return a * dy + k * xc + m;
+}
+
 // grid = (chunks, B). partial layout: [b][chunk][o][C] doubles, o in {0,1}.
 template <typename T, int MODE, int VW>
 __global__ __launch_bounds__(BLOCK) void k_colreduce(const T* __restrict__ x, int64_t ldx,
@@ -88,74 +275,9 @@ __global__ __launch_bounds__(BLOCK) void k_colreduce(const T* __restrict__ x, in
         double acc0[VW], acc1[VW];
 #pragma unroll
         for (int i = 0; i < VW; ++i) { acc0[i] = 0.0; acc1[i] = 0.0; }
-        if (live) {
-            // UR rows per trip with every load issued before the first use (round 3: the one-row-per-trip loop waited a
-            // full memory round trip per row - 22.6 us for the 18 k-row DOT_ELU reduction whose bytes take 6 us);
-            // the accumulation order per thread is unchanged (rows ascending): bit-identical sums
-            constexpr int UR = 4;
-            const int64_t step = (int64_t)nch * RL;
-            for (int64_t rb = r0 + (int64_t)chunk * RL + rl; rb < r1; rb += UR * step) {
-                V<VW> xv[UR], go[UR];
-                int gq[UR], sq[UR];
-                bool ok[UR];
-#pragma unroll
-                for (int u = 0; u < UR; ++u) {
-                    const int64_t r = rb + u * step;
-                    ok[u] = r < r1;
-                    const int64_t rc = ok[u] ? r : rb;                      // clamped: a valid row, its contribution is skipped
-                    xv[u] = V<VW>::load(x + rc * ldx + c);
-                    if (MODE == STIN_RED_DOT_ELU || DOT_BN) go[u] = V<VW>::load(gout + rc * ldg + c);
-                    gq[u] = (MODE != STIN_RED_SUM && MODE != STIN_RED_MOMENTS && gid != nullptr) ? gid[rc] : 0;
-                    sq[u] = (MODE == STIN_RED_COEF_XC && sid != nullptr) ? sid[rc] : 0;
-                }
-#pragma unroll
-                for (int u = 0; u < UR; ++u) {
-                    if (!ok[u]) continue;
-                    if (MODE == STIN_RED_SUM) {
-#pragma unroll
-                        for (int i = 0; i < VW; ++i) acc0[i] += (double)xv[u].v[i];
-                    } else if (MODE == STIN_RED_MOMENTS) {
-#pragma unroll
-                        for (int i = 0; i < VW; ++i) {
-                            const double d = (double)xv[u].v[i];
-                            acc0[i] += d;
-                            acc1[i] += d * d;
-                        }
-                    } else {
-                        const int g = gq[u];
-                        const V<VW> mu = V<VW>::load(mean + (int64_t)g * C + c);
-                        if (DOT_BN) {
-                            const V<VW> rs = V<VW>::load(rstd + c);
-                            const V<VW> ga = V<VW>::load(coef + c);
-                            const V<VW> be = V<VW>::load(coef + C + c);
-#pragma unroll
-                            for (int i = 0; i < VW; ++i) {
-                                const float n = (xv[u].v[i] - mu.v[i]) * rs.v[i];
-                                const float d = (MODE == STIN_RED_DOT_BN_RELU && !(ga.v[i] * n + be.v[i] > 0.f)) ? 0.f : go[u].v[i];
-                                acc0[i] += (double)(d * n);
-                                acc1[i] += (double)d;
-                            }
-                        } else if (MODE == STIN_RED_CSQ) {
-#pragma unroll
-                            for (int i = 0; i < VW; ++i) { const float d = xv[u].v[i] - mu.v[i]; acc0[i] += (double)(d * d); }
-                        } else if (MODE == STIN_RED_DOT_ELU) {
-                            const V<VW> rs = V<VW>::load(rstd + (int64_t)g * C + c);
-#pragma unroll
-                            for (int i = 0; i < VW; ++i) {
-                                const float xc = xv[u].v[i] - mu.v[i];
-                                const float dy = go[u].v[i] * elu_grad_from_pre(xc * rs.v[i]);
-                                acc0[i] += (double)(dy * xc);
-                                acc1[i] += (double)dy;
-                            }
-                        } else {  // STIN_RED_COEF_XC
-                            const V<VW> cf = V<VW>::load(coef + (int64_t)sq[u] * C + c);
-#pragma unroll
-                            for (int i = 0; i < VW; ++i) acc0[i] += (double)(cf.v[i] * (xv[u].v[i] - mu.v[i]));
-                        }
-                    }
-                }
-            }
-        }
+        if (live)
+            colreduce_rows<T, MODE, VW>(r0 + (int64_t)chunk * RL + rl, (int64_t)nch * RL, r1, c, x, ldx, gout, ldg, C, gid, sid, mean,
+                                        rstd, coef, acc0, acc1);
 #pragma unroll
         for (int i = 0; i < VW; ++i) {
             sm[0][threadIdx.x][i] = acc0[i];
@@ -186,8 +308,8 @@ __global__ __launch_bounds__(BLOCK) void k_colreduce(const T* __restrict__ x, in
 // (row chunks R) x (GC-column groups) x (ranges B): a block reduces its rows for ITS GC columns (GC / 4 column lanes x float4,
 // 1024 / GC row lanes; rows ascending per thread, fp64), publishes one [NOUT][GC] partial and takes a ticket of its (range,
 // column group); the block whose ticket is the last one folds that group's R partials in a fixed order (r ascending within
-// 256 / GC interleaved sub-sums, then those in order) and applies the post-op - the final arithmetic of k_colreduce_final /
-// k_moments_final.  Deterministic: which block arrives last changes who folds, never the order of the additions.
+// 256 / GC interleaved sub-sums, then those in order) and applies the post-op (colreduce_post / moments_post, shared with
+// k_colreduce_final / k_moments_final).  Deterministic: which block arrives last changes who folds, never the order of the additions.
 // Cross-block visibility without a release fence (a `fence(release, agent)` writes back the XCD's whole dirty L2 - the first
 // version of this kernel paid 6-10 us for it, profiles/r04_ticket_colreduce.md): the partials are WRITE-THROUGH (`sc1`) stores
 // -> every storing wave drains `s_waitcnt vmcnt(0)` -> barrier -> one lane's relaxed agent-scope atomic add (the ticket) ->
@@ -222,71 +344,9 @@ __global__ __launch_bounds__(BLOCK) void k_colreduce_t(const T* __restrict__ x, 
     double acc0[VW], acc1[VW];
 #pragma unroll
     for (int i = 0; i < VW; ++i) { acc0[i] = 0.0; acc1[i] = 0.0; }
-    if (live) {
-        constexpr int UR = 4;                                                      // rows in flight per thread
-        const int64_t step = (int64_t)R * RLN;
-        for (int64_t rb = r0 + (int64_t)r * RLN + rl; rb < r1; rb += UR * step) {
-            V<VW> xv[UR], go[UR];
-            int gq[UR], sq[UR];
-            bool ok[UR];
-#pragma unroll
-            for (int u = 0; u < UR; ++u) {
-                const int64_t row = rb + u * step;
-                ok[u] = row < r1;
-                const int64_t rc = ok[u] ? row : rb;
-                xv[u] = V<VW>::load(x + rc * ldx + c);
-                if (MODE == STIN_RED_DOT_ELU || DOT_BN) go[u] = V<VW>::load(gout + rc * ldg + c);
-                gq[u] = (MODE != STIN_RED_SUM && MODE != STIN_RED_MOMENTS && gid != nullptr) ? gid[rc] : 0;
-                sq[u] = (MODE == STIN_RED_COEF_XC && sid != nullptr) ? sid[rc] : 0;
-            }
-#pragma unroll
-            for (int u = 0; u < UR; ++u) {
-                if (!ok[u]) continue;
-                if (MODE == STIN_RED_SUM) {
-#pragma unroll
-                    for (int i = 0; i < VW; ++i) acc0[i] += (double)xv[u].v[i];
-                } else if (MODE == STIN_RED_MOMENTS) {
-#pragma unroll
-                    for (int i = 0; i < VW; ++i) {
-                        const double d = (double)xv[u].v[i];
-                        acc0[i] += d;
-                        acc1[i] += d * d;
-                    }
-                } else {
-                    const int g = gq[u];
-                    const V<VW> mu = V<VW>::load(mean + (int64_t)g * C + c);
-                    if (DOT_BN) {
-                        const V<VW> rs = V<VW>::load(rstd + c);
-                        const V<VW> ga = V<VW>::load(coef + c);
-                        const V<VW> be = V<VW>::load(coef + C + c);
-#pragma unroll
-                        for (int i = 0; i < VW; ++i) {
-                            const float n = (xv[u].v[i] - mu.v[i]) * rs.v[i];
-                            const float d = (MODE == STIN_RED_DOT_BN_RELU && !(ga.v[i] * n + be.v[i] > 0.f)) ? 0.f : go[u].v[i];
-                            acc0[i] += (double)(d * n);
-                            acc1[i] += (double)d;
-                        }
-                    } else if (MODE == STIN_RED_CSQ) {
-#pragma unroll
-                        for (int i = 0; i < VW; ++i) { const float d = xv[u].v[i] - mu.v[i]; acc0[i] += (double)(d * d); }
-                    } else if (MODE == STIN_RED_DOT_ELU) {
-                        const V<VW> rs = V<VW>::load(rstd + (int64_t)g * C + c);
-#pragma unroll
-                        for (int i = 0; i < VW; ++i) {
-                            const float xc = xv[u].v[i] - mu.v[i];
-                            const float dy = go[u].v[i] * elu_grad_from_pre(xc * rs.v[i]);
-                            acc0[i] += (double)(dy * xc);
-                            acc1[i] += (double)dy;
-                        }
-                    } else {  // STIN_RED_COEF_XC
-                        const V<VW> cf = V<VW>::load(coef + (int64_t)sq[u] * C + c);
-#pragma unroll
-                        for (int i = 0; i < VW; ++i) acc0[i] += (double)(cf.v[i] * (xv[u].v[i] - mu.v[i]));
-                    }
-                }
-            }
-        }
-    }
+    if (live)
+        colreduce_rows<T, MODE, VW>(r0 + (int64_t)r * RLN + rl, (int64_t)R * RLN, r1, c, x, ldx, gout, ldg, C, gid, sid, mean, rstd,
+                                    coef, acc0, acc1);
 #pragma unroll
     for (int i = 0; i < VW; ++i) {
         sm[0][rl][cl * VW + i] = acc0[i];
@@ -349,33 +409,17 @@ __global__ __launch_bounds__(BLOCK) void k_colreduce_t(const T* __restrict__ x, 
 #pragma unroll
             for (int k = 0; k < PARTS; ++k) t[o] += sm[o][k][cc];
         }
-        if (MODE == STIN_RED_MOMENTS) {                                           // as k_moments_final
-            const double ic = (double)inv_cnt[b];
-            const double mu = t[0] * ic;
-            double var = t[NOUT - 1] * ic - mu * mu;
-            if (var < 0.0) var = 0.0;
-            out0[(int64_t)b * C + col] = (float)mu;
-            out1[(int64_t)b * C + col] = (float)(1.0 / sqrt(var + (double)eps));
+        if (MODE == STIN_RED_MOMENTS) {
+            moments_post(t[0], t[NOUT - 1], (double)inv_cnt[b], eps, out0[(int64_t)b * C + col], out1[(int64_t)b * C + col]);
         } else {
 #pragma unroll
-            for (int o = 0; o < NOUT; ++o) {                                      // as k_colreduce_final
-                float rr = (float)t[o];
-                if (post == STIN_POST_SCALE) rr = rr * inv_cnt[b];
-                else if (post == STIN_POST_RSTD) rr = 1.0f / sqrtf(rr * inv_cnt[b] + eps);
-                else if (post == STIN_POST_NORM_COEF) {
-                    const float rs = rstd[(int64_t)b * C + col], ic = inv_cnt[b];
-                    rr = (o == 0) ? -(rs * rs * rs) * rr * ic : -(rs * rr) * ic;
-                }
-                (o == 0 ? out0 : out1)[(int64_t)b * C + col] = rr;
-            }
+            for (int o = 0; o < NOUT; ++o)
+                (o == 0 ? out0 : out1)[(int64_t)b * C + col] = colreduce_post(post, o, t[o], rstd, (int64_t)b * C + col, inv_cnt, b, eps);
         }
     }
 }
 
-// Second stage: out[b, o, c] = post(sum_k partial[b, k, o, c]).  One 256-thread block per 16 columns:
-// 16 k-lanes x 16 columns, each k-lane walks the chunk list with stride 16 (coalesced 128-byte reads),
-// then a fixed-order LDS reduction across the k-lanes -> deterministic.
-constexpr int FIN_COLS = 16, FIN_KL = 16;
+// Second stage: out[b, o, c] = post(sum_k partial[b, k, o, c]).  One 256-thread block per 16 columns x 16 k-lanes (fold_lane_sum).
 __global__ __launch_bounds__(BLOCK) void k_colreduce_final(const double* __restrict__ partial, int nch, int nout, int C,
                                                            int B, int post, const float* __restrict__ inv_cnt, float eps,
                                                            const float* __restrict__ aux, float* __restrict__ out0,
@@ -383,57 +427,17 @@ __global__ __launch_bounds__(BLOCK) void k_colreduce_final(const double* __restr
     __shared__ double sm[FIN_KL][FIN_COLS + 1];
     const int tx = threadIdx.x % FIN_COLS, ty = threadIdx.x / FIN_COLS;
     const int c = blockIdx.x * FIN_COLS + tx, o = blockIdx.y, b = blockIdx.z;
-    double s0 = 0.0, s1 = 0.0, s2 = 0.0, s3 = 0.0;
-    if (c < C) {
-        const double* p = partial + ((int64_t)b * nch * nout + o) * C + c;
-        const int64_t stride = (int64_t)nout * C;
-        // Every load of a lane's chunk list in flight before the first add, 32 at a time (round 3).  The partials were written by
-        // the previous kernel on other XCDs, so each dependent batch of loads is a trip to the fabric (~2 us under load): with
-        // 4 in flight the 564-chunk list of the bottleneck level took nine trips (9.4 us for 2 MB), now two.  The adds keep the
-        // order of the original loop - groups of four strides round-robin into s0..s3 while a whole group is in range, the
-        // ragged tail into s0 - so the sums are bit-identical; out-of-range slots load a clamped address and add nothing.
-        for (int k = ty; k < nch; k += 32 * FIN_KL) {
-            double v[32];
-#pragma unroll
-            for (int u = 0; u < 32; ++u) {
-                const int ku = k + u * FIN_KL;
-                v[u] = p[(int64_t)(ku < nch ? ku : ty) * stride];
-            }
-#pragma unroll
-            for (int q = 0; q < 8; ++q) {
-                const int k0 = k + 4 * q * FIN_KL;
-                if (k0 + 3 * FIN_KL < nch) {
-                    s0 += v[4 * q];
-                    s1 += v[4 * q + 1];
-                    s2 += v[4 * q + 2];
-                    s3 += v[4 * q + 3];
-                } else {
-#pragma unroll
-                    for (int j = 0; j < 4; ++j)
-                        if (k0 + j * FIN_KL < nch) s0 += v[4 * q + j];
-                }
-            }
-        }
-    }
-    sm[ty][tx] = (s0 + s1) + (s2 + s3);
+    sm[ty][tx] = c < C ? fold_lane_sum(partial + ((int64_t)b * nch * nout + o) * C + c, (int64_t)nout * C, nch, ty) : 0.0;
     __syncthreads();
     if (ty == 0 && c < C) {
         double s = 0.0;
 #pragma unroll
         for (int k = 0; k < FIN_KL; ++k) s += sm[k][tx];
-        float r = (float)s;
-        if (post == STIN_POST_SCALE) r = r * inv_cnt[b];
-        else if (post == STIN_POST_RSTD) r = 1.0f / sqrtf(r * inv_cnt[b] + eps);
-        else if (post == STIN_POST_NORM_COEF) {          // same float operations as k_norm_coef (stin_pack.hip)
-            const float rs = aux[(int64_t)b * C + c], ic = inv_cnt[b];
-            r = (o == 0) ? -(rs * rs * rs) * r * ic : -(rs * r) * ic;
-        }
-        (o == 0 ? out0 : out1)[(int64_t)b * C + c] = r;
+        (o == 0 ? out0 : out1)[(int64_t)b * C + c] = colreduce_post(post, o, s, aux, (int64_t)b * C + c, inv_cnt, b, eps);
     }
 }
 
-// (sum x, sum x^2) in fp64 -> mean and 1/sqrt(biased var + eps).  Exact to fp32 rounding: the fp64 sums carry
-// ~1e-16 relative error, so E[x^2] - mean^2 loses nothing visible unless mean^2/var exceeds ~1e8.
+// Second stage of the moments: partial [b][k][2][C] -> mean, rstd [b][C] (fold_lane_moments, moments_post)
 __global__ void k_moments_final(const double* __restrict__ partial, int nch, int C, int B,
                                 const float* __restrict__ inv_cnt, float eps, float* __restrict__ mean,
                                 float* __restrict__ rstd) {
@@ -442,38 +446,7 @@ __global__ void k_moments_final(const double* __restrict__ partial, int nch, int
     const int tx = threadIdx.x % FIN_COLS, ty = threadIdx.x / FIN_COLS;
     const int c = blockIdx.x * FIN_COLS + tx, b = blockIdx.z;
     double s1 = 0.0, s2 = 0.0;
-    if (c < C) {
-        const double* p = partial + (int64_t)b * nch * 2 * C + c;
-        const int64_t st = (int64_t)2 * C;
-        double t1 = 0.0, t2 = 0.0;
-        // (all loads of the lane's list in flight, 16 groups at a time; adds in the order of the original two-accumulator loop:
-        // pairs of strides alternate (s1, s2) / (t1, t2) while a whole pair is in range, a ragged last stride goes to (s1, s2))
-        for (int k = ty; k < nch; k += 16 * FIN_KL) {
-            double a[16], q[16];
-#pragma unroll
-            for (int u = 0; u < 16; ++u) {
-                const int ku = k + u * FIN_KL;
-                const int kc = ku < nch ? ku : ty;
-                a[u] = p[kc * st];
-                q[u] = p[kc * st + C];
-            }
-#pragma unroll
-            for (int h = 0; h < 8; ++h) {
-                const int k0 = k + 2 * h * FIN_KL;
-                if (k0 + FIN_KL < nch) {
-                    s1 += a[2 * h];
-                    s2 += q[2 * h];
-                    t1 += a[2 * h + 1];
-                    t2 += q[2 * h + 1];
-                } else if (k0 < nch) {
-                    s1 += a[2 * h];
-                    s2 += q[2 * h];
-                }
-            }
-        }
-        s1 += t1;
-        s2 += t2;
-    }
+    if (c < C) fold_lane_moments(partial + (int64_t)b * nch * 2 * C + c, (int64_t)2 * C, C, nch, ty, s1, s2);
     sm[0][ty][tx] = s1;
     sm[1][ty][tx] = s2;
     __syncthreads();
@@ -481,12 +454,7 @@ __global__ void k_moments_final(const double* __restrict__ partial, int nch, int
         double a = 0.0, q = 0.0;
 #pragma unroll
         for (int k = 0; k < FIN_KL; ++k) { a += sm[0][k][tx]; q += sm[1][k][tx]; }
-        const double ic = (double)inv_cnt[b];
-        const double mu = a * ic;
-        double var = q * ic - mu * mu;
-        if (var < 0.0) var = 0.0;
-        mean[(int64_t)b * C + c] = (float)mu;
-        rstd[(int64_t)b * C + c] = (float)(1.0 / sqrt(var + (double)eps));
+        moments_post(a, q, (double)inv_cnt[b], eps, mean[(int64_t)b * C + c], rstd[(int64_t)b * C + c]);
     }
 }
 
@@ -509,11 +477,7 @@ __device__ __forceinline__ void norm_fwd_body(const T* __restrict__ x, int64_t l
     const V<VW> rs = V<VW>::load(rstd + (int64_t)g * C + c);
     V<VW> o;
 #pragma unroll
-    for (int i = 0; i < VW; ++i) {
-        float n = (xv.v[i] - mu.v[i]) * rs.v[i];
-        if (act) n = n > 0.f ? n : expm1f(n);
-        o.v[i] = n;
-    }
+    for (int i = 0; i < VW; ++i) o.v[i] = norm_fwd_elem(xv.v[i], mu.v[i], rs.v[i], act);
     if (res != nullptr) {
         const V<VW> rv = V<VW>::load(res + (MAP ? (int64_t)row_map[r] : r) * ldres + c);
 #pragma unroll
@@ -563,11 +527,7 @@ __global__ __launch_bounds__(BLOCK) void k_norm_bwd(const T* __restrict__ x, int
     const V<VW> mv = V<VW>::load(m + (int64_t)s * C + c);
     V<VW> o;
 #pragma unroll
-    for (int i = 0; i < VW; ++i) {
-        const float xc = xv.v[i] - mu.v[i];
-        const float dy = act ? go.v[i] * elu_grad_from_pre(xc * rs.v[i]) : go.v[i];
-        o.v[i] = av.v[i] * dy + kv.v[i] * xc + mv.v[i];
-    }
+    for (int i = 0; i < VW; ++i) o.v[i] = norm_bwd_elem(xv.v[i], go.v[i], mu.v[i], rs.v[i], av.v[i], kv.v[i], mv.v[i], act);
     o.store(dx + r * lddx + c);
 }
 
@@ -578,68 +538,11 @@ __global__ __launch_bounds__(BLOCK) void k_norm_bwd(const T* __restrict__ x, int
 // workgroup with the others waiting on a flag (three versions, all slower: every poll / atomic on a shared line serialises).  Here
 // nobody waits for anybody: a workgroup owns NF_GC = 32 columns x a chunk of rows and folds ITS columns itself - the [groups][2][C]
 // partials are L2 / Infinity-Cache resident (226 groups at 18 063 rows: 115 KB per workgroup, 29 MB over the grid beside 55 MB of
-// elementwise traffic) - with exactly the per-lane sums, LDS reduction order and final float operations of k_moments_final /
-// k_colreduce_final (16 k-lanes per column, the loops below are theirs), so mean / rstd / k / m and the outputs are BIT-IDENTICAL
-// to the two-launch route.  The row-chunk-0 workgroups write mean / rstd (forward: saved for backward).  Host side: used when
+// elementwise traffic) - through the functions k_moments_final / k_colreduce_final and k_norm_fwd / k_norm_bwd are made of (16
+// k-lanes per column: fold_lane_moments / fold_lane_sum, the same LDS reduction order, moments_post / colreduce_post, norm_fwd_elem
+// / norm_bwd_elem), so mean / rstd / k / m and the outputs are BIT-IDENTICAL to the two-launch route.  The row-chunk-0 workgroups write mean / rstd (forward: saved for backward).  Host side: used when
 // the fold traffic stays below half the elementwise traffic (norm_fold_rows()).
 constexpr int NF_GC = 32, NF_BLOCK = 512, NF_RL = NF_BLOCK / (NF_GC / 4);      // 8 lanes per row, 64 rows per trip
-
-// one k-lane's share of k_colreduce_final's sum over the chunk list (same loads, same add order)
-__device__ __forceinline__ double fold_lane_sum(const double* __restrict__ p, int64_t stride, int nch, int ty) {
-    double s0 = 0.0, s1 = 0.0, s2 = 0.0, s3 = 0.0;
-    for (int k = ty; k < nch; k += 32 * FIN_KL) {
-        double v[32];
-#pragma unroll
-        for (int u = 0; u < 32; ++u) {
-            const int ku = k + u * FIN_KL;
-            v[u] = p[(int64_t)(ku < nch ? ku : ty) * stride];
-        }
-#pragma unroll
-        for (int q = 0; q < 8; ++q) {
-            const int k0 = k + 4 * q * FIN_KL;
-            if (k0 + 3 * FIN_KL < nch) {
-                s0 += v[4 * q];
-                s1 += v[4 * q + 1];
-                s2 += v[4 * q + 2];
-                s3 += v[4 * q + 3];
-            } else {
-#pragma unroll
-                for (int j = 0; j < 4; ++j)
-                    if (k0 + j * FIN_KL < nch) s0 += v[4 * q + j];
-            }
-        }
-    }
-    return (s0 + s1) + (s2 + s3);
-}
-// one k-lane's share of k_moments_final's two sums
-__device__ __forceinline__ void fold_lane_moments(const double* __restrict__ p, int64_t st, int C, int nch, int ty, double& o1, double& o2) {
-    double s1 = 0.0, s2 = 0.0, t1 = 0.0, t2 = 0.0;
-    for (int k = ty; k < nch; k += 16 * FIN_KL) {
-        double a[16], q[16];
-#pragma unroll
-        for (int u = 0; u < 16; ++u) {
-            const int ku = k + u * FIN_KL;
-            const int kc = ku < nch ? ku : ty;
-            a[u] = p[kc * st];
-            q[u] = p[kc * st + C];
-        }
-#pragma unroll
-        for (int h = 0; h < 8; ++h) {
-            const int k0 = k + 2 * h * FIN_KL;
-            if (k0 + FIN_KL < nch) {
-                s1 += a[2 * h];
-                s2 += q[2 * h];
-                t1 += a[2 * h + 1];
-                t2 += q[2 * h + 1];
-            } else if (k0 < nch) {
-                s1 += a[2 * h];
-                s2 += q[2 * h];
-            }
-        }
-    }
-    o1 = s1 + t1;
-    o2 = s2 + t2;
-}
 
 // BWD = false: y = ELU((x - mean) rstd) + res with (mean, rstd) folded from moment partials; mean_io / rstd_io are OUTPUTS.
 // BWD = true:  dx = rstd dy + k xc + m, dy = g ELU'((x - mean) rstd), (k, m) folded from the (dy xc, dy) partials; mean_io /
@@ -674,25 +577,20 @@ __device__ __forceinline__ void norm_fold_body(const double* __restrict__ partia
             double a = 0.0, q = 0.0;
 #pragma unroll
             for (int k = 0; k < FIN_KL; ++k) { a += sm[0][k][tx]; q += sm[1][k][tx]; }
-            if (!BWD) {                                                           // (= k_moments_final)
-                const double ic = (double)inv_cnt[0];
-                const double mu = a * ic;
-                double var = q * ic - mu * mu;
-                if (var < 0.0) var = 0.0;
-                const float mf = (float)mu, rf = (float)(1.0 / sqrt(var + (double)eps));
+            if (!BWD) {
+                float mf, rf;
+                moments_post(a, q, (double)inv_cnt[0], eps, mf, rf);
                 coef[0][tx] = mf;
                 coef[1][tx] = rf;
                 if (blockIdx.y == 0) {
                     mean_io[c] = mf;
                     rstd_io[c] = rf;
                 }
-            } else {                                                              // (= k_colreduce_final, STIN_POST_NORM_COEF)
-                const float rs = rstd_io[c], ic = inv_cnt[0];
-                const float t1 = (float)a, s0 = (float)q;
+            } else {                                                              // (a = sum dy xc -> k, q = sum dy -> m)
                 coef[0][tx] = mean_io[c];
-                coef[1][tx] = rs;
-                coef[2][tx] = -(rs * rs * rs) * t1 * ic;
-                coef[3][tx] = -(rs * s0) * ic;
+                coef[1][tx] = rstd_io[c];
+                coef[2][tx] = colreduce_post(STIN_POST_NORM_COEF, 0, a, rstd_io, c, inv_cnt, 0, 0.f);
+                coef[3][tx] = colreduce_post(STIN_POST_NORM_COEF, 1, q, rstd_io, c, inv_cnt, 0, 0.f);
             }
         }
         __syncthreads();
@@ -724,14 +622,11 @@ __device__ __forceinline__ void norm_fold_body(const double* __restrict__ partia
             float o[4];
 #pragma unroll
             for (int i = 0; i < 4; ++i) {
-                if (!BWD) {                                                       // (= k_norm_fwd, act = 1)
-                    float n = (xa[i] - mu[i]) * rs[i];
-                    n = n > 0.f ? n : expm1f(n);
+                if (!BWD) {
+                    const float n = norm_fwd_elem(xa[i], mu[i], rs[i], 1);
                     o[i] = other != nullptr ? n + oa[i] : n;
-                } else {                                                          // (= k_norm_bwd, act = 1, a = rstd)
-                    const float xc = xa[i] - mu[i];
-                    const float dy = oa[i] * elu_grad_from_pre(xc * rs[i]);
-                    o[i] = rs[i] * dy + kv[i] * xc + mv[i];
+                } else {                                                          // (a = rstd)
+                    o[i] = norm_bwd_elem(xa[i], oa[i], mu[i], rs[i], rs[i], kv[i], mv[i], 1);
                 }
             }
             st4(y + r * ldy + c, make_float4(o[0], o[1], o[2], o[3]));
@@ -875,6 +770,39 @@ inline stin_bf16* b16(stin_bf16_t* p) { return reinterpret_cast<stin_bf16*>(p); 
 
 inline int norm_cu_count() { return stin_cu_count_dev(); }          // (per device: stin_common.h)
 
+// Host dispatch: a run-time choice becomes a template argument by calling a generic lambda with int_c<value>.
+template <int I> using int_c = std::integral_constant<int, I>;
+
+// f(int_c<MODE>) for a (validated) reduction mode
+template <typename F>
+inline void for_mode(int mode, F&& f) {
+    switch (mode) {
+        case STIN_RED_SUM: f(int_c<STIN_RED_SUM>{}); break;
+        case STIN_RED_CSQ: f(int_c<STIN_RED_CSQ>{}); break;
+        case STIN_RED_DOT_ELU: f(int_c<STIN_RED_DOT_ELU>{}); break;
+        case STIN_RED_MOMENTS: f(int_c<STIN_RED_MOMENTS>{}); break;
+        case STIN_RED_DOT_BN: f(int_c<STIN_RED_DOT_BN>{}); break;
+        case STIN_RED_DOT_BN_RELU: f(int_c<STIN_RED_DOT_BN_RELU>{}); break;
+        default: f(int_c<STIN_RED_COEF_XC>{}); break;
+    }
+}
+
+// f(int_c<VW>): 4 channels per lane where the operands allow it (vec4_ok), else - fp32 rows only - 1; false: no kernel for T
+template <typename T, typename F>
+inline bool for_vw(bool vec4, F&& f) {
+    if (vec4) f(int_c<4>{});
+    else if constexpr (is_f32((const T*)nullptr)) f(int_c<1>{});
+    else return false;
+    return true;
+}
+
+// an elementwise kernel over rows x C, one thread per VW channels
+template <typename... P, typename... A>
+inline void launch_rows(void (*kernel)(P...), int64_t rows, int C, int VW, hipStream_t stream, A... args) {
+    const int64_t n = rows * (C / VW);
+    hipLaunchKernelGGL(kernel, dim3((unsigned)((n + BLOCK - 1) / BLOCK)), dim3(BLOCK), 0, stream, args...);
+}
+
 template <typename T>
 int colreduce_impl(int mode, const T* x, int64_t ldx, const T* gout, int64_t ldg, int64_t N, int C, const int32_t* ptr,
                    int B, const int32_t* gid, const int32_t* sid, const float* mean, const float* rstd,
@@ -918,28 +846,15 @@ int colreduce_impl(int mode, const T* x, int64_t ldx, const T* gout, int64_t ldg
             if (R > ws_cap / B) R = ws_cap / B;
             if (R < 1) R = 1;
             dim3 grid((unsigned)R, (unsigned)ncg, (unsigned)B);
-#define STIN_REDT_L(M, G)                                                                                                \
-            hipLaunchKernelGGL((k_colreduce_t<T, M, G>), grid, dim3(BLOCK), 0, stream, x, ldx, gout, ldg, N, C, ptr, gid, sid, mean, rstd, coef, \
-                               partial, slot, post, inv_cnt, eps, out0, out1)
-#define STIN_REDT_LAUNCH(M)                                                                                              \
-            do {                                                                                                         \
-                if (GC == 64) STIN_REDT_L(M, 64);                                                                        \
-                else if (GC == 32) STIN_REDT_L(M, 32);                                                                   \
-                else STIN_REDT_L(M, 16);                                                                                 \
-            } while (0)
-            {
-                switch (mode) {
-                    case STIN_RED_SUM: STIN_REDT_LAUNCH(STIN_RED_SUM); break;
-                    case STIN_RED_CSQ: STIN_REDT_LAUNCH(STIN_RED_CSQ); break;
-                    case STIN_RED_DOT_ELU: STIN_REDT_LAUNCH(STIN_RED_DOT_ELU); break;
-                    case STIN_RED_MOMENTS: STIN_REDT_LAUNCH(STIN_RED_MOMENTS); break;
-                    case STIN_RED_DOT_BN: STIN_REDT_LAUNCH(STIN_RED_DOT_BN); break;
-                    case STIN_RED_DOT_BN_RELU: STIN_REDT_LAUNCH(STIN_RED_DOT_BN_RELU); break;
-                    default: STIN_REDT_LAUNCH(STIN_RED_COEF_XC); break;
-                }
-            }
-#undef STIN_REDT_LAUNCH
-#undef STIN_REDT_L
+            for_mode(mode, [&](auto m) {
+                auto launch = [&](auto gc) {
+                    hipLaunchKernelGGL((k_colreduce_t<T, decltype(m)::value, decltype(gc)::value>), grid, dim3(BLOCK), 0, stream, x, ldx, gout,
+                                       ldg, N, C, ptr, gid, sid, mean, rstd, coef, partial, slot, post, inv_cnt, eps, out0, out1);
+                };
+                if (GC == 64) launch(int_c<64>{});
+                else if (GC == 32) launch(int_c<32>{});
+                else launch(int_c<16>{});
+            });
             return stin_launch_status();
         }
     }
@@ -955,21 +870,12 @@ int colreduce_impl(int mode, const T* x, int64_t ldx, const T* gout, int64_t ldg
     int nch = (int)(want < 1 ? 1 : (want > cap ? cap : want));
     const int nout = (mode == STIN_RED_DOT_ELU || mode == STIN_RED_MOMENTS || mode >= STIN_RED_DOT_BN) ? 2 : 1;
     dim3 grid((unsigned)nch, (unsigned)B);
-#define STIN_RED_LAUNCH(M)                                                                                          \
-    do {                                                                                                            \
-        if (vec) hipLaunchKernelGGL((k_colreduce<T, M, 4>), grid, dim3(BLOCK), 0, stream, x, ldx, gout, ldg, N, C, ptr, gid, sid, mean, rstd, coef, partial); \
-        else if constexpr (is_f32((const T*)nullptr)) hipLaunchKernelGGL((k_colreduce<T, M, 1>), grid, dim3(BLOCK), 0, stream, x, ldx, gout, ldg, N, C, ptr, gid, sid, mean, rstd, coef, partial);     \
-    } while (0)
-    switch (mode) {
-        case STIN_RED_SUM: STIN_RED_LAUNCH(STIN_RED_SUM); break;
-        case STIN_RED_CSQ: STIN_RED_LAUNCH(STIN_RED_CSQ); break;
-        case STIN_RED_DOT_ELU: STIN_RED_LAUNCH(STIN_RED_DOT_ELU); break;
-        case STIN_RED_MOMENTS: STIN_RED_LAUNCH(STIN_RED_MOMENTS); break;
-        case STIN_RED_DOT_BN: STIN_RED_LAUNCH(STIN_RED_DOT_BN); break;
-        case STIN_RED_DOT_BN_RELU: STIN_RED_LAUNCH(STIN_RED_DOT_BN_RELU); break;
-        default: STIN_RED_LAUNCH(STIN_RED_COEF_XC); break;
-    }
-#undef STIN_RED_LAUNCH
+    for_mode(mode, [&](auto m) {
+        for_vw<T>(vec, [&](auto vw) {
+            hipLaunchKernelGGL((k_colreduce<T, decltype(m)::value, decltype(vw)::value>), grid, dim3(BLOCK), 0, stream, x, ldx, gout, ldg, N,
+                               C, ptr, gid, sid, mean, rstd, coef, partial);
+        });
+    });
     if (mode == STIN_RED_MOMENTS) {
         hipLaunchKernelGGL(k_moments_final, dim3((unsigned)((C + FIN_COLS - 1) / FIN_COLS), 1u, (unsigned)B), dim3(BLOCK), 0,
                            stream, partial, nch, C, B, inv_cnt, eps, out0, out1);
@@ -987,33 +893,15 @@ int norm_fwd_impl(const T* x, int64_t ldx, const float* mean, const float* rstd,
     STIN_REQUIRE(N >= 0 && C > 0 && ldx >= C && ldy >= C && (res == nullptr || ldres >= C), STIN_E_SIZE);
     if (N == 0) return STIN_OK;
     STIN_REQUIRE(x && mean && rstd && y, STIN_E_NULL);
-    if (vec8_ok<T>(C, {x, res, y}, {mean, rstd}, {ldx, ldy, res ? ldres : 0})) {
-        const int64_t n = N * (C / 8);
+    auto launch = [&](auto vw) {
+        constexpr int VW = decltype(vw)::value;
         if (row_map != nullptr)
-            hipLaunchKernelGGL((k_norm_fwd_map<T, 8>), dim3((unsigned)((n + BLOCK - 1) / BLOCK)), dim3(BLOCK), 0, stream, x, ldx,
-                               mean, rstd, gid, res, ldres, row_map, N, C, act, y, ldy);
+            launch_rows(k_norm_fwd_map<T, VW>, N, C, VW, stream, x, ldx, mean, rstd, gid, res, ldres, row_map, N, C, act, y, ldy);
         else
-            hipLaunchKernelGGL((k_norm_fwd<T, 8>), dim3((unsigned)((n + BLOCK - 1) / BLOCK)), dim3(BLOCK), 0, stream, x, ldx,
-                               mean, rstd, gid, res, ldres, N, C, act, y, ldy);
-    } else if (vec4_ok<T>(C, {x, res, y}, {mean, rstd}, {ldx, ldy, res ? ldres : 0})) {
-        const int64_t n = N * (C / 4);
-        if (row_map != nullptr)
-            hipLaunchKernelGGL((k_norm_fwd_map<T, 4>), dim3((unsigned)((n + BLOCK - 1) / BLOCK)), dim3(BLOCK), 0, stream, x, ldx,
-                               mean, rstd, gid, res, ldres, row_map, N, C, act, y, ldy);
-        else
-            hipLaunchKernelGGL((k_norm_fwd<T, 4>), dim3((unsigned)((n + BLOCK - 1) / BLOCK)), dim3(BLOCK), 0, stream, x, ldx,
-                               mean, rstd, gid, res, ldres, N, C, act, y, ldy);
-    } else if constexpr (is_f32((const T*)nullptr)) {
-        const int64_t n = N * C;
-        if (row_map != nullptr)
-            hipLaunchKernelGGL((k_norm_fwd_map<T, 1>), dim3((unsigned)((n + BLOCK - 1) / BLOCK)), dim3(BLOCK), 0, stream, x, ldx,
-                               mean, rstd, gid, res, ldres, row_map, N, C, act, y, ldy);
-        else
-            hipLaunchKernelGGL((k_norm_fwd<T, 1>), dim3((unsigned)((n + BLOCK - 1) / BLOCK)), dim3(BLOCK), 0, stream, x, ldx,
-                               mean, rstd, gid, res, ldres, N, C, act, y, ldy);
-    } else {
-        return STIN_E_UNSUPPORTED;
-    }
+            launch_rows(k_norm_fwd<T, VW>, N, C, VW, stream, x, ldx, mean, rstd, gid, res, ldres, N, C, act, y, ldy);
+    };
+    if (vec8_ok<T>(C, {x, res, y}, {mean, rstd}, {ldx, ldy, res ? ldres : 0})) launch(int_c<8>{});
+    else if (!for_vw<T>(vec4_ok<T>(C, {x, res, y}, {mean, rstd}, {ldx, ldy, res ? ldres : 0}), launch)) return STIN_E_UNSUPPORTED;
     return stin_launch_status();
 }
 
@@ -1024,21 +912,12 @@ int norm_bwd_impl(const T* x, int64_t ldx, const T* gout, int64_t ldg, const flo
     STIN_REQUIRE(N >= 0 && C > 0 && ldx >= C && ldg >= C && lddx >= C, STIN_E_SIZE);
     if (N == 0) return STIN_OK;
     STIN_REQUIRE(x && gout && mean && rstd && a && k && m && dx, STIN_E_NULL);
-    if (vec8_ok<T>(C, {x, gout, dx}, {mean, rstd, a, k, m}, {ldx, ldg, lddx})) {
-        const int64_t n = N * (C / 8);
-        hipLaunchKernelGGL((k_norm_bwd<T, 8>), dim3((unsigned)((n + BLOCK - 1) / BLOCK)), dim3(BLOCK), 0, stream, x, ldx,
-                           gout, ldg, mean, rstd, a, k, m, gid, sid, N, C, act, dx, lddx);
-    } else if (vec4_ok<T>(C, {x, gout, dx}, {mean, rstd, a, k, m}, {ldx, ldg, lddx})) {
-        const int64_t n = N * (C / 4);
-        hipLaunchKernelGGL((k_norm_bwd<T, 4>), dim3((unsigned)((n + BLOCK - 1) / BLOCK)), dim3(BLOCK), 0, stream, x, ldx,
-                           gout, ldg, mean, rstd, a, k, m, gid, sid, N, C, act, dx, lddx);
-    } else if constexpr (is_f32((const T*)nullptr)) {
-        const int64_t n = N * C;
-        hipLaunchKernelGGL((k_norm_bwd<T, 1>), dim3((unsigned)((n + BLOCK - 1) / BLOCK)), dim3(BLOCK), 0, stream, x, ldx,
-                           gout, ldg, mean, rstd, a, k, m, gid, sid, N, C, act, dx, lddx);
-    } else {
-        return STIN_E_UNSUPPORTED;
-    }
+    auto launch = [&](auto vw) {
+        constexpr int VW = decltype(vw)::value;
+        launch_rows(k_norm_bwd<T, VW>, N, C, VW, stream, x, ldx, gout, ldg, mean, rstd, a, k, m, gid, sid, N, C, act, dx, lddx);
+    };
+    if (vec8_ok<T>(C, {x, gout, dx}, {mean, rstd, a, k, m}, {ldx, ldg, lddx})) launch(int_c<8>{});
+    else if (!for_vw<T>(vec4_ok<T>(C, {x, gout, dx}, {mean, rstd, a, k, m}, {ldx, ldg, lddx}), launch)) return STIN_E_UNSUPPORTED;
     return stin_launch_status();
 }
 
@@ -1132,7 +1011,7 @@ extern "C" int stin_colreduce_bf16(int mode, const stin_bf16_t* x, int64_t ldx, 
 
 // Second stage of the fused GEMM + backward statistics (stin_gemm_nt_dotelu_f32): partial [groups][2][C] doubles (sum of
 // dy xc, sum of dy per row group) -> the instance-norm backward coefficients k = -rstd^3 T1 / n, m = -rstd S0 / n of ONE graph -
-// what stin_colreduce_f32(STIN_RED_DOT_ELU, post = STIN_POST_NORM_COEF) ends with (same kernel, same float operations).
+// what stin_colreduce_f32(STIN_RED_DOT_ELU, post = STIN_POST_NORM_COEF) ends with (fold_lane_sum, colreduce_post).
 extern "C" int stin_norm_coef_from_partials_f32(const double* partial, int64_t groups, int C, const float* rstd,
                                                 const float* inv_cnt, float* k, float* m, stin_stream_t stream) {
     stin_clear_stale_error();
@@ -1144,8 +1023,8 @@ extern "C" int stin_norm_coef_from_partials_f32(const double* partial, int64_t g
 }
 
 // Second stage of the fused GEMM + statistics (stin_gemm_nt_colstats_f32): partial [groups][2][C] doubles (sum, sum of
-// squares per row group) -> mean, rstd [C] of ONE instance of N rows (inv_cnt[0] = 1 / N), same final arithmetic as the
-// MOMENTS mode of stin_colreduce_f32.
+// squares per row group) -> mean, rstd [C] of ONE instance of N rows (inv_cnt[0] = 1 / N): moments_post, as the
+// MOMENTS mode of stin_colreduce_f32 ends.
 extern "C" int stin_moments_final_f32(const double* partial, int64_t groups, int C, const float* inv_cnt, float eps, float* mean,
                                       float* rstd, stin_stream_t stream) {
     stin_clear_stale_error();
@@ -1200,15 +1079,10 @@ extern "C" int stin_bn_act_fwd_f32(const float* x, int64_t ldx, const float* mea
     STIN_REQUIRE(N >= 0 && C > 0 && ldx >= C && ldy >= C, STIN_E_SIZE);
     if (N == 0) return STIN_OK;
     STIN_REQUIRE(x && mean && rstd && gamma && beta && y, STIN_E_NULL);
-    if (vec4_ok<float>(C, {x, y}, {mean, rstd, gamma, beta}, {ldx, ldy})) {
-        const int64_t n = N * (C / 4);
-        hipLaunchKernelGGL((k_bn_fwd<4>), dim3((unsigned)((n + BLOCK - 1) / BLOCK)), dim3(BLOCK), 0, stream, x, ldx, mean, rstd, gamma,
-                           beta, N, C, act, y, ldy);
-    } else {
-        const int64_t n = N * C;
-        hipLaunchKernelGGL((k_bn_fwd<1>), dim3((unsigned)((n + BLOCK - 1) / BLOCK)), dim3(BLOCK), 0, stream, x, ldx, mean, rstd, gamma,
-                           beta, N, C, act, y, ldy);
-    }
+    for_vw<float>(vec4_ok<float>(C, {x, y}, {mean, rstd, gamma, beta}, {ldx, ldy}), [&](auto vw) {
+        constexpr int VW = decltype(vw)::value;
+        launch_rows(k_bn_fwd<VW>, N, C, VW, stream, x, ldx, mean, rstd, gamma, beta, N, C, act, y, ldy);
+    });
     return stin_launch_status();
 }
 
@@ -1220,15 +1094,10 @@ extern "C" int stin_bn_act_bwd_f32(const float* x, int64_t ldx, const float* gou
     STIN_REQUIRE(N >= 0 && C > 0 && ldx >= C && ldg >= C && lddx >= C, STIN_E_SIZE);
     if (N == 0) return STIN_OK;
     STIN_REQUIRE(x && gout && mean && rstd && gamma && beta && P && Q && dx, STIN_E_NULL);
-    if (vec4_ok<float>(C, {x, gout, dx}, {mean, rstd, gamma, beta, P, Q}, {ldx, ldg, lddx})) {
-        const int64_t n = N * (C / 4);
-        hipLaunchKernelGGL((k_bn_bwd<4>), dim3((unsigned)((n + BLOCK - 1) / BLOCK)), dim3(BLOCK), 0, stream, x, ldx, gout, ldg, mean,
-                           rstd, gamma, beta, P, Q, inv_n, N, C, act, dx, lddx);
-    } else {
-        const int64_t n = N * C;
-        hipLaunchKernelGGL((k_bn_bwd<1>), dim3((unsigned)((n + BLOCK - 1) / BLOCK)), dim3(BLOCK), 0, stream, x, ldx, gout, ldg, mean,
-                           rstd, gamma, beta, P, Q, inv_n, N, C, act, dx, lddx);
-    }
+    for_vw<float>(vec4_ok<float>(C, {x, gout, dx}, {mean, rstd, gamma, beta, P, Q}, {ldx, ldg, lddx}), [&](auto vw) {
+        constexpr int VW = decltype(vw)::value;
+        launch_rows(k_bn_bwd<VW>, N, C, VW, stream, x, ldx, gout, ldg, mean, rstd, gamma, beta, P, Q, inv_n, N, C, act, dx, lddx);
+    });
     return stin_launch_status();
 }
 
@@ -1241,15 +1110,10 @@ extern "C" int stin_bn_mean_bwd_f32(const float* m, int64_t ldm, const float* g,
     STIN_REQUIRE(E >= 0 && C > 0 && ldm >= C && ldg >= C && lddm >= C, STIN_E_SIZE);
     if (E == 0) return STIN_OK;
     STIN_REQUIRE(m && g && dst && inv_deg && mean && rstd && gamma && P && Q && dm, STIN_E_NULL);
-    if (vec4_ok<float>(C, {m, g, dm}, {mean, rstd, gamma, P, Q}, {ldm, ldg, lddm})) {
-        const int64_t n = E * (C / 4);
-        hipLaunchKernelGGL((k_bn_mean_bwd<4>), dim3((unsigned)((n + BLOCK - 1) / BLOCK)), dim3(BLOCK), 0, stream, m, ldm, g, ldg, dst,
-                           inv_deg, mean, rstd, gamma, P, Q, inv_e, E, C, dm, lddm);
-    } else {
-        const int64_t n = E * C;
-        hipLaunchKernelGGL((k_bn_mean_bwd<1>), dim3((unsigned)((n + BLOCK - 1) / BLOCK)), dim3(BLOCK), 0, stream, m, ldm, g, ldg, dst,
-                           inv_deg, mean, rstd, gamma, P, Q, inv_e, E, C, dm, lddm);
-    }
+    for_vw<float>(vec4_ok<float>(C, {m, g, dm}, {mean, rstd, gamma, P, Q}, {ldm, ldg, lddm}), [&](auto vw) {
+        constexpr int VW = decltype(vw)::value;
+        launch_rows(k_bn_mean_bwd<VW>, E, C, VW, stream, m, ldm, g, ldg, dst, inv_deg, mean, rstd, gamma, P, Q, inv_e, E, C, dm, lddm);
+    });
     return stin_launch_status();
 }
 

@@ -63,11 +63,6 @@ __device__ inline void seg_argmax(const float* __restrict__ z, int C, float& m, 
     }
 }
 
-__device__ inline double seg_wave_sum(double v) {
-    for (int o = STIN_WAVE / 2; o > 0; o >>= 1) v += __shfl_down(v, o, STIN_WAVE);
-    return v;
-}
-
 template <bool WANT_LOSS, bool WANT_CONF, bool HAS_ROWS>
 __global__ __launch_bounds__(SEG_BLOCK) void k_seg_ce_fwd(const float* __restrict__ logits, int64_t ld, int64_t M,
                                                           const int64_t* __restrict__ rows, const int64_t* __restrict__ target,
@@ -137,8 +132,8 @@ __global__ __launch_bounds__(SEG_BLOCK) void k_seg_ce_fwd(const float* __restric
         }
     }
     if (WANT_LOSS) {
-        num = seg_wave_sum(num);
-        den = seg_wave_sum(den);
+        num = stin_wave_sum(num);
+        den = stin_wave_sum(den);
         const int w = t / STIN_WAVE;
         if (t % STIN_WAVE == 0) {
             red[0][w] = num;
@@ -166,8 +161,8 @@ __global__ __launch_bounds__(SEG_BLOCK) void k_seg_ce_final(const double* __rest
         a += partial[2 * k];
         b += partial[2 * k + 1];
     }
-    a = seg_wave_sum(a);
-    b = seg_wave_sum(b);
+    a = stin_wave_sum(a);
+    b = stin_wave_sum(b);
     const int w = threadIdx.x / STIN_WAVE;
     if (threadIdx.x % STIN_WAVE == 0) {
         red[0][w] = a;

@@ -784,6 +784,58 @@ def test_norm_with_the_statistics_fold_inside_the_launch_is_bit_identical(N, C, 
     assert torch.equal(y3, y_ref)
 
 
+def test_colreduce_two_stage_route_at_four_channels_per_lane_against_fp64():
+    """stin_colreduce_f32 with more (range, column group) pairs than one row of ticket words (B * ncg = 257 * 2 > 512): the
+    two-stage route (k_colreduce at 4 channels per lane, then k_colreduce_final / k_moments_final), which shares its row loop
+    with the one-launch route.  Reference: torch fp64 sums over the same tensor.  Bounds, derived (n_b rows in range b):
+      SUM           |got - want| <= 2^-24 |want| + n_b 2^-52 sum|x|: one fp32 rounding of the result, fp64 accumulation in any order;
+      MOMENTS mean  the same bound times inv_cnt, against want_sum * double(inv_cnt as fp32);
+      MOMENTS rstd  2^-23 relative: one fp32 rounding (2^-24) of a value whose fp64 variance E[x^2] - mean^2 is good to
+                    ~(1 + mean^2 / var) 2^-52 - invisible while that ratio stays below ~1e8 (printed; < 1 for all but the shortest ranges).
+    SUM runs with range 0 empty (exact zeros) and range 1 of one row."""
+    from surface_texture_inpainting_net_amd.plan import _ptr, _stream
+    lib = _lib_load()
+    B, C = 257, 32
+    g = torch.Generator().manual_seed(257)
+    lens = torch.randint(2, 1200, (B,), generator=g)
+    gd = torch.Generator(device=DEV).manual_seed(32)
+    x = torch.randn(int(lens.sum()), C, generator=gd, device=DEV) * 1.7 + 0.3
+    xd = x.double()
+    ws_bytes = lib.stin_colreduce_workspace_bytes(C, B)
+    ws = torch.empty(ws_bytes, dtype=torch.uint8, device=DEV)
+
+    def run(mode, lens):
+        cuts = [0] + torch.cumsum(lens, 0).tolist()
+        ptr = torch.tensor(cuts, dtype=torch.int32, device=DEV)
+        inv = (1.0 / lens.clamp(min=1).double()).float().to(DEV)
+        out = torch.full((2, B, C), float('nan'), device=DEV)
+        SF._call('stin_colreduce_f32', mode, _ptr(x), C, 0, 0, cuts[-1], C, _ptr(ptr), B, 0, 0, 0, 0, 0, SF.POST_NONE, _ptr(inv),
+                 float(SF.EPS), _ptr(out[0]), _ptr(out[1]), _ptr(ws), ws_bytes, _stream(x))
+        sums = torch.stack([xd[a:b].sum(0) for a, b in zip(cuts, cuts[1:])])
+        sabs = torch.stack([xd[a:b].abs().sum(0) for a, b in zip(cuts, cuts[1:])])
+        bound = 2.0 ** -24 * sums.abs() + lens.double().to(DEV)[:, None] * 2.0 ** -52 * sabs
+        return cuts, inv.double()[:, None], out.double(), sums, bound
+
+    lens_sum = lens.clone()
+    lens_sum[0], lens_sum[1] = 0, 1
+    cuts, _, out, sums, bound = run(SF.RED_SUM, lens_sum)
+    err = (out[0] - sums).abs()
+    print('SUM: max |err| / bound = %.3f' % float((err / bound.clamp(min=1e-300)).max()))
+    assert bool((err <= bound).all())
+    assert float(out[0, 0].abs().max()) == 0.0 and torch.equal(out[0, 1].float(), x[0])
+
+    cuts, ic, out, sums, bound = run(SF.RED_MOMENTS, lens)
+    sq = torch.stack([xd[a:b].pow(2).sum(0) for a, b in zip(cuts, cuts[1:])])
+    mean = sums * ic
+    var = (sq * ic - mean * mean).clamp(min=0.0)
+    rstd = 1.0 / torch.sqrt(var + float(torch.tensor(SF.EPS, dtype=torch.float32)))
+    err_m, rel_r = (out[0] - mean).abs(), ((out[1] - rstd) / rstd).abs()
+    print('MOMENTS: mean max |err| / bound = %.3f, rstd max rel err = %.3e, max mean^2 / var = %.3g'
+          % (float((err_m / (bound * ic)).max()), float(rel_r.max()), float((mean * mean / var).max())))
+    assert bool((err_m <= bound * ic).all())
+    assert float(rel_r.max()) <= 2.0 ** -23
+
+
 # --------------------------------------------------------- segment sum / pool / unpool
 @pytest.mark.parametrize('C', [1, 3, 8, 64, 100, 256])
 def test_segment_sum_matches_scatter_and_is_linear(C):
