@@ -1063,6 +1063,62 @@ int stin_trace_check_i64(const int64_t* trace, int64_t n_old, const int64_t* row
 int stin_cluster_mean_f32(const float* coords, int64_t n, const int64_t* order, const int64_t* seg_ptr, int64_t n_seg, float* out,
                           stin_stream_t stream);
 
+/* QEM: a deterministic, parallel quadric-error-metric edge-collapse decimator and vertex normals (stin_qem.hip) - the step the
+ * reference shells out to vcglib's tridecimator for (graph_level_generation.py, --qem), with the fine -> coarse trace as a result
+ * instead of a CSV.  preprocessing.decimate_qem drives it: a loop of rounds, per round the sorts on the host side (torch) and the
+ * entry points below, one host read (the number of selected edges).  All arithmetic is fp64 with the association written out in the
+ * kernels and no contraction; tests/_qem_oracle.py restates it in numpy and agrees bit for bit.  Every index array is int64; every
+ * index read from memory is compared with its array's size before it is used (an entry that fails is skipped / makes its edge
+ * invalid); nothing allocates or synchronises.
+ * A quadric is the row q[10] = a00 a01 a02 a03 a11 a12 a13 a22 a23 a33 of a symmetric 4 x 4 matrix; the cost of a point h = (p, 1)
+ * is r_k = ((q_k0 x + q_k1 y) + q_k2 z) + q_k3, cost = ((x r_0 + y r_1) + z r_2) + r_3.
+ *   stin_qem_face_quadrics_f64      per face (a, b, c): n = (v_b - v_a) x (v_c - v_a), len = sqrt(n . n), u = n / len, d = -(u . v_a),
+ *                                   face_quadrics[f] = (len / 2) p p^T with p = (u, d), face_normals[f] = u; both zero when
+ *                                   len is not > 0 or an index is out of range.  Either output may be NULL.
+ *   stin_qem_boundary_quadrics_f64  per boundary edge b (bi[b] < bj[b], the one face bface[b]): e = v_j - v_i, m = e x
+ *                                   face_normals[bface], u = m / |m|, d = -(u . v_i): |e|^2 p p^T, zero when |m| is not > 0.
+ *   stin_qem_vertex_sum_f64         out[v] (+)= sum of table[col[s]] (rows of `width` <= 10 doubles) for s = rowptr[v] ..
+ *                                   rowptr[v + 1) IN THAT ORDER - the fixed-order segmented sum of the vertex quadrics (faces in
+ *                                   ascending face id, then, accumulate = 1, boundary edges in ascending (min, max) order); no float
+ *                                   atomics.  normalize = 1 (width 3): out[v] = sum / |sum|, (0, 0, 1) for a zero sum - vertex
+ *                                   normals from the unit face normals.
+ *   stin_qem_edges_f64              one round's candidate edges (ei[e] < ej[e], unique, sorted by (ei, ej); faces_on_edge[e] faces)
+ *                                   on the round's unmodified mesh: Q = Q_i + Q_j; A x = b (A = Q[:3,:3], b = -Q[:3,3]) by explicit
+ *                                   cofactors, taken when |det A| > 1e-10 (max|A|)^3 and |x - mid| <= |v_i - v_j|, else the cheapest
+ *                                   of v_i, v_j, mid (ties in that order); cost[e] = max(h^T Q h, 0), x[e] = h.
+ *                                   valid[e] = cost finite, 1 <= faces_on_edge <= 2, link condition (|N(i) & N(j)| == faces_on_edge,
+ *                                   two sorted lists of the neighbour CSR) and flip condition (every face of i or j without both,
+ *                                   through the vertex -> face CSR: n_old . n_new > 0.2 |n_old| |n_new|, so a zero-area face blocks).
+ *   stin_qem_select_i64             order of the valid edges: (cost, e).  vertex_min[v] = the first valid edge of v (nbr_edge[s] =
+ *                                   the edge of neighbour slot s; -1: none), ring_min[v] = the first of vertex_min over the closed
+ *                                   one-ring, selected[e] = valid and ring_min[ei] == ring_min[ej] == e: the minimum among all
+ *                                   valid edges with an endpoint in N[i] | N[j].  No two selected edges share or neighbour an
+ *                                   endpoint.  Segmented minima: no atomics, identical from run to run.
+ *   stin_qem_collapse_f64           per listed edge e (edge_ids[S]): vertices[i] = x[e], quadrics[i] += quadrics[j], parent[j] = i.
+ *   stin_qem_remap_faces_i64        faces [F, 3] in place through parent (NULL: unchanged); keep[f] = every index in [0, N) and no
+ *                                   repeated vertex (the caller compacts, keeping the order); *status (device int32, OR-ed) |= 1
+ *                                   for an index outside [0, N).  With parent == NULL this is the range check of the input.
+ *   stin_qem_trace_i64              trace[v] = rank[r], r the end of v's parent chain (parent[r] == r); *status |= 2 and -1 for a
+ *                                   chain that leaves [0, N) or does not end within N steps. */
+int stin_qem_face_quadrics_f64(const double* vertices, int64_t N, const int64_t* faces, int64_t F, double* face_quadrics,
+                               double* face_normals, stin_stream_t stream);
+int stin_qem_boundary_quadrics_f64(const double* vertices, int64_t N, const int64_t* bi, const int64_t* bj, const int64_t* bface,
+                                   int64_t B, const double* face_normals, int64_t F, double* boundary_quadrics, stin_stream_t stream);
+int stin_qem_vertex_sum_f64(const int64_t* rowptr, const int64_t* col, int64_t nnz, const double* table, int64_t n_items, int width,
+                            int64_t N, double* out, int accumulate, int normalize, stin_stream_t stream);
+int stin_qem_edges_f64(const double* vertices, const double* quadrics, int64_t N, const int64_t* ei, const int64_t* ej,
+                       const int64_t* faces_on_edge, int64_t E, const int64_t* nbr_rowptr, const int64_t* nbr_col, int64_t nbr_nnz,
+                       const int64_t* vf_rowptr, const int64_t* vf_face, int64_t vf_nnz, const int64_t* faces, int64_t F, double* x,
+                       double* cost, uint8_t* valid, stin_stream_t stream);
+int stin_qem_select_i64(const int64_t* ei, const int64_t* ej, int64_t E, const int64_t* nbr_rowptr, const int64_t* nbr_col,
+                        const int64_t* nbr_edge, int64_t nbr_nnz, const double* cost, const uint8_t* valid, int64_t N,
+                        int64_t* vertex_min, int64_t* ring_min, uint8_t* selected, stin_stream_t stream);
+int stin_qem_collapse_f64(const int64_t* edge_ids, int64_t S, const int64_t* ei, const int64_t* ej, int64_t E, const double* x,
+                          double* vertices, double* quadrics, int64_t* parent, int64_t N, stin_stream_t stream);
+int stin_qem_remap_faces_i64(int64_t* faces, int64_t F, const int64_t* parent, int64_t N, uint8_t* keep, int32_t* status,
+                             stin_stream_t stream);
+int stin_qem_trace_i64(const int64_t* parent, const int64_t* rank, int64_t N, int64_t* trace, int32_t* status, stin_stream_t stream);
+
 /* ------------------------------------------------- 2-D image-graph inpainting experiment --
  * What the reference's ImageGraphTextureDataSet builds per item on CPU workers (datasets/imagegraph_dataloader.py:46-160) and what
  * the graph branch of its 2-D trainer reads back per step (trainers/inpainting2d_trainer.py:382-398, without lpips), stin_image.hip.

@@ -14,17 +14,21 @@
   synchronisation; ``circle_mask_from_centres`` is the distance pass alone for given centres.
 
 * ``graph_levels``      - the body of ``preprocessing/graph_level_generation.process_frame`` (:298-539): mesh -> level hierarchy
-  -> the dict of ``graphs/<scene>.pt``, in vertex-clustering mode fully on the GPU and in decimator mode from the decimator's
-  outputs.  Its parts: ``nearest`` (exact fp64 nearest neighbour between two large point sets, tiled brute force:
+  -> the dict of ``graphs/<scene>.pt``, fully on the GPU in vertex-clustering mode and in decimator mode with percentage levels
+  (``['100', '30', '30', '30']``: ``decimate_qem``), or from an external decimator's outputs.  Its parts: ``nearest`` (exact fp64 nearest neighbour between two large point sets, tiled brute force:
   ``stin_nearest_f64``), ``read_trace_csv`` / ``trace_from_csv`` (``csv2npy`` :135-191: two batched searches, an integer scatter and
   one state vector instead of one BallTree query per CSV coordinate), ``fill_unassigned_trace``
   (``nearest_neighbor_interpolation_for_unassigned_traces`` :284-295), ``colors_and_labels`` (``get_color_and_labels`` :98-116) and
   ``remap_scannet_labels``; ``LevelError`` where the reference raises ``QEMError`` or trips an assert.
 
-All take and return tensors in the reference's own formats.  Out of scope: the QEM decimator itself (the reference shells out
-to vcglib's ``tridecimator``; its mesh and trace file are inputs here), reading mesh files and computing vertex normals from faces
-(neither open3d nor plyfile exists here to pin a reader against: vertices, faces, colours and normals are inputs), and the
-Matterport and S3DIS label paths.
+* ``decimate_qem``      - the QEM decimator the reference shells out to (vcglib's ``tridecimator``): a deterministic, parallel
+  edge-collapse decimator in HIP (``stin_qem_*``): rounds of independent collapses chosen by two per-vertex minimum passes, fixed-order
+  fp64 quadric sums, and the fine -> coarse trace as a direct result instead of a CSV and one BallTree query per row.  Its contract is
+  stated in include/stin_hip.h and restated in numpy by the test suite (bit-exact parity); it is NOT pinned against vcglib.
+  ``vertex_normals`` - open3d's documented ``compute_vertex_normals`` rule (unit face normals summed, normalised), for the levels it makes.
+
+All take and return tensors in the reference's own formats.  Out of scope: reading mesh files (neither open3d nor plyfile exists
+here to pin a reader against: vertices, faces and colours are inputs), and the Matterport and S3DIS label paths.
 """
 import ctypes
 
@@ -743,16 +747,216 @@ def _mesh_edges(faces, n):
     return edges_from_faces(faces, n).t().contiguous()
 
 
+# ------------------------------------------------------------------------------------------------------------- QEM decimation
+def _rowptr(sorted_keys, n):
+    rp = torch.zeros(n + 1, dtype=torch.int64, device=sorted_keys.device)
+    if sorted_keys.numel():
+        rp[1:] = torch.cumsum(torch.bincount(sorted_keys, minlength=n), 0)
+    return rp
+
+
+def _half_edges(faces, n):
+    """Faces [F, 3] int64 (checked) -> (keys i n + j of the unique undirected edges (i < j), ascending; faces per edge; a face of
+    each edge - THE face of a boundary edge)."""
+    a = torch.cat([faces[:, 0], faces[:, 1], faces[:, 2]])
+    b = torch.cat([faces[:, 1], faces[:, 2], faces[:, 0]])
+    keys, order = torch.sort(torch.minimum(a, b) * n + torch.maximum(a, b), stable=True)
+    uniq, counts = torch.unique_consecutive(keys, return_counts=True)
+    start = torch.cumsum(counts, 0) - counts
+    return uniq, counts, order[start] % max(int(faces.shape[0]), 1)
+
+
+def _vertex_faces(faces, n):
+    """-> (rowptr [n + 1], face ids): the faces of every vertex in ascending face id."""
+    flat, order = torch.sort(faces.reshape(-1), stable=True)
+    return _rowptr(flat, n), (order // 3).contiguous()
+
+
+def _checked_faces(faces, n, what):
+    """int64 [F, 3] copy of `faces` without the faces that repeat a vertex; IndexError (from a device status word: nothing reads
+    through the indices before) when one lies outside [0, n)."""
+    lib = _lib.load()
+    f = faces.long().reshape(-1, 3).contiguous().clone()
+    keep = torch.empty(max(f.shape[0], 1), dtype=torch.uint8, device=f.device)
+    status = torch.zeros(1, dtype=torch.int32, device=f.device)
+    _lib.check(lib.stin_qem_remap_faces_i64(_ptr(f), int(f.shape[0]), None, int(n), _ptr(keep), _ptr(status), _stream(f)),
+               'stin_qem_remap_faces_i64')
+    if int(status.item()) != 0:
+        raise IndexError('%s: a face refers to a vertex outside [0, %d)' % (what, n))
+    return f[keep[:f.shape[0]].bool()]
+
+
+def vertex_normals(vertices, faces):
+    """Vertex normals [N, 3] float64 of a triangle mesh (vertices [N, >= 3] float, faces [F, 3] int; CUDA) by the rule open3d
+    documents for compute_vertex_normals: the UNIT normals of a vertex's faces are summed (here in ascending face id, a fixed-order
+    segmented sum: stin_qem_vertex_sum_f64) and the sum is normalised; a zero sum - no face, or only zero-area ones - gives
+    (0, 0, 1).  This is the documented rule only: open3d is not available to pin it against the library itself."""
+    v = _xyz64(vertices, 'vertices')
+    if not (torch.is_tensor(faces) and faces.is_cuda):
+        raise TypeError('faces must be a CUDA tensor (no CPU fallback exists)')
+    lib = _lib.load()
+    n = int(v.shape[0])
+    f = _checked_faces(faces, n, 'vertex_normals')
+    nf = int(f.shape[0])
+    out = torch.empty(max(n, 1), 3, dtype=torch.float64, device=v.device)[:n]
+    fn = torch.empty(max(nf, 1), 3, dtype=torch.float64, device=v.device)
+    _lib.check(lib.stin_qem_face_quadrics_f64(_ptr(v), n, _ptr(f), nf, None, _ptr(fn), _stream(v)), 'stin_qem_face_quadrics_f64')
+    rp, col = _vertex_faces(f, n)
+    _lib.check(lib.stin_qem_vertex_sum_f64(_ptr(rp), _ptr(col), int(col.numel()), _ptr(fn), nf, 3, n, _ptr(out), 0, 1, _stream(v)),
+               'stin_qem_vertex_sum_f64')
+    return out
+
+
+class _Stages:
+    """Wall time per stage of decimate_qem when a `profile` dict is given (each stage is bracketed by a device synchronisation)."""
+
+    def __init__(self, profile):
+        self.profile, self.name, self.t0 = profile, None, 0.0
+
+    def __call__(self, name):
+        if self.profile is None:
+            return
+        import time
+        torch.cuda.synchronize()
+        now = time.perf_counter()
+        if self.name is not None:
+            self.profile[self.name] = self.profile.get(self.name, 0.0) + (now - self.t0)
+        self.name, self.t0 = name, now
+
+
+def decimate_qem(vertices, faces, percent=None, n_vertices=None, strict=False, profile=None):
+    """Quadric-error-metric edge-collapse decimation on the GPU (csrc/stin_qem.hip) - the step the reference shells out to vcglib's
+    tridecimator for - deterministic, parallel, and with the fine -> coarse trace as a result (no CSV, no nearest-neighbour search).
+    vertices [N, >= 3] float, faces [F, 3] int (CUDA); percent (of the vertices to keep) or n_vertices.
+    -> (vertices' float64 [N', 3], faces' int64 [F', 3], trace int64 [N] onto [0, N'), N').
+
+    Target: n_vertices, else max(3, N * percent // 100) (the rounding of the reference's decimator fork is unknown).  The contract
+    (include/stin_hip.h, "QEM"; restated in numpy by the test suite, which this reproduces bit for bit), fp64 throughout:
+    * quadrics: per face area p p^T (p = unit plane), per boundary edge |e|^2 q q^T (q = the plane through the edge, perpendicular to
+      its face) on both endpoints; Q_v = the faces of v in ascending id, then its boundary edges in ascending (min, max) order.
+    * a round, on the unmodified mesh: candidates = the unique edges (i < j) ordered by (i, j); Q = Q_i + Q_j; placement by Cramer's
+      rule when |det A| > 1e-10 max|A|^3 and |x - mid| <= |v_i - v_j|, else the cheapest of v_i, v_j, mid; cost = max(h^T Q h, 0).
+      Valid: finite cost, link condition (common neighbours == faces on the edge, at most two) and flip condition (every other face
+      of i or j keeps n_old . n_new > 0.2 |n_old| |n_new|; a zero-area face blocks).  Selected: the minimum in the order (cost, i, j)
+      among all valid edges with an endpoint in N[i] | N[j] - so no two selected edges touch or neighbour each other - and, when
+      more are selected than vertices are left to remove, the first of them in that order.
+    * collapse: j merges into i, v_i = x, Q_i += Q_j; faces are remapped, those with a repeated vertex dropped, the others keep
+      their relative order and orientation.  Stop at the target or when a round selects nothing.
+    * new ids are the ranks of the surviving original ids; vertices that no face references never collapse and count.
+    Faces of the input that repeat a vertex are dropped at once.  strict: LevelError when N' > target.  IndexError for a face index
+    outside [0, N) (a device status word, read before anything indexes with it).  One host read per round (the selected count); the
+    sorts of a round (unique edges, neighbour and face lists) are torch's.  profile: a dict that receives 'rounds', 'n_target' and
+    the wall seconds per stage ('structures', 'edges', 'select', 'collapse', 'remap')."""
+    v = _xyz64(vertices, 'vertices').clone()
+    if not (torch.is_tensor(faces) and faces.is_cuda):
+        raise TypeError('faces must be a CUDA tensor (no CPU fallback exists)')
+    if (percent is None) == (n_vertices is None):
+        raise ValueError('give percent or n_vertices')
+    lib = _lib.load()
+    n, dev, stream = int(v.shape[0]), v.device, _stream(v)
+    if n >= 2 ** 31:
+        raise ValueError('too many vertices')
+    n_target = int(n_vertices) if n_vertices is not None else max(3, n * int(percent) // 100)
+    stage = _Stages(profile)
+    stage('setup')
+    f = _checked_faces(faces, n, 'decimate_qem')
+    # ---- vertex quadrics: faces in ascending id, then boundary edges in ascending (min, max)
+    Q = torch.zeros(max(n, 1), 10, dtype=torch.float64, device=dev)
+    nf = int(f.shape[0])
+    if nf:
+        Kf = torch.empty(nf, 10, dtype=torch.float64, device=dev)
+        fn = torch.empty(nf, 3, dtype=torch.float64, device=dev)
+        _lib.check(lib.stin_qem_face_quadrics_f64(_ptr(v), n, _ptr(f), nf, _ptr(Kf), _ptr(fn), stream), 'stin_qem_face_quadrics_f64')
+        rp, col = _vertex_faces(f, n)
+        _lib.check(lib.stin_qem_vertex_sum_f64(_ptr(rp), _ptr(col), int(col.numel()), _ptr(Kf), nf, 10, n, _ptr(Q), 0, 0, stream),
+                   'stin_qem_vertex_sum_f64')
+        keys, counts, first = _half_edges(f, n)
+        b = counts == 1
+        bi, bj, bf = (keys[b] // n).contiguous(), (keys[b] % n).contiguous(), first[b].contiguous()
+        nb = int(bi.numel())
+        if nb:
+            Kb = torch.empty(nb, 10, dtype=torch.float64, device=dev)
+            _lib.check(lib.stin_qem_boundary_quadrics_f64(_ptr(v), n, _ptr(bi), _ptr(bj), _ptr(bf), nb, _ptr(fn), nf, _ptr(Kb), stream),
+                       'stin_qem_boundary_quadrics_f64')
+            ids = torch.arange(nb, dtype=torch.int64, device=dev)
+            vk = torch.sort(torch.cat([bi, bj]) * nb + torch.cat([ids, ids])).values
+            rp, col = _rowptr(vk // nb, n), (vk % nb).contiguous()
+            _lib.check(lib.stin_qem_vertex_sum_f64(_ptr(rp), _ptr(col), int(col.numel()), _ptr(Kb), nb, 10, n, _ptr(Q), 1, 0, stream),
+                       'stin_qem_vertex_sum_f64')
+    parent = torch.arange(n, dtype=torch.int64, device=dev)
+    m1 = torch.empty(max(n, 1), dtype=torch.int64, device=dev)
+    m2 = torch.empty(max(n, 1), dtype=torch.int64, device=dev)
+    status = torch.zeros(1, dtype=torch.int32, device=dev)
+    n_cur, rounds = n, 0
+    while n_cur > n_target and f.shape[0]:
+        stage('structures')
+        keys, counts, _ = _half_edges(f, n)
+        ei, ej = (keys // n).contiguous(), (keys % n).contiguous()
+        E, nf = int(ei.numel()), int(f.shape[0])
+        k2, order = torch.sort(torch.cat([keys, ej * n + ei]), stable=True)
+        nrp, ncol, neid = _rowptr(k2 // n, n), (k2 % n).contiguous(), (order % E).contiguous()
+        frp, fface = _vertex_faces(f, n)
+        x = torch.empty(E, 3, dtype=torch.float64, device=dev)
+        cost = torch.empty(E, dtype=torch.float64, device=dev)
+        valid = torch.empty(E, dtype=torch.uint8, device=dev)
+        sel = torch.empty(E, dtype=torch.uint8, device=dev)
+        stage('edges')
+        _lib.check(lib.stin_qem_edges_f64(_ptr(v), _ptr(Q), n, _ptr(ei), _ptr(ej), _ptr(counts), E, _ptr(nrp), _ptr(ncol), int(ncol.numel()),
+                                          _ptr(frp), _ptr(fface), int(fface.numel()), _ptr(f), nf, _ptr(x), _ptr(cost), _ptr(valid),
+                                          stream), 'stin_qem_edges_f64')
+        stage('select')
+        _lib.check(lib.stin_qem_select_i64(_ptr(ei), _ptr(ej), E, _ptr(nrp), _ptr(ncol), _ptr(neid), int(ncol.numel()), _ptr(cost),
+                                           _ptr(valid), n, _ptr(m1), _ptr(m2), _ptr(sel), stream), 'stin_qem_select_i64')
+        ids = torch.nonzero(sel).reshape(-1)                              # (the round's host read: how many were selected)
+        if ids.numel() == 0:
+            break
+        if ids.numel() > n_cur - n_target:                                # the first of them in the order (cost, edge id)
+            ids = ids[torch.sort(cost[ids], stable=True).indices[:n_cur - n_target]].contiguous()
+        stage('collapse')
+        _lib.check(lib.stin_qem_collapse_f64(_ptr(ids), int(ids.numel()), _ptr(ei), _ptr(ej), E, _ptr(x), _ptr(v), _ptr(Q), _ptr(parent),
+                                             n, stream), 'stin_qem_collapse_f64')
+        stage('remap')
+        keep = torch.empty(nf, dtype=torch.uint8, device=dev)
+        _lib.check(lib.stin_qem_remap_faces_i64(_ptr(f), nf, _ptr(parent), n, _ptr(keep), _ptr(status), stream),
+                   'stin_qem_remap_faces_i64')
+        f = f[keep.bool()]
+        n_cur -= int(ids.numel())
+        rounds += 1
+    stage('finish')
+    alive = parent == torch.arange(n, dtype=torch.int64, device=dev)
+    rank = (torch.cumsum(alive.long(), 0) - 1).contiguous()
+    trace = torch.empty(n, dtype=torch.int64, device=dev)
+    _lib.check(lib.stin_qem_trace_i64(_ptr(parent), _ptr(rank), n, _ptr(trace), _ptr(status), stream), 'stin_qem_trace_i64')
+    if int(status.item()) != 0:
+        raise RuntimeError('decimate_qem: inconsistent merge state (status %d)' % int(status.item()))
+    stage(None)
+    if profile is not None:
+        profile['rounds'], profile['n_target'] = rounds, n_target
+    if strict and n_cur > n_target:
+        raise LevelError('decimate_qem: %d vertices left, %d asked for (no valid collapse remains)' % (n_cur, n_target))
+    return v[alive], rank[f], trace, n_cur
+
+
+def _qem_percent(x):
+    """The percentage of a decimator-mode level given as a digit string '1' .. '99', else None."""
+    if isinstance(x, str) and x.isdigit() and 1 <= int(x) <= 99:
+        return int(x)
+    return None
+
+
 def graph_levels(mesh, levels, dilated_levels, dilation_dists, labels=None, reference_vc_normals=False):
     """The body of the reference's process_frame (preprocessing/graph_level_generation.py:298-539) on the GPU: from a mesh and, per
     level, either a voxel size or a decimator's output to the dict the reference passes to torch.save for graphs/<scene>.pt
     (scene_io.write_graph_levels writes it; crop_scene, circle_masks / write_circle_masks, load_scene and load_label_scene read it).
 
-    mesh: dict of CUDA tensors - vertices [N, 3] float64, faces [F, 3] int, colors [N, 3], normals [N, 3].
+    mesh: dict of CUDA tensors - vertices [N, 3] float64, faces [F, 3] int, colors [N, 3], normals [N, 3] (optional:
+    vertex_normals(vertices, faces) when absent).
     levels: one entry per --level_params item, all of one mode:
       * vertex-clustering mode (--vertex_clustering): every entry a voxel size (float / int).  Level l clusters level l - 1 (the
         first one the mesh itself) with `vertex_clustering`; runs fully on the GPU.
-      * decimator mode (--qem): each entry is '100' (the plain current mesh with an identity trace: extract_plain_mesh), a dict
+      * decimator mode (--qem): each entry is '100' (the plain current mesh with an identity trace: extract_plain_mesh), a digit
+        string '1' .. '99' (decimate_qem of the current mesh to that percentage of its vertices, on the GPU: the trace is the
+        decimator's own, the level's normals are vertex_normals of the result - `['100', '30', '30', '30']` from a mesh alone), a dict
         (vertices [n, 3] float64, faces, csv = path or read_trace_csv tuple, normals) with a decimator's result for the current
         mesh (extract_qem_mesh: trace_from_csv against the previous level), or a dict without 'csv' - an externally clustered
         mesh (the trimesh_clustering branch) whose trace is nearest(ORIGINAL mesh vertices, its vertices), as the reference has
@@ -767,8 +971,8 @@ def graph_levels(mesh, levels, dilated_levels, dilation_dists, labels=None, refe
     set order; and in vertex-clustering mode the normals of a dilated level are those of each coarse vertex's nearest original
     vertex - the reference walks with rows 0 .. N_l - 1 of the INPUT mesh's normals there because it never updates its current
     mesh (reference_vc_normals=True reproduces that for file parity).
-    Out of scope: the decimator itself (vcglib's tridecimator), reading mesh files, computing vertex normals from faces (normals
-    are inputs) and the Matterport / S3DIS label paths."""
+    Out of scope: reading mesh files and the Matterport / S3DIS label paths.  A dict level still takes the output of an external
+    decimator (vcglib's tridecimator in the reference) as it is."""
     if len(levels) != len(dilated_levels):
         raise ValueError('levels and dilated_levels need one entry per level')
     if len(levels) == 0:
@@ -780,17 +984,19 @@ def graph_levels(mesh, levels, dilated_levels, dilation_dists, labels=None, refe
     v64 = verts.double().contiguous()
     n = int(v64.shape[0])
     dists = [int(d) for d in dilation_dists] if dilation_dists is not None else []
-    normals0 = mesh['normals'].to(dev).double()
+    faces0 = mesh['faces'].to(dev)
+    normals0 = mesh['normals'].to(dev).double() if mesh.get('normals') is not None else vertex_normals(v64, faces0)
     cols = [v64, mesh['colors'].to(dev).double(), normals0, torch.arange(n, device=dev, dtype=torch.float64).unsqueeze(1)]
     if labels is not None:
         cols.append(torch.as_tensor(labels).to(dev).double().reshape(n, 1))
     original = torch.cat(cols, dim=1)
     vc_mode = all(isinstance(x, (int, float)) and not isinstance(x, bool) for x in levels)
-    if not vc_mode and any(not (isinstance(x, dict) or str(x) == '100') for x in levels):
-        raise ValueError("levels: all voxel sizes (vertex-clustering mode), or each '100' or a dict (decimator mode)")
+    if not vc_mode and any(not (isinstance(x, dict) or str(x) == '100' or _qem_percent(x) is not None) for x in levels):
+        raise ValueError("levels: all voxel sizes (vertex-clustering mode), or each '100', a percentage '1' .. '99' or a dict "
+                         "(decimator mode)")
     coords = [v64]
     edges, traces, level_normals = [], [], []
-    cur = dict(vertices=v64, faces=mesh['faces'].to(dev), normals=normals0)           # the reference's curr_mesh
+    cur = dict(vertices=v64, faces=faces0, normals=normals0)                          # the reference's curr_mesh
     cur_edges = _mesh_edges(cur['faces'], n)
     for l, spec in enumerate(levels):
         if vc_mode:
@@ -813,6 +1019,11 @@ def graph_levels(mesh, levels, dilated_levels, dilation_dists, labels=None, refe
             e_l = _mesh_edges(spec['faces'].to(dev), c_l.shape[0])
             tr = trace_from_csv(spec['csv'], coords[-1], c_l)
             cur = dict(vertices=c_l, faces=spec['faces'].to(dev), normals=spec['normals'].to(dev).double())
+            nrm = cur['normals']
+        elif _qem_percent(spec) is not None:                                      # the decimator itself: the trace comes with it
+            c_l, f_l, tr, _ = decimate_qem(cur['vertices'], cur['faces'], percent=_qem_percent(spec))
+            e_l = _mesh_edges(f_l, c_l.shape[0])
+            cur = dict(vertices=c_l, faces=f_l, normals=vertex_normals(c_l, f_l))
             nrm = cur['normals']
         else:
             c_l = cur['vertices']
