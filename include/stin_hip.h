@@ -1119,6 +1119,53 @@ int stin_qem_remap_faces_i64(int64_t* faces, int64_t F, const int64_t* parent, i
                              stin_stream_t stream);
 int stin_qem_trace_i64(const int64_t* parent, const int64_t* rank, int64_t N, int64_t* trace, int32_t* status, stin_stream_t stream);
 
+/* Observer masks: which vertices of a mesh does each camera pose of a scan see (stin_observe.hip) - the `observers` mode of the
+ * reference's preprocessing/observed_texture_map_generation.py (compute_observed_vertex_map :159-251, which renders the mesh with
+ * PyTorch3D's MeshRasterizer at 256 x 256 and keeps pix_to_face; generate_mask_from_vertex_observing_poses :259-267), as a
+ * depth-tested triangle rasteriser.  The projection below is what compute_projection_matrix (:117-133) composed with PyTorch3D's
+ * documented NDC convention amounts to (z_sign = -1 and the left / up NDC axes cancel into a plain pinhole with the principal point
+ * at the image centre and the full field of view stretched onto the square image); it is derived from reading that code and is NOT
+ * pinned against a PyTorch3D run.  Everything is fp64 and IEEE, the operations in the order written, nothing contracted;
+ * tests/_observers_oracle.py restates it in numpy (per pixel over all faces) and agrees bit for bit.
+ *
+ *   poses     RT [P][12] = the rows of E[:3, :4], E = inverse of the camera-to-world pose (ScanNet's *.pose.txt), formed on the host
+ *             (preprocessing.pose_extrinsics); valid [P] bytes: 0 for a pose with a non-finite entry (ScanNet writes -inf for lost
+ *             tracking) - it observes nothing.
+ *   view      xv = ((R00 x + R01 y) + R02 z) + t0, likewise yv, zv.
+ *   screen    X = (sx xv / zv + 1.0) (0.5 S) - 0.5, Y likewise with sy, yv; sx = 2 fx / width, sy = 2 fy / height; pixel (row i,
+ *             column j) has its centre at (X, Y) = (j, i).
+ *   cull      a face is skipped for a pose when a corner has zv < z_near (faces that cross the near plane are DROPPED, not clipped:
+ *             ScanNet faces are centimetres across), an index is outside [0, N), a screen coordinate is not finite, or
+ *             area2 = edge(a, b, c) is 0;  edge(p, q, r) = (q.x - p.x) (r.y - p.y) - (q.y - p.y) (r.x - p.x).
+ *   coverage  wa = edge(b, c, pix), wb = edge(c, a, pix), wc = edge(a, b, pix): covered when all three are >= 0 (area2 > 0) or all
+ *             <= 0 (area2 < 0): inclusive edges, no fill rule, both orientations.
+ *   depth     la = wa / area2, lb, lc likewise; zp = 1.0 / ((la / za + lb / zb) + lc / zc); key = bits(float32(zp)) << 32 | face id;
+ *             the pixel keeps the MINIMUM key (64-bit integer atomicMin): the nearest face after rounding to fp32, the lowest id on a tie.
+ *   observers vertex v is observed by pose p when it is a corner of the winning face of at least one pixel of p:
+ *             bits [N][words] uint32, bit (p & 31) of word (p >> 5); words >= ceil(P / 32).  Integer atomicOr.
+ * stin_observe_poses_f64: poses in batches of `batch` (1 .. STIN_OBSERVE_MAX_BATCH) whose z-buffers (batch S S 8 bytes) and screen
+ *     coordinates (batch N 24 bytes) live in the workspace; the result does not depend on batch.  Per batch: clear, transform every
+ *     vertex once, rasterise with one thread per (face, pose), resolve with one thread per (pixel, pose).  A face whose clamped box
+ *     holds more than large_box centres (<= 0: STIN_OBSERVE_LARGE_BOX) goes through a queue to a second rasteriser that spreads it
+ *     over a wavefront (64: a wavefront's worth of centres, measured in profiles/r20_observers.md); the result does not depend on
+ *     large_box either.  faces are narrowed to int32 once.  S <= STIN_OBSERVE_MAX_SIZE,
+ *     N, F < 2^31 - 1, z_near > 0 (STIN_E_SIZE otherwise).  *status (device int32, written): STIN_OBSERVE_BAD_INDEX - a face had an
+ *     index outside [0, N) (it is skipped, the others are unaffected); STIN_OBSERVE_LARGE_FACE - informational: a face went
+ *     through the large-face rasteriser.  bits is written in full.  Nothing allocates or synchronises.
+ * stin_observe_mask_u32: count[m][v] = popcount(bits[v] & visible_words[m]) over the words, mask[m][v] = (count >= min_num_poses) ^
+ *     invert as int64 - the reference's values with invert = 0 (1 = seen by enough poses of the subset).  mask or count may be NULL. */
+#define STIN_OBSERVE_BAD_INDEX 1
+#define STIN_OBSERVE_LARGE_FACE 2
+#define STIN_OBSERVE_LARGE_BOX 64
+#define STIN_OBSERVE_MAX_SIZE 4096
+#define STIN_OBSERVE_MAX_BATCH 1024
+size_t stin_observe_workspace_bytes(int64_t N, int64_t F, int S, int batch);
+int stin_observe_poses_f64(const double* vertices, int64_t N, const int64_t* faces, int64_t F, const double* RT, const uint8_t* valid,
+                           int64_t P, double sx, double sy, int S, double z_near, int batch, int64_t large_box, uint32_t* bits,
+                           int64_t words, int32_t* status, void* workspace, size_t workspace_bytes, stin_stream_t stream);
+int stin_observe_mask_u32(const uint32_t* bits, int64_t N, int64_t words, const uint32_t* visible_words, int M, int min_num_poses,
+                          int invert, int64_t* mask, int32_t* count, stin_stream_t stream);
+
 /* ------------------------------------------------- 2-D image-graph inpainting experiment --
  * What the reference's ImageGraphTextureDataSet builds per item on CPU workers (datasets/imagegraph_dataloader.py:46-160) and what
  * the graph branch of its 2-D trainer reads back per step (trainers/inpainting2d_trainer.py:382-398, without lpips), stin_image.hip.

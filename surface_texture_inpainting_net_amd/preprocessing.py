@@ -27,6 +27,17 @@
   stated in include/stin_hip.h and restated in numpy by the test suite (bit-exact parity); it is NOT pinned against vcglib.
   ``vertex_normals`` - open3d's documented ``compute_vertex_normals`` rule (unit face normals summed, normalised), for the levels it makes.
 
+* ``observe_vertices``  - ``preprocessing/observed_texture_map_generation.compute_observed_vertex_map`` (:159-251, ``generate_masks.sh
+  observers``), which renders the mesh from every camera pose with PyTorch3D and keeps the face seen at each pixel: a depth-tested
+  triangle rasteriser in HIP (``stin_observe_poses_f64``) that answers "which poses see vertex v" as one bit per (vertex, pose).
+  ``pose_extrinsics`` is ``load_camera_poses``' inverse (:58-63) plus the validity rule; ``observer_visible`` is
+  ``select_pose_random_subset`` (:254-256) with a stated seed; ``observer_masks`` is ``generate_mask_from_vertex_observing_poses``
+  (:259-267, ``stin_observe_mask_u32``) for every mask of a scene at once - ``process_frame_observers`` (:486-527) with the
+  ``masks_per_scene`` its TODO (:731) asks for; ``observer_counts`` are the two statistics of ``plot_statistics`` (:454-483);
+  ``observers_to_lists`` gives the reference's ``observed_poses_per_vert`` cache format.  The projection convention is derived from
+  reading the reference and PyTorch3D's documented conventions, NOT pinned against a PyTorch3D run (its imports are commented out
+  in the reference and it is not installed here); faces that cross the near plane are dropped, not clipped.
+
 All take and return tensors in the reference's own formats.  Out of scope: reading mesh files (neither open3d nor plyfile exists
 here to pin a reader against: vertices, faces and colours are inputs), and the Matterport and S3DIS label paths.
 """
@@ -1057,3 +1068,163 @@ def graph_levels(mesh, levels, dilated_levels, dilation_dists, labels=None, refe
     out['dilated_edges'] = dilated
     out['dilation_dists'] = dilation_dists
     return out
+
+
+# ------------------------------------------------------------------------------------------------------------- observer masks
+def pose_extrinsics(poses):
+    """Camera-to-world poses [P, 4, 4] (the content of ScanNet's *.pose.txt; array or tensor) -> (RT float64 [P, 12], valid uint8 [P])
+    numpy arrays on the host: RT[p] = the rows of E[:3, :4], E = np.linalg.inv(pose) - the reference's read_camera_pose (:58-63)
+    without its transpose for PyTorch3D's row-vector convention.  A pose with a non-finite entry (ScanNet writes -inf where tracking
+    was lost; the reference would crash on it) is invalid: valid[p] = 0, RT[p] = 0, it observes nothing."""
+    import numpy as np
+    p = poses.detach().cpu().numpy() if torch.is_tensor(poses) else np.asarray(poses)
+    p = np.asarray(p, dtype=np.float64).reshape(-1, 4, 4)
+    valid = np.isfinite(p).reshape(p.shape[0], 16).all(axis=1)
+    RT = np.zeros((p.shape[0], 12), dtype=np.float64)
+    for i in np.flatnonzero(valid):
+        RT[i] = np.linalg.inv(p[i])[:3, :4].reshape(12)
+    return RT, valid.astype(np.uint8)
+
+
+def observe_vertices(vertices, faces, poses, fx, fy, width, height, image_size=256, z_near=0.01, batch=64, large_box=None,
+                     return_status=False):
+    """Which camera poses see which vertices: the reference's compute_observed_vertex_map (:159-251) as a depth-tested triangle
+    rasteriser on the GPU (csrc/stin_observe.hip).  vertices [N, >= 3] float, faces [F, 3] int (CUDA); poses [P, 4, 4] camera-to-world
+    (array or tensor, any device: they are inverted on the host); fx, fy = entries [0, 0] and [1, 1] of the colour intrinsic; width,
+    height of the colour image.
+    -> (bits uint32 [N, ceil(P / 32)] on the device: bit (p & 31) of word (p >> 5) = pose p observes the vertex, i.e. it is a corner of
+        the face seen at one pixel centre at least; valid_pose_ids int64 numpy: the poses without a non-finite entry).
+    return_status=True: also the status word (int): bit STIN_OBSERVE_BAD_INDEX - a face had an index outside [0, N) and was skipped;
+    bit STIN_OBSERVE_LARGE_FACE - a face went through the large-face rasteriser (informational).
+
+    The contract (include/stin_hip.h, "Observer masks"; restated per pixel in numpy by the test suite, which this reproduces bit
+    for bit), fp64 throughout: view = E [x y z 1], E the inverse pose; screen X = (sx xv / zv + 1) (S / 2) - 1 / 2 with sx = 2 fx /
+    width (Y likewise), pixel (row i, column j) centred at (X, Y) = (j, i) - a pinhole with the principal point at the image centre and
+    the full field of view stretched onto the S x S image, which is what the reference's compute_projection_matrix composed with
+    PyTorch3D's NDC convention amounts to.  This was derived from reading that code and PyTorch3D's documented conventions; it is NOT
+    pinned against a PyTorch3D run.  A face with a corner nearer than z_near is DROPPED, not clipped; so is one with no area on
+    screen.  Coverage is inclusive on every edge and takes both orientations; the nearest face wins a pixel after its depth is rounded
+    to fp32, the lowest face id on a tie.  The result does not depend on `batch` (poses per pass: batch * S * S * 8 bytes of depth
+    keys and batch * N * 24 bytes of screen coordinates) nor on `large_box` (faces whose clamped box holds more centres go to a
+    wavefront each; default STIN_OBSERVE_LARGE_BOX)."""
+    import numpy as np
+    if not (torch.is_tensor(faces) and faces.is_cuda):
+        raise TypeError('faces must be a CUDA tensor (no CPU fallback exists)')
+    v = _xyz64(vertices, 'vertices')
+    lib = _lib.load()
+    S, B = int(image_size), int(batch)
+    if not 1 <= S <= _lib.CONSTANTS['STIN_OBSERVE_MAX_SIZE'] or not 1 <= B <= _lib.CONSTANTS['STIN_OBSERVE_MAX_BATCH']:
+        raise ValueError('image_size must be in [1, %d] and batch in [1, %d]' % (_lib.CONSTANTS['STIN_OBSERVE_MAX_SIZE'],
+                                                                                _lib.CONSTANTS['STIN_OBSERVE_MAX_BATCH']))
+    if not float(z_near) > 0.0:
+        raise ValueError('z_near must be positive')
+    RT, valid = pose_extrinsics(poses)
+    n, dev, P = int(v.shape[0]), v.device, int(RT.shape[0])
+    f = faces.long().reshape(-1, 3).contiguous()
+    F, words = int(f.shape[0]), (P + 31) // 32
+    B = max(1, min(B, P))
+    bits = torch.empty(n, words, dtype=torch.uint32, device=dev)
+    status = torch.empty(1, dtype=torch.int32, device=dev)
+    rt_d, valid_d = torch.from_numpy(RT).to(dev), torch.from_numpy(valid).to(dev)
+    ws_bytes = lib.stin_observe_workspace_bytes(n, F, S, B)
+    ws = torch.empty(ws_bytes, dtype=torch.uint8, device=dev)
+    sx, sy = 2.0 * float(fx) / float(width), 2.0 * float(fy) / float(height)
+    _lib.check(lib.stin_observe_poses_f64(_ptr(v), n, _ptr(f) if F else None, F, _ptr(rt_d) if P else None, _ptr(valid_d) if P else None,
+                                          P, sx, sy, S, float(z_near), B, int(large_box) if large_box is not None else 0,
+                                          _ptr(bits) if bits.numel() else None, words, _ptr(status), _ptr(ws), ws_bytes, _stream(v)),
+               'stin_observe_poses_f64')
+    ids = np.flatnonzero(valid).astype(np.int64)
+    return (bits, ids, int(status.item())) if return_status else (bits, ids)
+
+
+def observer_visible(valid_pose_ids, num_poses, keep_probability=0.5, num_masks=1, seed=0):
+    """The pose subsets of num_masks masks -> bool [num_masks, num_poses] numpy: row m keeps the valid poses where
+    np.random.RandomState(seed + m).rand(len(valid_pose_ids)) <= keep_probability - the reference's select_pose_random_subset
+    (:254-256), with a stated seed instead of the global generator."""
+    import numpy as np
+    ids = np.asarray(valid_pose_ids, dtype=np.int64).reshape(-1)
+    if ids.size and (ids.min() < 0 or ids.max() >= int(num_poses)):
+        raise IndexError('a valid pose id lies outside [0, %d)' % int(num_poses))
+    out = np.zeros((int(num_masks), int(num_poses)), dtype=bool)
+    for m in range(int(num_masks)):
+        out[m, ids] = np.random.RandomState(int(seed) + m).rand(ids.size) <= keep_probability
+    return out
+
+
+def _pack_pose_bits(visible, words):
+    """bool [M, P] -> uint32 [M, words] with bit (p & 31) of word (p >> 5) (numpy, little-endian words)."""
+    import numpy as np
+    vis = np.asarray(visible, dtype=bool)
+    padded = np.zeros((vis.shape[0], words * 32), dtype=np.uint8)
+    padded[:, :vis.shape[1]] = vis
+    w = padded.reshape(vis.shape[0], words, 32).astype(np.uint64) << np.arange(32, dtype=np.uint64)
+    return w.sum(axis=2).astype(np.uint32)
+
+
+def _observer_counts(bits, visible_words, min_num_poses, invert, want_mask, want_count):
+    lib = _lib.load()
+    if not (torch.is_tensor(bits) and bits.is_cuda):
+        raise TypeError('bits must be a CUDA tensor (no CPU fallback exists)')
+    if bits.dtype != torch.uint32 or bits.dim() != 2:
+        raise TypeError('bits must be uint32 [N, words], as observe_vertices returns it')
+    b = bits.contiguous()
+    n, words, M = int(b.shape[0]), int(b.shape[1]), int(visible_words.shape[0])
+    vw = torch.from_numpy(visible_words).to(b.device)
+    mask = torch.empty(M, n, dtype=torch.int64, device=b.device) if want_mask else None
+    count = torch.empty(M, n, dtype=torch.int32, device=b.device) if want_count else None
+    _lib.check(lib.stin_observe_mask_u32(_ptr(b) if b.numel() else None, n, words, _ptr(vw) if vw.numel() else None, M, int(min_num_poses),
+                                         int(bool(invert)), _ptr(mask), _ptr(count), _stream(b)), 'stin_observe_mask_u32')
+    return mask, count
+
+
+def observer_masks(bits, valid_pose_ids, num_poses, keep_probability=0.5, min_num_poses=40, num_masks=1, seed=0, visible=None,
+                   invert=False, return_counts=False):
+    """Observer masks of one scene: int64 [num_masks, N] on the device, the reference's generate_mask_from_vertex_observing_poses
+    (:259-267) for every mask at once (stin_observe_mask_u32).  bits: observe_vertices' result.  Mask m takes the pose subset
+    visible[m] (bool [M, num_poses]; default observer_visible(valid_pose_ids, num_poses, keep_probability, num_masks, seed)), counts
+    per vertex the poses of the subset that observe it, and writes
+        invert=False (default, the reference's values): 1 where at least min_num_poses poses of the subset see the vertex, else 0;
+        invert=True:                                    1 where FEWER than min_num_poses see it, else 0.
+    The reference's loader inpaints where mask > 0 (scene_io.load_scene): with the default the network is asked to repaint what the
+    subset observed and is shown what it did not; invert=True asks it to fill in what the partial capture missed.  The default keeps
+    the reference's values as they are.  return_counts=True: also the counts (int32 [M, N]).
+    scene_io.write_circle_masks writes either kind to the mask files."""
+    import numpy as np
+    if visible is None:
+        visible = observer_visible(valid_pose_ids, num_poses, keep_probability, num_masks, seed)
+    vis = visible.detach().cpu().numpy() if torch.is_tensor(visible) else np.asarray(visible)
+    vis = np.atleast_2d(vis.astype(bool))
+    if vis.ndim != 2 or vis.shape[1] != int(num_poses):
+        raise ValueError('visible must be [num_masks, %d]' % int(num_poses))
+    words = (int(num_poses) + 31) // 32
+    if torch.is_tensor(bits) and bits.dim() == 2 and int(bits.shape[1]) != words:
+        raise ValueError('bits has %d words per vertex, %d poses need %d' % (int(bits.shape[1]), int(num_poses), words))
+    mask, count = _observer_counts(bits, _pack_pose_bits(vis, words), min_num_poses, invert, True, return_counts)
+    return (mask, count) if return_counts else mask
+
+
+def observer_counts(bits, num_poses=None):
+    """The two statistics the reference plots (plot_statistics :454-483) -> (per_vertex int64 [N]: poses that observe each vertex;
+    per_pose int64 [P]: vertices each pose observes; P = num_poses, default 32 * words), on the device.  per_vertex is
+    stin_observe_mask_u32's count with every pose visible; per_pose sums each bit position over the vertices (32 integer
+    reductions in torch: a statistic beside the path, not on it)."""
+    import numpy as np
+    words = int(bits.shape[1]) if torch.is_tensor(bits) and bits.dim() == 2 else 0
+    _, count = _observer_counts(bits, np.full((1, words), 0xFFFFFFFF, dtype=np.uint32), 0, False, False, True)
+    P = 32 * words if num_poses is None else int(num_poses)
+    b = bits.contiguous().view(torch.int32)
+    per_bit = torch.stack([((b >> k) & 1).sum(dim=0) for k in range(32)], dim=1)        # [words, 32]
+    return count[0].long(), per_bit.reshape(-1)[:P].contiguous()
+
+
+def observers_to_lists(bits, num_poses=None):
+    """bits (uint32 [N, words]; tensor on any device or array) -> the reference's observed_poses_per_vert: a list with, per vertex, the
+    ascending list of the pose ids that observe it (the content of its observers_per_vert/<scene>.npz cache), on the host."""
+    import numpy as np
+    b = bits.detach().cpu().numpy() if torch.is_tensor(bits) else np.asarray(bits)
+    b = np.ascontiguousarray(b, dtype=np.uint32)
+    n, words = b.shape
+    flags = ((b[:, :, None] >> np.arange(32, dtype=np.uint32)) & 1).astype(bool).reshape(n, words * 32)
+    if num_poses is not None:
+        flags = flags[:, :int(num_poses)]
+    return [np.flatnonzero(row).tolist() for row in flags]

@@ -186,7 +186,8 @@ def write_circle_masks(graph_path, masks_dir, masks):
     mask (masks: [num_masks, N_orig] int, e.g. preprocessing.circle_masks on the original mesh) is gathered to the file's level 0
     by round(vertices[0][:, -1]), rejected when less than MIN_FRAC_MASKED_VERTS of those vertices are masked, else written as
     masks_dir/'{:06d}.npz' (key vertex_mask) numbered by mask index - rejected masks leave gaps.  -> the paths written.
-    load_scene(graph_path, path) reads each back unchanged."""
+    load_scene(graph_path, path) reads each back unchanged.  It serves both mask types of generate_masks.sh: `circles`
+    (preprocessing.circle_masks) and `observers` (preprocessing.observer_masks)."""
     import os
     saved = torch.load(graph_path, map_location='cpu', weights_only=False)
     v0 = saved['vertices'][0]
@@ -264,3 +265,65 @@ def write_graph_levels(out_dir, scene_name, mesh, levels, dilated_levels, dilati
     path = os.path.join(out_dir, '%s.pt' % scene_name)
     torch.save({k: to(v, 'cpu') for k, v in saved.items()}, path)
     return path
+
+
+# ------------------------------------------------------------------------------------------------------------- observer masks
+def load_camera_poses(path, max_num_poses=None, cpp_sens_reader=True):
+    """The camera-to-world matrices of a scan as the reference's load_camera_poses (observed_texture_map_generation.py:57-79) finds
+    them: `*.pose.txt` (the C++ SensReader's export; `*.txt` for the python one) of directory `path`, sorted by name, the first
+    max_num_poses of them -> float64 [P, 4, 4] numpy (pose id = position).  The files are returned as they are: the inverse and the
+    validity rule (ScanNet writes -inf for lost tracking) are preprocessing.pose_extrinsics'."""
+    import glob
+    import os
+    names = sorted(glob.glob(os.path.join(path, '*.pose.txt' if cpp_sens_reader else '*.txt')))
+    if max_num_poses is not None:
+        names = names[:int(max_num_poses)]
+    poses = np.zeros((len(names), 4, 4), dtype=np.float64)
+    for i, name in enumerate(names):
+        poses[i] = np.loadtxt(name, dtype=np.float64).reshape(4, 4)
+    return poses
+
+
+def load_scan_config(path, scan_name, cpp_sens_reader=True):
+    """The reference's load_scan_config (:82-114) -> {'colorheight': int, 'colorwidth': int, 'colorintrinsic': float64 [4, 4]}.
+    cpp_sens_reader: path/_info.txt with m_colorWidth, m_colorHeight and the 16 numbers of m_calibrationColorIntrinsic; else
+    path/<scan_name>.txt with colorWidth, colorHeight, and the matrix from path/intrinsic_color.txt.  `key = value` lines, keys
+    compared without case (as configparser does for the reference); fx, fy of observe_vertices are entries [0, 0] and [1, 1]."""
+    import os
+    config = {}
+    with open(os.path.join(path, '_info.txt' if cpp_sens_reader else '%s.txt' % scan_name), 'r') as f:
+        for line in f:
+            key, sep, value = line.partition('=')
+            if sep:
+                config[key.strip().lower()] = value.strip()
+    prefix = 'm_' if cpp_sens_reader else ''
+    if cpp_sens_reader:
+        intrinsic = np.array([float(v) for v in config['m_calibrationcolorintrinsic'].split()], dtype=np.float64).reshape(4, 4)
+    else:
+        intrinsic = np.loadtxt(os.path.join(path, 'intrinsic_color.txt'), dtype=np.float64).reshape(4, 4)
+    return {'colorheight': int(config[prefix + 'colorheight']), 'colorwidth': int(config[prefix + 'colorwidth']),
+            'colorintrinsic': intrinsic}
+
+
+def write_observers(path, bits, valid_pose_ids, num_poses):
+    """The per-scene cache the reference keeps under observers_per_vert/<scene>.npz (:489-507), as plain arrays instead of a pickled
+    dict of lists: bits (uint32 [N, words], preprocessing.observe_vertices), valid_pose_ids (int64), num_poses.  -> path."""
+    import os
+    b = bits.detach().cpu().numpy() if torch.is_tensor(bits) else np.asarray(bits)
+    if os.path.dirname(str(path)):
+        os.makedirs(os.path.dirname(str(path)), exist_ok=True)
+    with open(path, 'wb') as f:
+        np.savez_compressed(f, bits=np.ascontiguousarray(b, dtype=np.uint32), valid_pose_ids=np.asarray(valid_pose_ids, dtype=np.int64),
+                            num_poses=np.asarray(int(num_poses), dtype=np.int64))
+    return path
+
+
+def read_observers(path, device=None):
+    """-> (bits uint32 [N, words], valid_pose_ids int64 numpy, num_poses int) of a write_observers file, read without pickle.  bits is
+    a numpy array, or a tensor on `device` when one is given (what preprocessing.observer_masks takes)."""
+    with open(path, 'rb') as f:
+        data = np.load(f, allow_pickle=False)
+        bits, ids, num_poses = data['bits'], data['valid_pose_ids'], int(data['num_poses'])
+    if device is not None:
+        bits = torch.from_numpy(bits).to(device)
+    return bits, ids, num_poses

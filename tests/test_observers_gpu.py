@@ -1,0 +1,293 @@
+"""Observer masks on the GPU (csrc/stin_observe.hip through preprocessing.observe_vertices / observer_masks / observer_counts):
+bit-exact against the numpy restatement of the contract (tests/_observers_oracle.py: `bits.tobytes()` and `valid_pose_ids` equal) on
+closed and open meshes, at the word and batch edges, through the large-face rasteriser and on both sides of its threshold, for
+everything the contract culls; geometric sanity and run-to-run identity at S = 256 where the restatement is too slow; the mask
+kernel against popcounts in numpy; and the chain from poses to mask files to one forward pass of the network."""
+import functools
+
+import numpy as np
+import pytest
+import torch
+
+import _levels_oracle as LO
+import _observers_oracle as OO
+import _qem_oracle as QO
+from surface_texture_inpainting_net_amd import _lib, preprocessing as P, scene_io
+from test_qem import SEED
+
+DEV = 'cuda:0'
+pytestmark = pytest.mark.gpu
+
+CAM = dict(fx=1170.19, fy=1165.37, width=1296, height=968)              # ScanNet's colour camera: fx != fy, width != height
+BAD, LARGE = _lib.CONSTANTS['STIN_OBSERVE_BAD_INDEX'], _lib.CONSTANTS['STIN_OBSERVE_LARGE_FACE']
+NET = dict(input_nc=10, output_nc=3, ngf=64, filter_type='edgeconvtransinv', norm='instance', n_blocks=3, n_levels=2,
+           pooling_type='max', dilations=[1, 2, 4])
+
+
+def dev(a):
+    return torch.from_numpy(np.ascontiguousarray(a)).to(DEV)
+
+
+def run(V, F, poses, S, **kw):
+    bits, ids, status = P.observe_vertices(dev(V), dev(np.asarray(F, dtype=np.int64).reshape(-1, 3)), poses, image_size=S,
+                                           return_status=True, **CAM, **kw)
+    assert bits.is_cuda and bits.dtype == torch.uint32 and bits.shape == (V.shape[0], (len(poses) + 31) // 32)
+    assert ids.dtype == np.int64
+    return bits.cpu().numpy(), ids, status
+
+
+def check_parity(V, F, poses, S, want=None, **kw):
+    want = want if want is not None else OO.observe(V, F, poses, image_size=S, **CAM, **{k: v for k, v in kw.items() if k == 'z_near'})
+    bits, ids, status = run(V, F, poses, S, **kw)
+    assert np.array_equal(ids, want[1])
+    assert bits.tobytes() == want[0].tobytes()
+    return bits, status
+
+
+def sphere_poses():
+    outside = [OO.look_at(e, (0, 0, 0)) for e in
+               3.0 * np.array([[np.cos(a) * np.cos(h), np.sin(a) * np.cos(h), np.sin(h)]
+                               for a, h in zip(0.2 + 2 * np.pi * np.arange(12) / 12, np.tile([0.0, 0.5, -0.7], 4))])]
+    inside = [OO.look_at((0, 0, 0), (1, 0.3, 0.2)), OO.look_at((0.2, 0.1, -0.1), (-1, 1, 0.5))]
+    return np.stack(outside + inside)
+
+
+@pytest.mark.parametrize('S', [32, 64])
+def test_parity_on_a_jittered_icosphere_from_outside_and_inside(S):
+    V, F = QO.icosphere(2, 3)
+    assert V.shape == (162, 3) and F.shape == (320, 3)
+    bits, _ = check_parity(V, F, sphere_poses(), S)
+    seen = OO.unpack(bits, 14)
+    assert seen[:, :12].any(axis=0).all() and seen[:, 12:].any(axis=0).all()     # every pose sees something, those inside too
+    assert not seen.all(axis=0).any()                                            # and none sees the far side
+
+
+def grid_poses(m):
+    c = m['vertices'].mean(axis=0)
+    lo, hi = m['vertices'].min(axis=0), m['vertices'].max(axis=0)
+    oblique = [OO.look_at((lo[0] - 1.0, lo[1] - 0.5, 1.5), c), OO.look_at((hi[0] + 0.5, c[1], 0.8), c), OO.look_at((c[0], c[1], 2.5), c)]
+    grazing = [OO.look_at((lo[0] - 0.5, c[1], 0.45), (hi[0], c[1], 0.3)), OO.look_at((c[0], hi[1] + 0.3, 0.05), (c[0], lo[1], 0.0)),
+               OO.look_at((lo[0] - 0.2, lo[1] - 0.2, -0.1), (hi[0], hi[1], 0.1))]
+    return np.stack(oblique + grazing)
+
+
+def test_parity_on_a_height_field_seen_obliquely_and_at_grazing_angles():
+    m = LO.grid_mesh(12, SEED)
+    bits, _ = check_parity(m['vertices'], m['faces'], grid_poses(m), 32)
+    assert OO.unpack(bits, 6).any(axis=0).all()
+
+
+# ------------------------------------------------------------------------------------------------------- word and batch edges
+@functools.lru_cache(maxsize=None)
+def many_poses():
+    """42 vertices (no multiple of 32), 80 faces, 70 poses of which one is lost; the restatement once, for all of them."""
+    V, F = QO.icosphere(1, 5)
+    assert V.shape[0] == 42
+    poses = np.concatenate([OO.orbit(35, 3.0, 0.8), OO.orbit(35, 2.5, -1.2, phase=0.4)])
+    poses[5] = -np.inf
+    return V, F, poses, OO.observe(V, F, poses, image_size=16, **CAM)
+
+
+@pytest.mark.parametrize('num', [1, 31, 32, 33, 70])
+def test_pose_counts_at_the_word_edges_and_every_batch_size(num):
+    V, F, poses, (want_bits, want_ids, _) = many_poses()
+    want = (P._pack_pose_bits(OO.unpack(want_bits, num), (num + 31) // 32), want_ids[want_ids < num], None)
+    runs = [check_parity(V, F, poses[:num], 16, want=want, batch=b)[0] for b in (1, 7, 64)]
+    assert runs[0].tobytes() == runs[1].tobytes() == runs[2].tobytes()
+    if num > 1:
+        assert runs[0].any()
+
+
+# ------------------------------------------------------------------------------------------------------- large faces
+def wall_in_front():
+    V, F = QO.icosphere(2, 3)
+    W, G = OO.wall(1, 4.0, origin=(1.5, 0.0, 0.0), u=(0.0, 1.0, 0.0), v=(0.0, 0.0, 1.0))
+    return np.concatenate([V, W]), np.concatenate([F, G + V.shape[0]]), V.shape[0]
+
+
+def test_a_wall_filling_the_view_goes_through_the_large_face_rasteriser():
+    V, F, n_sphere = wall_in_front()
+    poses = np.stack([OO.look_at((3.0, 0.0, 0.0), (0, 0, 0)), OO.look_at((-3.0, 0.0, 0.0), (0, 0, 0))])
+    bits, status = check_parity(V, F, poses, 64)
+    assert status & LARGE and not status & BAD
+    seen = OO.unpack(bits, 2)
+    assert not seen[:n_sphere, 0].any() and seen[n_sphere:, 0].all()             # pose 0: the wall and nothing behind it
+    assert seen[:n_sphere, 1].any()                                              # pose 1, from the other side: the sphere is in front
+
+
+def wall_on_screen(pose, X0, X1, Y0, Y1, depth, S):
+    """Two triangles whose common box on the screen of `pose` is [X0, X1] x [Y0, Y1] (pixel units) at `depth`."""
+    sx, sy = 2 * CAM['fx'] / CAM['width'], 2 * CAM['fy'] / CAM['height']
+    cam = [[((X + 0.5) / (0.5 * S) - 1.0) * depth / sx, ((Y + 0.5) / (0.5 * S) - 1.0) * depth / sy, depth, 1.0]
+           for X, Y in ((X0, Y0), (X1, Y0), (X0, Y1), (X1, Y1))]
+    return (pose @ np.array(cam).T).T[:, :3].copy(), np.array([[0, 1, 3], [0, 3, 2]], dtype=np.int64)
+
+
+THRESHOLD = _lib.CONSTANTS['STIN_OBSERVE_LARGE_BOX']
+BOXES = [(a, THRESHOLD // a + more) for a in (5, 8, 16) for more in (0, 1)]      # a x b <= THRESHOLD < a x (b + 1)
+
+
+@pytest.mark.parametrize('nx,ny', BOXES + [(ny, nx) for nx, ny in BOXES[:2]])
+def test_boxes_just_below_and_just_above_the_threshold(nx, ny):
+    """A wall of nx x ny centres (the corners 0.3 pixels outside the outermost ones, so rounding cannot move the count): the default
+    threshold takes boxes of MORE than STIN_OBSERVE_LARGE_BOX centres, and an explicit one splits at the box's own size."""
+    assert 16 <= THRESHOLD <= 256 and max(nx, ny) <= 53                 # the walls below fit the 64 x 64 image
+    pose = OO.look_at((3.0, 0.2, -0.1), (0, 0, 0))
+    W, G = wall_on_screen(pose, 6 - 0.3, 6 + nx - 1 + 0.3, 4 - 0.3, 4 + ny - 1 + 0.3, 1.5, 64)
+    want = OO.observe(W, G, pose[None], image_size=64, **CAM)
+    assert int((want[2] >= 0).sum()) == nx * ny
+    bits, status = check_parity(W, G, pose[None], 64, want=want)
+    assert bool(status & LARGE) == (nx * ny > THRESHOLD) and bits.all()
+    _, status = check_parity(W, G, pose[None], 64, want=want, large_box=nx * ny)
+    assert not status & LARGE
+    _, status = check_parity(W, G, pose[None], 64, want=want, large_box=nx * ny - 1)
+    assert status & LARGE
+
+
+# ------------------------------------------------------------------------------------------------------- culling
+def test_poses_looking_away_see_nothing():
+    V, F = QO.icosphere(1, 5)
+    poses = np.stack([OO.look_at((3.0, 0, 0), (6.0, 0, 0)), OO.look_at((0, -3.0, 1.0), (0, -6.0, 1.0))])
+    bits, status = check_parity(V, F, poses, 32)
+    assert not bits.any() and status == 0
+
+
+def test_a_pose_inside_the_surface_drops_the_faces_across_the_near_plane():
+    m = LO.grid_mesh(12, SEED)
+    V, F = m['vertices'], m['faces']
+    k = int(np.argmin(np.linalg.norm(V[:, :2] - V[:, :2].mean(axis=0), axis=1)))
+    eye = V[k] + [0.0, 0.0, 0.002]                                       # two millimetres above a vertex in the middle of the mesh
+    poses = np.stack([OO.look_at(eye, eye + [1.0, 0.2, 0.0]), OO.look_at(eye, eye + [-0.3, 1.0, -0.05])])
+    RT, _ = P.pose_extrinsics(poses)
+    z = OO.screen(V, RT[0], 1.0, 1.0, 32)[2][F]
+    assert ((z < 0.01).any(axis=1) & (z >= 0.01).any(axis=1)).any()     # the case is there: faces with corners on both sides
+    bits, _ = check_parity(V, F, poses, 32)
+    assert bits.any()
+    check_parity(V, F, poses, 32, z_near=0.3)
+
+
+def test_lost_poses_observe_nothing_and_are_left_out():
+    V, F = QO.icosphere(1, 5)
+    poses = OO.orbit(5, 3.0, 0.5)
+    poses[1, 1, 2] = np.nan
+    poses[3] = -np.inf
+    bits, ids, status = run(V, F, poses, 32)
+    assert ids.tolist() == [0, 2, 4] and not status & BAD
+    seen = OO.unpack(bits, 5)
+    assert not seen[:, 1].any() and not seen[:, 3].any() and seen[:, [0, 2, 4]].any(axis=0).all()
+    check_parity(V, F, poses, 32)
+
+
+def test_faces_with_an_index_out_of_range_are_skipped_and_reported():
+    V, F = QO.icosphere(1, 5)
+    poses = OO.orbit(3, 3.0, 0.5)
+    clean, status = check_parity(V, F, poses, 32)
+    assert not status & BAD                                              # (the large-face bit is informational)
+    G = np.concatenate([F, [[0, 1, V.shape[0]], [-1, 2, 3], [2 ** 40, 4, 5], [2 ** 31, 1, 2], [7, 8, -2 ** 33]]])
+    bits, status = check_parity(V, G, poses, 32)
+    assert status & BAD and bits.tobytes() == clean.tobytes()            # the others are unaffected
+    H = F.copy()
+    H[11, 2] = V.shape[0] + 3
+    bits, status = check_parity(V, H, poses, 32)
+    assert status & BAD
+    assert not check_parity(V, F, poses, 32)[1] & BAD                    # and the next call is clean
+
+
+def test_degenerate_faces_and_empty_inputs():
+    V, F = QO.icosphere(1, 5)
+    poses = OO.orbit(3, 3.0, 0.5)
+    G = np.concatenate([[[4, 4, 9], [6, 6, 6]], F, [[1, 2, 1]]])
+    check_parity(V, G, poses, 32)
+    bits, ids, status = run(V, np.zeros((0, 3), dtype=np.int64), poses, 32)
+    assert bits.shape == (42, 1) and not bits.any() and ids.tolist() == [0, 1, 2] and status == 0
+    bits, ids, status = run(V, F, np.zeros((0, 4, 4)), 32)
+    assert bits.shape == (42, 0) and ids.shape == (0,) and status == 0
+    masks = P.observer_masks(torch.zeros(42, 0, dtype=torch.uint32, device=DEV), ids, 0, min_num_poses=1)
+    assert masks.shape == (1, 42) and not bool(masks.any())
+
+
+# ------------------------------------------------------------------------------------------------------- geometry, no oracle
+def test_a_convex_sphere_shows_only_front_faces_and_all_of_itself():
+    V, F = QO.icosphere(2, 3, jitter=0)
+    n = np.cross(V[F[:, 1]] - V[F[:, 0]], V[F[:, 2]] - V[F[:, 0]])
+    centroid = V[F].mean(axis=1)
+    n = n * np.sign((n * centroid).sum(axis=1))[:, None]                 # outward
+    eyes = 3.0 * np.array([[a, b, c] for a in (-1, 1) for b in (-1, 1) for c in (-1, 1)]) / np.sqrt(3.0)
+    poses = np.stack([OO.look_at(e, (0, 0, 0)) for e in eyes])
+    bits, ids, status = run(V, F, poses, 256)
+    seen = OO.unpack(bits, 8)
+    for p, eye in enumerate(eyes):
+        front = ((eye - centroid) * n).sum(axis=1) > 0
+        has_front = np.zeros(V.shape[0], dtype=bool)
+        has_front[F[front].reshape(-1)] = True
+        assert seen[:, p].any() and not (seen[:, p] & ~has_front).any()
+        assert seen[:, p].sum() < V.shape[0]
+    assert seen.any(axis=1).all()                                        # together they observe every vertex
+
+
+def test_two_runs_under_contention_give_identical_bits():
+    m = LO.grid_mesh(60, SEED, spacing=0.1)
+    c = m['vertices'].mean(axis=0)
+    poses = np.concatenate([OO.orbit(20, 4.0, 2.0, target=c), OO.orbit(20, 1.0, 0.6, target=c, phase=0.3)])
+    a, ids, _ = run(m['vertices'], m['faces'], poses, 256)
+    again, _, _ = run(m['vertices'], m['faces'], poses, 256)
+    b, _, _ = run(m['vertices'], m['faces'], poses, 256, batch=16)
+    assert len(ids) == 40 and a.tobytes() == again.tobytes() == b.tobytes()
+    seen = OO.unpack(a, 40)
+    assert seen.any(axis=0).all() and seen.any(axis=1).sum() > m['vertices'].shape[0] // 2
+
+
+# ------------------------------------------------------------------------------------------------------- masks
+@pytest.mark.parametrize('M', [1, 3])
+def test_masks_and_counts_against_popcounts(M):
+    V, F, poses, (want_bits, ids, _) = many_poses()
+    num = 70
+    bits = dev(want_bits)
+    visible = np.random.default_rng(M).uniform(size=(M, num)) < 0.6
+    for least in (0, 1, 5, num + 1):
+        for invert in (False, True):
+            mask, count = P.observer_masks(bits, ids, num, min_num_poses=least, visible=visible, invert=invert, return_counts=True)
+            assert mask.dtype == torch.int64 and count.dtype == torch.int32 and mask.shape == (M, 42) and mask.is_cuda
+            want_mask, want_count = OO.masks(want_bits, visible, least, invert)
+            assert np.array_equal(mask.cpu().numpy(), want_mask) and np.array_equal(count.cpu().numpy(), want_count)
+    default = P.observer_masks(bits, ids, num, keep_probability=0.5, min_num_poses=5, num_masks=M, seed=3)
+    assert np.array_equal(default.cpu().numpy(), OO.masks(want_bits, P.observer_visible(ids, num, 0.5, M, 3), 5)[0])
+    per_vertex, per_pose = P.observer_counts(bits, num)
+    seen = OO.unpack(want_bits, num)
+    assert per_vertex.dtype == torch.int64 and np.array_equal(per_vertex.cpu().numpy(), seen.sum(axis=1))
+    assert per_pose.shape == (num,) and np.array_equal(per_pose.cpu().numpy(), seen.sum(axis=0))
+    assert per_pose[5] == 0                                              # the lost pose
+
+
+# ------------------------------------------------------------------------------------------------------- end to end
+def test_from_poses_to_mask_files_to_one_forward_pass(tmp_path):
+    from surface_texture_inpainting_net_amd import surfacetextureinpaintingnet as S
+    m = LO.grid_mesh(24, SEED)
+    N = m['vertices'].shape[0]
+    graph = scene_io.write_graph_levels(str(tmp_path / 'graphs'), 'scene0000_00', m, ['100', '30', '30'], [0, 0, 1], [2, 4], device=DEV)
+    c = m['vertices'].mean(axis=0)
+    ring = [c + [1.2 * np.cos(a), 1.2 * np.sin(a), 0.0] for a in 2 * np.pi * np.arange(12) / 12]
+    poses = np.stack([OO.look_at(t + [0.0, 0.0, 2.0], t) for t in ring])
+    bits, ids = P.observe_vertices(dev(m['vertices']), dev(m['faces']), poses, image_size=64, **CAM)
+    assert ids.tolist() == list(range(12))
+    cache = scene_io.write_observers(str(tmp_path / 'observers_per_vert' / 'scene0000_00.npz'), bits, ids, 12)
+    cached, cached_ids, num = scene_io.read_observers(cache, device=DEV)
+    assert torch.equal(cached.view(torch.int32), bits.view(torch.int32)) and num == 12
+    masks = P.observer_masks(cached, cached_ids, num, keep_probability=0.5, min_num_poses=2, num_masks=3)
+    assert masks.shape == (3, N)
+    written = scene_io.write_circle_masks(graph, str(tmp_path / 'masks' / 'observers' / 'scene0000_00'), masks)
+    assert len(written) >= 1
+    saved = torch.load(graph, weights_only=False)
+    order = np.round(saved['vertices'][0][:, -1].numpy()).astype(int)
+    for path in written:
+        k = int(path.rsplit('/', 1)[-1].split('.')[0])
+        s = scene_io.load_scene(graph, path, end_level=3)
+        want = masks[k].cpu().numpy()[order]
+        assert np.array_equal(np.load(path)['vertex_mask'], want) and 0 < want.sum() < N
+        assert np.array_equal(s.mask.reshape(-1).numpy(), want)
+        assert np.array_equal(s.x[:, 9].numpy(), (want == 0).astype(np.float32))
+    torch.manual_seed(0)
+    net = S.define_G(**NET).to(DEV)
+    with torch.no_grad():
+        y = net(s.to(DEV))
+    assert y.shape == (N, 3) and bool(torch.isfinite(y).all())
