@@ -383,6 +383,14 @@ size_t stin_gemm_tn_workspace_bytes(int64_t M, int Nc, int K, int ones_column);
 int stin_gemm_tn_f32(const float* G, int64_t ldg, const float* X, int64_t ldx, int64_t M, int Nc, int K,
                      int ones_column, const float* row_weight, int64_t ld_weight, float* dW, int64_t lddw,
                      int precision, void* workspace, size_t workspace_bytes, stin_stream_t stream);
+/* The geometry a TN product of this shape runs on - host only: nothing is launched, no device is touched.  storage 0 = fp32 rows,
+ * 1 = bf16 rows; ldg / ldx in elements; aligned16 != 0: both operand bases are 16-byte aligned; precision as stin_gemm_tn_f32
+ * (bf16 rows: STIN_GEMM_BF16X3).  out8 = { TI, TJ, tiles_i, tiles_j, rows_per_chunk, chunks, vec, ws_eligible }: the output tile
+ * (TI == 0: the skinny-K kernel, whose block owns all columns), the tile counts along Nc and K, the rows of one chunk and the number
+ * of chunks = partial slabs, vec = 16-byte operand loads, ws_eligible = the producer / consumer kernel takes it.  The A/B switches
+ * STIN_TN_WS and STIN_TN_BIG are honoured as by the products themselves; returns their argument errors. */
+int stin_gemm_tn_geometry(int storage, int64_t M, int Nc, int K, int64_t ldg, int64_t ldx, int aligned16, int ones_column,
+                          int precision, int32_t* out8);
 
 /* The same product with the weight gradient dW [Nc, K] (row pitch lddw >= K) and the bias gradient db [Nc] as SEPARATE
  * destinations (ones column implied): what torch.nn.Linear's backward hands to weight.grad / bias.grad

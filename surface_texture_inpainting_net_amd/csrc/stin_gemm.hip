@@ -605,6 +605,30 @@ int stin_tn_problem_init(stin_tn_problem* p, int storage, const void* G, int64_t
     return STIN_OK;
 }
 
+// The geometry stin_tn_problem_init gives a product of this shape, for tests and tools: which tile class (TI == 0: the skinny
+// kernel), how many row chunks = partial slabs, whether the 16-byte loads and the producer / consumer kernel apply.  Host only:
+// the placeholder operands (16-byte aligned or not) are never read through, nothing is launched, no device is touched.
+extern "C" int stin_gemm_tn_geometry(int storage, int64_t M, int Nc, int K, int64_t ldg, int64_t ldx, int aligned16, int ones_column,
+                                     int precision, int32_t* out8) {
+    STIN_REQUIRE(out8 != nullptr, STIN_E_NULL);
+    STIN_REQUIRE(storage == 0 || storage == 1, STIN_E_UNSUPPORTED);
+    void* const some = reinterpret_cast<void*>(uintptr_t(aligned16 ? 256 : 260));
+    stin_tn_problem p;
+    int ws = 0;
+    const int rc = stin_tn_problem_init(&p, storage, some, ldg, some, ldx, M, Nc, K, ones_column, nullptr, 0, precision,
+                                        static_cast<float*>(some), &ws);
+    if (rc != STIN_OK) return rc;
+    out8[0] = p.TI;
+    out8[1] = p.TJ;
+    out8[2] = p.tiles_i;
+    out8[3] = p.tiles_j;
+    out8[4] = p.rows_per_chunk;
+    out8[5] = (int32_t)p.chunks;
+    out8[6] = p.vec;
+    out8[7] = ws;
+    return STIN_OK;
+}
+
 // The TN kernel of one product: partial slabs only (k_reduce_slabs / k_wgrad_finalize add them).
 int stin_tn_slabs(const stin_tn_problem* p, int storage, int precision, stin_stream_t stream_) {
     hipStream_t stream = (hipStream_t)stream_;
