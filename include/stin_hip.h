@@ -1174,6 +1174,74 @@ int stin_observe_poses_f64(const double* vertices, int64_t N, const int64_t* fac
 int stin_observe_mask_u32(const uint32_t* bits, int64_t N, int64_t words, const uint32_t* visible_words, int M, int min_num_poses,
                           int invert, int64_t* mask, int32_t* count, stin_stream_t stream);
 
+/* Frame colours: per-vertex colours of a mesh from a scan's RGB-D frames and camera trajectory (stin_frames.hip) - what the
+ * reference's preprocessing/texture_map_optimization.py asks of Open3D's colour-map pipeline with maximum_iteration = 0: nothing is
+ * optimised, every vertex is projected into every frame that sees it, the colour image is sampled bilinearly and the samples are
+ * averaged.  Neither Open3D nor cv2 can run beside this project, so this is a contract of the project's own, NOT a port and NOT
+ * pinned against an Open3D run; tests/_frames_oracle.py restates it in numpy (per pose over all vertices) and agrees bit for bit.
+ * Everything is fp64 and IEEE, the operations in the order written, nothing contracted; integers where stated.
+ *
+ *   poses     RT [B][12], valid [B]: the rows of preprocessing.pose_extrinsics' output for one batch of poses (see "Observer
+ *             masks"); first_pose = the scan-wide id of the batch's first pose, p = first_pose + b.  An invalid pose contributes nothing.
+ *   view      xv = ((R00 x + R01 y) + R02 z) + t0, likewise yv, zv (the observers' expression).
+ *   cameras   one for the colour frames (Hc x Wc) and one for the depth frames (Hd x Wd), each (fx, fy, cx, cy) in pixels of its own
+ *             frame size; the sizes may differ.  u = fx xv / zv + cx, v = fy yv / zv + cy; pixel (row i, column j) is centred at
+ *             (u, v) = (j, i).  A pair (vertex, pose) is skipped when zv < z_near (z_near > 0; no clipping at the near plane) or when
+ *             any of u, v of a camera in use is not finite.
+ *   depth     uint16 [B][Hd][Wd] raw sensor units; r = raw, r = 0 where raw / depth_scale > depth_trunc; 0 = no measurement.
+ *   edges     the depth-discontinuity mask, exact integer arithmetic on r with row and column indices clamped to the image:
+ *               gx = (r[i-1,j+1] + 2 r[i,j+1] + r[i+1,j+1]) - (r[i-1,j-1] + 2 r[i,j-1] + r[i+1,j-1])
+ *               gy = (r[i+1,j-1] + 2 r[i+1,j] + r[i+1,j+1]) - (r[i-1,j-1] + 2 r[i-1,j] + r[i-1,j+1])
+ *             edge0 = (double)(gx gx + gy gy) > T T (the sum in int64), T = discontinuity_threshold depth_scale;
+ *             edge[i,j] = any edge0 in the (2 k + 1)^2 window around it that lies inside the image, k = half_kernel >= 0.
+ *             UNIT of discontinuity_threshold: metres of SOBEL response, not metres of depth - a depth step of s metres between two
+ *             columns gives |gx| = 4 s (8 s across a two-pixel ramp).  Open3D's option value 0.1 is in the same unit.
+ *   visible   from depth: ui = rint(u_d), vi = rint(v_d) (ties to even), 0 <= ui < Wd, 0 <= vi < Hd, rr = r[b, vi, ui] != 0,
+ *             d = rr / depth_scale, !(d > max_depth), !edge[b, vi, ui], |zv - d| < depth_threshold;
+ *             or, depth == NULL, from observer bits: bit (p & 31) of word (p >> 5) of bits[v] (stin_observe_poses_f64's layout).
+ *   sample    colour frames uint8 [B][Hc][Wc][3], RGB, channel last (3-byte pixels: read as bytes, no alignment assumed).  Required:
+ *             margin <= u <= Wc - 1 - margin and margin <= v <= Hc - 1 - margin (integer margin >= 0).  x0 = floor(u), y0 = floor(v),
+ *             a = u - x0, b = v - y0, x1 = min(x0 + 1, Wc - 1), y1 likewise; per channel
+ *               val = (((1-a)(1-b)) I[y0,x0] + (a(1-b)) I[y0,x1]) + (((1-a) b) I[y1,x0] + (a b) I[y1,x1]),  q = (int64) rint(val 65536.0).
+ *   sums      sum[v][c] += q (int64), count[v] += 1 (int32), bit p of seen[v] set (optional; uint32 [N][seen_words]).  Integers: the
+ *             result depends neither on the order of the poses, nor on the batching, nor on how the work is split over threads.
+ *             q < 2^24: int64 cannot overflow below 2^31 poses.  Integer atomics only; no float atomics.
+ *   finish    colour[v][c] = float32(sum[v][c] / (count[v] 16711680.0)) in [0, 1] (16711680 = 65536 * 255); observed[v] = count[v] > 0;
+ *             a vertex with count 0 gets (fill_r, fill_g, fill_b).  Open3D's k-nearest-neighbour fill of unseen vertices is left out.
+ * stin_frames_depth_edges_u16: depth [B][Hd][Wd] -> edge bytes [B][Hd][Wd] (0 / 1), two passes: the gradient test into the
+ *     workspace (stin_frames_edges_workspace_bytes), then the dilation (separable, through LDS).  half_kernel <=
+ *     STIN_FRAMES_MAX_HALF_KERNEL, depth_scale > 0, sizes in [1, STIN_FRAMES_MAX_SIZE], B <= STIN_FRAMES_MAX_BATCH (STIN_E_SIZE).
+ * stin_frames_accumulate_f64: one batch of poses into sum / count / seen, which are ACCUMULATED INTO, not cleared: the caller zeroes
+ *     them once per scene; batches of one scene arrive in any order and any size (on one stream, or otherwise ordered).
+ *     cameras: HOST array of STIN_FRAMES_CAMERA_DOUBLES doubles = colour (fx, fy, cx, cy), depth (fx, fy, cx, cy); params: HOST array
+ *     of STIN_FRAMES_PARAM_DOUBLES doubles = depth_scale, depth_trunc, max_depth, depth_threshold, z_near (read during the call).  Depth mode:
+ *     depth, edge and the depth camera and parameters; bits mode (depth == NULL): bits with words >= ceil((first_pose + B) / 32).
+ *     seen may be NULL; else seen_words >= ceil((first_pose + B) / 32).  Lanes run along the vertices and a thread keeps its vertex's
+ *     sums in registers over a chunk of poses.  route: STIN_FRAMES_ROUTE_AUTO - a host decision from N and B alone: with enough
+ *     vertices to fill the chip (or few poses) one thread owns a vertex for the whole batch and stores without atomics
+ *     (STIN_FRAMES_ROUTE_OWNER), else the poses are split over a second grid dimension and every chunk adds its four values with one
+ *     integer atomicAdd each (STIN_FRAMES_ROUTE_SPLIT); both give identical bits.  N < 2^31 - 1, first_pose + B < 2^31.
+ * stin_frames_finish_f32: sum, count -> colours float32 [N][3], observed bytes [N] (either may be NULL).
+ * Null pointers are allowed where a count is 0.  Nothing allocates or synchronises. */
+#define STIN_FRAMES_MAX_SIZE 16384
+#define STIN_FRAMES_MAX_BATCH 4096
+#define STIN_FRAMES_MAX_HALF_KERNEL 15
+#define STIN_FRAMES_CAMERA_DOUBLES 8
+#define STIN_FRAMES_PARAM_DOUBLES 5
+#define STIN_FRAMES_ROUTE_AUTO 0
+#define STIN_FRAMES_ROUTE_OWNER 1
+#define STIN_FRAMES_ROUTE_SPLIT 2
+size_t stin_frames_edges_workspace_bytes(int B, int Hd, int Wd);
+int stin_frames_depth_edges_u16(const uint16_t* depth, int B, int Hd, int Wd, double depth_scale, double depth_trunc,
+                                double discontinuity_threshold, int half_kernel, uint8_t* edge, void* workspace,
+                                size_t workspace_bytes, stin_stream_t stream);
+int stin_frames_accumulate_f64(const double* vertices, int64_t N, const double* RT, const uint8_t* valid, int B, int64_t first_pose,
+                               const uint8_t* color, int Hc, int Wc, const uint16_t* depth, const uint8_t* edge, int Hd, int Wd,
+                               const double* cameras, const double* params, const uint32_t* bits, int64_t words, int margin,
+                               int route, int64_t* sum, int32_t* count, uint32_t* seen, int64_t seen_words, stin_stream_t stream);
+int stin_frames_finish_f32(const int64_t* sum, const int32_t* count, int64_t N, float fill_r, float fill_g, float fill_b,
+                           float* colors, uint8_t* observed, stin_stream_t stream);
+
 /* ------------------------------------------------- 2-D image-graph inpainting experiment --
  * What the reference's ImageGraphTextureDataSet builds per item on CPU workers (datasets/imagegraph_dataloader.py:46-160) and what
  * the graph branch of its 2-D trainer reads back per step (trainers/inpainting2d_trainer.py:382-398, without lpips), stin_image.hip.

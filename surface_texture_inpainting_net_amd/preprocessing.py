@@ -38,6 +38,12 @@
   reading the reference and PyTorch3D's documented conventions, NOT pinned against a PyTorch3D run (its imports are commented out
   in the reference and it is not installed here); faces that cross the near plane are dropped, not clipped.
 
+* ``FrameColors`` / ``vertex_colors_from_frames`` - ``preprocessing/texture_map_optimization.py``, which hands a mesh, the scan's colour
+  and depth frames and the camera trajectory to Open3D's colour-map pipeline with ``maximum_iteration=0``: per vertex and frame a
+  visibility test (against the sensor's depth away from depth discontinuities, or ``observe_vertices``' bits), a projection and a
+  bilinear colour sample, averaged in integers (``stin_frames_*``).  ``frame_intrinsics`` is its rescaled camera (:104-107).  A
+  contract of this project's own, NOT pinned against an Open3D run; no optimisation of the poses, no fill of unseen vertices.
+
 All take and return tensors in the reference's own formats.  Out of scope: reading mesh files (neither open3d nor plyfile exists
 here to pin a reader against: vertices, faces and colours are inputs), and the Matterport and S3DIS label paths.
 """
@@ -1228,3 +1234,186 @@ def observers_to_lists(bits, num_poses=None):
     if num_poses is not None:
         flags = flags[:, :int(num_poses)]
     return [np.flatnonzero(row).tolist() for row in flags]
+
+
+# ------------------------------------------------------------------------------------------------------------- frame colours
+def frame_intrinsics(colorintrinsic, orig_width, orig_height, width, height):
+    """The reference's camera for colour frames resized from orig_width x orig_height to width x height
+    (texture_map_optimization.py:104-107) -> (fx, fy, cx, cy) floats: fx * width / orig_width, fy * height / orig_height,
+    width / 2 - 0.5, height / 2 - 0.5; fx, fy = entries [0, 0] and [1, 1] of colorintrinsic (scene_io.load_scan_config's
+    'colorintrinsic', with its 'colorwidth' / 'colorheight' as the original size).  The principal point of the file is NOT used: the
+    reference puts it at the image centre."""
+    import numpy as np
+    ic = colorintrinsic.detach().cpu().numpy() if torch.is_tensor(colorintrinsic) else np.asarray(colorintrinsic)
+    ic = np.asarray(ic, dtype=np.float64)
+    return (float(ic[0, 0]) * width / orig_width, float(ic[1, 1]) * height / orig_height, width / 2.0 - 0.5, height / 2.0 - 0.5)
+
+
+def _camera4(cam, what):
+    c = tuple(float(v) for v in cam)
+    if len(c) != 4:
+        raise ValueError('%s must be (fx, fy, cx, cy)' % what)
+    return c
+
+
+def _frames_u(t, dtype, tail, what):
+    if not (torch.is_tensor(t) and t.is_cuda):
+        raise TypeError('%s must be a CUDA tensor (no CPU fallback exists)' % what)
+    if t.dtype != dtype:
+        raise TypeError('%s must be %s' % (what, dtype))
+    if t.dim() != 3 + len(tail) or tuple(t.shape[3:]) != tail:
+        raise ValueError('%s must be [B, H, W%s]' % (what, ''.join(', %d' % d for d in tail)))
+    return t.contiguous()
+
+
+class FrameColors:
+    """Per-vertex colours of a mesh from a scan's colour and depth frames and its camera trajectory, on the GPU
+    (csrc/stin_frames.hip) - the step the reference's preprocessing/texture_map_optimization.py hands to Open3D's colour-map
+    pipeline with maximum_iteration = 0: nothing is optimised; per vertex and frame a visibility test, a projection, a bilinear
+    sample of the colour image, and the average over the frames that see the vertex.  The result is what becomes
+    vertices[0][:, 3:6] of graphs/<scene>.pt (pass it to graph_levels as mesh['colors']); the count is the honest mask of what the
+    scan never observed.
+
+    vertices [N, >= 3] float CUDA tensor; color_camera, depth_camera = (fx, fy, cx, cy) in pixels of the colour / depth frames
+    (frame_intrinsics; depth_camera None: the colour camera, for colour frames resized to the depth size as the reference does).
+    The object owns sum int64 [N, 3], count int32 [N] and, when num_poses is given, seen uint32 [N, ceil(num_poses / 32)] (bit
+    (p & 31) of word (p >> 5): pose p coloured the vertex) on the vertices' device.
+
+    The contract (include/stin_hip.h, "Frame colours"; restated in numpy by the test suite, which this reproduces bit for bit), fp64:
+    view = E [x y z 1], E the inverse pose; u = fx xv / zv + cx, v = fy yv / zv + cy, pixel (row i, column j) centred at (j, i); a pair
+    with zv < z_near or a non-finite u, v is skipped.  Depth: raw uint16, 0 = no measurement, also where raw / depth_scale >
+    depth_trunc.  A vertex is visible in a frame when the depth pixel nearest to its projection (rint, ties to even) lies in the
+    image, holds a measurement d = raw / depth_scale <= max_depth with |zv - d| < depth_threshold, and is not within half_kernel
+    pixels of a depth discontinuity: a pixel whose 3 x 3 Sobel response on the raw depth exceeds discontinuity_threshold *
+    depth_scale (the threshold is in metres of SOBEL response: a step of s metres gives 4 s to 8 s).  Or, without depth frames, when
+    observe_vertices' bit says so.  The sample: bilinear in the uint8 colour frame, required to lie `margin` pixels inside it,
+    rounded to 1 / 65536 of a grey level and summed as integers - the result does not depend on the order or the batching.
+
+    Not Open3D's result bit for bit and not pinned against a run of it.  Out of scope: reading image files and any resize (frames
+    arrive decoded, as everywhere here), Open3D's rigid / non-rigid optimisation (iterations > 0), its k-nearest-neighbour fill of
+    unseen vertices (they get `fill` and count 0), clipping at the near plane, and a CPU fallback."""
+
+    def __init__(self, vertices, color_camera, depth_camera=None, *, depth_scale=1000.0, depth_trunc=3.0, max_depth=2.5,
+                 depth_threshold=0.03, discontinuity_threshold=0.1, half_kernel=3, margin=10, z_near=0.01, num_poses=None):
+        self.vertices = _xyz64(vertices, 'vertices')
+        self.color_camera = _camera4(color_camera, 'color_camera')
+        self.depth_camera = self.color_camera if depth_camera is None else _camera4(depth_camera, 'depth_camera')
+        self.depth_scale, self.depth_trunc, self.max_depth = float(depth_scale), float(depth_trunc), float(max_depth)
+        self.depth_threshold, self.discontinuity_threshold = float(depth_threshold), float(discontinuity_threshold)
+        self.half_kernel, self.margin, self.z_near = int(half_kernel), int(margin), float(z_near)
+        if not self.z_near > 0.0:
+            raise ValueError('z_near must be positive')
+        if not self.depth_scale > 0.0:
+            raise ValueError('depth_scale must be positive')
+        if self.margin < 0 or not 0 <= self.half_kernel <= _lib.CONSTANTS['STIN_FRAMES_MAX_HALF_KERNEL']:
+            raise ValueError('margin must be >= 0 and half_kernel in [0, %d]' % _lib.CONSTANTS['STIN_FRAMES_MAX_HALF_KERNEL'])
+        n, dev = int(self.vertices.shape[0]), self.vertices.device
+        self.num_poses = None if num_poses is None else int(num_poses)
+        self.sum = torch.zeros(n, 3, dtype=torch.int64, device=dev)
+        self.count = torch.zeros(n, dtype=torch.int32, device=dev)
+        self.seen = None if num_poses is None else torch.zeros(n, (self.num_poses + 31) // 32, dtype=torch.int32,
+                                                               device=dev).view(torch.uint32)
+
+    def depth_edges(self, depth):
+        """depth uint16 [B, Hd, Wd] (CUDA) -> the depth-discontinuity mask uint8 [B, Hd, Wd] of the contract."""
+        d = _frames_u(depth, torch.uint16, (), 'depth')
+        lib = _lib.load()
+        B, H, W = (int(s) for s in d.shape)
+        edge = torch.empty(B, H, W, dtype=torch.uint8, device=d.device)
+        if B == 0 or H == 0 or W == 0:
+            return edge
+        ws_bytes = lib.stin_frames_edges_workspace_bytes(B, H, W)
+        if ws_bytes == 0:
+            raise ValueError('depth frames of %d x %d x %d are outside what the edge kernel supports' % (B, H, W))
+        ws = torch.empty(ws_bytes, dtype=torch.uint8, device=d.device)
+        _lib.check(lib.stin_frames_depth_edges_u16(_ptr(d), B, H, W, self.depth_scale, self.depth_trunc, self.discontinuity_threshold,
+                                                   self.half_kernel, _ptr(edge), _ptr(ws), ws_bytes, _stream(d)),
+                   'stin_frames_depth_edges_u16')
+        return edge
+
+    def add(self, poses, color, depth=None, bits=None, first_pose=0, _route=None):
+        """One batch: poses [B, 4, 4] camera-to-world (array or tensor; inverted on the host), color uint8 [B, Hc, Wc, 3] RGB and
+        either depth uint16 [B, Hd, Wd] or bits (observe_vertices' uint32 [N, words], indexed by first_pose + b) - CUDA tensors.
+        first_pose: the scan-wide id of the batch's first pose (for bits and seen).  Batches arrive in any order and any size.
+        _route (tests): STIN_FRAMES_ROUTE_OWNER / _SPLIT instead of the host's choice from N and B."""
+        if (depth is None) == (bits is None):
+            raise ValueError('exactly one of depth and bits must be given')
+        c = _frames_u(color, torch.uint8, (3,), 'color')
+        RT, valid = pose_extrinsics(poses)
+        B, n, dev, first = int(RT.shape[0]), int(self.vertices.shape[0]), self.vertices.device, int(first_pose)
+        if int(c.shape[0]) != B:
+            raise ValueError('%d poses but %d colour frames' % (B, int(c.shape[0])))
+        if first < 0 or (self.num_poses is not None and first + B > self.num_poses):
+            raise ValueError('poses %d .. %d lie outside [0, num_poses)' % (first, first + B))
+        if B > _lib.CONSTANTS['STIN_FRAMES_MAX_BATCH']:
+            raise ValueError('at most %d poses per batch' % _lib.CONSTANTS['STIN_FRAMES_MAX_BATCH'])
+        lib = _lib.load()
+        d = edge = b = None
+        Hd = Wd = words = 0
+        if depth is not None:
+            d = _frames_u(depth, torch.uint16, (), 'depth')
+            if int(d.shape[0]) != B:
+                raise ValueError('%d poses but %d depth frames' % (B, int(d.shape[0])))
+            Hd, Wd = int(d.shape[1]), int(d.shape[2])
+        else:
+            if not (torch.is_tensor(bits) and bits.is_cuda):
+                raise TypeError('bits must be a CUDA tensor (no CPU fallback exists)')
+            if bits.dtype != torch.uint32 or bits.dim() != 2 or int(bits.shape[0]) != n:
+                raise TypeError('bits must be uint32 [N, words], as observe_vertices returns it')
+            b, words = bits.contiguous(), int(bits.shape[1])
+            if words < (first + B + 31) // 32:
+                raise ValueError('bits has %d words per vertex, poses up to %d need %d' % (words, first + B, (first + B + 31) // 32))
+        if B == 0 or n == 0:
+            return self
+        if 0 in c.shape or (d is not None and 0 in d.shape):
+            raise ValueError('empty frames')
+        if d is not None:
+            edge = self.depth_edges(d)
+        rt_d, valid_d = torch.from_numpy(RT).to(dev), torch.from_numpy(valid).to(dev)
+        cameras = (ctypes.c_double * _lib.CONSTANTS['STIN_FRAMES_CAMERA_DOUBLES'])(*(self.color_camera + self.depth_camera))
+        params = (ctypes.c_double * _lib.CONSTANTS['STIN_FRAMES_PARAM_DOUBLES'])(self.depth_scale, self.depth_trunc, self.max_depth,
+                                                                                 self.depth_threshold, self.z_near)
+        _lib.check(lib.stin_frames_accumulate_f64(_ptr(self.vertices), n, _ptr(rt_d), _ptr(valid_d), B, first, _ptr(c), int(c.shape[1]),
+                                                  int(c.shape[2]), _ptr(d), _ptr(edge), Hd, Wd, cameras, params, _ptr(b), words,
+                                                  self.margin, _lib.CONSTANTS['STIN_FRAMES_ROUTE_AUTO'] if _route is None else int(_route),
+                                                  _ptr(self.sum), _ptr(self.count), _ptr(self.seen),
+                                                  0 if self.seen is None else int(self.seen.shape[1]), _stream(self.vertices)),
+                   'stin_frames_accumulate_f64')
+        return self
+
+    def result(self, fill=(0, 0, 0)):
+        """-> (colors float32 [N, 3] in [0, 1], count int32 [N]): the mean of the samples; `fill` where count is 0."""
+        lib = _lib.load()
+        n = int(self.vertices.shape[0])
+        f = tuple(float(v) for v in fill)
+        if len(f) != 3:
+            raise ValueError('fill must have three entries')
+        colors = torch.empty(n, 3, dtype=torch.float32, device=self.vertices.device)
+        _lib.check(lib.stin_frames_finish_f32(_ptr(self.sum), _ptr(self.count), n, f[0], f[1], f[2], _ptr(colors), None,
+                                              _stream(self.vertices)), 'stin_frames_finish_f32')
+        return colors, self.count
+
+
+def vertex_colors_from_frames(vertices, poses, color, depth=None, bits=None, batch=64, color_camera=None, depth_camera=None,
+                              fill=(0, 0, 0), return_seen=False, _route=None, **params):
+    """FrameColors for frames that are all resident: poses [P, 4, 4], color uint8 [P, Hc, Wc, 3], depth uint16 [P, Hd, Wd] or bits
+    (observe_vertices), added in batches of `batch` poses (the result does not depend on it) -> (colors float32 [N, 3], count int32
+    [N]), with return_seen=True also seen uint32 [N, ceil(P / 32)].  color_camera is required; the other keywords are FrameColors'.
+    Out of scope, as there: image files and resizing, optimisation of the poses, the fill of unseen vertices, near-plane clipping, a
+    CPU fallback."""
+    if color_camera is None:
+        raise ValueError('color_camera = (fx, fy, cx, cy) is required')
+    _frames_u(color, torch.uint8, (3,), 'color')
+    P, step = int(color.shape[0]), int(batch)
+    if step < 1:
+        raise ValueError('batch must be positive')
+    if len(poses) != P:
+        raise ValueError('%d poses but %d colour frames' % (len(poses), P))
+    fc = FrameColors(vertices, color_camera, depth_camera, num_poses=P if return_seen else None, **params)
+    if (depth is None) == (bits is None):
+        raise ValueError('exactly one of depth and bits must be given')
+    for p0 in range(0, P, step):
+        p1 = min(p0 + step, P)
+        fc.add(poses[p0:p1], color[p0:p1], None if depth is None else depth[p0:p1], bits, first_pose=p0, _route=_route)
+    colors, count = fc.result(fill)
+    return (colors, count, fc.seen) if return_seen else (colors, count)
