@@ -4,7 +4,7 @@
 // 64/G rows and every neighbour-row gather is a run of coalesced 16-byte loads.  U neighbour
 // rows are requested before the first is consumed (memory-level parallelism; mean mesh
 // degree is ~6).  Contract: include/stin_hip.h.
-#include <cstdlib>
+#include <type_traits>
 #include "stin_common.h"
 
 thread_local hipEvent_t stin_tl_stop_event = nullptr;   // (stin_common.h)
@@ -49,33 +49,33 @@ __device__ __forceinline__ float4 ld4_stream(const stin_bf16* p) { return ld4(p)
 template <typename T> struct is_f32_type { static constexpr bool value = false; };
 template <> struct is_f32_type<float> { static constexpr bool value = true; };
 
-// Block -> logical block.  Row kernels are launched as a plain 1-D grid (logical = blockIdx.x) or, as an experiment switch
-// (xcd_rows_on below), as an (8, q) grid: workgroups are dealt round-robin to the 8 XCDs in linear order (x fastest), so
-// blockIdx.x is the XCD and the logical block x * q + y gives every XCD one CONTIGUOUS range of rows.  One formula serves
-// both launch shapes.
-__device__ __forceinline__ unsigned vblock_id() { return blockIdx.x * gridDim.y + blockIdx.y; }
-// two-role launches (role 0 first): plain = 2 nb blocks in x; XCD order = (8, 2 q) with the roles split along y
+// Row kernels are launched as a plain 1-D grid: block b owns rows [b * BLOCK / G, (b + 1) * BLOCK / G).  Workgroups are dealt
+// round-robin to the 8 XCDs, so neighbouring row ranges run on different XCDs at the same time.  The other order - an (8, q) grid
+// that gives every XCD one CONTIGUOUS range of rows - was measured in round 3 and removed: no gain on the randomly numbered
+// benchmark meshes (nothing to reuse), and on coherently numbered ones the plain order is the better one (level-0 forward at
+// 200 704 vertices, grid order: 82 us plain vs 96 us chunked; 1 M bf16: 344 vs 353) - with round-robin dealing the 8 XCDs sweep
+// the SAME neighbourhood together and share its lines in the Infinity Cache, chunked they stream eight distant regions at once.
+// two-role launches: 2 nb blocks, role 0 first
 __device__ __forceinline__ unsigned vblock_role(unsigned nb, unsigned& role) {
-    if (gridDim.y == 1) {
-        role = blockIdx.x >= nb ? 1u : 0u;
-        return blockIdx.x - role * nb;
-    }
-    const unsigned q = gridDim.y >> 1;
-    role = blockIdx.y >= q ? 1u : 0u;
-    return blockIdx.x * q + (blockIdx.y - role * q);
+    role = blockIdx.x >= nb ? 1u : 0u;
+    return blockIdx.x - role * nb;
 }
 
-template <int G, int VPL>
+// A lane of the group of G lanes that owns one row; the lane holds chunks of CH channels (4: 16 bytes of fp32 / 8 bytes of bf16
+// rows, 8: 16 bytes of bf16 rows), chunk k of lane lg being channels [(k G + lg) CH, +CH).
+template <int G, int CH>
 struct Lane {
     int lg;        // lane within the group
     int64_t row;   // row owned by the group
-    __device__ __forceinline__ Lane() : Lane(vblock_id()) {}
+    __device__ __forceinline__ Lane() : Lane(blockIdx.x) {}
     __device__ __forceinline__ explicit Lane(unsigned vblock) {          // vblock: the block index the kernel body should see
         lg = threadIdx.x % G;
         row = (int64_t)vblock * (BLOCK / G) + threadIdx.x / G;
     }
-    __device__ __forceinline__ int chan(int k) const { return (k * G + lg) * 4; }
+    __device__ __forceinline__ int chan(int k) const { return (k * G + lg) * CH; }
 };
+template <int G> using Lane4 = Lane<G, 4>;
+template <int G> using Lane8 = Lane<G, 8>;
 
 // ------------------------------------------------------------------ edge stage, forward
 // EXACT: H == 4 * G * VPL (every width the saved-mask path supports): no per-chunk predicates on the gathers
@@ -96,7 +96,7 @@ __device__ __forceinline__ void edge_fwd_body(const T* __restrict__ A, int64_t l
                                               const int32_t* __restrict__ col, int64_t N, int H,
                                               T* __restrict__ out, int64_t ldo, int indicator,
                                               uint32_t* __restrict__ mask, const int32_t* __restrict__ row_map = nullptr) {
-    Lane<G, VPL> L;
+    Lane4<G> L;
     const bool row_ok = L.row < N;
     if (!row_ok) return;
     const int beg = rowptr[L.row], end = rowptr[L.row + 1];
@@ -212,7 +212,7 @@ __global__ __launch_bounds__(BLOCK) void k_edge_bwd_dst(const T* __restrict__ A,
                                                         const int32_t* __restrict__ rowptr,
                                                         const int32_t* __restrict__ col, int64_t N, int H,
                                                         T* __restrict__ dA, int64_t ldda) {
-    Lane<G, VPL> L;
+    Lane4<G> L;
     if (L.row >= N) return;
     const int beg = rowptr[L.row], end = rowptr[L.row + 1];
     float4 a[VPL], cnt[VPL];
@@ -264,7 +264,7 @@ __global__ __launch_bounds__(BLOCK) void k_edge_bwd_src(const T* __restrict__ A,
                                                         const int32_t* __restrict__ rowptr,
                                                         const int32_t* __restrict__ col, int64_t N, int H,
                                                         T* __restrict__ dB, int64_t lddb) {
-    Lane<G, VPL> L;
+    Lane4<G> L;
     if (L.row >= N) return;
     const int beg = rowptr[L.row], end = rowptr[L.row + 1];
     float4 b[VPL], acc[VPL];
@@ -307,43 +307,39 @@ __global__ __launch_bounds__(BLOCK) void k_edge_bwd_src(const T* __restrict__ A,
 }
 
 // ----------------------------- edge stage backward from the saved ReLU bit-mask (no recompute)
-// dA[i,c] = G[i,c]/deg_i * popcount_e mask[e][c] over the in-edge slots e of i: a pure streaming kernel
-// (reads H/8 bytes per edge instead of gathering a B row).
-template <typename T, int G, int VPL, int U>
-__device__ __forceinline__ void edge_bwd_dst_mask_body(unsigned vblock, const T* __restrict__ Gr, int64_t ldg,
-                                                       const uint32_t* __restrict__ mask,
-                                                       const int32_t* __restrict__ rowptr, int64_t N, int H,
-                                                       T* __restrict__ dA, int64_t ldda) {
-    Lane<G, VPL> L(vblock);
-    if (L.row >= N) return;
-    const int beg = rowptr[L.row], end = rowptr[L.row + 1];
-    const int mwords = H >> 5;
-    int cnt[VPL][4];
-    bool on[VPL];
-#pragma unroll
-    for (int k = 0; k < VPL; ++k) {
-        on[k] = true;                                    // the mask path exists for H == 4 * G * VPL only
-        cnt[k][0] = cnt[k][1] = cnt[k][2] = cnt[k][3] = 0;
+// The mask path exists for H == 4 * G * VPL only (G = 32 or 64: full rows), so no chunk is predicated.
+// this lane's 4 mask words (one per component) of slot `m` for chunk k, and the bit to test
+template <int G>
+__device__ __forceinline__ void mask_words4(const uint32_t* __restrict__ m, int k, int lg, uint32_t (&w)[4], int& bit) {
+    const uint32_t* p = m + k * (G / 8);
+    if (G == 32) {                                       // one 32-bit word per component
+        const uint4 q = *reinterpret_cast<const uint4*>(p);         // all lanes of the row: same address
+        w[0] = q.x; w[1] = q.y; w[2] = q.z; w[3] = q.w;
+    } else {                                             // two words per component: the lane's half of the wave picks one
+        const int wsel = lg >> 5;
+        const uint4 q0 = reinterpret_cast<const uint4*>(p)[0], q1 = reinterpret_cast<const uint4*>(p)[1];
+        w[0] = wsel ? q0.y : q0.x; w[1] = wsel ? q0.w : q0.z;
+        w[2] = wsel ? q1.y : q1.x; w[3] = wsel ? q1.w : q1.z;
     }
-    constexpr int WPC = G / 32;                          // 32-bit words per component
-    const int wsel = L.lg >> 5, bit = L.lg & 31;
+    bit = lg & 31;
+}
+
+// The STREAMING half: cnt[k][c] = popcount over the in-edge slots e of the row of mask[e][channel]; returns the degree.
+// dA[i,c] = G[i,c] / deg_i * cnt: reads H/8 bytes per edge instead of gathering a B row.
+template <int G, int VPL, int U>
+__device__ __forceinline__ int edge_bwd_mask_count(const Lane4<G>& L, const uint32_t* __restrict__ mask,
+                                                   const int32_t* __restrict__ rowptr, int mwords, int (&cnt)[VPL][4]) {
+    const int beg = rowptr[L.row], end = rowptr[L.row + 1];
+#pragma unroll
+    for (int k = 0; k < VPL; ++k) cnt[k][0] = cnt[k][1] = cnt[k][2] = cnt[k][3] = 0;
     for (int e = beg; e < end; e += U) {
         uint32_t wv[U][VPL][4];
+        int bit = 0;
 #pragma unroll
         for (int u = 0; u < U; ++u) {
             const int ee = min(e + u, end - 1);
 #pragma unroll
-            for (int k = 0; k < VPL; ++k) {
-                const uint32_t* m = mask + (int64_t)ee * mwords + k * (G / 8);
-                if (WPC == 1) {
-                    const uint4 q = *reinterpret_cast<const uint4*>(m);     // all lanes of the row: same address
-                    wv[u][k][0] = q.x; wv[u][k][1] = q.y; wv[u][k][2] = q.z; wv[u][k][3] = q.w;
-                } else {
-                    const uint4 q0 = reinterpret_cast<const uint4*>(m)[0], q1 = reinterpret_cast<const uint4*>(m)[1];
-                    wv[u][k][0] = wsel ? q0.y : q0.x; wv[u][k][1] = wsel ? q0.w : q0.z;
-                    wv[u][k][2] = wsel ? q1.y : q1.x; wv[u][k][3] = wsel ? q1.w : q1.z;
-                }
-            }
+            for (int k = 0; k < VPL; ++k) mask_words4<G>(mask + (int64_t)ee * mwords, k, L.lg, wv[u][k], bit);
         }
 #pragma unroll
         for (int u = 0; u < U; ++u) {
@@ -356,51 +352,29 @@ __device__ __forceinline__ void edge_bwd_dst_mask_body(unsigned vblock, const T*
             }
         }
     }
-    const int deg = end - beg;
-    const float s = 1.0f / (float)(deg > 0 ? deg : 1);
-#pragma unroll
-    for (int k = 0; k < VPL; ++k)
-        if (on[k]) {
-            const float4 g = ld4(Gr + L.row * ldg + L.chan(k));
-            st4(dA + L.row * ldda + L.chan(k), make_float4(g.x * s * (float)cnt[k][0], g.y * s * (float)cnt[k][1],
-                                                           g.z * s * (float)cnt[k][2], g.w * s * (float)cnt[k][3]));
-        }
+    return end - beg;
 }
-template <typename T, int G, int VPL, int U>
-__global__ __launch_bounds__(BLOCK) void k_edge_bwd_dst_mask(const T* __restrict__ Gr, int64_t ldg,
-                                                             const uint32_t* __restrict__ mask,
-                                                             const int32_t* __restrict__ rowptr, int64_t N, int H,
-                                                             T* __restrict__ dA, int64_t ldda) {
-    edge_bwd_dst_mask_body<T, G, VPL, U>(vblock_id(), Gr, ldg, mask, rowptr, N, H, dA, ldda);
+// dA chunk k of a row from its gradient chunk, s = 1 / max(deg, 1) and its counts: g * s * cnt, left to right
+__device__ __forceinline__ float4 edge_bwd_mask_dA(float4 g, float s, const int (&cnt)[4]) {
+    return make_float4(g.x * s * (float)cnt[0], g.y * s * (float)cnt[1], g.z * s * (float)cnt[2], g.w * s * (float)cnt[3]);
 }
 
-// dB[j,c] = sum over out-edges (j -> i) of inv_deg[i] * G[i,c] * mask[xslot][c]: gathers G rows and 32-bit mask
-// words (xslot = destination-CSR slot of the same edge), half the bytes of the recompute form.
+// The GATHERING half: acc[k] = sum over the out-edges (j -> i) of the row j of w_slot * G[i, chunk] * mask[xslot][chunk] in
+// source-CSR order (w_slot = inv_deg[i]; xslot = destination-CSR slot of the same edge): gathers G rows and 32-bit mask words,
+// half the bytes of the recompute form.
 template <typename T, int G, int VPL, int U>
-__device__ __forceinline__ void edge_bwd_src_mask_body(unsigned vblock, const T* __restrict__ Gr, int64_t ldg,
-                                                       const float* __restrict__ w_slot,
-                                                       const uint32_t* __restrict__ mask,
-                                                       const int32_t* __restrict__ rowptr,
-                                                       const int32_t* __restrict__ col,
-                                                       const int32_t* __restrict__ xslot, int64_t N, int H,
-                                                       T* __restrict__ dB, int64_t lddb) {
-    Lane<G, VPL> L(vblock);
-    if (L.row >= N) return;
+__device__ __forceinline__ void edge_bwd_mask_gather(const Lane4<G>& L, const T* __restrict__ Gr, int64_t ldg,
+                                                     const float* __restrict__ w_slot, const uint32_t* __restrict__ mask,
+                                                     const int32_t* __restrict__ rowptr, const int32_t* __restrict__ col,
+                                                     const int32_t* __restrict__ xslot, int mwords, float4 (&acc)[VPL]) {
     const int beg = rowptr[L.row], end = rowptr[L.row + 1];
-    const int mwords = H >> 5;
-    float4 acc[VPL];
-    bool on[VPL];
 #pragma unroll
-    for (int k = 0; k < VPL; ++k) {
-        on[k] = true;                                    // the mask path exists for H == 4 * G * VPL only
-        acc[k] = f4zero();
-    }
-    constexpr int WPC = G / 32;
-    const int wsel = L.lg >> 5, bit = L.lg & 31;
+    for (int k = 0; k < VPL; ++k) acc[k] = f4zero();
     for (int e = beg; e < end; e += U) {
         float4 g[U][VPL];
         uint32_t wv[U][VPL][4];
         float w[U];
+        int bit = 0;
 #pragma unroll
         for (int u = 0; u < U; ++u) {
             const int ee = min(e + u, end - 1);
@@ -411,15 +385,7 @@ __device__ __forceinline__ void edge_bwd_src_mask_body(unsigned vblock, const T*
 #pragma unroll
             for (int k = 0; k < VPL; ++k) {
                 g[u][k] = ld4(Gr + i * ldg + L.chan(k));
-                const uint32_t* m = mask + xs * mwords + k * (G / 8);
-                if (WPC == 1) {
-                    const uint4 q = *reinterpret_cast<const uint4*>(m);
-                    wv[u][k][0] = q.x; wv[u][k][1] = q.y; wv[u][k][2] = q.z; wv[u][k][3] = q.w;
-                } else {
-                    const uint4 q0 = reinterpret_cast<const uint4*>(m)[0], q1 = reinterpret_cast<const uint4*>(m)[1];
-                    wv[u][k][0] = wsel ? q0.y : q0.x; wv[u][k][1] = wsel ? q0.w : q0.z;
-                    wv[u][k][2] = wsel ? q1.y : q1.x; wv[u][k][3] = wsel ? q1.w : q1.z;
-                }
+                mask_words4<G>(mask + xs * mwords, k, L.lg, wv[u][k], bit);
             }
         }
 #pragma unroll
@@ -433,9 +399,44 @@ __device__ __forceinline__ void edge_bwd_src_mask_body(unsigned vblock, const T*
             }
         }
     }
+}
+
+template <typename T, int G, int VPL, int U>
+__device__ __forceinline__ void edge_bwd_dst_mask_body(unsigned vblock, const T* __restrict__ Gr, int64_t ldg,
+                                                       const uint32_t* __restrict__ mask,
+                                                       const int32_t* __restrict__ rowptr, int64_t N, int H,
+                                                       T* __restrict__ dA, int64_t ldda) {
+    Lane4<G> L(vblock);
+    if (L.row >= N) return;
+    int cnt[VPL][4];
+    const int deg = edge_bwd_mask_count<G, VPL, U>(L, mask, rowptr, H >> 5, cnt);
+    const float s = 1.0f / (float)(deg > 0 ? deg : 1);
 #pragma unroll
     for (int k = 0; k < VPL; ++k)
-        if (on[k]) st4(dB + L.row * lddb + L.chan(k), acc[k]);
+        st4(dA + L.row * ldda + L.chan(k), edge_bwd_mask_dA(ld4(Gr + L.row * ldg + L.chan(k)), s, cnt[k]));
+}
+template <typename T, int G, int VPL, int U>
+__global__ __launch_bounds__(BLOCK) void k_edge_bwd_dst_mask(const T* __restrict__ Gr, int64_t ldg,
+                                                             const uint32_t* __restrict__ mask,
+                                                             const int32_t* __restrict__ rowptr, int64_t N, int H,
+                                                             T* __restrict__ dA, int64_t ldda) {
+    edge_bwd_dst_mask_body<T, G, VPL, U>(blockIdx.x, Gr, ldg, mask, rowptr, N, H, dA, ldda);
+}
+
+template <typename T, int G, int VPL, int U>
+__device__ __forceinline__ void edge_bwd_src_mask_body(unsigned vblock, const T* __restrict__ Gr, int64_t ldg,
+                                                       const float* __restrict__ w_slot,
+                                                       const uint32_t* __restrict__ mask,
+                                                       const int32_t* __restrict__ rowptr,
+                                                       const int32_t* __restrict__ col,
+                                                       const int32_t* __restrict__ xslot, int64_t N, int H,
+                                                       T* __restrict__ dB, int64_t lddb) {
+    Lane4<G> L(vblock);
+    if (L.row >= N) return;
+    float4 acc[VPL];
+    edge_bwd_mask_gather<T, G, VPL, U>(L, Gr, ldg, w_slot, mask, rowptr, col, xslot, H >> 5, acc);
+#pragma unroll
+    for (int k = 0; k < VPL; ++k) st4(dB + L.row * lddb + L.chan(k), acc[k]);
 }
 template <typename T, int G, int VPL, int U>
 __global__ __launch_bounds__(BLOCK) void k_edge_bwd_src_mask(const T* __restrict__ Gr, int64_t ldg,
@@ -445,12 +446,12 @@ __global__ __launch_bounds__(BLOCK) void k_edge_bwd_src_mask(const T* __restrict
                                                              const int32_t* __restrict__ col,
                                                              const int32_t* __restrict__ xslot, int64_t N, int H,
                                                              T* __restrict__ dB, int64_t lddb) {
-    edge_bwd_src_mask_body<T, G, VPL, U>(vblock_id(), Gr, ldg, w_slot, mask, rowptr, col, xslot, N, H, dB, lddb);
+    edge_bwd_src_mask_body<T, G, VPL, U>(blockIdx.x, Gr, ldg, w_slot, mask, rowptr, col, xslot, N, H, dB, lddb);
 }
 
 // Both halves of the mask backward in ONE launch: blocks [0, nb) compute dB rows (the longer, gather-bound half first),
 // blocks [nb, 2 nb) the dA rows - one launch overhead less per block backward, and the streaming half fills the tail of the
-// gather half.  Same arithmetic per row as the two kernels (bit-identical).  (Interleaving the two roles block by block
+// gather half.  The two roles ARE the two kernels' bodies: bit-identical.  (Interleaving the two roles block by block
 // measured 13 % SLOWER than the two launches: it halves the locality of both.)
 template <typename T, int G, int VPL, int UD, int US>
 __global__ __launch_bounds__(BLOCK) void k_edge_bwd_mask_pair(const T* __restrict__ Gr, int64_t ldg,
@@ -471,7 +472,7 @@ __global__ __launch_bounds__(BLOCK) void k_edge_bwd_mask_pair(const T* __restric
         // optional row copy riding on the streaming role (the block backward's dY[:, 2H:] = g of a shortcut block: one
         // 2-D memcpy launch less); Ccp <= H channels, 4 per lane
         if (cp_src != nullptr) {
-            Lane<G, VPL> L(vb);
+            Lane4<G> L(vb);
             if (L.row < N) {
 #pragma unroll
                 for (int k = 0; k < VPL; ++k)
@@ -484,11 +485,16 @@ __global__ __launch_bounds__(BLOCK) void k_edge_bwd_mask_pair(const T* __restric
 
 // ---- translation-invariant blocks in the compact layout (round 6): A_i = b1 - B_i, so dL/dB_i collects BOTH roles of vertex i:
 //   D_i = dB_i - dA_i,   dB_i = sum over out-edges (the gathering half above),  dA_i = G_i / deg_i * popcount of the in-edge masks
-// (the streaming half).  One block computes both halves of its rows - same arithmetic per half as the two bodies above - and writes
+// (the streaming half).  One block computes both halves of its rows and writes
 // ONE row of H channels where the pair kernel wrote two; the first Linear's backward products (dx = D W1, dW1 = D^T x) then run
 // over H columns instead of 2 H.  db1 = sum_i dA_i no longer falls out of the transposed product's ones column (sum_i D_i is ~ 0):
 // every lane adds up dA over the TI_ITER rows it visits (a lane keeps its channels from row to row), the block folds its row slots
 // in a fixed order through LDS and writes colsum[blockIdx][H]; stin_wgrad.hip's finalize adds the block rows in a fixed order.
+// The two halves are WRITTEN OUT here, the same arithmetic per half as edge_bwd_mask_gather / edge_bwd_mask_count (pinned bit for
+// bit by tests/test_row_geometry_gpu.py): calling the two functions instead costs the H = 256 class two registers
+// (k_edge_bwd_mask_ti<float, 64, 1, 4, 2>: 64 -> 66 VGPRs, 8 -> 7 waves per SIMD; hipcc of ROCm 7.2 packs the counts and sums
+// into register pairs there - whether the lane, the arrays and `s` are passed by reference or by value, with or without
+// __restrict__), so this kernel keeps its own copy of the two loops.
 constexpr int TI_ITER = 4;                                 // row groups per block (fixes the number of partial rows: see ti_colsum_rows)
 template <typename T, int G, int VPL, int UD, int US>
 __global__ __launch_bounds__(BLOCK) void k_edge_bwd_mask_ti(const T* __restrict__ Gr, int64_t ldg, const uint32_t* __restrict__ mask,
@@ -500,14 +506,13 @@ __global__ __launch_bounds__(BLOCK) void k_edge_bwd_mask_ti(const T* __restrict_
     constexpr int RPB = BLOCK / G;                          // rows per block and iteration
     __shared__ float4 red[RPB][G * VPL];
     const int mwords = H >> 5;
-    constexpr int WPC = G / 32;
     float4 csum[VPL];
 #pragma unroll
     for (int k = 0; k < VPL; ++k) csum[k] = f4zero();
     for (int it = 0; it < TI_ITER; ++it) {
-        Lane<G, VPL> L(blockIdx.x * TI_ITER + it);
+        Lane4<G> L(blockIdx.x * TI_ITER + it);
         if (L.row >= N) break;                              // (rows ascend with `it`: nothing further for this row slot)
-        const int wsel = L.lg >> 5, bit = L.lg & 31;
+        int bit = 0;
         // ---- gathering half: dB (edge_bwd_src_mask_body)
         float4 acc[VPL];
 #pragma unroll
@@ -528,15 +533,7 @@ __global__ __launch_bounds__(BLOCK) void k_edge_bwd_mask_ti(const T* __restrict_
 #pragma unroll
                     for (int k = 0; k < VPL; ++k) {
                         g[u][k] = ld4(Gr + i * ldg + L.chan(k));
-                        const uint32_t* m = mask + xs * mwords + k * (G / 8);
-                        if (WPC == 1) {
-                            const uint4 q = *reinterpret_cast<const uint4*>(m);
-                            wv[u][k][0] = q.x; wv[u][k][1] = q.y; wv[u][k][2] = q.z; wv[u][k][3] = q.w;
-                        } else {
-                            const uint4 q0 = reinterpret_cast<const uint4*>(m)[0], q1 = reinterpret_cast<const uint4*>(m)[1];
-                            wv[u][k][0] = wsel ? q0.y : q0.x; wv[u][k][1] = wsel ? q0.w : q0.z;
-                            wv[u][k][2] = wsel ? q1.y : q1.x; wv[u][k][3] = wsel ? q1.w : q1.z;
-                        }
+                        mask_words4<G>(mask + xs * mwords, k, L.lg, wv[u][k], bit);
                     }
                 }
 #pragma unroll
@@ -563,15 +560,7 @@ __global__ __launch_bounds__(BLOCK) void k_edge_bwd_mask_ti(const T* __restrict_
                 const int ee = min(e + u, end - 1);
 #pragma unroll
                 for (int k = 0; k < VPL; ++k) {
-                    const uint32_t* m = mask + (int64_t)ee * mwords + k * (G / 8);
-                    if (WPC == 1) {
-                        const uint4 q = *reinterpret_cast<const uint4*>(m);
-                        wv[u][k][0] = q.x; wv[u][k][1] = q.y; wv[u][k][2] = q.z; wv[u][k][3] = q.w;
-                    } else {
-                        const uint4 q0 = reinterpret_cast<const uint4*>(m)[0], q1 = reinterpret_cast<const uint4*>(m)[1];
-                        wv[u][k][0] = wsel ? q0.y : q0.x; wv[u][k][1] = wsel ? q0.w : q0.z;
-                        wv[u][k][2] = wsel ? q1.y : q1.x; wv[u][k][3] = wsel ? q1.w : q1.z;
-                    }
+                    mask_words4<G>(mask + (int64_t)ee * mwords, k, L.lg, wv[u][k], bit);
                 }
             }
 #pragma unroll
@@ -652,19 +641,7 @@ __device__ __forceinline__ void st8_stream(stin_bf16* p, const F8& a) {
     st16_stream(p, make_uint4(pk2(a.v[0], a.v[1]), pk2(a.v[2], a.v[3]), pk2(a.v[4], a.v[5]), pk2(a.v[6], a.v[7])));
 }
 
-template <int G>
-struct Lane8 {
-    int lg;
-    int64_t row;
-    __device__ __forceinline__ Lane8() : Lane8(vblock_id()) {}
-    __device__ __forceinline__ explicit Lane8(unsigned vblock) {
-        lg = threadIdx.x % G;
-        row = (int64_t)vblock * (BLOCK / G) + threadIdx.x / G;
-    }
-    __device__ __forceinline__ int chan(int k) const { return (k * G + lg) * 8; }
-};
-
-// Every launch of the 8-channel kernels is EXACT: H == 8 G VPL (STIN_DISPATCH8 / wide8_ok admit H = 128 .. 2048 only), so no
+// Every launch of the 8-channel kernels is EXACT: H == 8 G VPL (ROW8 / wide8_ok admit H = 128 .. 2048 only), so no
 // lane is idle and no load is predicated.  (Round 4: the per-chunk `chan < H` predicates of the first version put every
 // neighbour-row load behind its own branch; hipcc then issued index load -> wait -> row load -> index load -> wait ..., i.e. ONE
 // row in flight per lane group whatever U said - the kernel ran at 0.60-0.76 of peak where its fp32 twin reaches 0.88.)
@@ -820,7 +797,7 @@ __global__ __launch_bounds__(BLOCK) void k_edge_bwd_dst_mask8(const stin_bf16* _
                                                               const uint32_t* __restrict__ mask,
                                                               const int32_t* __restrict__ rowptr, int64_t N, int H,
                                                               stin_bf16* __restrict__ dA, int64_t ldda) {
-    edge_bwd_dst_mask8_body<G, VPL, U>(vblock_id(), Gr, ldg, mask, rowptr, N, H, dA, ldda);
+    edge_bwd_dst_mask8_body<G, VPL, U>(blockIdx.x, Gr, ldg, mask, rowptr, N, H, dA, ldda);
 }
 
 template <int G, int VPL, int U>
@@ -879,7 +856,7 @@ __global__ __launch_bounds__(BLOCK) void k_edge_bwd_src_mask8(const stin_bf16* _
                                                               const int32_t* __restrict__ col,
                                                               const int32_t* __restrict__ xslot, int64_t N, int H,
                                                               stin_bf16* __restrict__ dB, int64_t lddb) {
-    edge_bwd_src_mask8_body<G, VPL, U>(vblock_id(), Gr, ldg, w_slot, mask, rowptr, col, xslot, N, H, dB, lddb);
+    edge_bwd_src_mask8_body<G, VPL, U>(blockIdx.x, Gr, ldg, w_slot, mask, rowptr, col, xslot, N, H, dB, lddb);
 }
 // dB blocks then dA blocks in one launch, as k_edge_bwd_mask_pair does for fp32 rows
 template <int G, int VPL, int UD, int US>
@@ -913,96 +890,25 @@ __global__ __launch_bounds__(BLOCK) void k_edge_bwd_mask_pair8(const stin_bf16* 
     }
 }
 
-// H in {128, 256, 512, 1024, 2048}: G = H/8 capped at 64, VPL = H / (8 G).
-// U (neighbour rows in flight per lane group), MI355X, after the predicate-free rewrite (round 4, profiles/probes/edge8_sweep.py and
-// _edge8_bwd_sweep.py; regular and Delaunay meshes): forward U = 2 up to H = 1024 (200 704 x 128: 63 us at U = 2, 65 / 68 / 66 at
-// 3 / 4 / 6; the Delaunay mesh 71 / 71 / 73 / 97 - a row whose degree is not a multiple of U re-loads its last neighbour; 1 M
-// vertices would take U = 6: 316 vs 342 us, not worth the irregular-mesh loss), U = 1 at H = 2048 (41 us vs 44 / 59 at 2 / 3);
-// backward gathering role 2 / 2 / 2 / 1 / 1, streaming dA role 6 / 3 / 3 / 2 / 1.
-#define STIN_BWD8_US_16 2
-#define STIN_BWD8_US_32 2
-#define STIN_BWD8_US_64 2
-#define STIN_BWD8_US_64X2 1
-#define STIN_BWD8_US_64X4 1
-#define STIN_FWD8_U_SMALL 2      /* H <= 1024 (one or two 16-byte chunks per lane) */
-#define STIN_FWD8_U_BIG 1        /* H = 2048 (4 chunks per lane) */
-#define STIN_L8(KERNEL_, G_, V_, U_, grid_, ...) hipLaunchKernelGGL((KERNEL_<G_, V_, U_>), rows_grid(grid_), dim3(BLOCK), 0, stream, __VA_ARGS__)
-#define STIN_DISPATCH8(H_, KERNEL, U16_, U32_, U64_, U64X2_, U64X4_, ...)                                            \
-    do {                                                                                                             \
-        if ((H_) == 128) STIN_L8(KERNEL, 16, 1, U16_, grid_rows(N, 16), __VA_ARGS__);                                \
-        else if ((H_) == 256) STIN_L8(KERNEL, 32, 1, U32_, grid_rows(N, 32), __VA_ARGS__);                           \
-        else if ((H_) == 512) STIN_L8(KERNEL, 64, 1, U64_, grid_rows(N, 64), __VA_ARGS__);                           \
-        else if ((H_) == 1024) STIN_L8(KERNEL, 64, 2, U64X2_, grid_rows(N, 64), __VA_ARGS__);                        \
-        else STIN_L8(KERNEL, 64, 4, U64X4_, grid_rows(N, 64), __VA_ARGS__);                                          \
-    } while (0)
-
 // --------------------------------------------------------------- segment sum / mean
-template <typename T, int G, int VPL, int U>
-__global__ __launch_bounds__(BLOCK) void k_segment_sum(const T* __restrict__ src, int64_t lds_,
-                                                       const int32_t* __restrict__ rowptr,
-                                                       const int32_t* __restrict__ col, int64_t N, int C,
-                                                       int mean, T* __restrict__ out, int64_t ldo) {
-    Lane<G, VPL> L;
+// One body, two kernels.  EXACT: the row's chunks divide evenly over the lanes (C / 4 = G * VPL), no per-chunk predicates.
+// NT: non-temporal loads of the gathered fp32 rows.  Summation order per row: sequential over the row's entries, whatever
+// the flags - the two kernels give bit-identical results.
+template <typename T, int G, int VPL, int U, bool EXACT, bool NT>
+__device__ __forceinline__ void segment_sum_body(const T* __restrict__ src, int64_t lds_,
+                                                 const int32_t* __restrict__ rowptr,
+                                                 const int32_t* __restrict__ col, int64_t N, int C,
+                                                 int mean, T* __restrict__ out, int64_t ldo) {
+    Lane4<G> L;
     if (L.row >= N) return;
     const int beg = rowptr[L.row], end = rowptr[L.row + 1];
     float4 acc[VPL];
     bool on[VPL];
 #pragma unroll
     for (int k = 0; k < VPL; ++k) {
-        on[k] = L.chan(k) < C;
+        on[k] = EXACT || L.chan(k) < C;
         acc[k] = f4zero();
     }
-    for (int e = beg; e < end; e += U) {
-        float4 v[U][VPL];
-#pragma unroll
-        for (int u = 0; u < U; ++u) {
-            const int ee = min(e + u, end - 1);
-            const int64_t j = col != nullptr ? (int64_t)col[ee] : (int64_t)ee;
-#pragma unroll
-            for (int k = 0; k < VPL; ++k) v[u][k] = on[k] ? ld4(src + j * lds_ + L.chan(k)) : f4zero();
-        }
-#pragma unroll
-        for (int u = 0; u < U; ++u) {
-            const float w = (e + u < end) ? 1.f : 0.f;
-#pragma unroll
-            for (int k = 0; k < VPL; ++k) {
-                acc[k].x += w * v[u][k].x;
-                acc[k].y += w * v[u][k].y;
-                acc[k].z += w * v[u][k].z;
-                acc[k].w += w * v[u][k].w;
-            }
-        }
-    }
-    float s = 1.f;
-    if (mean) {
-        const int deg = end - beg;
-        s = (float)(deg > 0 ? deg : 1);
-    }
-#pragma unroll
-    for (int k = 0; k < VPL; ++k)
-        if (on[k]) st4(out + L.row * ldo + L.chan(k), make_float4(acc[k].x / s, acc[k].y / s, acc[k].z / s, acc[k].w / s));
-}
-
-// Round 3 form for rows whose chunks divide evenly over the lanes (C / 4 = G * VPL): no per-chunk predicates, and FEWER
-// lanes per row than chunks - each lane owns VPL = 2 chunks 16 G bytes apart, so a wave covers twice the rows and every
-// load instruction touches twice as many independent rows (memory-level parallelism at the same register cost).  Measured on
-// MI355X (profiles/probes/seg_tune.py): the standalone scatter-add (E = 1.2 M random 256-byte rows -> N = 200 k) 90.1 us with
-// G = 16 / U = 4 -> 72.6 us with G = 8 / VPL = 2 / U = 2 -> 68.9 us with non-temporal loads on top (0.50 -> 0.66 of the HBM
-// peak); the unpool backward of the step 28.5 -> 23.3 us (C = 128), 17.6 -> 15.5 us (C = 256).  NT (non-temporal loads of the
-// gathered rows) only pays when the gathered source cannot stay in the 256 MB Infinity Cache anyway: cache-resident sources
-// LOSE 25-40 % with it, so the host sets it by the source's size.  Same summation order per row as k_segment_sum
-// (sequential over the row's entries): bit-identical results.
-template <typename T, int G, int VPL, int U, bool NT>
-__global__ __launch_bounds__(BLOCK) void k_segment_sum_x(const T* __restrict__ src, int64_t lds_,
-                                                         const int32_t* __restrict__ rowptr,
-                                                         const int32_t* __restrict__ col, int64_t N, int C,
-                                                         int mean, T* __restrict__ out, int64_t ldo) {
-    Lane<G, VPL> L;
-    if (L.row >= N) return;
-    const int beg = rowptr[L.row], end = rowptr[L.row + 1];
-    float4 acc[VPL];
-#pragma unroll
-    for (int k = 0; k < VPL; ++k) acc[k] = f4zero();
     for (int e = beg; e < end; e += U) {
         float4 v[U][VPL];
 #pragma unroll
@@ -1019,7 +925,7 @@ __global__ __launch_bounds__(BLOCK) void k_segment_sum_x(const T* __restrict__ s
                     v[u][k].z = __builtin_nontemporal_load(q + 2);
                     v[u][k].w = __builtin_nontemporal_load(q + 3);
                 } else {
-                    v[u][k] = ld4(p);
+                    v[u][k] = on[k] ? ld4(p) : f4zero();
                 }
             }
         }
@@ -1042,7 +948,30 @@ __global__ __launch_bounds__(BLOCK) void k_segment_sum_x(const T* __restrict__ s
     }
 #pragma unroll
     for (int k = 0; k < VPL; ++k)
-        st4(out + L.row * ldo + L.chan(k), make_float4(acc[k].x / s, acc[k].y / s, acc[k].z / s, acc[k].w / s));
+        if (on[k]) st4(out + L.row * ldo + L.chan(k), make_float4(acc[k].x / s, acc[k].y / s, acc[k].z / s, acc[k].w / s));
+}
+template <typename T, int G, int VPL, int U>
+__global__ __launch_bounds__(BLOCK) void k_segment_sum(const T* __restrict__ src, int64_t lds_,
+                                                       const int32_t* __restrict__ rowptr,
+                                                       const int32_t* __restrict__ col, int64_t N, int C,
+                                                       int mean, T* __restrict__ out, int64_t ldo) {
+    segment_sum_body<T, G, VPL, U, false, false>(src, lds_, rowptr, col, N, C, mean, out, ldo);
+}
+
+// Round 3 form for rows whose chunks divide evenly over the lanes: no per-chunk predicates, and FEWER lanes per row than
+// chunks - each lane owns VPL = 2 chunks 16 G bytes apart, so a wave covers twice the rows and every load instruction
+// touches twice as many independent rows (memory-level parallelism at the same register cost).  Measured on
+// MI355X (profiles/probes/seg_tune.py): the standalone scatter-add (E = 1.2 M random 256-byte rows -> N = 200 k) 90.1 us with
+// G = 16 / U = 4 -> 72.6 us with G = 8 / VPL = 2 / U = 2 -> 68.9 us with non-temporal loads on top (0.50 -> 0.66 of the HBM
+// peak); the unpool backward of the step 28.5 -> 23.3 us (C = 128), 17.6 -> 15.5 us (C = 256).  NT (non-temporal loads of the
+// gathered rows) only pays when the gathered source cannot stay in the 256 MB Infinity Cache anyway: cache-resident sources
+// LOSE 25-40 % with it, so the host sets it by the source's size.
+template <typename T, int G, int VPL, int U, bool NT>
+__global__ __launch_bounds__(BLOCK) void k_segment_sum_x(const T* __restrict__ src, int64_t lds_,
+                                                         const int32_t* __restrict__ rowptr,
+                                                         const int32_t* __restrict__ col, int64_t N, int C,
+                                                         int mean, T* __restrict__ out, int64_t ldo) {
+    segment_sum_body<T, G, VPL, U, true, NT>(src, lds_, rowptr, col, N, C, mean, out, ldo);
 }
 
 // Segment MEAN over a CSR (out[i] = mean of src[col[e]] over the slots e of row i; 0 for an empty row) AND the first stage of the
@@ -1112,7 +1041,7 @@ __global__ __launch_bounds__(BLOCK) void k_pool_max_fwd(const T* __restrict__ x,
                                                         const int32_t* __restrict__ col, int64_t N, int C,
                                                         T* __restrict__ out, int64_t ldo,
                                                         int32_t* __restrict__ arg) {
-    Lane<G, VPL> L;
+    Lane4<G> L;
     if (L.row >= N) return;
     const int beg = rowptr[L.row], end = rowptr[L.row + 1];
     float4 best[VPL];
@@ -1161,7 +1090,7 @@ __global__ __launch_bounds__(BLOCK) void k_pool_max_bwd(const T* __restrict__ g,
                                                         const int32_t* __restrict__ arg,
                                                         const int32_t* __restrict__ trace, int64_t N, int C,
                                                         T* __restrict__ gx, int64_t ldgx) {
-    Lane<G, VPL> L;
+    Lane4<G> L;
     if (L.row >= N) return;
     const int64_t t = trace[L.row];
     const int v = (int)L.row;
@@ -1180,7 +1109,7 @@ __global__ __launch_bounds__(BLOCK) void k_gather_rows(const T* __restrict__ src
                                                        const int32_t* __restrict__ idx,
                                                        const float* __restrict__ row_scale, int64_t N, int C,
                                                        T* __restrict__ out, int64_t ldo) {
-    Lane<G, VPL> L;
+    Lane4<G> L;
     if (L.row >= N) return;
     const int64_t t = idx[L.row];
     const float s = row_scale != nullptr ? row_scale[t] : 1.f;
@@ -1197,7 +1126,7 @@ template <typename T, int G, int VPL>
 __global__ __launch_bounds__(BLOCK) void k_gather_add_rows(const T* __restrict__ a, int64_t lda, const int32_t* __restrict__ ia,
                                                            const T* __restrict__ b, int64_t ldb, const int32_t* __restrict__ ib,
                                                            int64_t N, int C, T* __restrict__ out, int64_t ldo) {
-    Lane<G, VPL> L;
+    Lane4<G> L;
     if (L.row >= N) return;
     const int64_t ta = ia[L.row], tb = ib[L.row];
 #pragma unroll
@@ -1428,15 +1357,6 @@ inline bool vec_ok(int C, std::initializer_list<const void*> ptrs, std::initiali
 // full rows of 32 or 64 lanes (every lane live), so a slot is exactly H bits of ballot words
 inline bool mask_shape_ok(int H) { return H == 128 || H == 256 || H == 512 || H == 1024 || H == 2048; }
 
-inline unsigned grid_rows(int64_t N, int G) { return (unsigned)((N + (BLOCK / G) - 1) / (BLOCK / G)); }
-// Launch shape of a row kernel (see vblock_id): plain 1-D order by default; STIN_XCD_ROWS=1 (re-read per call) selects (8, q) =
-// one contiguous row range per XCD.  Measured in round 3 and left OFF: no gain on the randomly numbered benchmark meshes
-// (nothing to reuse), and on coherently numbered ones the plain order is the better one (level-0 forward at 200 704 vertices,
-// grid order: 82 us plain vs 96 us chunked; 1 M bf16: 344 vs 353) - with round-robin dealing the 8 XCDs sweep the SAME
-// neighbourhood together and share its lines in the Infinity Cache, chunked they stream eight distant regions at once.
-inline bool xcd_rows_on(unsigned) { return false; }   // (the (8, q) launch shape measured no gain - comment above - and stays off)
-inline dim3 rows_grid(unsigned nwg) { return xcd_rows_on(nwg) ? dim3(8, (nwg + 7) / 8) : dim3(nwg); }
-inline dim3 pair_grid(unsigned nb) { return xcd_rows_on(nb) ? dim3(8, 2 * ((nb + 7) / 8)) : dim3(2 * nb); }
 inline unsigned grid_elems(int64_t n) { return (unsigned)((n + BLOCK - 1) / BLOCK); }
 
 inline bool wide8_ok(int H, std::initializer_list<const void*> ptrs, std::initializer_list<int64_t> lds) {
@@ -1448,47 +1368,87 @@ inline bool wide8_ok(int H, std::initializer_list<const void*> ptrs, std::initia
     return true;
 }
 
+// =================================================================== launch geometry: the single home of (G, VPL, U)
+// A row of C channels goes to G lanes with VPL chunks per lane, and U neighbour rows are requested per loop trip.  Every
+// launch, grid size and workspace query below reads these tables; no kernel is instantiated for a class its dispatcher
+// cannot reach.
+struct Row4 { int G, VPL, U; };
+// 4-channel classes (C % 4 == 0, C <= 2048): G = stin_group_lanes(C / 4), VPL = ceil(C / 4 / G).  U tuned on MI355X at mean
+// degree ~6 (level-0/1/2 edge kernels and the standalone scatter-add, U in {8, 6, 4}): rows of <= 256 B: 4; 512-B rows
+// (G = 32): 6 - one trip for a typical mesh vertex; 1-KB rows (G = 64): 4; then 2, 2, 1 as a lane holds 2, 4, 8 chunks.
+constexpr Row4 ROW4[10] = {{1, 1, 4},  {2, 1, 4},  {4, 1, 4},  {8, 1, 4},  {16, 1, 4},
+                           {32, 1, 6}, {64, 1, 4}, {64, 2, 2}, {64, 4, 2}, {64, 8, 1}};
+constexpr int ROW4_MASK0 = 5;               // ROW4[5 .. 9]: the saved-mask widths H = 128 .. 2048 (full rows of 32 or 64 lanes)
+// kernels that gather TWO rows per neighbour (k_edge_bwd_src: A and G; k_edge_bwd_src_mask: G and the mask words) halve U
+constexpr int halved(int u) { return u / 2 > 0 ? u / 2 : 1; }
+// the one-launch mask backward (k_edge_bwd_mask_pair, k_edge_bwd_mask_ti) at the saved-mask classes: rows in flight of the
+// streaming role (UD = U) and of the gathering role (US = halved(U)) - except H = 512, which keeps TWO rows in flight in the
+// gathering role (18 063 x 512: 56.8 us at 1, 54.0 at 2, 56.1 / 58.8 at 3 / 4)
+struct PairU { int UD, US; };
+constexpr PairU PAIR4[5] = {{6, 3}, {4, 2}, {2, 2}, {2, 1}, {1, 1}};
+static_assert(PAIR4[0].US == halved(ROW4[5].U) && PAIR4[1].US == halved(ROW4[6].U) && PAIR4[2].US != halved(ROW4[7].U) &&
+                  PAIR4[3].US == halved(ROW4[8].U) && PAIR4[4].US == halved(ROW4[9].U),
+              "the gathering role halves U everywhere but at H = 512");
 
-// Dispatch on (G, VPL) for a channel count C (C % 4 == 0, C <= 2048).  U = neighbour rows requested per loop trip,
-// tuned on MI355X at mean degree ~6 (level-0/1/2 edge kernels and the standalone scatter-add, U in {8, 6, 4}):
-// rows of <= 256 B: 4; 512-B rows (G = 32): 6 - one trip for a typical mesh vertex; 1-KB rows (G = 64): 4; then 2, 2, 1
-// as a lane holds 2, 4, 8 chunks.  DIV halves it for kernels that gather two rows per neighbour.
-#define STIN_U(base, DIV) (((base) / (DIV)) > 0 ? ((base) / (DIV)) : 1)
-#define STIN_DISPATCH(C_, KERNEL, DIV, ...)                                                                  \
-    do {                                                                                                     \
-        const int c4_ = (C_) / 4;                                                                            \
-        const int g_ = stin_group_lanes(c4_);                                                                \
-        const int vpl_ = (c4_ + g_ - 1) / g_;                                                                \
-        const unsigned grid_ = grid_rows(N, g_);                                                             \
-        if (g_ == 1) hipLaunchKernelGGL((KERNEL<T, 1, 1, STIN_U(4, DIV)>), rows_grid(grid_), dim3(BLOCK), 0, stream, __VA_ARGS__);        \
-        else if (g_ == 2) hipLaunchKernelGGL((KERNEL<T, 2, 1, STIN_U(4, DIV)>), rows_grid(grid_), dim3(BLOCK), 0, stream, __VA_ARGS__);   \
-        else if (g_ == 4) hipLaunchKernelGGL((KERNEL<T, 4, 1, STIN_U(4, DIV)>), rows_grid(grid_), dim3(BLOCK), 0, stream, __VA_ARGS__);   \
-        else if (g_ == 8) hipLaunchKernelGGL((KERNEL<T, 8, 1, STIN_U(4, DIV)>), rows_grid(grid_), dim3(BLOCK), 0, stream, __VA_ARGS__);   \
-        else if (g_ == 16) hipLaunchKernelGGL((KERNEL<T, 16, 1, STIN_U(4, DIV)>), rows_grid(grid_), dim3(BLOCK), 0, stream, __VA_ARGS__); \
-        else if (g_ == 32) hipLaunchKernelGGL((KERNEL<T, 32, 1, STIN_U(6, DIV)>), rows_grid(grid_), dim3(BLOCK), 0, stream, __VA_ARGS__); \
-        else if (vpl_ == 1) hipLaunchKernelGGL((KERNEL<T, 64, 1, STIN_U(4, DIV)>), rows_grid(grid_), dim3(BLOCK), 0, stream, __VA_ARGS__); \
-        else if (vpl_ == 2) hipLaunchKernelGGL((KERNEL<T, 64, 2, STIN_U(2, DIV)>), rows_grid(grid_), dim3(BLOCK), 0, stream, __VA_ARGS__); \
-        else if (vpl_ <= 4) hipLaunchKernelGGL((KERNEL<T, 64, 4, STIN_U(2, DIV)>), rows_grid(grid_), dim3(BLOCK), 0, stream, __VA_ARGS__); \
-        else hipLaunchKernelGGL((KERNEL<T, 64, 8, 1>), rows_grid(grid_), dim3(BLOCK), 0, stream, __VA_ARGS__);       \
-    } while (0)
+// 8-channel bf16 classes, H = 128 .. 2048: G = H / 8 capped at 64, VPL = H / (8 G).  MI355X, after the predicate-free rewrite
+// (round 4; regular and Delaunay meshes): forward UF = 2 up to H = 1024 (200 704 x 128: 63 us at U = 2, 65 / 68 / 66 at
+// 3 / 4 / 6; the Delaunay mesh 71 / 71 / 73 / 97 - a row whose degree is not a multiple of U re-loads its last neighbour; 1 M
+// vertices would take U = 6: 316 vs 342 us, not worth the irregular-mesh loss), 1 at H = 2048 (41 us vs 44 / 59 at 2 / 3).
+// Round 6 (profiles/r06_edge8_u_sweep.log, random graph of mean degree 6): 1 M x 128 reads 549 / 407 / 416 / 393 / 439 us at
+// U = 1 / 2 / 3 / 4 / 6, 200 704 x 128 82 / 76 / 73 / 76 / 98; on config 5's 6-regular mesh U = 4 measured 383.0 us against
+// 383.7 at U = 2 - nothing: the rate of 256-byte random rows, not the rows in flight, bounds this kernel - U stays 2.
+// UD: streaming dA role (k_edge_bwd_dst_mask8 and the pair's role 1); US: gathering role of the pair; USS: the standalone
+// gathering kernel k_edge_bwd_src_mask8.
+struct Row8 { int G, VPL, UF, UD, US, USS; };
+constexpr Row8 ROW8[5] = {{16, 1, 2, 6, 2, 2}, {32, 1, 2, 3, 2, 2}, {64, 1, 2, 3, 2, 2}, {64, 2, 2, 2, 1, 1}, {64, 4, 1, 1, 1, 1}};
 
-#define STIN_DISPATCH_NOU(C_, KERNEL, ...)                                                                   \
-    do {                                                                                                     \
-        const int c4_ = (C_) / 4;                                                                            \
-        const int g_ = stin_group_lanes(c4_);                                                                \
-        const int vpl_ = (c4_ + g_ - 1) / g_;                                                                \
-        const unsigned grid_ = grid_rows(N, g_);                                                             \
-        if (g_ == 1) hipLaunchKernelGGL((KERNEL<T, 1, 1>), rows_grid(grid_), dim3(BLOCK), 0, stream, __VA_ARGS__);   \
-        else if (g_ == 2) hipLaunchKernelGGL((KERNEL<T, 2, 1>), rows_grid(grid_), dim3(BLOCK), 0, stream, __VA_ARGS__);   \
-        else if (g_ == 4) hipLaunchKernelGGL((KERNEL<T, 4, 1>), rows_grid(grid_), dim3(BLOCK), 0, stream, __VA_ARGS__);   \
-        else if (g_ == 8) hipLaunchKernelGGL((KERNEL<T, 8, 1>), rows_grid(grid_), dim3(BLOCK), 0, stream, __VA_ARGS__);   \
-        else if (g_ == 16) hipLaunchKernelGGL((KERNEL<T, 16, 1>), rows_grid(grid_), dim3(BLOCK), 0, stream, __VA_ARGS__); \
-        else if (g_ == 32) hipLaunchKernelGGL((KERNEL<T, 32, 1>), rows_grid(grid_), dim3(BLOCK), 0, stream, __VA_ARGS__); \
-        else if (vpl_ == 1) hipLaunchKernelGGL((KERNEL<T, 64, 1>), rows_grid(grid_), dim3(BLOCK), 0, stream, __VA_ARGS__); \
-        else if (vpl_ == 2) hipLaunchKernelGGL((KERNEL<T, 64, 2>), rows_grid(grid_), dim3(BLOCK), 0, stream, __VA_ARGS__); \
-        else if (vpl_ <= 4) hipLaunchKernelGGL((KERNEL<T, 64, 4>), rows_grid(grid_), dim3(BLOCK), 0, stream, __VA_ARGS__); \
-        else hipLaunchKernelGGL((KERNEL<T, 64, 8>), rows_grid(grid_), dim3(BLOCK), 0, stream, __VA_ARGS__);          \
-    } while (0)
+// k_segment_sum_x classes, C / 4 = 4 .. 512 a power of two: an even split of the row over G = C / 8 lanes with VPL = 2 chunks
+// each (U = 2), wider rows on a full wave (see the kernel comment)
+constexpr Row4 SEGX[8] = {{2, 2, 2}, {4, 2, 2}, {8, 2, 2}, {16, 2, 2}, {32, 2, 2}, {64, 2, 2}, {64, 4, 2}, {64, 8, 1}};
+
+inline int row4_class(int C) {                         // C % 4 == 0, C <= 2048 (vec_ok)
+    const int c4 = C / 4, g = stin_group_lanes(c4), vpl = (c4 + g - 1) / g;
+    int i = 0;
+    while ((1 << i) < g) ++i;                          // G = 1 .. 64 -> 0 .. 6
+    return g < STIN_WAVE ? i : vpl == 1 ? 6 : vpl == 2 ? 7 : vpl <= 4 ? 8 : 9;
+}
+inline int mask_class(int H) { return H == 128 ? 0 : H == 256 ? 1 : H == 512 ? 2 : H == 1024 ? 3 : 4; }     // mask_shape_ok(H)
+inline int segx_class(int c4) {                        // c4 = 4 .. 512, a power of two
+    int i = 0;
+    while ((4 << i) < c4) ++i;
+    return i;
+}
+inline unsigned grid_rows(int64_t N, int G) { return (unsigned)((N + (BLOCK / G) - 1) / (BLOCK / G)); }
+
+// f(std::integral_constant<int, i>) for the run-time index i in [LO, HI]: the class of a launch as a compile-time constant
+template <int LO, int HI, typename F>
+inline void with_class(int i, F&& f) {
+    if constexpr (LO < HI) {
+        if (i == LO) f(std::integral_constant<int, LO>{});
+        else with_class<LO + 1, HI>(i, f);
+    } else {
+        f(std::integral_constant<int, HI>{});
+    }
+}
+// BLOCK threads per block, no dynamic LDS; `stop`: the launch may carry the caller's completion event (stin_tl_stop_event)
+template <typename... P, typename... A>
+inline void launch(void (*kernel)(P...), unsigned nblocks, hipStream_t stream, A... args) {
+    hipLaunchKernelGGL(kernel, dim3(nblocks), dim3(BLOCK), 0, stream, static_cast<P>(args)...);
+}
+template <typename... P, typename... A>
+inline void launch_stop(void (*kernel)(P...), unsigned nblocks, hipStream_t stream, A... args) {
+    STIN_LAUNCH_STOP(kernel, dim3(nblocks), dim3(BLOCK), stream, static_cast<P>(args)...);
+}
+
+// the optional row copy riding on the one-launch mask backward: one lane chunk (4 fp32 / 8 bf16 channels = 16 bytes) per access
+template <typename T>
+inline int row_copy_check(const T* cp_src, int64_t ld_cps, const T* cp_dst, int64_t ld_cpd, int Ccp, int H) {
+    constexpr int CH = is_f32_type<T>::value ? 4 : 8;
+    if (cp_src == nullptr) return STIN_OK;
+    STIN_REQUIRE(cp_dst != nullptr && Ccp > 0 && Ccp <= H && Ccp % CH == 0 && ld_cps >= Ccp && ld_cpd >= Ccp, STIN_E_SIZE);
+    STIN_REQUIRE(stin_aligned16(cp_src) && stin_aligned16(cp_dst) && ld_cps % CH == 0 && ld_cpd % CH == 0, STIN_E_ALIGN);
+    return STIN_OK;
+}
 
 constexpr bool is_f32(const float*) { return true; }
 constexpr bool is_f32(const stin_bf16*) { return false; }
@@ -1511,31 +1471,25 @@ int edge_fwd_impl(const T* A, int64_t lda, const T* B, int64_t ldb, const int32_
         const bool wide = wide8_ok(H, {A, B, out}, {lda, ldb, ldo});
         STIN_REQUIRE(mask == nullptr || wide, STIN_E_ALIGN);
         if (wide) {
-            // rows in flight per lane group: tuning aid STIN_EDGE8_U = "u16,u32,u64,u64x2,u64x4" digits, e.g. 44422 (re-read per call)
-            const char* eu = getenv("STIN_EDGE8_U");
-            const int cfg = eu ? atoi(eu) : 0;
-            auto pick = [&](int pos, int dflt) { int d = cfg; for (int i = 0; i < 4 - pos; ++i) d /= 10; d %= 10; return (cfg > 0 && d > 0) ? d : dflt; };
-            const int hsel = H == 128 ? 0 : H == 256 ? 1 : H == 512 ? 2 : H == 1024 ? 3 : 4;
-            // (round 6, profiles/probes/edge8_u_sweep.py, random graph of mean degree 6: 1 M x 128 reads 549 / 407 / 416 / 393 / 439 us at
-            // U = 1 / 2 / 3 / 4 / 6, 200 704 x 128 82 / 76 / 73 / 76 / 98; on config 5's 6-regular mesh U = 4 measured 383.0 us against
-            // 383.7 at U = 2 - nothing: the rate of 256-byte random rows, not the rows in flight, bounds this kernel - U stays 2)
-            const int u = pick(hsel, hsel <= 3 ? STIN_FWD8_U_SMALL : STIN_FWD8_U_BIG);
-#define STIN_FWD8(U_) STIN_DISPATCH8(H, k_edge_fwd8, U_, U_, U_, U_, U_, A, lda, B, ldb, rowptr, col, N, H, out, ldo, indicator, mask)
-            if (u == 1) STIN_FWD8(1);
-            else if (u == 2) STIN_FWD8(2);
-            else if (u == 3) STIN_FWD8(3);
-            else if (u == 4) STIN_FWD8(4);
-            else STIN_FWD8(6);
-#undef STIN_FWD8
+            with_class<0, 4>(mask_class(H), [&](auto i) {
+                constexpr Row8 c = ROW8[decltype(i)::value];
+                launch(k_edge_fwd8<c.G, c.VPL, c.UF>, grid_rows(N, c.G), stream, A, lda, B, ldb, rowptr, col, N, H, out, ldo, indicator, mask);
+            });
             return stin_launch_status();
         }
     }
     // (round 6) mask == NULL at a mask shape - the forward of a no-grad / evaluation pass - runs the SAME kernel without the mask
     // stores (edge_fwd_body tests the pointer): same gathers, same summation order, bit-identical rows, E * H / 8 bytes less written
-    if (vec && (mask != nullptr || mask_shape_ok(H))) {   // mask shapes are exact multiples of the lane geometry
-        STIN_DISPATCH(H, k_edge_fwd_exact, 1, A, lda, B, ldb, rowptr, col, N, H, out, ldo, indicator, mask);
+    if (vec && mask_shape_ok(H)) {                        // mask shapes are exact multiples of the lane geometry
+        with_class<ROW4_MASK0, 9>(row4_class(H), [&](auto i) {
+            constexpr Row4 c = ROW4[decltype(i)::value];
+            launch(k_edge_fwd_exact<T, c.G, c.VPL, c.U>, grid_rows(N, c.G), stream, A, lda, B, ldb, rowptr, col, N, H, out, ldo, indicator, mask);
+        });
     } else if (vec) {
-        STIN_DISPATCH(H, k_edge_fwd, 1, A, lda, B, ldb, rowptr, col, N, H, out, ldo, indicator, mask);
+        with_class<0, 9>(row4_class(H), [&](auto i) {
+            constexpr Row4 c = ROW4[decltype(i)::value];
+            launch(k_edge_fwd<T, c.G, c.VPL, c.U>, grid_rows(N, c.G), stream, A, lda, B, ldb, rowptr, col, N, H, out, ldo, indicator, mask);
+        });
     } else if constexpr (is_f32((const T*)nullptr)) {
         hipLaunchKernelGGL((k_scalar<OP_EDGE_FWD>), dim3(grid_elems(N * H)), dim3(BLOCK), 0, stream, A, lda, B, ldb,
                            (const float*)nullptr, (int64_t)0, (const float*)nullptr, rowptr, col, N, H, indicator, out, ldo,
@@ -1555,7 +1509,10 @@ int edge_fwd_map_impl(const float* A, int64_t lda, const float* B, int64_t ldb, 
     STIN_REQUIRE(mask_shape_ok(H) && vec_ok<T>(H, {A, B, out}, {lda, ldb, ldo}), STIN_E_UNSUPPORTED);
     if (N == 0) return STIN_OK;
     STIN_REQUIRE(A && B && rowptr && row_map && out, STIN_E_NULL);
-    STIN_DISPATCH(H, k_edge_fwd_map, 1, A, lda, B, ldb, rowptr, col, row_map, N, H, out, ldo, indicator, mask);
+    with_class<ROW4_MASK0, 9>(row4_class(H), [&](auto i) {
+        constexpr Row4 c = ROW4[decltype(i)::value];
+        launch(k_edge_fwd_map<T, c.G, c.VPL, c.U>, grid_rows(N, c.G), stream, A, lda, B, ldb, rowptr, col, row_map, N, H, out, ldo, indicator, mask);
+    });
     return stin_launch_status();
 }
 
@@ -1568,10 +1525,16 @@ int edge_bwd_dst_mask_impl(const T* G, int64_t ldg, const uint32_t* mask, const 
     STIN_REQUIRE(mask_shape_ok(H) && vec_ok<T>(H, {G, dA}, {ldg, ldda}), STIN_E_UNSUPPORTED);
     if constexpr (!is_f32((const T*)nullptr)) {
         STIN_REQUIRE(wide8_ok(H, {G, dA}, {ldg, ldda}), STIN_E_ALIGN);       // the geometry the forward kernel wrote the mask in
-        STIN_DISPATCH8(H, k_edge_bwd_dst_mask8, 6, 3, 3, 2, 1, G, ldg, mask, rowptr, N, H, dA, ldda);
-        return stin_launch_status();
+        with_class<0, 4>(mask_class(H), [&](auto i) {
+            constexpr Row8 c = ROW8[decltype(i)::value];
+            launch(k_edge_bwd_dst_mask8<c.G, c.VPL, c.UD>, grid_rows(N, c.G), stream, G, ldg, mask, rowptr, N, H, dA, ldda);
+        });
+    } else {
+        with_class<ROW4_MASK0, 9>(row4_class(H), [&](auto i) {
+            constexpr Row4 c = ROW4[decltype(i)::value];
+            launch(k_edge_bwd_dst_mask<T, c.G, c.VPL, c.U>, grid_rows(N, c.G), stream, G, ldg, mask, rowptr, N, H, dA, ldda);
+        });
     }
-    STIN_DISPATCH(H, k_edge_bwd_dst_mask, 1, G, ldg, mask, rowptr, N, H, dA, ldda);
     return stin_launch_status();
 }
 
@@ -1585,48 +1548,43 @@ int edge_bwd_src_mask_impl(const T* G, int64_t ldg, const float* w_src, const ui
     STIN_REQUIRE(mask_shape_ok(H) && vec_ok<T>(H, {G, dB}, {ldg, lddb}), STIN_E_UNSUPPORTED);
     if constexpr (!is_f32((const T*)nullptr)) {
         STIN_REQUIRE(wide8_ok(H, {G, dB}, {ldg, lddb}), STIN_E_ALIGN);
-        STIN_DISPATCH8(H, k_edge_bwd_src_mask8, 2, 2, 2, 1, 1, G, ldg, w_src, mask, rowptr_src, col_src, xslot, N, H, dB, lddb);
-        return stin_launch_status();
+        with_class<0, 4>(mask_class(H), [&](auto i) {
+            constexpr Row8 c = ROW8[decltype(i)::value];
+            launch(k_edge_bwd_src_mask8<c.G, c.VPL, c.USS>, grid_rows(N, c.G), stream, G, ldg, w_src, mask, rowptr_src, col_src, xslot, N, H, dB, lddb);
+        });
+    } else {
+        with_class<ROW4_MASK0, 9>(row4_class(H), [&](auto i) {
+            constexpr Row4 c = ROW4[decltype(i)::value];
+            launch(k_edge_bwd_src_mask<T, c.G, c.VPL, halved(c.U)>, grid_rows(N, c.G), stream, G, ldg, w_src, mask, rowptr_src, col_src, xslot, N, H, dB, lddb);
+        });
     }
-    STIN_DISPATCH(H, k_edge_bwd_src_mask, 2, G, ldg, w_src, mask, rowptr_src, col_src, xslot, N, H, dB, lddb);
     return stin_launch_status();
 }
 
-// fp32 rows only (the block backward's path); unroll factors per (G, VPL) are STIN_DISPATCH's with DIV 1 (dA) and 2 (dB)
+// fp32 rows only (the block backward's path); rows in flight per role: PAIR4
 int edge_bwd_mask_pair_impl(const float* G, int64_t ldg, const uint32_t* mask, const int32_t* rowptr_dst, const float* w_src,
                             const int32_t* rowptr_src, const int32_t* col_src, const int32_t* xslot, int64_t N, int H,
                             float* dA, int64_t ldda, float* dB, int64_t lddb, const float* cp_src, int64_t ld_cps, float* cp_dst,
                             int64_t ld_cpd, int Ccp, hipStream_t stream) {
     using T = float;
     STIN_REQUIRE(N >= 0 && H > 0 && ldg >= H && ldda >= H && lddb >= H, STIN_E_SIZE);
-    if (cp_src != nullptr) {
-        STIN_REQUIRE(cp_dst != nullptr && Ccp > 0 && Ccp <= H && Ccp % 4 == 0 && ld_cps >= Ccp && ld_cpd >= Ccp, STIN_E_SIZE);
-        STIN_REQUIRE(stin_aligned16(cp_src) && stin_aligned16(cp_dst) && ld_cps % 4 == 0 && ld_cpd % 4 == 0, STIN_E_ALIGN);
-    }
+    if (const int e = row_copy_check(cp_src, ld_cps, cp_dst, ld_cpd, Ccp, H)) return e;
     if (N == 0) return STIN_OK;
     STIN_REQUIRE(G && mask && rowptr_dst && w_src && rowptr_src && col_src && xslot && dA && dB, STIN_E_NULL);
     STIN_REQUIRE(mask_shape_ok(H) && vec_ok<T>(H, {G, dA, dB}, {ldg, ldda, lddb}), STIN_E_UNSUPPORTED);
-    const int c4 = H / 4, g = stin_group_lanes(c4), vpl = (c4 + g - 1) / g;
-    const unsigned nb = grid_rows(N, g);
-#define STIN_PAIR(G_, VPL_, BASE_)                                                                                       \
-    STIN_LAUNCH_STOP((k_edge_bwd_mask_pair<T, G_, VPL_, STIN_U(BASE_, 1), STIN_U(BASE_, 2)>), pair_grid(nb), dim3(BLOCK),      \
-                     stream, G, ldg, mask, rowptr_dst, w_src, rowptr_src, col_src, xslot, N, H, dA, ldda, dB, lddb, nb, cp_src,       \
-                     ld_cps, cp_dst, ld_cpd, Ccp)
-    if (g == 32) STIN_PAIR(32, 1, 6);                 // H = 128
-    else if (vpl == 1) STIN_PAIR(64, 1, 4);           // 256
-    else if (vpl == 2) {                              // 512: two rows in flight in the gathering role (18 063 x 512: 56.8 us at 1, 54.0 at 2, 56.1 / 58.8 at 3 / 4)
-        STIN_LAUNCH_STOP((k_edge_bwd_mask_pair<T, 64, 2, 2, 2>), pair_grid(nb), dim3(BLOCK), stream, G, ldg, mask, rowptr_dst, w_src, rowptr_src, col_src, xslot, N, H, dA, ldda, dB, lddb, nb, cp_src, ld_cps, cp_dst, ld_cpd, Ccp);
-    }
-    else if (vpl <= 4) STIN_PAIR(64, 4, 2);           // 1024
-    else STIN_PAIR(64, 8, 1);                         // 2048
-#undef STIN_PAIR
+    with_class<0, 4>(mask_class(H), [&](auto i) {
+        constexpr Row4 c = ROW4[ROW4_MASK0 + decltype(i)::value];
+        constexpr PairU u = PAIR4[decltype(i)::value];
+        const unsigned nb = grid_rows(N, c.G);
+        launch_stop(k_edge_bwd_mask_pair<T, c.G, c.VPL, u.UD, u.US>, 2 * nb, stream, G, ldg, mask, rowptr_dst, w_src, rowptr_src, col_src,
+                    xslot, N, H, dA, ldda, dB, lddb, nb, cp_src, ld_cps, cp_dst, ld_cpd, Ccp);
+    });
     return stin_launch_status();
 }
 
 // translation-invariant compact layout, fp32 rows (see k_edge_bwd_mask_ti): D [N, H] = dB - dA, colsum [ti_colsum_rows(N, H)][H]
-inline int64_t ti_colsum_rows(int64_t N, int H) {
-    const int c4 = H / 4, g = stin_group_lanes(c4);
-    const int64_t nb = (N + (BLOCK / g) - 1) / (BLOCK / g);
+inline int64_t ti_colsum_rows(int64_t N, int H) {          // mask_shape_ok(H)
+    const int64_t nb = grid_rows(N, ROW4[ROW4_MASK0 + mask_class(H)].G);
     return (nb + TI_ITER - 1) / TI_ITER;
 }
 int edge_bwd_mask_ti_impl(const float* G, int64_t ldg, const uint32_t* mask, const int32_t* rowptr_dst, const float* w_src,
@@ -1635,26 +1593,18 @@ int edge_bwd_mask_ti_impl(const float* G, int64_t ldg, const uint32_t* mask, con
                           int64_t colsum_rows, hipStream_t stream) {
     using T = float;
     STIN_REQUIRE(N >= 0 && H > 0 && ldg >= H && ldd >= H, STIN_E_SIZE);
-    if (cp_src != nullptr) {
-        STIN_REQUIRE(cp_dst != nullptr && Ccp > 0 && Ccp <= H && Ccp % 4 == 0 && ld_cps >= Ccp && ld_cpd >= Ccp, STIN_E_SIZE);
-        STIN_REQUIRE(stin_aligned16(cp_src) && stin_aligned16(cp_dst) && ld_cps % 4 == 0 && ld_cpd % 4 == 0, STIN_E_ALIGN);
-    }
+    if (const int e = row_copy_check(cp_src, ld_cps, cp_dst, ld_cpd, Ccp, H)) return e;
     if (N == 0) return STIN_OK;
     STIN_REQUIRE(G && mask && rowptr_dst && w_src && rowptr_src && col_src && xslot && D && colsum, STIN_E_NULL);
     STIN_REQUIRE(mask_shape_ok(H) && vec_ok<T>(H, {G, D}, {ldg, ldd}) && stin_aligned16(colsum), STIN_E_UNSUPPORTED);
     const int64_t nblk = ti_colsum_rows(N, H);
     STIN_REQUIRE(colsum_rows >= nblk, STIN_E_WORKSPACE);
-    const int c4 = H / 4, g = stin_group_lanes(c4), vpl = (c4 + g - 1) / g;
-    // rows in flight per role: the pair kernel's choices (UD = STIN_U(base, 1), US = STIN_U(base, 2))
-#define STIN_TI(G_, VPL_, UD_, US_)                                                                                      \
-    STIN_LAUNCH_STOP((k_edge_bwd_mask_ti<T, G_, VPL_, UD_, US_>), dim3((unsigned)nblk), dim3(BLOCK), stream, G, ldg, mask,  \
-                     rowptr_dst, w_src, rowptr_src, col_src, xslot, N, H, D, ldd, cp_src, ld_cps, cp_dst, ld_cpd, Ccp, colsum)
-    if (g == 32) STIN_TI(32, 1, STIN_U(6, 1), STIN_U(6, 2));          // H = 128
-    else if (vpl == 1) STIN_TI(64, 1, STIN_U(4, 1), STIN_U(4, 2));    // 256
-    else if (vpl == 2) STIN_TI(64, 2, 2, 2);                          // 512
-    else if (vpl <= 4) STIN_TI(64, 4, STIN_U(2, 1), STIN_U(2, 2));    // 1024
-    else STIN_TI(64, 8, 1, 1);                                        // 2048
-#undef STIN_TI
+    with_class<0, 4>(mask_class(H), [&](auto i) {          // rows in flight per role: the pair kernel's choices
+        constexpr Row4 c = ROW4[ROW4_MASK0 + decltype(i)::value];
+        constexpr PairU u = PAIR4[decltype(i)::value];
+        launch_stop(k_edge_bwd_mask_ti<T, c.G, c.VPL, u.UD, u.US>, (unsigned)nblk, stream, G, ldg, mask, rowptr_dst, w_src, rowptr_src,
+                    col_src, xslot, N, H, D, ldd, cp_src, ld_cps, cp_dst, ld_cpd, Ccp, colsum);
+    });
     return stin_launch_status();
 }
 
@@ -1665,9 +1615,10 @@ int edge_fwd_ti_impl(const float* b1, const float* B, int64_t ldb, const int32_t
     if (N == 0) return STIN_OK;
     STIN_REQUIRE(B && rowptr && out, STIN_E_NULL);
     STIN_REQUIRE(mask_shape_ok(H) && vec_ok<T>(H, {B, out}, {ldb, ldo}) && (b1 == nullptr || stin_aligned16(b1)), STIN_E_UNSUPPORTED);
-    const float* A = b1;
-    const int64_t lda = 0;
-    STIN_DISPATCH(H, k_edge_fwd_ti, 1, A, lda, B, ldb, rowptr, col, N, H, out, ldo, indicator, mask);
+    with_class<ROW4_MASK0, 9>(row4_class(H), [&](auto i) {
+        constexpr Row4 c = ROW4[decltype(i)::value];
+        launch(k_edge_fwd_ti<T, c.G, c.VPL, c.U>, grid_rows(N, c.G), stream, b1, (int64_t)0, B, ldb, rowptr, col, N, H, out, ldo, indicator, mask);
+    });
     return stin_launch_status();
 }
 
@@ -1676,42 +1627,17 @@ int edge_bwd_mask_pair8_impl(const stin_bf16* G, int64_t ldg, const uint32_t* ma
                              int64_t N, int H, stin_bf16* dA, int64_t ldda, stin_bf16* dB, int64_t lddb, const stin_bf16* cp_src,
                              int64_t ld_cps, stin_bf16* cp_dst, int64_t ld_cpd, int Ccp, hipStream_t stream) {
     STIN_REQUIRE(N >= 0 && H > 0 && ldg >= H && ldda >= H && lddb >= H, STIN_E_SIZE);
-    if (cp_src != nullptr) {
-        STIN_REQUIRE(cp_dst != nullptr && Ccp > 0 && Ccp <= H && Ccp % 8 == 0 && ld_cps >= Ccp && ld_cpd >= Ccp, STIN_E_SIZE);
-        STIN_REQUIRE(stin_aligned16(cp_src) && stin_aligned16(cp_dst) && ld_cps % 8 == 0 && ld_cpd % 8 == 0, STIN_E_ALIGN);
-    }
+    if (const int e = row_copy_check(cp_src, ld_cps, cp_dst, ld_cpd, Ccp, H)) return e;
     if (N == 0) return STIN_OK;
     STIN_REQUIRE(G && mask && rowptr_dst && w_src && rowptr_src && col_src && xslot && dA && dB, STIN_E_NULL);
     STIN_REQUIRE(mask_shape_ok(H), STIN_E_UNSUPPORTED);
     STIN_REQUIRE(wide8_ok(H, {G, dA, dB}, {ldg, ldda, lddb}), STIN_E_ALIGN);    // the geometry the forward kernel wrote the mask in
-#define STIN_PAIR8(G_, V_, UD_, US_)                                                                                          \
-    do {                                                                                                                      \
-        const unsigned nb = grid_rows(N, G_);                                                                                 \
-        STIN_LAUNCH_STOP((k_edge_bwd_mask_pair8<G_, V_, UD_, US_>), pair_grid(nb), dim3(BLOCK), stream, G, ldg, mask,          \
-                           rowptr_dst, w_src, rowptr_src, col_src, xslot, N, H, dA, ldda, dB, lddb, nb, cp_src, ld_cps,        \
-                           cp_dst, ld_cpd, Ccp);                                                                               \
-    } while (0)
-    // (UD, US): rows in flight of the streaming / the gathering role.  Tuning aid STIN_EDGE8_US = digits "u16,u32,u64,u64x2,u64x4"
-    // for the gathering role, as STIN_EDGE8_U for the forward kernel (re-read per call).
-    const char* eu = getenv("STIN_EDGE8_US");
-    const int cfg = eu ? atoi(eu) : 0;
-    auto pick = [&](int pos, int dflt) { int d = cfg; for (int i = 0; i < 4 - pos; ++i) d /= 10; d %= 10; return (cfg > 0 && d > 0) ? d : dflt; };
-#define STIN_PAIR8_U(G_, V_, UD_, POS_, DFLT_)                  \
-    do {                                                        \
-        const int us_ = pick(POS_, DFLT_);                      \
-        if (us_ == 1) STIN_PAIR8(G_, V_, UD_, 1);               \
-        else if (us_ == 2) STIN_PAIR8(G_, V_, UD_, 2);          \
-        else if (us_ == 3) STIN_PAIR8(G_, V_, UD_, 3);          \
-        else if (us_ == 4) STIN_PAIR8(G_, V_, UD_, 4);          \
-        else STIN_PAIR8(G_, V_, UD_, 6);                        \
-    } while (0)
-    if (H == 128) STIN_PAIR8_U(16, 1, 6, 0, STIN_BWD8_US_16);
-    else if (H == 256) STIN_PAIR8_U(32, 1, 3, 1, STIN_BWD8_US_32);
-    else if (H == 512) STIN_PAIR8_U(64, 1, 3, 2, STIN_BWD8_US_64);
-    else if (H == 1024) STIN_PAIR8_U(64, 2, 2, 3, STIN_BWD8_US_64X2);
-    else STIN_PAIR8_U(64, 4, 1, 4, STIN_BWD8_US_64X4);
-#undef STIN_PAIR8_U
-#undef STIN_PAIR8
+    with_class<0, 4>(mask_class(H), [&](auto i) {
+        constexpr Row8 c = ROW8[decltype(i)::value];
+        const unsigned nb = grid_rows(N, c.G);
+        launch_stop(k_edge_bwd_mask_pair8<c.G, c.VPL, c.UD, c.US>, 2 * nb, stream, G, ldg, mask, rowptr_dst, w_src, rowptr_src, col_src, xslot,
+                    N, H, dA, ldda, dB, lddb, nb, cp_src, ld_cps, cp_dst, ld_cpd, Ccp);
+    });
     return stin_launch_status();
 }
 
@@ -1723,32 +1649,22 @@ int segment_sum_impl(const T* src, int64_t ld_src, const int32_t* rowptr, const 
     STIN_REQUIRE(N >= 0 && C > 0 && ld_src >= C && ld_out >= C, STIN_E_SIZE);
     if (N == 0) return STIN_OK;
     STIN_REQUIRE(src && rowptr && out, STIN_E_NULL);
-    {
-        // even split of the row over G = C / 8 lanes with 2 chunks each (C / 4 a power of two, 16 <= C <= 512), wider rows on a
-        // full wave; anything else (ragged channel counts) keeps the predicated kernel below
-        const int c4 = C / 4;
-        if (C % 4 == 0 && c4 >= 4 && (c4 & (c4 - 1)) == 0 && c4 <= 512 && vec_ok<T>(C, {src, out}, {ld_src, ld_out})) {
-            // non-temporal loads only for a source that cannot be Infinity-Cache resident (see the kernel comment)
-            const bool nt = is_f32((const T*)nullptr) && want_nt;
-#define SEGX(G_, V_, U_)                                                                                                  \
-    do {                                                                                                                  \
-        if (nt) hipLaunchKernelGGL((k_segment_sum_x<T, G_, V_, U_, true>), rows_grid(grid_rows(N, G_)), dim3(BLOCK), 0, stream, src, ld_src, rowptr, col, N, C, mean, out, ld_out); \
-        else hipLaunchKernelGGL((k_segment_sum_x<T, G_, V_, U_, false>), rows_grid(grid_rows(N, G_)), dim3(BLOCK), 0, stream, src, ld_src, rowptr, col, N, C, mean, out, ld_out);   \
-    } while (0)
-            if (c4 == 4) SEGX(2, 2, 2);
-            else if (c4 == 8) SEGX(4, 2, 2);
-            else if (c4 == 16) SEGX(8, 2, 2);
-            else if (c4 == 32) SEGX(16, 2, 2);
-            else if (c4 == 64) SEGX(32, 2, 2);
-            else if (c4 == 128) SEGX(64, 2, 2);
-            else if (c4 == 256) SEGX(64, 4, 2);
-            else SEGX(64, 8, 1);
-#undef SEGX
-            return stin_launch_status();
-        }
-    }
-    if (vec_ok<T>(C, {src, out}, {ld_src, ld_out})) {
-        STIN_DISPATCH(C, k_segment_sum, 1, src, ld_src, rowptr, col, N, C, mean, out, ld_out);
+    const bool vec = vec_ok<T>(C, {src, out}, {ld_src, ld_out});
+    const int c4 = C / 4;
+    if (vec && c4 >= 4 && (c4 & (c4 - 1)) == 0) {
+        // the even split of SEGX (C / 4 a power of two, 16 <= C <= 2048); ragged channel counts keep the predicated kernel below.
+        // Non-temporal loads only for a source that cannot be Infinity-Cache resident (see the kernel comment).
+        const bool nt = is_f32((const T*)nullptr) && want_nt;
+        with_class<0, 7>(segx_class(c4), [&](auto i) {
+            constexpr Row4 c = SEGX[decltype(i)::value];
+            if (nt) launch(k_segment_sum_x<T, c.G, c.VPL, c.U, true>, grid_rows(N, c.G), stream, src, ld_src, rowptr, col, N, C, mean, out, ld_out);
+            else launch(k_segment_sum_x<T, c.G, c.VPL, c.U, false>, grid_rows(N, c.G), stream, src, ld_src, rowptr, col, N, C, mean, out, ld_out);
+        });
+    } else if (vec) {
+        with_class<0, 9>(row4_class(C), [&](auto i) {
+            constexpr Row4 c = ROW4[decltype(i)::value];
+            launch(k_segment_sum<T, c.G, c.VPL, c.U>, grid_rows(N, c.G), stream, src, ld_src, rowptr, col, N, C, mean, out, ld_out);
+        });
     } else if constexpr (is_f32((const T*)nullptr)) {
         hipLaunchKernelGGL((k_scalar<OP_SEG_SUM>), dim3(grid_elems(N * C)), dim3(BLOCK), 0, stream, src, ld_src,
                            (const float*)nullptr, (int64_t)0, (const float*)nullptr, (int64_t)0, (const float*)nullptr,
@@ -1766,7 +1682,10 @@ int pool_max_fwd_impl(const T* x, int64_t ldx, const int32_t* rowptr, const int3
     if (N == 0) return STIN_OK;
     STIN_REQUIRE(x && rowptr && col && out && arg, STIN_E_NULL);
     if (vec_ok<T>(C, {x, out}, {ldx, ldo}) && stin_aligned16(arg)) {
-        STIN_DISPATCH(C, k_pool_max_fwd, 1, x, ldx, rowptr, col, N, C, out, ldo, arg);
+        with_class<0, 9>(row4_class(C), [&](auto i) {
+            constexpr Row4 c = ROW4[decltype(i)::value];
+            launch(k_pool_max_fwd<T, c.G, c.VPL, c.U>, grid_rows(N, c.G), stream, x, ldx, rowptr, col, N, C, out, ldo, arg);
+        });
     } else if constexpr (is_f32((const T*)nullptr)) {
         hipLaunchKernelGGL((k_scalar<OP_POOL_MAX>), dim3(grid_elems(N * C)), dim3(BLOCK), 0, stream, x, ldx,
                            (const float*)nullptr, (int64_t)0, (const float*)nullptr, (int64_t)0, (const float*)nullptr,
@@ -1784,7 +1703,10 @@ int pool_max_bwd_impl(const T* g, int64_t ldg, const int32_t* arg, const int32_t
     if (N == 0) return STIN_OK;
     STIN_REQUIRE(g && arg && trace && gx, STIN_E_NULL);
     if (vec_ok<T>(C, {g, gx}, {ldg, ldgx}) && stin_aligned16(arg)) {
-        STIN_DISPATCH_NOU(C, k_pool_max_bwd, g, ldg, arg, trace, N, C, gx, ldgx);
+        with_class<0, 9>(row4_class(C), [&](auto i) {
+            constexpr Row4 c = ROW4[decltype(i)::value];
+            launch(k_pool_max_bwd<T, c.G, c.VPL>, grid_rows(N, c.G), stream, g, ldg, arg, trace, N, C, gx, ldgx);
+        });
     } else if constexpr (is_f32((const T*)nullptr)) {
         hipLaunchKernelGGL((k_scalar<OP_POOL_MAX_BWD>), dim3(grid_elems(N * C)), dim3(BLOCK), 0, stream, g, ldg,
                            (const float*)nullptr, (int64_t)0, (const float*)nullptr, (int64_t)0, (const float*)nullptr,
@@ -1802,7 +1724,10 @@ int gather_rows_impl(const T* src, int64_t ld_src, const int32_t* idx, const flo
     if (N == 0) return STIN_OK;
     STIN_REQUIRE(src && idx && out, STIN_E_NULL);
     if (vec_ok<T>(C, {src, out}, {ld_src, ldo})) {
-        STIN_DISPATCH_NOU(C, k_gather_rows, src, ld_src, idx, row_scale, N, C, out, ldo);
+        with_class<0, 9>(row4_class(C), [&](auto i) {
+            constexpr Row4 c = ROW4[decltype(i)::value];
+            launch(k_gather_rows<T, c.G, c.VPL>, grid_rows(N, c.G), stream, src, ld_src, idx, row_scale, N, C, out, ldo);
+        });
     } else if constexpr (is_f32((const T*)nullptr)) {
         hipLaunchKernelGGL((k_scalar<OP_GATHER>), dim3(grid_elems(N * C)), dim3(BLOCK), 0, stream, src, ld_src,
                            (const float*)nullptr, (int64_t)0, (const float*)nullptr, (int64_t)0, row_scale,
@@ -1869,7 +1794,10 @@ extern "C" int stin_edge_relu_mean_bwd_dst_f32(const float* A, int64_t lda, cons
     if (N == 0) return STIN_OK;
     STIN_REQUIRE(A && B && G && rowptr && dA, STIN_E_NULL);
     if (vec_ok<T>(H, {A, B, G, dA}, {lda, ldb, ldg, ldda})) {
-        STIN_DISPATCH(H, k_edge_bwd_dst, 1, A, lda, B, ldb, G, ldg, rowptr, col, N, H, dA, ldda);
+        with_class<0, 9>(row4_class(H), [&](auto i) {
+            constexpr Row4 c = ROW4[decltype(i)::value];
+            launch(k_edge_bwd_dst<T, c.G, c.VPL, c.U>, grid_rows(N, c.G), stream, A, lda, B, ldb, G, ldg, rowptr, col, N, H, dA, ldda);
+        });
     } else {
         hipLaunchKernelGGL((k_scalar<OP_EDGE_BWD_DST>), dim3(grid_elems(N * H)), dim3(BLOCK), 0, stream, A, lda, B, ldb,
                            G, ldg, (const float*)nullptr, rowptr, col, N, H, 0, dA, ldda, (int32_t*)nullptr);
@@ -1888,7 +1816,10 @@ extern "C" int stin_edge_relu_mean_bwd_src_f32(const float* A, int64_t lda, cons
     if (N == 0) return STIN_OK;
     STIN_REQUIRE(A && B && G && inv_deg && rowptr_src && dB, STIN_E_NULL);
     if (vec_ok<T>(H, {A, B, G, dB}, {lda, ldb, ldg, lddb})) {
-        STIN_DISPATCH(H, k_edge_bwd_src, 2, A, lda, B, ldb, G, ldg, inv_deg, rowptr_src, col_src, N, H, dB, lddb);
+        with_class<0, 9>(row4_class(H), [&](auto i) {
+            constexpr Row4 c = ROW4[decltype(i)::value];
+            launch(k_edge_bwd_src<T, c.G, c.VPL, halved(c.U)>, grid_rows(N, c.G), stream, A, lda, B, ldb, G, ldg, inv_deg, rowptr_src, col_src, N, H, dB, lddb);
+        });
     } else {
         hipLaunchKernelGGL((k_scalar<OP_EDGE_BWD_SRC>), dim3(grid_elems(N * H)), dim3(BLOCK), 0, stream, A, lda, B, ldb,
                            G, ldg, inv_deg, rowptr_src, col_src, N, H, 0, dB, lddb, (int32_t*)nullptr);
@@ -1997,7 +1928,10 @@ extern "C" int stin_gather_add_rows_f32(const float* a, int64_t lda, const int32
         const unsigned grid = (unsigned)((threads + BLOCK - 1) / BLOCK);
         hipLaunchKernelGGL((k_gather_add_rows_u<4>), dim3(grid), dim3(BLOCK), 0, stream, a, lda, idx_a, b, ldb, idx_b, N, c4, out, ldo);
     } else if (vec_ok<T>(C, {a, b, out}, {lda, ldb, ldo})) {
-        STIN_DISPATCH_NOU(C, k_gather_add_rows, a, lda, idx_a, b, ldb, idx_b, N, C, out, ldo);
+        with_class<0, 9>(row4_class(C), [&](auto i) {
+            constexpr Row4 c = ROW4[decltype(i)::value];
+            launch(k_gather_add_rows<T, c.G, c.VPL>, grid_rows(N, c.G), stream, a, lda, idx_a, b, ldb, idx_b, N, C, out, ldo);
+        });
     } else {
         hipLaunchKernelGGL(k_gather_add_rows_scalar, dim3(grid_elems(N * C)), dim3(BLOCK), 0, stream, a, lda, idx_a, b, ldb,
                            idx_b, N, C, out, ldo);
