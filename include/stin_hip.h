@@ -392,6 +392,41 @@ int stin_gemm_tn_f32(const float* G, int64_t ldg, const float* X, int64_t ldx, i
 int stin_gemm_tn_geometry(int storage, int64_t M, int Nc, int K, int64_t ldg, int64_t ldx, int aligned16, int ones_column,
                           int precision, int32_t* out8);
 
+/* The route an NT product takes - which kernel family, on what tile, grid and LDS - host only: nothing is launched, no device is
+ * touched.  The counterpart of stin_gemm_tn_geometry; the NT entry points ask the same function (csrc/gemm_nt_route.inc).
+ *   storage 0 = fp32 rows (stin_gemm_nt_f32 and its variants), 1 = bf16 rows (stin_gemm_nt_bf16);
+ *   precision: fp32 rows - STIN_GEMM_* with its W_PRESPLIT / W_FRAG flags; bf16 rows - 0 or STIN_GEMM_W_BF16;
+ *   parts: STIN_NT_PART_* OR-ed - what the call carries besides the product; align: STIN_NT_ALIGN_* OR-ed - the 16-byte facts;
+ *   cu > 0: the compute units of the device the rules are asked for.
+ * out10 (ten int32) = { family (STIN_NT_*), BM, BN (the block's output tile), the family's parameter (panel: 32-row tiles per block;
+ * strip: 21 / 22 / 41; all-columns: waves along M; stream: column tiles per block), vec (16-byte operand loads), vec_out (16-byte
+ * stores; strip: the restaged epilogue), dynamic LDS bytes, grid x, grid y, statistics groups of the fused epilogue (0: none) }.
+ * The STIN_NT_* / STIN_STRIP_CFG / STIN_DOTELU_FUSED switches are honoured as by the products themselves.  Returns the refusal the
+ * product itself would answer (STIN_E_UNSUPPORTED, STIN_E_ALIGN) or an argument error, and then writes nothing. */
+#define STIN_NT_NONE 0        /* no rows: nothing is launched */
+#define STIN_NT_TILED 1       /* k_gemm_nt / k_gemm_nt_bf16s */
+#define STIN_NT_STREAM 2      /* k_gemm_nt_stream */
+#define STIN_NT_STRIP 3       /* k_gemm_nt_strip (fragment-order weights) */
+#define STIN_NT_WIDE 4        /* k_gemm_nt_wide, the all-columns kernel (fragment-order weights, Nc = 128 / 256) */
+#define STIN_NT_PANEL 5       /* k_gemm_nt_panel (fragment-order weights, Nc % 128 == 0) */
+#define STIN_NT_B16_TILED 6   /* k_gemm_nt_b16 */
+#define STIN_NT_B16_GLDS 7    /* k_gemm_nt_b16_glds */
+#define STIN_NT_PART_BIAS 0x1
+#define STIN_NT_PART_ROW_MASK 0x2
+#define STIN_NT_PART_RESIDUAL 0x4
+#define STIN_NT_PART_COLSTATS 0x8         /* stin_gemm_nt_colstats_f32; with DOTELU: stin_gemm_nt_dotelu_f32 */
+#define STIN_NT_PART_DOTELU 0x10
+#define STIN_NT_PART_BN_TF 0x20           /* the BatchNorm + ReLU operand transform (stin_gemm_nt_bn_f32) */
+#define STIN_NT_PART_BN_BWD_STATS 0x40    /* stin_gemm_nt_bn_bwd_stats_f32 */
+#define STIN_NT_PART_BN_BWD_APPLY 0x80    /* stin_gemm_nt_bn_bwd_apply_f32 */
+#define STIN_NT_PART_OUT_F32 0x100        /* bf16 rows: fp32 output */
+#define STIN_NT_PART_STREAM_ONLY 0x200    /* the streaming kernel asked for by name (stin_gemm_nt_stream_f32): no row threshold */
+#define STIN_NT_ALIGN_IN 0x1              /* rows of A and W (BatchNorm backward: and of X) are 16-byte vectors: ld and base */
+#define STIN_NT_ALIGN_OUT 0x2             /* rows of C and of the residual are */
+#define STIN_NT_ALIGN_TF 0x4              /* the four vectors of the operand transform are */
+#define STIN_NT_ALIGN_BIAS 0x8            /* the bias vector is (the streaming kernel's epilogue reads it 16 bytes at a time) */
+int stin_gemm_nt_geometry(int storage, int64_t M, int Nc, int K, int precision, int parts, int align, int cu, int32_t* out10);
+
 /* The same product with the weight gradient dW [Nc, K] (row pitch lddw >= K) and the bias gradient db [Nc] as SEPARATE
  * destinations (ones column implied): what torch.nn.Linear's backward hands to weight.grad / bias.grad
  * (models/surfacetextureinpaintingnet.py:461-466 `final_linear1`, and every generic nn.Linear of the build) without an
@@ -503,7 +538,7 @@ int stin_gemm_tn_bn_f32(const float* G, int64_t ldg, const float* X, int64_t ldx
  *   stin_gemm_nt_bn_bwd_stats_f32: nothing stored; sums [2][Nc] floats = P | Q (P = sum d nhat, Q = sum d, d = dh [gamma nhat + beta > 0],
  *     nhat = (X - mean) rstd: the gradients of gamma | beta) through partial [groups][2][Nc] doubles (fixed-order fp64 fold);
  *   stin_gemm_nt_bn_bwd_apply_f32: dx [M, Nc] = rstd gamma (d - Q inv_n - nhat P inv_n) - stin_bn_act_bwd_f32's expression.
- * groups = stin_gemm_nt_bn_bwd_groups(M, Nc, K, precision); 0: not served (K not 64 or 128, a pre-split precision flag,
+ * groups = stin_gemm_nt_bn_bwd_groups(M, Nc, K, precision); 0: not served (K not 64 or 128: the pair is kept to K <= 128, the plain product below takes every multiple of 64 up to 512; a pre-split precision flag,
  * STIN_NT_BNBWD=0) - keep the three-launch route.  Rows of A / W 16-byte aligned.  The accumulators equal stin_gemm_nt_f32's
  * bit for bit (same tiles, k order, MFMA order); the sums differ from the reduction kernel's only by fp64 summation order. */
 /* The streaming-rows kernel behind them, as the plain product (mean == NULL) or with stin_gemm_nt_bn_f32's operand transform:

@@ -174,9 +174,6 @@ inline int tn_tile(int n) {
     return n > 64 ? 128 : 64;    // (measured: 64x64 wgrad tiles are 2-5 % slower end to end at any slab count)
 }
 
-// (the STIN_NT_TILE sweep aid of rounds 1-5 is gone: 0 = the measured rule below)
-inline int stin_nt_force_tile() { return 0; }
-
 inline int stin_cu_count() { return stin_cu_count_dev(); }          // (per device: stin_common.h)
 
 inline int tn_rows_per_chunk(int64_t M, int tiles, bool one_per_cu = false) {
@@ -197,23 +194,6 @@ inline int tn_rows_per_chunk(int64_t M, int tiles, bool one_per_cu = false) {
     rows = (rows + TN_R - 1) / TN_R * TN_R;
     return (int)rows;
 }
-// bf16-storage NT: when the 128 x 128 LDS-DMA kernel (k_gemm_nt_b16_glds) replaces the register-staged tiles.  It needs enough
-// k-tiles to amortise its prologue and enough 128 x 128 tiles to fill the chip; the tall-skinny level-0 / level-1 shapes
-// (K <= 128, bound by their output bytes) stay on the small tiles.  STIN_NT_GLDS = 0 | 1 forces (re-read per call).
-inline bool nt_b16_glds_pays(int64_t M, int Nc, int K) {
-    const char* e = getenv("STIN_NT_GLDS");
-    if (e) return atoi(e) != 0;
-    // measured (profiles/r03_nt_bf16_fat.md): +10..25 % from K = 1024 up (8 100 x 4096 x 1024: 124 -> 110 us, x 1024 x 4096: 104 -> 82),
-    // a loss at K <= 512 where four to eight k-tiles do not amortise the two-buffer prologue and the output bytes dominate
-    return K >= 1024 && Nc >= 256 && ((M + 127) / 128) * ((Nc + 127) / 128) >= 128;
-}
-// bf16-storage NT on the LDS-DMA kernel: 256 x 256 tiles when they still fill the chip (>= 200 tiles).  STIN_NT_BIG = 0 | 1 forces.
-inline bool nt_b16_big_tile(int64_t M, int Nc, int K) {
-    const char* e = getenv("STIN_NT_BIG");
-    if (e) return atoi(e) != 0;
-    (void)K;
-    return Nc >= 512 && ((M + 255) / 256) * ((Nc + 255) / 256) >= 200;
-}
 // bf16-storage TN: 256 x 256 tiles (k_gemm_tn_b16_tr<2, 4, 4, 2>) for the fat products.  STIN_TN_BIG = 0 | 1 forces (re-read per call;
 // the workspace bound covers both choices).
 inline bool tn_b16_big_tile(int Nc, int K) {
@@ -229,48 +209,6 @@ inline bool tn_b16_tr_enabled(int Nc, int K) {
     // whole tiles only: with a ragged third tile (161 362 x 320 x 128, the level-0 product of the crop batches) the 64 KB of LDS
     // (two blocks per CU instead of four) cost more than the transposes: 54.6 -> 68.6 us; whole-tile shapes gain 5-17 %
     return Nc % 128 == 0 && K % 128 == 0;
-}
-// Strip-kernel configuration (see k_gemm_nt_strip): 21 / 22 / 41.  STIN_STRIP_CFG overrides (tuning aid).
-inline int strip_config(int64_t M, int Nc, int KC) {
-    const char* e = getenv("STIN_STRIP_CFG");                         // re-read per call: profiles/gemm_shapes.py flips it
-    const int forced = e ? atoi(e) : 0;
-    if (forced == 21 || forced == 22 || forced == 41) return forced;
-    // measured (profiles/r03_strip_cfg.md): two quads gain 2-5 % where a strip has many panels (18 063 x 1024 x 256: 46.6 -> 44.4 us,
-    // x 1280 x 128 43.3 -> 42.1, 60 211 x 640 x 256 79.7 -> 77.8, 200 704 x 320 x 128 135.5 -> 133.2) and lose 3 % at Nc = 512
-    // (30.2 -> 31.2); MT = 4 on one quad (one wave per SIMD) is 25-40 % slower everywhere and stays a tested tuning variant
-    (void)M; (void)KC;
-    return Nc >= 640 ? 22 : 21;
-}
-// all-columns NT kernel: waves along the rows of a block (see k_gemm_nt_wide).  8 waves per block (128 rows) for Nc = 256
-// while the 128-row blocks fit the chip in one round: 18 063 x 256 x 1024 41.6 -> 36.7 us, x 512 29.3 -> 27.7; slower for 60 k
-// rows (471 blocks: 59 -> 64 us) and for Nc = 128 (256-row blocks: 71 of them at 18 k rows, 34 -> 52 us), which keep 4 waves.
-inline int wide_waves_m(int64_t M, int Nc) {
-    const int nw = Nc / 64;
-    return (Nc == 256 && (M + 127) / 128 <= (int64_t)stin_cu_count()) ? 2 : 4 / nw;
-}
-// Balanced column-panel kernel (k_gemm_nt_panel): 32-row tiles per block (MT0 + MT1, 2 .. 9) so that (row blocks) x (128-column
-// panels) fills the chip in ONE round, or 0 = this shape stays on the strip / all-columns kernels.  Measured (MI355X, round 4,
-// strip / all-columns -> panel, bf16x3): 18 063 x 256 x 1024 43.4 -> 36.7-38.8 us, x 256 x 512 26.4 -> 23.3, x 512 x 256 31.3 -> 24.2,
-// x 128 x 1280 35.1 -> 28.8; grids of two and more rounds (one 147 KB block per CU at a time: nothing overlaps a block's
-// prologue and its 5 us store phase) are no faster than the strip kernel (18 063 x 1024 x 256 44.0 -> 42.9-46.7, 60 211 x 640 x 256
-// 80.6 -> 93.1) and stay there.  STIN_NT_PANEL = 0 disables, = 1 forces it for every fragment-order shape whatever the number
-// of rounds (re-read per call: profiles/gemm_shapes.py flips it).
-inline int panel_tiles(int64_t M, int Nc, int K) {
-    const char* e = getenv("STIN_NT_PANEL");
-    const int forced = e ? atoi(e) : -1;
-    if (forced == 0 || Nc % 128 != 0 || K % WD_KC != 0 || M <= 0) return 0;
-    const int P = Nc / 128;
-    const int64_t rg = (M + 31) / 32, cu = stin_cu_count();
-    const int max_rounds = forced == 1 ? 64 : 1;
-    for (int rounds = 1; rounds <= max_rounds; ++rounds) {
-        const int64_t slots = cu * rounds / P;
-        if (slots < 1) continue;
-        const int64_t mts = (rg + slots - 1) / slots;
-        // (fewer row groups than slots - the coarse levels of a small crop, 1 806 x 256 x 1024: the finest blocks, 64 rows; the
-        // all-columns kernel ran that shape on 15 workgroups, 41.8 us; STIN_NT_PANEL_SMALL=0 keeps it there)
-        if (mts <= 9) return mts < 2 ? 2 : (int)mts;
-    }
-    return 0;
 }
 inline bool tn_one_per_cu(int storage, int precision, int TI, int TJ, int64_t M) {
     return storage == 0 && precision == STIN_GEMM_BF16X3 && TI == 128 && TJ == 128 && M <= 32768;

@@ -101,11 +101,16 @@ static inline int stin_cu_count_dev() {
 }
 struct stin_once_per_device {
     std::atomic<unsigned long long> mask{0};
-    bool first() {                                     // true exactly once per device
-        const unsigned long long bit = 1ull << stin_device_slot();
-        return (mask.fetch_or(bit, std::memory_order_relaxed) & bit) == 0;
-    }
+    bool done() const { return (mask.load(std::memory_order_acquire) >> stin_device_slot() & 1ull) != 0; }
+    void publish() { mask.fetch_or(1ull << stin_device_slot(), std::memory_order_release); }
 };
+// Raise a kernel's dynamic-LDS limit on the current device.  "Raised" is published only AFTER hipFuncSetAttribute has returned: a
+// second host thread that arrives earlier sets the attribute again (idempotent) instead of launching without it.
+static inline void stin_raise_dynamic_lds(stin_once_per_device& raised, const void* kernel, int bytes) {
+    if (raised.done()) return;
+    (void)hipFuncSetAttribute(kernel, hipFuncAttributeMaxDynamicSharedMemorySize, bytes);
+    raised.publish();
+}
 
 static inline bool stin_aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15u) == 0; }
 

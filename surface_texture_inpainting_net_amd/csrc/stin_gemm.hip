@@ -12,6 +12,7 @@
 // A[i = l&31][k = l>>5], B operand B[k = l>>5][j = l&31]; C/D reg r of lane l is
 // row (r&3) + 8*(r>>2) + 4*(l>>5), col l&31.
 #include <cstdlib>
+#include <tuple>
 #include <type_traits>
 #include "stin_common.h"
 
@@ -41,10 +42,6 @@ __device__ __forceinline__ bool nt_block_tile(int64_t M, int Nc, int BM, int BN,
     n0 = (int)(j % ncol) * BN;
     return true;
 }
-inline unsigned nt_grid(int64_t M, int Nc, int BM, int BN) {
-    const int64_t nrow = (M + BM - 1) / BM, ncol = (Nc + BN - 1) / BN;
-    return (unsigned)((nrow < 16 ? nrow : ((nrow + 7) / 8) * 8) * ncol);
-}
 
 #include "gemm_nt_tiled.inc"   // NT products: the exact-fp32 tiling and the split-16-bit tiling (k_gemm_nt, k_gemm_nt_bf16s)
 #include "gemm_nt_stream.inc"   // NT products, streaming rows through wave-private LDS (k_gemm_nt_stream and its epilogue modes)
@@ -52,229 +49,177 @@ inline unsigned nt_grid(int64_t M, int Nc, int BM, int BN) {
 #include "gemm_tn.inc"   // TN (weight-gradient) products of fp32 rows: exact-fp32 and split-bf16 tilings (k_gemm_tn, k_gemm_tn_bf16s)
 #include "gemm_b16.inc"   // GEMMs of bf16-STORAGE rows: NT tiled / LDS-DMA, TN register-transpose / hardware-transposed reads
 #include "gemm_tn_skinny.inc"   // TN products with K <= 16 (k_gemm_tn_skinny), the slab reduction and the host-side tile / chunk rules
+#include "gemm_nt_route.inc"   // host only: which kernel runs an NT product - the switches, the rules, nt_route
 }  // namespace
 
-// colstats != NULL: the launch must be the all-columns kernel (its blocks own whole rows) - STIN_E_UNSUPPORTED otherwise
-// the streaming-rows kernel for a pre-split (not fragment-ordered) weight operand with the tiled kernels' epilogue; defined below
-static int stream_nt_presplit_try(const float* A, int64_t lda, const float* W, int64_t ldw, const float* bias, const float* row_mask,
-                                  int64_t ld_mask, const float* residual, int64_t ld_res, int64_t M, int Nc, int K, float* C,
-                                  int64_t ldc, int precision, hipStream_t stream);
-static int stream_nt_epi_try(const float* A, int64_t lda, const float* W, int64_t ldw, const float* bias, const float* row_mask,
-                             int64_t ld_mask, const float* residual, int64_t ld_res, int64_t M, int Nc, int K, float* C, int64_t ldc,
-                             int precision, hipStream_t stream, int wpre);
-
-static int gemm_nt_f32_impl(const float* A, int64_t lda, const float* W, int64_t ldw, const float* bias,
-                            const float* row_mask, int64_t ld_mask, const float* residual, int64_t ld_res, int64_t M,
-                            int Nc, int K, float* C, int64_t ldc, int precision, double* colstats, stin_stream_t stream_,
-                            const NtDotElu* dotelu = nullptr, const stin_bn_tf* tf = nullptr) {
-    stin_clear_stale_error();
-    hipStream_t stream = (hipStream_t)stream_;
-    STIN_REQUIRE(M >= 0 && Nc > 0 && K > 0 && lda >= K && ldw >= K && ldc >= Nc, STIN_E_SIZE);
-    STIN_REQUIRE(residual == nullptr || ld_res >= Nc, STIN_E_SIZE);
-    const bool wpre = (precision & STIN_GEMM_W_PRESPLIT) != 0;
-    const bool wfrag = wpre && (precision & STIN_GEMM_W_FRAG) != 0 && stin_w_frag_shape(Nc, K);
-    precision &= ~(STIN_GEMM_W_PRESPLIT | STIN_GEMM_W_FRAG);
-    STIN_REQUIRE(precision == STIN_GEMM_F32 || precision == STIN_GEMM_BF16X3 || precision == STIN_GEMM_BF16X6 ||
-                     precision == STIN_GEMM_F16X3,
-                 STIN_E_UNSUPPORTED);
-    STIN_REQUIRE(!wpre || precision == STIN_GEMM_BF16X3 || precision == STIN_GEMM_F16X3, STIN_E_UNSUPPORTED);
-    STIN_REQUIRE(tf == nullptr || (!wpre && colstats == nullptr && dotelu == nullptr), STIN_E_UNSUPPORTED);   // (the tiled kernels only)
-    if (M == 0) return STIN_OK;
-    STIN_REQUIRE(A && W && C, STIN_E_NULL);
-    bool vec = (K % 4 == 0) && (lda % 4 == 0) && (ldw % 4 == 0) && stin_aligned16(A) && stin_aligned16(W);
-    if (tf != nullptr) {
-        STIN_REQUIRE(tf->mean && tf->rstd && tf->gamma && tf->beta, STIN_E_NULL);
-        vec = vec && stin_aligned16(tf->mean) && stin_aligned16(tf->rstd) && stin_aligned16(tf->gamma) && stin_aligned16(tf->beta);
-    }
-    // Tile choice, from per-shape sweeps on MI355X (profiles/gemm_tiles.py) and whole-step A/B runs: the skinny GEMMs of the
-    // shipped 3-level network (K <= 256, or K >= 512 with only 256 output columns) are latency-bound, so the 64x64 tile (4x
-    // the blocks in flight) wins there.  Long reductions with enough tiles (the 1024..4096-wide layers of a 5-level network:
-    // K >= 512, >= 500 tiles of 128x128) are 1.15-1.35x faster on 128x128.
-    auto blocks = [&](int bm, int bn) { return ((M + bm - 1) / bm) * ((Nc + bn - 1) / bn); };
-    constexpr int64_t min_blocks = 500;
-    const int force_tile = stin_nt_force_tile();   // tuning aid: 0 = rule above, 1 = 128x128, 2 = 128x64, 3 = 64x64
-    const bool big_tile = Nc % 128 == 0 && K >= 512 && blocks(128, 128) >= min_blocks;
-    stin_bn_tf tf_arg;
-    tf_arg.mean = tf_arg.rstd = tf_arg.gamma = tf_arg.beta = nullptr;
-    if (tf != nullptr) tf_arg = *tf;
-#define STIN_NT_ARGS A, lda, W, ldw, bias, row_mask, ld_mask, residual, ld_res, M, Nc, K, C, ldc, tf_arg
-#define STIN_NT(KERNEL, BM_, BN_, WM_, WN_, ...)                                                                  \
-    do {                                                                                                          \
-        dim3 grid(nt_grid(M, Nc, BM_, BN_));                                                                      \
-        if (vec) hipLaunchKernelGGL((KERNEL<BM_, BN_, WM_, WN_, ##__VA_ARGS__, true>), grid, dim3(BLOCK), 0, stream, STIN_NT_ARGS); \
-        else hipLaunchKernelGGL((KERNEL<BM_, BN_, WM_, WN_, ##__VA_ARGS__, false>), grid, dim3(BLOCK), 0, stream, STIN_NT_ARGS);    \
-    } while (0)
-#define STIN_NT_PICK(KERNEL, ...)                                                              \
-    do {                                                                                       \
-        if (Nc <= 32) STIN_NT(KERNEL, 128, 32, 4, 1, ##__VA_ARGS__);                           \
-        else if (force_tile == 1 || (force_tile == 0 && big_tile)) STIN_NT(KERNEL, 128, 128, 2, 2, ##__VA_ARGS__); \
-        else if (force_tile == 2) STIN_NT(KERNEL, 128, 64, 2, 2, ##__VA_ARGS__);  \
-        else STIN_NT(KERNEL, 64, 64, 2, 2, ##__VA_ARGS__);                                     \
-    } while (0)
-    STIN_REQUIRE(colstats == nullptr || (wfrag && (Nc <= 256 || dotelu != nullptr)), STIN_E_UNSUPPORTED);
-    const bool out16 = ldc % 4 == 0 && stin_aligned16(C) && (residual == nullptr || (ld_res % 4 == 0 && stin_aligned16(residual)));
-    const int pmts = (wfrag && vec && out16 && !(colstats != nullptr && residual != nullptr && dotelu == nullptr)) ? panel_tiles(M, Nc, K) : 0;
-    STIN_REQUIRE(dotelu == nullptr || (pmts > 0 && colstats != nullptr), STIN_E_UNSUPPORTED);      // (the panel kernel's epilogue only)
-    NtDotElu de_arg;
-    de_arg.x = nullptr;
-    de_arg.ldx = 0;
-    de_arg.mean = de_arg.rstd = nullptr;
-    if (dotelu != nullptr) de_arg = *dotelu;
-    // (stin_gemm_nt_colstats_groups promised the panel kernel's group count from the shape alone)
-    STIN_REQUIRE(colstats == nullptr || pmts > 0 || !wfrag || panel_tiles(M, Nc, K) == 0, STIN_E_ALIGN);
-    if (pmts > 0) {
-        // balanced column-panel kernel (k_gemm_nt_panel)
-        const int P = Nc / 128, bm = 32 * pmts;
-        const int nrb = (int)((M + bm - 1) / bm);
-        const int xmap = nrb >= 16 ? 1 : 0;
-        const unsigned grid = (unsigned)((xmap ? ((nrb + 7) / 8) * 8 : nrb) * P);
-        const size_t lds = (size_t)bm * 512 > (size_t)(8 * 4096 + bm * 4) ? (size_t)bm * 512 : (size_t)(8 * 4096 + bm * 4);
-#define STIN_PANEL_L(PT_, A_, B_)                                                                                         \
-    do {                                                                                                                  \
-        static stin_once_per_device attr_once;                                                                                     \
-        if (attr_once.first()) {                                                                                                  \
-            (void)hipFuncSetAttribute((const void*)k_gemm_nt_panel<PT_, A_, B_>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024); \
-        }                                                                                                                 \
-        hipLaunchKernelGGL((k_gemm_nt_panel<PT_, A_, B_>), dim3(grid), dim3(512), lds, stream, A, lda, W, bias, row_mask, ld_mask, \
-                           residual, ld_res, M, Nc, K, C, ldc, colstats, nrb, P, xmap, de_arg);                           \
-    } while (0)
-#define STIN_PANEL(PT_)                                                                                                   \
-    do {                                                                                                                  \
-        switch (pmts) {                                                                                                   \
-            case 2: STIN_PANEL_L(PT_, 1, 1); break;                                                                       \
-            case 3: STIN_PANEL_L(PT_, 2, 1); break;                                                                       \
-            case 4: STIN_PANEL_L(PT_, 2, 2); break;                                                                       \
-            case 5: STIN_PANEL_L(PT_, 3, 2); break;                                                                       \
-            case 6: STIN_PANEL_L(PT_, 3, 3); break;                                                                       \
-            case 7: STIN_PANEL_L(PT_, 4, 3); break;                                                                       \
-            case 8: STIN_PANEL_L(PT_, 4, 4); break;                                                                       \
-            default: STIN_PANEL_L(PT_, 5, 4); break;                                                                      \
-        }                                                                                                                 \
-    } while (0)
-        if (precision == STIN_GEMM_BF16X3) STIN_PANEL(__bf16);
-        else STIN_PANEL(_Float16);
-#undef STIN_PANEL_L
-#undef STIN_PANEL
-    } else if (wfrag && Nc <= 256) {
-        // all-columns kernel (k_gemm_nt_wide): Nc = 128 / 256, the fragment-order weight operand cannot be read by any other kernel
-        STIN_REQUIRE(vec, STIN_E_ALIGN);
-        const int wm = wide_waves_m(M, Nc);
-        // the LDS-restaged epilogue stores 16 bytes per lane: C (and the residual) rows must allow it
-        const int vec_out = (ldc % 4 == 0 && stin_aligned16(C) && (residual == nullptr || (ld_res % 4 == 0 && stin_aligned16(residual))) &&
-                             !(colstats != nullptr && residual != nullptr)) ? 1 : 0;
-#define STIN_WIDE_L(PT_, NW_, WM_)                                                                                        \
-    hipLaunchKernelGGL((k_gemm_nt_wide<PT_, NW_, WM_>), dim3((unsigned)((M + 64 * WM_ - 1) / (64 * WM_))), dim3(64 * NW_ * WM_), 0, stream, \
-                       A, lda, W, bias, row_mask, ld_mask, residual, ld_res, M, K, C, ldc, colstats, vec_out)
-#define STIN_WIDE(PT_, NW_)                                                                                               \
-    do {                                                                                                                  \
-        if (wm == 8 / NW_) STIN_WIDE_L(PT_, NW_, 8 / NW_);                                                                \
-        else STIN_WIDE_L(PT_, NW_, 4 / NW_);                                                                              \
-    } while (0)
-        if (precision == STIN_GEMM_BF16X3) {
-            if (Nc == 256) STIN_WIDE(__bf16, 4);
-            else STIN_WIDE(__bf16, 2);
-        } else {
-            if (Nc == 256) STIN_WIDE(_Float16, 4);
-            else STIN_WIDE(_Float16, 2);
-        }
-#undef STIN_WIDE_L
-#undef STIN_WIDE
-    } else if (wfrag) {
-        // resident-strip kernel (k_gemm_nt_strip): the fragment-order weight operand cannot be read by any other kernel
-        STIN_REQUIRE(vec && ldc % 4 == 0 && stin_aligned16(C) && (residual == nullptr || (ld_res % 4 == 0 && stin_aligned16(residual))),
-                     STIN_E_ALIGN);
-        const int KC = K < 256 ? K : 256;                             // resident K chunk: 64 rows x 256 k x 4 B = 64 KB -> 2 blocks per CU
-        const int P = (Nc + ST_PANEL - 1) / ST_PANEL;
-        const int cfg = strip_config(M, Nc, KC);                      // 21 = (MT 2, one quad), 22 = two quads, 41 = MT 4
-        const int bm = cfg == 21 ? 64 : 128, waves = cfg == 22 ? 8 : 4;
-        size_t lds = (size_t)2 * (KC / 32) * bm * 64 + (size_t)P * ST_PANEL * 4 + bm * 4;
-        // the epilogue's restage area (2 KB per wave) only where it does not cost a resident block (K chunks of 256: 2 blocks
-        // per CU either way; chunks of 128 would drop from 4 to 3 and lose more than the wide stores gain: 130 -> 155 us at
-        // 200 704 x 320 x 128)
-        const size_t occ_plain = 160 * 1024 / lds, occ_rest = 160 * 1024 / (lds + waves * 2048);
-        const int restage = ((occ_rest > 2 ? 2 : occ_rest) == (occ_plain > 2 ? 2 : occ_plain)) ? 1 : 0;     // (occupancy is capped at 2 below)
-        if (restage) lds += waves * 2048;
-        const int64_t units = ((M + bm - 1) / bm) * P;
-        int occ = (int)(160 * 1024 / lds);
-        // (round 4) at most two resident blocks per CU: with three or four (K chunks of 128: 32-44 KB of LDS per block) the blocks
-        // of a CU re-stream the W panels against each other - 200 704 x 320 x 128: 136.6 us at four / three, 126.5 at two, 124 at one
-        // two-quad block (profiles/probes/nt_probe.py, STIN_STRIP_OCC sweep)
-        if (occ > 2) occ = 2;
-        if (cfg == 22) occ = 1;                                       // eight-wave blocks: one per CU (18 063 x 1280 x 128: 39.2 -> 35.6 us)
-        if (occ < 1) occ = 1;
-        int64_t grid = (int64_t)stin_cu_count() * occ;
-        if (grid > units) grid = units;
-#define STIN_STRIP_L(PT_, MT_, QM_)                                                                                       \
-    do {                                                                                                                  \
-        static stin_once_per_device attr_once;                                                                                     \
-        if (attr_once.first()) {                                                                                                  \
-            (void)hipFuncSetAttribute((const void*)k_gemm_nt_strip<PT_, MT_, QM_>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024); \
-        }                                                                                                                 \
-        hipLaunchKernelGGL((k_gemm_nt_strip<PT_, MT_, QM_>), dim3((unsigned)grid), dim3(256 * QM_), lds, stream, A, lda, W, bias, row_mask, \
-                           ld_mask, residual, ld_res, M, Nc, K, C, ldc, KC, units, P, restage);                          \
-    } while (0)
-#define STIN_STRIP(PT_)                                                                                                   \
-    do {                                                                                                                  \
-        if (cfg == 22) STIN_STRIP_L(PT_, 2, 2);                                                                           \
-        else if (cfg == 41) STIN_STRIP_L(PT_, 4, 1);                                                                      \
-        else STIN_STRIP_L(PT_, 2, 1);                                                                                     \
-    } while (0)
-        if (precision == STIN_GEMM_BF16X3) STIN_STRIP(__bf16);
-        else STIN_STRIP(_Float16);
-#undef STIN_STRIP_L
-#undef STIN_STRIP
-    } else if (wpre) {
-        // pre-split W: the 16-byte vector path only (K % 4 == 0, aligned rows) - one tile shape, the data is per-network
-        STIN_REQUIRE(vec, STIN_E_ALIGN);
-        if (tf == nullptr && colstats == nullptr) {       // (round 5) very tall products: the streaming-rows kernel, bit-identical
-            const int rc = stream_nt_presplit_try(A, lda, W, ldw, bias, row_mask, ld_mask, residual, ld_res, M, Nc, K, C, ldc, precision, stream);
-            if (rc != STIN_E_UNSUPPORTED) return rc;
-        }
-        if (force_tile == 1 || (force_tile == 0 && big_tile)) {
-            dim3 grid(nt_grid(M, Nc, 128, 128));
-            if (precision == STIN_GEMM_BF16X3)
-                hipLaunchKernelGGL((k_gemm_nt_bf16s<128, 128, 2, 2, 2, __bf16, true, true>), grid, dim3(BLOCK), 0, stream, STIN_NT_ARGS);
-            else
-                hipLaunchKernelGGL((k_gemm_nt_bf16s<128, 128, 2, 2, 2, _Float16, true, true>), grid, dim3(BLOCK), 0, stream, STIN_NT_ARGS);
-        } else {
-            dim3 grid(nt_grid(M, Nc, 64, 64));
-            if (precision == STIN_GEMM_BF16X3)
-                hipLaunchKernelGGL((k_gemm_nt_bf16s<64, 64, 2, 2, 2, __bf16, true, true>), grid, dim3(BLOCK), 0, stream, STIN_NT_ARGS);
-            else
-                hipLaunchKernelGGL((k_gemm_nt_bf16s<64, 64, 2, 2, 2, _Float16, true, true>), grid, dim3(BLOCK), 0, stream, STIN_NT_ARGS);
-        }
-    } else if (precision == STIN_GEMM_BF16X3) STIN_NT_PICK(k_gemm_nt_bf16s, 2, __bf16);
-    else if (precision == STIN_GEMM_BF16X6) STIN_NT_PICK(k_gemm_nt_bf16s, 3, __bf16);
-    else if (precision == STIN_GEMM_F16X3) STIN_NT_PICK(k_gemm_nt_bf16s, 2, _Float16);
-    else STIN_NT_PICK(k_gemm_nt);
-#undef STIN_NT_PICK
-#undef STIN_NT
-#undef STIN_NT_ARGS
-    return stin_launch_status();
+// ------------------------------------------------------------------ NT products: route (gemm_nt_route.inc), then launch
+namespace {
+struct NtOperands {                    // one NT product of fp32 rows as the kernels take it; what an entry point does not have stays zero
+    const float* A; int64_t lda; const float* W; int64_t ldw;                             // (in the order of the entry points' arguments)
+    const float *bias, *row_mask; int64_t ld_mask; const float* residual; int64_t ld_res;
+    float* C; int64_t ldc;
+    double* stats;                     // [groups][2][Nc] partial sums of a fused epilogue (column statistics, dot-ELU, BatchNorm backward)
+    NtDotElu de;
+    stin_bn_tf tf;
+    const float *X, *P, *Q;            // BatchNorm backward (the streaming kernel's modes 1 / 2): pre-norm rows, the two column sums
+    int64_t ldx;
+    float inv_n;
+};
+inline int nt_parts(const float* bias, const float* row_mask, const float* residual) {
+    return (bias ? STIN_NT_PART_BIAS : 0) | (row_mask ? STIN_NT_PART_ROW_MASK : 0) | (residual ? STIN_NT_PART_RESIDUAL : 0);
 }
 
-extern "C" int stin_gemm_nt_stream_f32(const float* A, int64_t lda, const float* W, int64_t ldw, const float* mean, const float* rstd,
-                                       const float* gamma, const float* beta, int64_t M, int Nc, int K, float* C, int64_t ldc,
-                                       int precision, stin_stream_t stream);
-namespace {
-constexpr int64_t STREAM_MIN_ROWS = 65536;      // below this the tiling's many short blocks fill the chip better than 32-row wave tiles
-inline bool stream_enabled() {
-    const char* e = getenv("STIN_NT_STREAM");                                  // A/B switch, re-read per call (tests flip it)
-    return e == nullptr || atoi(e) != 0;
+// THE launch of every NT kernel: raise the kernel's dynamic-LDS limit on this device where it needs more than 64 KB (max_lds > 0),
+// then launch.  One flag per kernel instantiation.
+struct NtLaunch { dim3 grid; int threads; int64_t lds; int max_lds; hipStream_t stream; };
+template <auto KERNEL, typename... Args>
+void nt_launch(const NtLaunch& l, const std::tuple<Args...>& args) {
+    if (l.max_lds > 0) {
+        static stin_once_per_device raised;
+        stin_raise_dynamic_lds(raised, (const void*)KERNEL, l.max_lds);
+    }
+    std::apply([&](auto... a) { hipLaunchKernelGGL(KERNEL, l.grid, dim3(l.threads), (size_t)l.lds, l.stream, a...); }, args);
+}
+
+// ---- one launch table per family: the route's tile / parameter -> the template arguments
+template <int BM, int BN, int WM, int WN, typename Args>
+void nt_launch_tile(const NtRoute& r, int precision, bool wpre, const NtLaunch& l, const Args& a) {
+    if (wpre) {                                                     // (pre-split W: 16-byte rows, 64 x 64 and 128 x 128 only)
+        if constexpr (BN != 32) {
+            if (precision == STIN_GEMM_BF16X3) nt_launch<k_gemm_nt_bf16s<BM, BN, WM, WN, 2, __bf16, true, true>>(l, a);
+            else nt_launch<k_gemm_nt_bf16s<BM, BN, WM, WN, 2, _Float16, true, true>>(l, a);
+        }
+    } else if (precision == STIN_GEMM_F32)
+        r.vec ? nt_launch<k_gemm_nt<BM, BN, WM, WN, true>>(l, a) : nt_launch<k_gemm_nt<BM, BN, WM, WN, false>>(l, a);
+    else if (precision == STIN_GEMM_BF16X3)
+        r.vec ? nt_launch<k_gemm_nt_bf16s<BM, BN, WM, WN, 2, __bf16, true>>(l, a) : nt_launch<k_gemm_nt_bf16s<BM, BN, WM, WN, 2, __bf16, false>>(l, a);
+    else if (precision == STIN_GEMM_BF16X6)
+        r.vec ? nt_launch<k_gemm_nt_bf16s<BM, BN, WM, WN, 3, __bf16, true>>(l, a) : nt_launch<k_gemm_nt_bf16s<BM, BN, WM, WN, 3, __bf16, false>>(l, a);
+    else
+        r.vec ? nt_launch<k_gemm_nt_bf16s<BM, BN, WM, WN, 2, _Float16, true>>(l, a) : nt_launch<k_gemm_nt_bf16s<BM, BN, WM, WN, 2, _Float16, false>>(l, a);
+}
+void nt_launch_tiled(const NtRoute& r, const NtProblem& p, int precision, const NtOperands& o, hipStream_t stream) {
+    const NtLaunch l = {dim3((unsigned)r.grid), BLOCK, 0, 0, stream};
+    const auto a = std::make_tuple(o.A, o.lda, o.W, o.ldw, o.bias, o.row_mask, o.ld_mask, o.residual, o.ld_res, p.M, p.Nc, p.K, o.C, o.ldc, o.tf);
+    const bool wpre = (p.precision & STIN_GEMM_W_PRESPLIT) != 0;
+    if (r.bn == 32) nt_launch_tile<128, 32, 4, 1>(r, precision, wpre, l, a);
+    else if (r.bm == 128) nt_launch_tile<128, 128, 2, 2>(r, precision, wpre, l, a);
+    else nt_launch_tile<64, 64, 2, 2>(r, precision, wpre, l, a);
+}
+
+template <int NT, int MODE, bool TF, typename Args>
+void nt_launch_stream_tiles(int precision, const NtLaunch& l, const Args& a) {
+    if (precision == STIN_GEMM_BF16X3) nt_launch<k_gemm_nt_stream<64, NT, 2, __bf16, MODE, TF>>(l, a);
+    else if (precision == STIN_GEMM_BF16X6) nt_launch<k_gemm_nt_stream<64, NT, 3, __bf16, MODE, TF>>(l, a);
+    else nt_launch<k_gemm_nt_stream<64, NT, 2, _Float16, MODE, TF>>(l, a);
+}
+template <int MODE, bool TF>
+void nt_launch_stream_mode(const NtRoute& r, const NtProblem& p, int precision, const NtOperands& o, hipStream_t stream) {
+    const NtLaunch l = {dim3((unsigned)r.grid, (unsigned)r.grid_y), BLOCK, r.lds, 160 * 1024, stream};
+    const auto a = std::make_tuple(o.A, o.lda, o.W, o.ldw, p.M, p.Nc, p.K, o.X, o.ldx, o.tf, o.P, o.Q, o.inv_n, o.stats, o.C, o.ldc, o.bias,
+                                   o.row_mask, o.ld_mask, o.residual, o.ld_res, (p.precision & STIN_GEMM_W_PRESPLIT) ? 1 : 0);
+    if (r.param == 2) nt_launch_stream_tiles<2, MODE, TF>(precision, l, a);
+    else nt_launch_stream_tiles<4, MODE, TF>(precision, l, a);
+}
+void nt_launch_stream(const NtRoute& r, const NtProblem& p, int precision, const NtOperands& o, hipStream_t stream) {
+    if (p.has(STIN_NT_PART_BN_BWD_STATS)) nt_launch_stream_mode<1, false>(r, p, precision, o, stream);
+    else if (p.has(STIN_NT_PART_BN_BWD_APPLY)) nt_launch_stream_mode<2, false>(r, p, precision, o, stream);
+    else if (p.has(STIN_NT_PART_BN_TF)) nt_launch_stream_mode<0, true>(r, p, precision, o, stream);
+    else nt_launch_stream_mode<0, false>(r, p, precision, o, stream);
+}
+
+template <typename PT>
+void nt_launch_strip(const NtRoute& r, const NtProblem& p, const NtOperands& o, hipStream_t stream) {
+    const int KC = p.K < 256 ? p.K : 256, P = (p.Nc + ST_PANEL - 1) / ST_PANEL;
+    const int64_t units = ((p.M + r.bm - 1) / r.bm) * P;
+    const NtLaunch l = {dim3((unsigned)r.grid), r.param == 22 ? 512 : 256, r.lds, 160 * 1024, stream};
+    const auto a = std::make_tuple(o.A, o.lda, o.W, o.bias, o.row_mask, o.ld_mask, o.residual, o.ld_res, p.M, p.Nc, p.K, o.C, o.ldc, KC, units,
+                                   P, r.vec_out);
+    switch (r.param) {
+        case 22: nt_launch<k_gemm_nt_strip<PT, 2, 2>>(l, a); break;
+        case 41: nt_launch<k_gemm_nt_strip<PT, 4, 1>>(l, a); break;
+        default: nt_launch<k_gemm_nt_strip<PT, 2, 1>>(l, a); break;
+    }
+}
+template <typename PT>
+void nt_launch_wide(const NtRoute& r, const NtProblem& p, const NtOperands& o, hipStream_t stream) {
+    const NtLaunch l = {dim3((unsigned)r.grid), p.Nc * r.param, 0, 0, stream};       // Nc / 64 column waves x param row waves x 64 lanes
+    const auto a = std::make_tuple(o.A, o.lda, o.W, o.bias, o.row_mask, o.ld_mask, o.residual, o.ld_res, p.M, p.K, o.C, o.ldc, o.stats, r.vec_out);
+    if (p.Nc == 128) nt_launch<k_gemm_nt_wide<PT, 2, 2>>(l, a);
+    else if (r.param == 2) nt_launch<k_gemm_nt_wide<PT, 4, 2>>(l, a);
+    else nt_launch<k_gemm_nt_wide<PT, 4, 1>>(l, a);
+}
+template <typename PT>
+void nt_launch_panel(const NtRoute& r, const NtProblem& p, const NtOperands& o, hipStream_t stream) {
+    const int P = p.Nc / 128, nrb = (int)((p.M + r.bm - 1) / r.bm);
+    const NtLaunch l = {dim3((unsigned)r.grid), 512, r.lds, 160 * 1024, stream};
+    const auto a = std::make_tuple(o.A, o.lda, o.W, o.bias, o.row_mask, o.ld_mask, o.residual, o.ld_res, p.M, p.Nc, p.K, o.C, o.ldc, o.stats, nrb,
+                                   P, nrb >= 16 ? 1 : 0, o.de);
+    switch (r.param) {                                              // 32-row tiles per block = MT0 + MT1
+        case 2: nt_launch<k_gemm_nt_panel<PT, 1, 1>>(l, a); break;
+        case 3: nt_launch<k_gemm_nt_panel<PT, 2, 1>>(l, a); break;
+        case 4: nt_launch<k_gemm_nt_panel<PT, 2, 2>>(l, a); break;
+        case 5: nt_launch<k_gemm_nt_panel<PT, 3, 2>>(l, a); break;
+        case 6: nt_launch<k_gemm_nt_panel<PT, 3, 3>>(l, a); break;
+        case 7: nt_launch<k_gemm_nt_panel<PT, 4, 3>>(l, a); break;
+        case 8: nt_launch<k_gemm_nt_panel<PT, 4, 4>>(l, a); break;
+        default: nt_launch<k_gemm_nt_panel<PT, 5, 4>>(l, a); break;
+    }
+}
+
+// sizes and alignment facts of an fp32-row call -> its route (p: storage, M, Nc, K, precision, parts, null_operand set by the caller)
+int nt_f32_route(NtProblem& p, const NtOperands& o, const NtSwitches& sw, NtRoute* r) {
+    stin_clear_stale_error();
+    const bool bn_bwd = p.has(STIN_NT_PART_BN_BWD_STATS | STIN_NT_PART_BN_BWD_APPLY);
+    // (the streaming kernel asked for by name answers STIN_E_UNSUPPORTED for a shape it does not serve, an empty one included)
+    STIN_REQUIRE(bn_bwd || p.has(STIN_NT_PART_STREAM_ONLY) || (p.M >= 0 && p.Nc > 0 && p.K > 0), STIN_E_SIZE);
+    STIN_REQUIRE(o.lda >= p.K && o.ldw >= p.K && (p.has(STIN_NT_PART_BN_BWD_STATS) || o.ldc >= p.Nc), STIN_E_SIZE);
+    STIN_REQUIRE((o.residual == nullptr || o.ld_res >= p.Nc) && (!bn_bwd || o.ldx >= p.Nc), STIN_E_SIZE);
+    const bool in16 = o.lda % 4 == 0 && o.ldw % 4 == 0 && o.ldx % 4 == 0 && stin_aligned16(o.A) && stin_aligned16(o.W) && stin_aligned16(o.X);
+    const bool out16 = o.ldc % 4 == 0 && stin_aligned16(o.C) && (o.residual == nullptr || (o.ld_res % 4 == 0 && stin_aligned16(o.residual)));
+    const bool tf16 = stin_aligned16(o.tf.mean) && stin_aligned16(o.tf.rstd) && stin_aligned16(o.tf.gamma) && stin_aligned16(o.tf.beta);
+    p.align = (in16 ? STIN_NT_ALIGN_IN : 0) | (out16 ? STIN_NT_ALIGN_OUT : 0) | (tf16 ? STIN_NT_ALIGN_TF : 0) |
+              (stin_aligned16(o.bias) ? STIN_NT_ALIGN_BIAS : 0);
+    *r = nt_route(p, sw, stin_cu_count());
+    return r->status;
+}
+int nt_f32_launch(const NtRoute& r, const NtProblem& p, const NtOperands& o, stin_stream_t stream_) {
+    hipStream_t stream = (hipStream_t)stream_;
+    const int precision = p.precision & ~(STIN_GEMM_W_PRESPLIT | STIN_GEMM_W_FRAG);
+    const bool bf = precision == STIN_GEMM_BF16X3;                  // (the fragment-order kernels: bf16 or fp16 pieces)
+    switch (r.family) {
+        case STIN_NT_NONE: return STIN_OK;
+        case STIN_NT_TILED: nt_launch_tiled(r, p, precision, o, stream); break;
+        case STIN_NT_STREAM: nt_launch_stream(r, p, precision, o, stream); break;
+        case STIN_NT_STRIP: bf ? nt_launch_strip<__bf16>(r, p, o, stream) : nt_launch_strip<_Float16>(r, p, o, stream); break;
+        case STIN_NT_WIDE: bf ? nt_launch_wide<__bf16>(r, p, o, stream) : nt_launch_wide<_Float16>(r, p, o, stream); break;
+        case STIN_NT_PANEL: bf ? nt_launch_panel<__bf16>(r, p, o, stream) : nt_launch_panel<_Float16>(r, p, o, stream); break;
+        default: return STIN_E_UNSUPPORTED;
+    }
+    return stin_launch_status();
+}
+int nt_f32(int parts, int precision, int64_t M, int Nc, int K, const NtOperands& o, bool null_operand, const NtSwitches& sw,
+           stin_stream_t stream) {
+    NtProblem p = {0, M, Nc, K, precision, parts, 0, null_operand};
+    NtRoute r;
+    const int rc = nt_f32_route(p, o, sw, &r);
+    return rc != STIN_OK ? rc : nt_f32_launch(r, p, o, stream);
+}
+// the statistics groups a fused epilogue will write: the route of the ALIGNED form of the problem (what the launches carry);
+// 0: not served
+int64_t nt_groups(int parts, int precision, int64_t M, int Nc, int K, const NtSwitches& sw) {
+    if (M <= 0 || Nc <= 0 || K <= 0) return 0;
+    const NtProblem p = {0, M, Nc, K, precision, parts, STIN_NT_ALIGN_IN | STIN_NT_ALIGN_OUT | STIN_NT_ALIGN_TF | STIN_NT_ALIGN_BIAS, false};
+    const NtRoute r = nt_route(p, sw, stin_cu_count());
+    return r.status == STIN_OK ? r.groups : 0;
 }
 }  // namespace
 
 extern "C" int stin_gemm_nt_f32(const float* A, int64_t lda, const float* W, int64_t ldw, const float* bias,
                                 const float* row_mask, int64_t ld_mask, const float* residual, int64_t ld_res, int64_t M,
                                 int Nc, int K, float* C, int64_t ldc, int precision, stin_stream_t stream) {
-    if (M >= STREAM_MIN_ROWS && bias == nullptr && row_mask == nullptr && residual == nullptr && stream_enabled()) {
-        const int rc = stin_gemm_nt_stream_f32(A, lda, W, ldw, nullptr, nullptr, nullptr, nullptr, M, Nc, K, C, ldc, precision, stream);
-        if (rc != STIN_E_UNSUPPORTED) return rc;                               // (plain fp32 weights, K = 64 .. 512: the streaming kernel)
-    } else if (M >= STREAM_MIN_ROWS && stream_enabled()) {                      // ... with the tiled kernels' epilogue (bias [* mask], residual)
-        const int rc = stream_nt_epi_try(A, lda, W, ldw, bias, row_mask, ld_mask, residual, ld_res, M, Nc, K, C, ldc, precision, (hipStream_t)stream, 0);
-        if (rc != STIN_E_UNSUPPORTED) return rc;
-    }
-    return gemm_nt_f32_impl(A, lda, W, ldw, bias, row_mask, ld_mask, residual, ld_res, M, Nc, K, C, ldc, precision, nullptr, stream);
+    return nt_f32(nt_parts(bias, row_mask, residual), precision, M, Nc, K,
+                  {A, lda, W, ldw, bias, row_mask, ld_mask, residual, ld_res, C, ldc}, !(A && W && C), nt_switches(), stream);
 }
 
 // C = relu(gamma ((A - mean) rstd) + beta) W^T: BatchNorm1d + ReLU over the columns of A applied while the rows are staged
@@ -283,16 +228,20 @@ extern "C" int stin_gemm_nt_bn_f32(const float* A, int64_t lda, const float* W, 
                                    const float* gamma, const float* beta, int64_t M, int Nc, int K, float* C, int64_t ldc,
                                    int precision, stin_stream_t stream) {
     STIN_REQUIRE((precision & (STIN_GEMM_W_PRESPLIT | STIN_GEMM_W_FRAG)) == 0, STIN_E_UNSUPPORTED);
-    if (M >= STREAM_MIN_ROWS && mean != nullptr && stream_enabled()) {
-        const int rc = stin_gemm_nt_stream_f32(A, lda, W, ldw, mean, rstd, gamma, beta, M, Nc, K, C, ldc, precision, stream);
-        if (rc != STIN_E_UNSUPPORTED) return rc;
-    }
-    stin_bn_tf tf;
-    tf.mean = mean;
-    tf.rstd = rstd;
-    tf.gamma = gamma;
-    tf.beta = beta;
-    return gemm_nt_f32_impl(A, lda, W, ldw, nullptr, nullptr, 0, nullptr, 0, M, Nc, K, C, ldc, precision, nullptr, stream, nullptr, &tf);
+    NtOperands o = {A, lda, W, ldw, nullptr, nullptr, 0, nullptr, 0, C, ldc};
+    o.tf = {mean, rstd, gamma, beta};
+    return nt_f32(STIN_NT_PART_BN_TF, precision, M, Nc, K, o, !(A && W && C && mean && rstd && gamma && beta), nt_switches(), stream);
+}
+// The plain product C = A W^T (mean == NULL) or C = relu(gamma ((A - mean) rstd) + beta) W^T on the streaming kernel BY NAME, whatever
+// the row count; STIN_E_UNSUPPORTED for the shapes it does not serve (K not a multiple of 64 in 64 .. 512, rows not 16-byte aligned,
+// a pre-split precision flag).  stin_gemm_nt_f32 / stin_gemm_nt_bn_f32 route M >= 65 536 rows to it (STIN_NT_STREAM=0: never).
+extern "C" int stin_gemm_nt_stream_f32(const float* A, int64_t lda, const float* W, int64_t ldw, const float* mean, const float* rstd,
+                                       const float* gamma, const float* beta, int64_t M, int Nc, int K, float* C, int64_t ldc,
+                                       int precision, stin_stream_t stream) {
+    NtOperands o = {A, lda, W, ldw, nullptr, nullptr, 0, nullptr, 0, C, ldc};
+    o.tf = {mean, rstd, gamma, beta};
+    return nt_f32(STIN_NT_PART_STREAM_ONLY | (mean ? STIN_NT_PART_BN_TF : 0), precision, M, Nc, K, o,
+                  !(A && W && C && (mean == nullptr || (rstd && gamma && beta))), nt_switches(), stream);
 }
 
 // dh = A W^T used ONLY as the output gradient of BatchNorm1d + ReLU over the rows X (k_gemm_nt_stream MODE 1 / 2; SingleConvMeshNet's
@@ -300,233 +249,92 @@ extern "C" int stin_gemm_nt_bn_f32(const float* A, int64_t lda, const float* W, 
 // partial [groups][2][Nc] doubles, then sums [2][Nc] floats = P | Q, the gradients of gamma | beta); `apply` = the product again,
 // stored as dx = rstd gamma (d - Q / n - nhat P / n).  groups = stin_gemm_nt_bn_bwd_groups (0: shape / precision not served -
 // the caller keeps stin_gemm_nt_f32 + stin_colreduce_f32(DOT_BN_RELU) + stin_bn_act_bwd_f32).  W plain fp32 [Nc, K].
-namespace {
-// geometry of the streaming kernel for a shape: KC (staged k chunk), NT (32-column tiles per block), LDS bytes, blocks per CU
-struct StreamGeo {
-    int kc, nt, ncb, bpc;
-    size_t lds;
-    int64_t gx;
-};
-inline bool stream_geo(int64_t M, int Nc, int K, bool tf, StreamGeo* g, int mode = 0, int precision = STIN_GEMM_BF16X3) {
-    if (M <= 0 || Nc <= 0 || Nc % 4 != 0 || K < 64 || K > 512 || K % 64 != 0) return false;
-    // staged chunk: 64 columns (8 KB per wave in flight, 32 KB of staging per block: two blocks per CU up to K = 128 -
-    // 1 200 642 x 64 x 128 with the BatchNorm transform: 184 us against 212 with 128-column chunks, profiles/probes/kc_probe.sh)
-    g->kc = 64;
-    const char* e = getenv("STIN_NT_STREAM_NT");
-    int nt = e != nullptr ? atoi(e) : 0;
-    // (the statistics pass is faster with two column tiles although the A rows then come from L2 a second time: 207 against 232 us at
-    // 1 200 642 x 128 x 64, 178 against 277 at 361 000 x 256 x 128 - STIN_NT_STREAM_STATS4=1 is the four-tile form, a tuning aid)
-    if (nt != 2 && nt != 4) nt = (Nc <= 64 || mode == 1) ? 2 : 4;
-    const size_t esz = precision == STIN_GEMM_BF16X6 ? 6 : 4;                   // bytes per operand element in LDS: 2 or 3 pieces of 16 bits
-    auto lds_of = [&](int nt_) { return esz * ((size_t)K * 32 * nt_ + (size_t)128 * g->kc) + (tf ? (size_t)8 * K : 0) + (mode != 0 ? (size_t)24 * 32 * nt_ : 0); };
-    if (lds_of(nt) > 160 * 1024) nt = 2;
-    if (lds_of(nt) > 160 * 1024) return false;
-    g->nt = nt;
-    g->lds = lds_of(nt);
-    if (g->lds < 4 * 2 * 32 * nt * sizeof(double)) g->lds = 4 * 2 * 32 * nt * sizeof(double);
-    g->ncb = (Nc + 32 * nt - 1) / (32 * nt);
-    g->bpc = (int)((160 * 1024) / g->lds);
-    if (g->bpc > 2) g->bpc = 2;
-    int64_t gx = (int64_t)stin_cu_count() * g->bpc / g->ncb;
-    if (gx < 1) gx = 1;
-    const int64_t need = ((M + 31) / 32 + 3) / 4;                                 // blocks that have a tile for every wave
-    g->gx = need < gx ? need : gx;
-    return true;
-}
-inline bool stream_ok(const float* A, int64_t lda, const float* W, int64_t ldw, const float* X, int64_t ldx, const float* C, int64_t ldc,
-                      int precision) {
-    return lda % 4 == 0 && ldw % 4 == 0 && stin_aligned16(A) && stin_aligned16(W) && ldx % 4 == 0 && ldc % 4 == 0 && stin_aligned16(X) &&
-           stin_aligned16(C) &&
-           (precision == STIN_GEMM_BF16X3 || precision == STIN_GEMM_BF16X6 || precision == STIN_GEMM_F16X3);
-}
-struct StreamEpi {                     // MODE 0 only: C = (acc + bias [* row_mask]) + res; wpre: W pre-split (not in fragment order)
-    const float *bias = nullptr, *row_mask = nullptr, *res = nullptr;
-    int64_t ld_mask = 0, ld_res = 0;
-    int wpre = 0;
-};
-template <int MODE, bool TF>
-int stream_launch(const float* A, int64_t lda, const float* W, int64_t ldw, const float* X, int64_t ldx, const stin_bn_tf& tf,
-                  const float* P, const float* Q, float inv_n, int64_t M, int Nc, int K, double* partial, float* C, int64_t ldc,
-                  int precision, hipStream_t stream, const StreamEpi epi = StreamEpi()) {
-    StreamGeo g;
-    if (!stream_geo(M, Nc, K, TF, &g, MODE, precision)) return STIN_E_UNSUPPORTED;
-    const dim3 grid((unsigned)g.gx, (unsigned)g.ncb);
-#define STIN_STREAM(KC_, NT_, NS_, PT_)                                                                                              \
-    do {                                                                                                                             \
-        static stin_once_per_device attr_once;                                                                                                \
-        if (attr_once.first()) {                                                                                                             \
-            (void)hipFuncSetAttribute((const void*)k_gemm_nt_stream<KC_, NT_, NS_, PT_, MODE, TF>, hipFuncAttributeMaxDynamicSharedMemorySize, \
-                                      160 * 1024);                                                                                   \
-        }                                                                                                                            \
-        hipLaunchKernelGGL((k_gemm_nt_stream<KC_, NT_, NS_, PT_, MODE, TF>), grid, dim3(BLOCK), g.lds, stream, A, lda, W, ldw, M, Nc, K, X, \
-                           ldx, tf, P, Q, inv_n, partial, C, ldc, epi.bias, epi.row_mask, epi.ld_mask, epi.res, epi.ld_res, epi.wpre);       \
-    } while (0)
-#define STIN_STREAM_P(KC_, NT_)                                                  \
-    do {                                                                         \
-        if (precision == STIN_GEMM_BF16X3) STIN_STREAM(KC_, NT_, 2, __bf16);     \
-        else if (precision == STIN_GEMM_BF16X6) STIN_STREAM(KC_, NT_, 3, __bf16); \
-        else STIN_STREAM(KC_, NT_, 2, _Float16);                                 \
-    } while (0)
-    if (g.kc == 64 && g.nt == 2) STIN_STREAM_P(64, 2);
-    else if (g.kc == 64) STIN_STREAM_P(64, 4);
-    else if (g.nt == 2) STIN_STREAM_P(128, 2);
-    else STIN_STREAM_P(128, 4);
-#undef STIN_STREAM_P
-#undef STIN_STREAM
-    return stin_launch_status();
-}
-}  // namespace
-static int stream_nt_presplit_try(const float* A, int64_t lda, const float* W, int64_t ldw, const float* bias, const float* row_mask,
-                                  int64_t ld_mask, const float* residual, int64_t ld_res, int64_t M, int Nc, int K, float* C,
-                                  int64_t ldc, int precision, hipStream_t stream) {
-    // in-step A/B (profiles/r05_experiments_not_shipped.md): at 200 704 rows the headline step is 0.03 ms SLOWER with it (7.36-7.39
-    // against 7.34 ms), at 1 M rows (config 5 in fp32) 0.35 ms faster (41.45 against 41.81 ms) - the default sits between
-    const char* er = getenv("STIN_NT_STREAM_PRE_ROWS");                        // (re-read per call: tests flip it)
-    const int64_t min_rows = er != nullptr ? atoll(er) : 500000;
-    const char* e = getenv("STIN_NT_STREAM");
-    if (M < min_rows || (e != nullptr && atoi(e) == 0)) return STIN_E_UNSUPPORTED;
-    return stream_nt_epi_try(A, lda, W, ldw, bias, row_mask, ld_mask, residual, ld_res, M, Nc, K, C, ldc, precision, stream, 1);
-}
-static int stream_nt_epi_try(const float* A, int64_t lda, const float* W, int64_t ldw, const float* bias, const float* row_mask,
-                             int64_t ld_mask, const float* residual, int64_t ld_res, int64_t M, int Nc, int K, float* C, int64_t ldc,
-                             int precision, hipStream_t stream, int wpre) {
-    StreamGeo g;
-    if (!(precision == STIN_GEMM_BF16X3 || precision == STIN_GEMM_F16X3) || !stream_geo(M, Nc, K, false, &g, 0, precision) ||
-        !stream_ok(A, lda, W, ldw, nullptr, 0, C, ldc, precision) || (bias != nullptr && !stin_aligned16(bias)) ||
-        (residual != nullptr && (ld_res % 4 != 0 || !stin_aligned16(residual))))
-        return STIN_E_UNSUPPORTED;
-    StreamEpi epi;
-    epi.bias = bias;
-    epi.row_mask = row_mask;
-    epi.ld_mask = ld_mask;
-    epi.res = residual;
-    epi.ld_res = ld_res;
-    epi.wpre = wpre;
-    stin_bn_tf tf;
-    tf.mean = tf.rstd = tf.gamma = tf.beta = nullptr;
-    return stream_launch<0, false>(A, lda, W, ldw, nullptr, 0, tf, nullptr, nullptr, 0.f, M, Nc, K, nullptr, C, ldc, precision, stream, epi);
-}
 extern "C" int64_t stin_gemm_nt_bn_bwd_groups(int64_t M, int Nc, int K, int precision) {
-    if (!(precision == STIN_GEMM_BF16X3 || precision == STIN_GEMM_BF16X6 || precision == STIN_GEMM_F16X3)) return 0;
-    const char* e = getenv("STIN_NT_BNBWD");                                   // A/B switch, re-read per call (tests flip it)
-    if (e != nullptr && atoi(e) == 0) return 0;
-    // K = 256 (Nc = 512, the 18 063-vertex level of SingleConvMeshNet): the weight slice leaves room for two column tiles per block, so the
-    // A rows are re-read by 8 column blocks and the two passes (436 us) lose to the three launches (377 us, profiles/probes/bnbwd_probe.py)
-    StreamGeo g;
-    return (K <= 128 && stream_geo(M, Nc, K, false, &g, 1, precision)) ? g.gx : 0;
+    const NtSwitches sw = nt_switches();
+    return sw.bnbwd ? nt_groups(STIN_NT_PART_BN_BWD_STATS, precision, M, Nc, K, sw) : 0;
 }
 extern "C" int stin_gemm_nt_bn_bwd_stats_f32(const float* A, int64_t lda, const float* W, int64_t ldw, const float* X, int64_t ldx,
                                              const float* mean, const float* rstd, const float* gamma, const float* beta, int64_t M,
                                              int Nc, int K, int precision, double* partial, size_t partial_bytes, float* sums,
                                              stin_stream_t stream) {
-    stin_clear_stale_error();
-    STIN_REQUIRE(lda >= K && ldw >= K && ldx >= Nc, STIN_E_SIZE);
-    StreamGeo g;
-    STIN_REQUIRE(K <= 128 && stream_geo(M, Nc, K, false, &g, 1, precision) && stream_ok(A, lda, W, ldw, X, ldx, nullptr, 0, precision), STIN_E_UNSUPPORTED);
-    STIN_REQUIRE(A && W && X && mean && rstd && gamma && beta && partial && sums, STIN_E_NULL);
-    STIN_REQUIRE(partial_bytes >= (size_t)g.gx * 2 * (size_t)Nc * sizeof(double), STIN_E_WORKSPACE);
-    stin_bn_tf tf;
-    tf.mean = mean;
-    tf.rstd = rstd;
-    tf.gamma = gamma;
-    tf.beta = beta;
-    const int rc = stream_launch<1, false>(A, lda, W, ldw, X, ldx, tf, nullptr, nullptr, 0.f, M, Nc, K, partial, nullptr, 0, precision,
-                                           (hipStream_t)stream);
+    NtOperands o = {A, lda, W, ldw, nullptr, nullptr, 0, nullptr, 0, nullptr, 0};
+    o.X = X, o.ldx = ldx, o.tf = {mean, rstd, gamma, beta}, o.stats = partial;
+    NtProblem p = {0, M, Nc, K, precision, STIN_NT_PART_BN_BWD_STATS, 0, !(A && W && X && mean && rstd && gamma && beta && partial && sums)};
+    NtRoute r;
+    int rc = nt_f32_route(p, o, nt_switches(), &r);
     if (rc != STIN_OK) return rc;
-    hipLaunchKernelGGL(k_partial_sums_final, dim3((unsigned)((2 * Nc + 63) / 64)), dim3(1024), 0, (hipStream_t)stream, partial, g.gx, 2 * Nc,
-                       sums);
+    STIN_REQUIRE(partial_bytes >= (size_t)r.groups * 2 * (size_t)Nc * sizeof(double), STIN_E_WORKSPACE);
+    rc = nt_f32_launch(r, p, o, stream);
+    if (rc != STIN_OK) return rc;
+    hipLaunchKernelGGL(k_partial_sums_final, dim3((unsigned)((2 * Nc + 63) / 64)), dim3(1024), 0, (hipStream_t)stream, partial, r.groups,
+                       2 * Nc, sums);
     return stin_launch_status();
 }
 extern "C" int stin_gemm_nt_bn_bwd_apply_f32(const float* A, int64_t lda, const float* W, int64_t ldw, const float* X, int64_t ldx,
                                              const float* mean, const float* rstd, const float* gamma, const float* beta,
                                              const float* sums, float inv_n, int64_t M, int Nc, int K, float* dx, int64_t lddx,
                                              int precision, stin_stream_t stream) {
-    stin_clear_stale_error();
-    STIN_REQUIRE(lda >= K && ldw >= K && ldx >= Nc && lddx >= Nc, STIN_E_SIZE);
-    StreamGeo g;
-    STIN_REQUIRE(K <= 128 && stream_geo(M, Nc, K, false, &g, 2, precision) && stream_ok(A, lda, W, ldw, X, ldx, dx, lddx, precision), STIN_E_UNSUPPORTED);
-    STIN_REQUIRE(A && W && X && mean && rstd && gamma && beta && sums && dx, STIN_E_NULL);
-    stin_bn_tf tf;
-    tf.mean = mean;
-    tf.rstd = rstd;
-    tf.gamma = gamma;
-    tf.beta = beta;
-    return stream_launch<2, false>(A, lda, W, ldw, X, ldx, tf, sums, sums + Nc, inv_n, M, Nc, K, nullptr, dx, lddx, precision,
-                                   (hipStream_t)stream);
-}
-// The plain product C = A W^T (mean == NULL) or C = relu(gamma ((A - mean) rstd) + beta) W^T on the streaming kernel; returns
-// STIN_E_UNSUPPORTED for the shapes it does not serve (K not 64 / 128 / 256, rows not 16-byte aligned, a pre-split precision flag):
-// stin_gemm_nt_f32 / stin_gemm_nt_bn_f32 try it first for M >= 65 536 rows (STIN_NT_STREAM=0: never).
-extern "C" int stin_gemm_nt_stream_f32(const float* A, int64_t lda, const float* W, int64_t ldw, const float* mean, const float* rstd,
-                                       const float* gamma, const float* beta, int64_t M, int Nc, int K, float* C, int64_t ldc,
-                                       int precision, stin_stream_t stream) {
-    stin_clear_stale_error();
-    STIN_REQUIRE(lda >= K && ldw >= K && ldc >= Nc, STIN_E_SIZE);
-    StreamGeo g;
-    STIN_REQUIRE(stream_geo(M, Nc, K, mean != nullptr, &g, 0, precision) && stream_ok(A, lda, W, ldw, nullptr, 0, C, ldc, precision), STIN_E_UNSUPPORTED);
-    STIN_REQUIRE(A && W && C && (mean == nullptr || (rstd && gamma && beta)), STIN_E_NULL);
-    stin_bn_tf tf;
-    tf.mean = mean;
-    tf.rstd = rstd;
-    tf.gamma = gamma;
-    tf.beta = beta;
-    if (mean != nullptr)
-        return stream_launch<0, true>(A, lda, W, ldw, nullptr, 0, tf, nullptr, nullptr, 0.f, M, Nc, K, nullptr, C, ldc, precision,
-                                      (hipStream_t)stream);
-    return stream_launch<0, false>(A, lda, W, ldw, nullptr, 0, tf, nullptr, nullptr, 0.f, M, Nc, K, nullptr, C, ldc, precision,
-                                   (hipStream_t)stream);
+    NtOperands o = {A, lda, W, ldw, nullptr, nullptr, 0, nullptr, 0, dx, lddx};
+    o.X = X, o.ldx = ldx, o.tf = {mean, rstd, gamma, beta}, o.P = sums, o.Q = sums + Nc, o.inv_n = inv_n;
+    return nt_f32(STIN_NT_PART_BN_BWD_APPLY, precision, M, Nc, K, o, !(A && W && X && mean && rstd && gamma && beta && sums && dx),
+                  nt_switches(), stream);
 }
 
-// The GEMM plus the FIRST stage of the instance-norm statistics of its output: colstats [groups][2][Nc] doubles, groups =
-// ceil(M / 64) (stin_gemm_nt_colstats_groups; 0 = this shape / precision does not support it: only the all-columns kernel's
-// blocks own whole rows).  Second stage: stin_moments_final_f32.
+// The GEMM plus the FIRST stage of the instance-norm statistics of its output: colstats [groups][2][Nc] doubles (groups =
+// stin_gemm_nt_colstats_groups; 0 = this shape / precision does not support it: only the all-columns kernel's blocks own whole
+// rows - one group per 64 rows - and the panel kernel folds two groups per row block).  Second stage: stin_moments_final_f32.
 extern "C" int64_t stin_gemm_nt_colstats_groups(int64_t M, int Nc, int K, int precision) {
-    const bool ok = (precision & STIN_GEMM_W_PRESPLIT) && (precision & STIN_GEMM_W_FRAG) && Nc <= 256 && stin_w_frag_shape(Nc, K);
-    const int p = precision & ~(STIN_GEMM_W_PRESPLIT | STIN_GEMM_W_FRAG);
-    if (!ok || M <= 0 || (p != STIN_GEMM_BF16X3 && p != STIN_GEMM_F16X3)) return 0;
-    const int pmts = panel_tiles(M, Nc, K);                 // (the colstats launches carry 16-byte aligned rows: the same choice
-    if (pmts > 0) return 2 * ((M + 32 * pmts - 1) / (32 * pmts));   //  as gemm_nt_f32_impl) two row groups per panel-kernel row block
-    return (M + 63) / 64;                                   // one statistics group per wave row group (64 rows)
+    return nt_groups(STIN_NT_PART_COLSTATS, precision, M, Nc, K, nt_switches());
 }
 extern "C" int stin_gemm_nt_colstats_f32(const float* A, int64_t lda, const float* W, int64_t ldw, const float* bias,
                                          const float* row_mask, int64_t ld_mask, const float* residual, int64_t ld_res,
                                          int64_t M, int Nc, int K, float* C, int64_t ldc, int precision, double* colstats,
                                          size_t colstats_bytes, stin_stream_t stream) {
-    const int64_t groups = stin_gemm_nt_colstats_groups(M, Nc, K, precision);
+    const NtSwitches sw = nt_switches();
+    const int64_t groups = nt_groups(STIN_NT_PART_COLSTATS, precision, M, Nc, K, sw);
     STIN_REQUIRE(groups > 0, STIN_E_UNSUPPORTED);
     STIN_REQUIRE(colstats != nullptr, STIN_E_NULL);
     STIN_REQUIRE(colstats_bytes >= (size_t)groups * 2 * (size_t)Nc * sizeof(double), STIN_E_WORKSPACE);
-    return gemm_nt_f32_impl(A, lda, W, ldw, bias, row_mask, ld_mask, residual, ld_res, M, Nc, K, C, ldc, precision, colstats, stream);
+    NtOperands o = {A, lda, W, ldw, bias, row_mask, ld_mask, residual, ld_res, C, ldc};
+    o.stats = colstats;
+    return nt_f32(nt_parts(bias, row_mask, residual) | STIN_NT_PART_COLSTATS, precision, M, Nc, K, o, !(A && W && C), sw, stream);
 }
 
 // The GEMM plus the first stage of the instance-norm + ELU BACKWARD statistics of the layer whose output gradient it produces
-// (NtDotElu above): partial [groups][2][Nc] doubles, groups = stin_gemm_nt_dotelu_groups (0: this shape / precision is not served
+// (NtDotElu): partial [groups][2][Nc] doubles, groups = stin_gemm_nt_dotelu_groups (0: this shape / precision is not served
 // by the panel kernel - the caller keeps its separate reduction).  Second stage: stin_norm_coef_from_partials_f32.
 extern "C" int64_t stin_gemm_nt_dotelu_groups(int64_t M, int Nc, int K, int precision) {
-    const bool ok = (precision & STIN_GEMM_W_PRESPLIT) && (precision & STIN_GEMM_W_FRAG) && stin_w_frag_shape(Nc, K);
-    const int p = precision & ~(STIN_GEMM_W_PRESPLIT | STIN_GEMM_W_FRAG);
-    if (!ok || M <= 0 || (p != STIN_GEMM_BF16X3 && p != STIN_GEMM_F16X3)) return 0;
-    const char* e = getenv("STIN_DOTELU_FUSED");                           // A/B switch, re-read per call (tests flip it)
-    if (e != nullptr && atoi(e) == 0) return 0;
-    const int pmts = panel_tiles(M, Nc, K);
-    return pmts > 0 ? 2 * ((M + 32 * pmts - 1) / (32 * pmts)) : 0;
+    return nt_groups(STIN_NT_PART_COLSTATS | STIN_NT_PART_DOTELU, precision, M, Nc, K, nt_switches());
 }
 extern "C" int stin_gemm_nt_dotelu_f32(const float* A, int64_t lda, const float* W, int64_t ldw, const float* bias,
                                        const float* residual, int64_t ld_res, int64_t M, int Nc, int K, float* C, int64_t ldc,
                                        int precision, const float* nx, int64_t ld_nx, const float* nmean, const float* nrstd,
                                        double* partial, size_t partial_bytes, stin_stream_t stream) {
-    const int64_t groups = stin_gemm_nt_dotelu_groups(M, Nc, K, precision);
+    const NtSwitches sw = nt_switches();
+    const int64_t groups = nt_groups(STIN_NT_PART_COLSTATS | STIN_NT_PART_DOTELU, precision, M, Nc, K, sw);
     STIN_REQUIRE(groups > 0, STIN_E_UNSUPPORTED);
     STIN_REQUIRE(nx && nmean && nrstd && partial, STIN_E_NULL);
     STIN_REQUIRE(ld_nx >= Nc, STIN_E_SIZE);
     STIN_REQUIRE(ld_nx % 4 == 0 && stin_aligned16(nx) && stin_aligned16(nmean) && stin_aligned16(nrstd), STIN_E_ALIGN);
     STIN_REQUIRE(partial_bytes >= (size_t)groups * 2 * (size_t)Nc * sizeof(double), STIN_E_WORKSPACE);
-    NtDotElu de;
-    de.x = nx;
-    de.ldx = ld_nx;
-    de.mean = nmean;
-    de.rstd = nrstd;
-    return gemm_nt_f32_impl(A, lda, W, ldw, bias, nullptr, 0, residual, ld_res, M, Nc, K, C, ldc, precision, partial, stream, &de);
+    NtOperands o = {A, lda, W, ldw, bias, nullptr, 0, residual, ld_res, C, ldc};
+    o.stats = partial;
+    o.de.x = nx, o.de.ldx = ld_nx, o.de.mean = nmean, o.de.rstd = nrstd;
+    return nt_f32(nt_parts(bias, nullptr, residual) | STIN_NT_PART_COLSTATS | STIN_NT_PART_DOTELU, precision, M, Nc, K, o, !(A && W && C), sw,
+                  stream);
+}
+
+// The route an NT product of this description takes - host only: nothing is launched, no device is touched (stin_hip.h).
+extern "C" int stin_gemm_nt_geometry(int storage, int64_t M, int Nc, int K, int precision, int parts, int align, int cu, int32_t* out10) {
+    STIN_REQUIRE(out10 != nullptr, STIN_E_NULL);
+    STIN_REQUIRE(storage == 0 || storage == 1, STIN_E_UNSUPPORTED);
+    STIN_REQUIRE(M >= 0 && Nc > 0 && K > 0 && cu > 0, STIN_E_SIZE);
+    const NtProblem p = {storage, M, Nc, K, precision, parts, align, false};
+    const NtRoute r = nt_route(p, nt_switches(), cu);
+    if (r.status != STIN_OK) return r.status;
+    const int64_t v[10] = {r.family, r.bm, r.bn, r.param, r.vec, r.vec_out, r.lds, r.grid, r.grid_y, r.groups};
+    for (int i = 0; i < 10; ++i) out10[i] = (int32_t)v[i];
+    return STIN_OK;
 }
 
 extern "C" size_t stin_gemm_tn_workspace_bytes(int64_t M, int Nc, int K, int ones_column) {
@@ -651,10 +459,8 @@ int stin_tn_slabs(const stin_tn_problem* p, int storage, int precision, stin_str
 #define STIN_TNTR(WI_, WJ_, MT_, NT_)                                                                                  \
     do {                                                                                                              \
         typedef TrGeom<WI_, WJ_, MT_, NT_> Geo_;                                                                      \
-        static stin_once_per_device attr_once;                                                                                 \
-        if (attr_once.first()) {                                                                                              \
-            (void)hipFuncSetAttribute((const void*)k_gemm_tn_b16_tr<WI_, WJ_, MT_, NT_>, hipFuncAttributeMaxDynamicSharedMemorySize, Geo_::LDS); \
-        }                                                                                                             \
+        static stin_once_per_device raised;                                                                           \
+        stin_raise_dynamic_lds(raised, (const void*)k_gemm_tn_b16_tr<WI_, WJ_, MT_, NT_>, Geo_::LDS);                 \
         hipLaunchKernelGGL((k_gemm_tn_b16_tr<WI_, WJ_, MT_, NT_>), dim3((unsigned)blocks), dim3(Geo_::THREADS), Geo_::LDS, stream, G, ldg, X, \
                            ldx, M, Nc, K, Kq, has_bias, row_weight, ld_weight, rows, tiles_i, tiles_j, chunks, slab);  \
     } while (0)
@@ -778,6 +584,14 @@ extern "C" int stin_gemm_tn_wb_f32(const float* G, int64_t ldg, const float* X, 
 }
 
 // ------------------------------------------------------------------ bf16-storage entry points
+namespace {
+template <int BM, int BN, int WM, int WN, typename OUT, typename Args>
+void nt_launch_b16_tile(const NtRoute& r, bool wb, const NtLaunch& l, const Args& a) {
+    if (wb) nt_launch<k_gemm_nt_b16<BM, BN, WM, WN, OUT, true, true>>(l, a);
+    else if (r.vec) nt_launch<k_gemm_nt_b16<BM, BN, WM, WN, OUT, true>>(l, a);
+    else nt_launch<k_gemm_nt_b16<BM, BN, WM, WN, OUT, false>>(l, a);
+}
+}  // namespace
 extern "C" int stin_gemm_nt_bf16(const stin_bf16_t* A_, int64_t lda, const float* W, int64_t ldw, const float* bias,
                                  const stin_bf16_t* row_mask_, int64_t ld_mask, const stin_bf16_t* residual_,
                                  int64_t ld_res, int64_t M, int Nc, int K, void* C, int64_t ldc, int c_is_f32,
@@ -789,61 +603,31 @@ extern "C" int stin_gemm_nt_bf16(const stin_bf16_t* A_, int64_t lda, const float
     const stin_bf16* residual = reinterpret_cast<const stin_bf16*>(residual_);
     STIN_REQUIRE(M >= 0 && Nc > 0 && K > 0 && lda >= K && ldw >= K && ldc >= Nc, STIN_E_SIZE);
     STIN_REQUIRE(residual == nullptr || ld_res >= Nc, STIN_E_SIZE);
-    if (M == 0) return STIN_OK;
-    STIN_REQUIRE(A && W && C, STIN_E_NULL);
     const bool wb = (c_is_f32 & STIN_GEMM_W_BF16) != 0;          // flags: bit 0 = fp32 output, STIN_GEMM_W_BF16 = bf16 weight operand
-    c_is_f32 &= 1;
-    const bool vec = (K % 8 == 0) && (lda % 8 == 0) && (ldw % (wb ? 8 : 4) == 0) && stin_aligned16(A) && stin_aligned16(W);
-    STIN_REQUIRE(!wb || vec, STIN_E_ALIGN);
-    const int vec_out = (!c_is_f32 && Nc % 8 == 0 && ldc % 8 == 0 && stin_aligned16(C)) ? 1 : 0;
-    // 64x64 is the best tile for every shape of the shipped 3-level network; long reductions with enough tiles (the wide
-    // layers of a 5-level network) are 1.1-1.5x faster on 128x64 (profiles/gemm_tiles.py)
-    const int force_tile = stin_nt_force_tile();
-    const bool tall_tile = K >= 512 && ((M + 127) / 128) * ((Nc + 63) / 64) >= 1000;
-#define STIN_NTB(BM_, BN_, WM_, WN_, OUT_)                                                                             \
-    do {                                                                                                               \
-        dim3 grid(nt_grid(M, Nc, BM_, BN_));                                                                           \
-        if (wb) hipLaunchKernelGGL((k_gemm_nt_b16<BM_, BN_, WM_, WN_, OUT_, true, true>), grid, dim3(BLOCK), 0, stream, A, lda, W, ldw, bias, row_mask, ld_mask, residual, ld_res, M, Nc, K, (OUT_*)C, ldc, vec_out); \
-        else if (vec) hipLaunchKernelGGL((k_gemm_nt_b16<BM_, BN_, WM_, WN_, OUT_, true>), grid, dim3(BLOCK), 0, stream, A, lda, W, ldw, bias, row_mask, ld_mask, residual, ld_res, M, Nc, K, (OUT_*)C, ldc, vec_out); \
-        else hipLaunchKernelGGL((k_gemm_nt_b16<BM_, BN_, WM_, WN_, OUT_, false>), grid, dim3(BLOCK), 0, stream, A, lda, W, ldw, bias, row_mask, ld_mask, residual, ld_res, M, Nc, K, (OUT_*)C, ldc, vec_out);    \
-    } while (0)
-#define STIN_NTB_PICK(OUT_)                                                                          \
-    do {                                                                                             \
-        if (Nc <= 32) STIN_NTB(128, 32, 4, 1, OUT_);                                                 \
-        else if (force_tile == 1) STIN_NTB(128, 128, 2, 2, OUT_);                                    \
-        else if (force_tile == 2 || (force_tile == 0 && tall_tile)) STIN_NTB(128, 64, 2, 2, OUT_);   \
-        else STIN_NTB(64, 64, 2, 2, OUT_);                                                           \
-    } while (0)
-    // fat shapes with bf16 weights: the LDS-DMA kernel (STIN_NT_GLDS=0 keeps the register-staged tiles: tuning aid / A-B)
-    if (wb && K % BKB == 0 && nt_b16_glds_pays(M, Nc, K)) {
-        const stin_bf16* Wb = reinterpret_cast<const stin_bf16*>(W);
-#define STIN_GLDS(OUT_, WM_, WN_, MT_, NT_)                                                                             \
-    do {                                                                                                               \
-        typedef GlGeom<WM_, WN_, MT_, NT_> Geo_;                                                                       \
-        static stin_once_per_device attr_once;                                                                                  \
-        if (attr_once.first()) {                                                                                               \
-            (void)hipFuncSetAttribute((const void*)k_gemm_nt_b16_glds<OUT_, WM_, WN_, MT_, NT_>, hipFuncAttributeMaxDynamicSharedMemorySize, Geo_::LDS); \
-        }                                                                                                              \
-        const int64_t nrow = (M + Geo_::BM - 1) / Geo_::BM, ncol = (Nc + Geo_::BN - 1) / Geo_::BN;                     \
-        dim3 grid(ncol % 8 == 0 ? (unsigned)(nrow * ncol) : nt_grid(M, Nc, Geo_::BM, Geo_::BN));                       \
-        hipLaunchKernelGGL((k_gemm_nt_b16_glds<OUT_, WM_, WN_, MT_, NT_>), grid, dim3(Geo_::THREADS), Geo_::LDS, stream, A, lda, Wb, ldw, \
-                           bias, row_mask, ld_mask, residual, ld_res, M, Nc, K, (OUT_*)C, ldc, vec_out);                \
-    } while (0)
-        const bool big = nt_b16_big_tile(M, Nc, K);
-        if (c_is_f32) {
-            if (big) STIN_GLDS(float, 2, 4, 4, 2);
-            else STIN_GLDS(float, 2, 2, 2, 2);
-        } else {
-            if (big) STIN_GLDS(stin_bf16, 2, 4, 4, 2);
-            else STIN_GLDS(stin_bf16, 2, 2, 2, 2);
+    const bool in16 = lda % 8 == 0 && ldw % (wb ? 8 : 4) == 0 && stin_aligned16(A) && stin_aligned16(W);
+    const NtProblem p = {1, M, Nc, K, wb ? STIN_GEMM_W_BF16 : 0, (c_is_f32 & 1) ? STIN_NT_PART_OUT_F32 : 0,
+                         (in16 ? STIN_NT_ALIGN_IN : 0) | ((ldc % 8 == 0 && stin_aligned16(C)) ? STIN_NT_ALIGN_OUT : 0), !(A && W && C)};
+    const NtRoute r = nt_route(p, nt_switches(), stin_cu_count());
+    if (r.status != STIN_OK || r.family == STIN_NT_NONE) return r.status;
+    auto launch = [&](auto* c) {                                    // c: the output rows in their type, float or bf16
+        typedef typename std::remove_pointer<decltype(c)>::type OUT;
+        const auto head = std::make_tuple(A, lda);
+        const auto tail = std::make_tuple(ldw, bias, row_mask, ld_mask, residual, ld_res, M, Nc, K, c, ldc, r.vec_out);
+        if (r.family == STIN_NT_B16_GLDS) {
+            const auto a = std::tuple_cat(head, std::make_tuple(reinterpret_cast<const stin_bf16*>(W)), tail);
+            const NtLaunch l = {dim3((unsigned)r.grid), r.bm == 256 ? 512 : 256, r.lds, (int)r.lds, stream};
+            if (r.bm == 256) nt_launch<k_gemm_nt_b16_glds<OUT, 2, 4, 4, 2>>(l, a);
+            else nt_launch<k_gemm_nt_b16_glds<OUT, 2, 2, 2, 2>>(l, a);
+            return;
         }
-#undef STIN_GLDS
-        return stin_launch_status();
-    }
-    if (c_is_f32) STIN_NTB_PICK(float);
-    else STIN_NTB_PICK(stin_bf16);
-#undef STIN_NTB_PICK
-#undef STIN_NTB
+        const auto a = std::tuple_cat(head, std::make_tuple(W), tail);
+        const NtLaunch l = {dim3((unsigned)r.grid), BLOCK, 0, 0, stream};
+        if (r.bn == 32) nt_launch_b16_tile<128, 32, 4, 1, OUT>(r, wb, l, a);
+        else if (r.bm == 128) nt_launch_b16_tile<128, 64, 2, 2, OUT>(r, wb, l, a);
+        else nt_launch_b16_tile<64, 64, 2, 2, OUT>(r, wb, l, a);
+    };
+    if (c_is_f32 & 1) launch(static_cast<float*>(C));
+    else launch(static_cast<stin_bf16*>(C));
     return stin_launch_status();
 }
 

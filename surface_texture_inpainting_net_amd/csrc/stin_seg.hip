@@ -238,9 +238,8 @@ void seg_launch_fwd(int blocks, size_t lds, hipStream_t stream, const float* log
                     const int64_t* target, int64_t N, int C, const float* weight, int64_t ignore_index, double* partial,
                     unsigned long long* conf, int32_t* bad) {
     if (lds > 64 * 1024) {
-        static stin_once_per_device attr_once;
-        if (attr_once.first())
-            (void)hipFuncSetAttribute((const void*)k_seg_ce_fwd<L, F, R>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
+        static stin_once_per_device raised;
+        stin_raise_dynamic_lds(raised, (const void*)k_seg_ce_fwd<L, F, R>, 160 * 1024);
     }
     hipLaunchKernelGGL((k_seg_ce_fwd<L, F, R>), dim3((unsigned)blocks), dim3(SEG_BLOCK), lds, stream, logits, ld, M, rows, target, N,
                        C, weight, ignore_index, partial, conf, bad);

@@ -313,10 +313,8 @@ int linear_tanh_bwd_impl(const float* g, const float* y, const T* x, int64_t ldx
     const int CH = K <= 64 ? 1 : (K <= 128 ? 2 : 4);
 #define STIN_TL_B(NC_, CH_)                                                                                                          \
     do {                                                                                                                             \
-        static stin_once_per_device attr_once;                                                                                                \
-        if (attr_once.first()) {                                                                                                             \
-            (void)hipFuncSetAttribute((const void*)k_linear_tanh_bwd<T, NC_, CH_>, hipFuncAttributeMaxDynamicSharedMemorySize, 64 * 1024); \
-        }                                                                                                                            \
+        static stin_once_per_device raised;                                                                                          \
+        stin_raise_dynamic_lds(raised, (const void*)k_linear_tanh_bwd<T, NC_, CH_>, 64 * 1024);                                      \
         hipLaunchKernelGGL((k_linear_tanh_bwd<T, NC_, CH_>), dim3((unsigned)blocks), dim3(TL_BWD_BLOCK), lds, stream, g, y, x, ldx, W, N, K, \
                            dx, lddx, partial, slot, dW, db);                                                                         \
     } while (0)

@@ -342,7 +342,7 @@ PREC_BWD = int(os.environ.get('STIN_GEMM_BWD', GEMM_BF16X3))
 GEMM_W_PRESPLIT = _C['STIN_GEMM_W_PRESPLIT']   # nt: the weight operand already holds its two 16-bit pieces (stin_hip.h)
 GEMM_W_BF16 = _C['STIN_GEMM_W_BF16']           # stin_gemm_nt_bf16: the weight operand holds bf16 [Nc][K] (stin_hip.h)
 # pre-split operands in MFMA fragment order where the shape allows (stin_hip.h STIN_GEMM_W_FRAG): what the resident-strip NT
-# kernel reads.  STIN_NT_STRIP=0 keeps the k-group layout and with it the tiled kernel (A/B aid).
+# kernel reads.  Without the flag the operand keeps the k-group layout and with it the tiled kernel (tests flip GEMM_W_FRAG for that A/B).
 GEMM_W_FRAG = _C['STIN_GEMM_W_FRAG']           # (a module constant since round 6; tests flip the attribute)
 WEIGHT_PRESPLIT = True
 # one C call per direction for a GraphResnetBlock or a run of them (NetFn: stin_net_fwd / _bwd enqueue the same kernels in the

@@ -465,19 +465,16 @@ def test_edgeconv_wgrad_equals_two_tn_gemms_plus_unpack(N, Cin, Cout, shortcut, 
     assert float((got[2].double() - ref).abs().max()) <= 3e-5 * float(ref.abs().max()) + 1e-6
 
 
-def _panel_tiles(M, Nc, K, forced, cu=256):
-    """Host mirror of panel_tiles() in csrc/stin_gemm.hip: 32-row tiles per block of the balanced column-panel NT kernel (0 = not used)."""
-    if forced == 0 or Nc % 128 or K % 64 or M <= 0:
-        return 0
-    P, rg = Nc // 128, (M + 31) // 32
-    for rounds in range(1, (64 if forced == 1 else 1) + 1):
-        slots = cu * rounds // P
-        if slots < 1:
-            continue
-        mts = (rg + slots - 1) // slots
-        if mts <= 9:
-            return (2 if forced == 1 else 0) if mts < 2 else mts
-    return 0
+def _panel_tiles_on_device(M, Nc, K):
+    """32-row tiles per block of the balanced column-panel NT kernel for a fragment-order product of this shape (0 = another kernel runs
+    it): asked of the route query stin_gemm_nt_geometry with the device's CU count, under the switches in force."""
+    import ctypes
+    out = (ctypes.c_int32 * 10)()
+    prec = SF.GEMM_BF16X3 | SF.GEMM_W_PRESPLIT | SF.GEMM_W_FRAG
+    cu = torch.cuda.get_device_properties(torch.device(DEV)).multi_processor_count
+    rc = _lib_load().stin_gemm_nt_geometry(0, M, Nc, K, prec, 0, 15, cu, ctypes.addressof(out))
+    assert rc == 0, rc
+    return out[3] if out[0] == SF._C['STIN_NT_PANEL'] else 0
 
 
 @pytest.mark.parametrize('panel', ['0', '1'])
@@ -507,7 +504,7 @@ def test_gemm_nt_with_fused_column_statistics(M, Nc, K, panel, monkeypatch):
     SF._call('stin_gemm_nt_colstats_f32', SF._ptr(A), A.stride(0), SF._ptr(Wf), K, SF._ptr(b), SF._ptr(A[:, K]), A.stride(0), None, 0,
              M, Nc, K, SF._ptr(C), Nc, prec, SF._ptr(guard), partial.numel() * 8, SF._stream(A))
     assert torch.equal(guard[:partial.numel()].view_as(partial), partial) and float((guard[partial.numel():] + 7.0).abs().max()) == 0.0
-    mts = _panel_tiles(M, Nc, K, int(panel))
+    mts = _panel_tiles_on_device(M, Nc, K)
     if mts == 0:
         bounds = [(i * 64, min(M, i * 64 + 64)) for i in range((M + 63) // 64)]
     else:                                                   # row block rb: rows [rb BM, rb BM + 32 MT0) and [.., (rb + 1) BM)
@@ -555,7 +552,7 @@ def test_gemm_nt_with_fused_norm_backward_statistics(M, Nc, K, res, monkeypatch)
     assert got is not None
     C, partial = got
     assert torch.equal(C, plain)
-    mts = _panel_tiles(M, Nc, K, 1)
+    mts = _panel_tiles_on_device(M, Nc, K)
     bm, mt0 = 32 * mts, 32 * ((mts + 1) // 2)
     bounds = []
     for rb in range((M + bm - 1) // bm):
@@ -608,7 +605,7 @@ def test_gemm_nt_panel_kernel_equals_tiled_kernel(M, Nc, K, monkeypatch):
                 new = SF.gemm_nt(A, Wf, precision=prec | SF.GEMM_W_PRESPLIT | FR, **kw)
                 assert torch.equal(new, tiled) and torch.equal(old, tiled), (prec, sorted(kw))
         if frag and Nc % 128 == 0:
-            assert _panel_tiles(M, Nc, K, 1) >= 2
+            assert _panel_tiles_on_device(M, Nc, K) >= 2
             wide = torch.full((M + 2, Nc + 8), 3.0, device=DEV)              # output as a view into a wider matrix
             SF.gemm_nt(A, Wf, b, residual=res, out=wide[1:M + 1, 4:Nc + 4], precision=prec | SF.GEMM_W_PRESPLIT | FR)
             assert torch.equal(wide[1:M + 1, 4:Nc + 4], SF.gemm_nt(A, Wk, b, residual=res, precision=prec | SF.GEMM_W_PRESPLIT))
