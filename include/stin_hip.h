@@ -383,14 +383,26 @@ size_t stin_gemm_tn_workspace_bytes(int64_t M, int Nc, int K, int ones_column);
 int stin_gemm_tn_f32(const float* G, int64_t ldg, const float* X, int64_t ldx, int64_t M, int Nc, int K,
                      int ones_column, const float* row_weight, int64_t ld_weight, float* dW, int64_t lddw,
                      int precision, void* workspace, size_t workspace_bytes, stin_stream_t stream);
-/* The geometry a TN product of this shape runs on - host only: nothing is launched, no device is touched.  storage 0 = fp32 rows,
- * 1 = bf16 rows; ldg / ldx in elements; aligned16 != 0: both operand bases are 16-byte aligned; precision as stin_gemm_tn_f32
- * (bf16 rows: STIN_GEMM_BF16X3).  out8 = { TI, TJ, tiles_i, tiles_j, rows_per_chunk, chunks, vec, ws_eligible }: the output tile
- * (TI == 0: the skinny-K kernel, whose block owns all columns), the tile counts along Nc and K, the rows of one chunk and the number
- * of chunks = partial slabs, vec = 16-byte operand loads, ws_eligible = the producer / consumer kernel takes it.  The A/B switches
- * STIN_TN_WS and STIN_TN_BIG are honoured as by the products themselves; returns their argument errors. */
+/* The geometry a TN product of this shape runs on - host only: nothing is launched, no device is touched; the TN entry points ask the
+ * same function (tn_route, csrc/gemm_tn_route.inc).  storage 0 = fp32 rows, 1 = bf16 rows; ldg / ldx in elements; aligned16 != 0: both
+ * operand bases are 16-byte aligned; precision as stin_gemm_tn_f32 (bf16 rows: STIN_GEMM_BF16X3).  out8 = { TI, TJ, tiles_i, tiles_j,
+ * rows_per_chunk, chunks, vec, ws_eligible }: the output tile (TI == 0: the skinny-K kernel, whose block owns all columns), the tile
+ * counts along Nc and K, the rows of one chunk and the number of chunks = partial slabs, vec = 16-byte operand loads, ws_eligible =
+ * the producer / consumer kernel takes it.  The A/B switches STIN_TN_WS, STIN_TN_BIG and STIN_TN_TR are honoured as by the products
+ * themselves; returns their argument errors and then writes nothing. */
 int stin_gemm_tn_geometry(int storage, int64_t M, int Nc, int K, int64_t ldg, int64_t ldx, int aligned16, int ones_column,
                           int precision, int32_t* out8);
+/* The same query with the kernel named: out10 (ten int32) = the eight values of stin_gemm_tn_geometry, then the kernel family
+ * (STIN_TN_FAMILY_*) and the blocks of its grid.  A query of its own because stin_gemm_tn_geometry's callers hold eight values. */
+#define STIN_TN_FAMILY_NONE 0      /* no rows: only the fold is launched */
+#define STIN_TN_FAMILY_SKINNY 1    /* k_gemm_tn_skinny (fp32 rows, K <= 16: exact fp32 whatever the precision) */
+#define STIN_TN_FAMILY_F32 2       /* k_gemm_tn, exact fp32 tiles */
+#define STIN_TN_FAMILY_BF16S 3     /* k_gemm_tn_bf16s, the four-wave split-bf16 kernel (bf16x3 / bf16x6) */
+#define STIN_TN_FAMILY_PC 4        /* k_gemm_tn_ws, the producer / consumer kernel (bf16x3, 128 x 128) */
+#define STIN_TN_FAMILY_B16_REG 5   /* k_gemm_tn_b16, bf16 rows transposed in registers */
+#define STIN_TN_FAMILY_B16_TR 6    /* k_gemm_tn_b16_tr, bf16 rows through transposed LDS reads (128 x 128, 256 x 256) */
+int stin_gemm_tn_route(int storage, int64_t M, int Nc, int K, int64_t ldg, int64_t ldx, int aligned16, int ones_column,
+                       int precision, int32_t* out10);
 
 /* The route an NT product takes - which kernel family, on what tile, grid and LDS - host only: nothing is launched, no device is
  * touched.  The counterpart of stin_gemm_tn_geometry; the NT entry points ask the same function (csrc/gemm_nt_route.inc).

@@ -1,6 +1,8 @@
 // Profiling harness (not part of the library): the producer / consumer TN kernel compiled with in-kernel s_memtime stamps.
 //   hipcc --offload-arch=gfx950 -O3 -std=c++17 -ffp-contract=off -fno-slp-vectorize -DSTIN_WS_STAMPS -I surface_texture_inpainting_net_amd/csrc \
-//       profiles/tn_stamps.hip surface_texture_inpainting_net_amd/csrc/{stin_gemm,stin_api}.o -o profiles/probes/tn_stamps
+//       -c profiles/tn_stamps.hip -o tn_stamps.o
+//   hipcc --offload-arch=gfx950 tn_stamps.o surface_texture_inpainting_net_amd/csrc/{stin_gemm,stin_api}.o -o profiles/probes/tn_stamps
+// (the rules and the tiled kernels come from stin_gemm.o: stin_tn_setup gives the kernel argument and the route of the product)
 // Prints, for a few blocks, the cycle stamps of producer wave 4 and consumer wave 0 (deltas between consecutive stamps).
 #include "../surface_texture_inpainting_net_amd/csrc/stin_wgrad.hip"
 #include <cstdio>
@@ -19,18 +21,16 @@ int main(int argc, char** argv) {
     const size_t wsb = stin_gemm_tn_workspace_bytes(M, Nc, K, 1);
     hipMalloc(&slab, wsb);
     stin_tn_problem p;
-    int ok = 0;
-    stin_tn_problem_init(&p, 0, G, Nc, X, K, M, Nc, K, 1, nullptr, 0, STIN_GEMM_BF16X3, slab, &ok);
-    printf("chunks %lld rows/chunk %d tiles %d x %d eligible %d\n", (long long)p.chunks, p.rows_per_chunk, p.tiles_i, p.tiles_j, ok);
-    stin_tn_batch b;
-    b.p[0] = p;
-    b.p[1] = p;
-    b.n = 1;
+    TnRoute r;
+    const int rc = stin_tn_setup(&p, &r, stin_tn_switches(), 0, G, Nc, X, K, M, Nc, K, 1, nullptr, 0, STIN_GEMM_BF16X3, slab, nullptr, nullptr);
+    printf("chunks %lld rows/chunk %d tiles %d x %d family %d grid %lld\n", (long long)p.chunks, p.rows_per_chunk, p.tiles_i, p.tiles_j,
+           r.family, (long long)r.grid);
+    if (rc != STIN_OK || r.family != STIN_TN_FAMILY_PC) return 1;      // (not a shape of the producer / consumer kernel)
     unsigned long long* stamps;
     const size_t nblk = 4096;
     hipMalloc(&stamps, nblk * 8 * 64 * 8);
     hipMemset(stamps, 0, nblk * 8 * 64 * 8);
-    for (int it = 0; it < 3; ++it) stin_tn_ws_launch(b, nullptr);      // warm (stamps off)
+    for (int it = 0; it < 3; ++it) stin_tn_ws_launch(&p, &r, nullptr, nullptr, nullptr);      // warm (stamps off)
     hipDeviceSynchronize();
     hipMemcpyToSymbol(HIP_SYMBOL(stin_ws_stamp_buf), &stamps, sizeof(stamps));
     hipEvent_t e0, e1;
@@ -38,7 +38,7 @@ int main(int argc, char** argv) {
     hipEventCreate(&e1);
     if (argc > 4) setenv("STIN_TN_WS_PRIO", argv[4], 1);      // prio | ablation bits << 4
     hipEventRecord(e0, nullptr);
-    stin_tn_ws_launch(b, nullptr);
+    stin_tn_ws_launch(&p, &r, nullptr, nullptr, nullptr);
     hipEventRecord(e1, nullptr);
     hipDeviceSynchronize();
     float ms = 0;

@@ -364,13 +364,9 @@ __global__ __launch_bounds__(BLOCK) void k_gemm_tn_b16(const stin_bf16* __restri
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int wi = wave >> 1, wj = wave & 1;
     const int tiles = tiles_i * tiles_j;
-    const int64_t b = blockIdx.x;
-    // chunks >= 8: XCD x (blocks b = x mod 8) owns the row chunks x, x+8, ... - its tiles re-read the same rows from its own L2.
-    // Fewer chunks than XCDs (the wide layers: >= 64 output tiles): plain order, so that every XCD gets tiles of every chunk.
-    const int64_t xcd = b % 8, q = b / 8;
-    const int64_t chunk = chunks >= 8 ? (q / tiles) * 8 + xcd : b / tiles;
-    const int tile = (int)(chunks >= 8 ? q % tiles : b % tiles);
-    if (chunk >= chunks) return;
+    int64_t chunk;
+    int tile;
+    if (!tn_block_map(blockIdx.x, chunks, tiles, chunk, tile)) return;   // block-uniform
     const int tj = tile % tiles_j, ti = tile / tiles_j;
     const int i0 = ti * TI, j0 = tj * TJ;
     const int64_t mb = chunk * rows_per_chunk;
@@ -565,11 +561,9 @@ __global__ __launch_bounds__(64 * WI * WJ) void k_gemm_tn_b16_tr(const stin_bf16
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int wi = wave / WJ, wj = wave % WJ;
     const int tiles = tiles_i * tiles_j;
-    const int64_t b = blockIdx.x;
-    const int64_t xcd = b % 8, q8 = b / 8;                                     // (block -> chunk / tile as k_gemm_tn_b16)
-    const int64_t chunk = chunks >= 8 ? (q8 / tiles) * 8 + xcd : b / tiles;
-    const int tile = (int)(chunks >= 8 ? q8 % tiles : b % tiles);
-    if (chunk >= chunks) return;
+    int64_t chunk;
+    int tile;
+    if (!tn_block_map(blockIdx.x, chunks, tiles, chunk, tile)) return;   // block-uniform
     const int tj = tile % tiles_j, ti = tile / tiles_j;
     const int i0 = ti * TI, j0 = tj * TJ;
     const int64_t mb = chunk * rows_per_chunk;

@@ -1,6 +1,6 @@
 // Host only: WHICH kernel runs an NT product C = A W^T (+ epilogue), on what tile, grid and LDS.  One pure function, nt_route, asked
 // by every NT entry point of stin_gemm.hip, the three *_groups queries and stin_gemm_nt_geometry (tests/_nt_table.py: the points it
-// must reach).  Of the kernel files it names only constants (ST_PANEL, WD_KC, BKB, GlGeom).  The TN rules: gemm_tn_skinny.inc.
+// must reach).  Of the kernel files it names only constants (ST_PANEL, WD_KC, BKB, GlGeom).  The TN rules: gemm_tn_route.inc.
 // The A/B switches of the NT routes, read ONCE per entry-point call (tests flip them between calls) - the only getenv of NT host code.
 struct NtSwitches {
     bool stream;               // STIN_NT_STREAM=0: never the streaming kernel on its own account (rows >= a threshold)

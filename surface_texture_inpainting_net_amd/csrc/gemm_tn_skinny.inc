@@ -1,4 +1,4 @@
-// TN products with K <= 16 (k_gemm_tn_skinny), the slab reduction and the host-side tile / chunk rules
+// TN products with K <= 16 (k_gemm_tn_skinny) and the slab reduction (k_reduce_slabs).  The host rules: gemm_tn_route.inc.
 // Part of stin_gemm.hip (included inside its anonymous namespace; not a translation unit of its own).
 // ----------------------------------------------------------------------------- TN, skinny K (round 4)
 // dW[Nc, K] = G^T [X | w] with K <= 16 (the first block of the network: [dA | dB | g] against the 12 padded input channels,
@@ -90,67 +90,23 @@ __global__ __launch_bounds__(BLOCK) void k_gemm_tn_skinny(const float* __restric
     if (has_bias)
         for (int c = threadIdx.x; c < Nc; c += BLOCK) out[(int64_t)Nc * Kq + c] = sk_smem[c * (KP + 1) + KP];
 }
-inline bool tn_skinny_shape(int storage, int Nc, int K, int64_t ldg, int64_t ldx, const void* G, const void* X) {
-    return storage == 0 && K <= 16 && K % 4 == 0 && Nc % 4 == 0 && Nc >= 64 && Nc <= 4 * BLOCK && ldg % 4 == 0 && ldx % 4 == 0 &&
-           stin_aligned16(G) && stin_aligned16(X);
-}
-inline int tn_skinny_rows(int64_t M) {                                         // ~1024 chunks, a multiple of 32 rows, at least 128
-    constexpr int want = 1024;                                                  // measured: 256 / 512 / 1024 / 2048 chunks: 106 / 75 / 72 / 79 us at 200 704 x 320 x 12
-    int64_t rows = (M + want - 1) / want;
-    rows = (rows + 31) / 32 * 32;
-    // the chunk's [X | w] image is rows x (KP + 4 <= 20) floats of dynamic LDS: capped at 512 rows = 40 KB (below the 64 KB a
-    // launch gets without hipFuncSetAttribute) - beyond ~0.5 M rows the chunk COUNT grows instead of the chunk
-    // (stin_gemm_tn_workspace_bytes sizes the slab from the same function)
-    if (rows > 512) rows = 512;
-    return (int)(rows < 128 ? 128 : rows);
-}
 
 // dW[row][col] = sum_c slab[c][row][col] (and the bias column from the chunk's bias block): 16 chunk-lanes x 16 float4
-// groups per block, each chunk-lane walks the chunk list with stride 16 (4 x 16-byte loads in flight), then a
-// fixed-order LDS reduction over the chunk-lanes -> deterministic.
-constexpr int RS_COLS = 16, RS_KL = 16;
-__device__ __forceinline__ void add4(float4& a, const float4 b) { a.x += b.x; a.y += b.y; a.z += b.z; a.w += b.w; }
+// groups per block, each chunk-lane folds its share of the chunk list (fn_partial, stin_common.h: the fold of k_wgrad_finalize),
+// then a fixed-order LDS reduction over the chunk-lanes -> deterministic.
 __global__ __launch_bounds__(BLOCK) void k_reduce_slabs(const float* __restrict__ slab, int64_t chunks, int Nc, int K, int Kq,
                                                         int has_bias, float* __restrict__ out, int64_t ldo,
                                                         float* __restrict__ bias_out) {
-    __shared__ float4 sm[RS_KL][RS_COLS + 1];
-    const int tx = threadIdx.x % RS_COLS, ty = threadIdx.x / RS_COLS;
-    const int64_t cs = tn_chunk_stride(Nc, Kq);
+    __shared__ float4 sm[FN_KL][FN_COLS + 1];
+    const int tx = threadIdx.x % FN_COLS, ty = threadIdx.x / FN_COLS;
     const int64_t nw4 = (int64_t)Nc * Kq / 4, nb4 = has_bias ? (Nc + 3) / 4 : 0;
-    const int64_t g = (int64_t)blockIdx.x * RS_COLS + tx;          // float4 group: weight block first, then the bias block
-    float4 s0 = make_float4(0.f, 0.f, 0.f, 0.f), s1 = s0, s2 = s0, s3 = s0;
-    if (g < nw4 + nb4) {
-        const float* p = slab + 4 * g;
-        int64_t c = ty;
-        for (; c + 15 * RS_KL < chunks; c += 16 * RS_KL) {          // (sixteen loads in flight on long chunk lists; same addition order)
-            float4 v[16];
-#pragma unroll
-            for (int u = 0; u < 16; ++u) v[u] = ld4(p + (c + u * RS_KL) * cs);
-#pragma unroll
-            for (int u = 0; u < 16; u += 4) {
-                add4(s0, v[u]);
-                add4(s1, v[u + 1]);
-                add4(s2, v[u + 2]);
-                add4(s3, v[u + 3]);
-            }
-        }
-        for (; c + 3 * RS_KL < chunks; c += 4 * RS_KL) {
-            add4(s0, ld4(p + c * cs));
-            add4(s1, ld4(p + (c + RS_KL) * cs));
-            add4(s2, ld4(p + (c + 2 * RS_KL) * cs));
-            add4(s3, ld4(p + (c + 3 * RS_KL) * cs));
-        }
-        for (; c < chunks; c += RS_KL) add4(s0, ld4(p + c * cs));
-    }
-    add4(s0, s1);
-    add4(s2, s3);
-    add4(s0, s2);
-    sm[ty][tx] = s0;
+    const int64_t g = (int64_t)blockIdx.x * FN_COLS + tx;          // float4 group: weight block first, then the bias block
+    sm[ty][tx] = fn_partial(g < nw4 + nb4 ? slab + 4 * g : nullptr, tn_chunk_stride(Nc, Kq), chunks, ty);
     __syncthreads();
     if (ty == 0 && g < nw4 + nb4) {
         float4 s = make_float4(0.f, 0.f, 0.f, 0.f);
 #pragma unroll
-        for (int k = 0; k < RS_KL; ++k) add4(s, sm[k][tx]);
+        for (int k = 0; k < FN_KL; ++k) add4(s, sm[k][tx]);
         const float v[4] = {s.x, s.y, s.z, s.w};
         if (g < nw4) {
             const int64_t row = (4 * g) / Kq;
@@ -169,48 +125,3 @@ __global__ __launch_bounds__(BLOCK) void k_reduce_slabs(const float* __restrict_
         }
     }
 }
-
-inline int tn_tile(int n) {
-    return n > 64 ? 128 : 64;    // (measured: 64x64 wgrad tiles are 2-5 % slower end to end at any slab count)
-}
-
-inline int stin_cu_count() { return stin_cu_count_dev(); }          // (per device: stin_common.h)
-
-inline int tn_rows_per_chunk(int64_t M, int tiles, bool one_per_cu = false) {
-    // ~384 blocks (up to 2 resident per CU, one round), chunks a multiple of the LDS slab.  Round 1 measured 512 best of
-    // 256..1536; with loads two slabs ahead a block hides more latency by itself and fewer chunks mean fewer partial slabs to
-    // store and reduce: 384 is 0.3-0.5 % faster on the step than 512 (256: 0.4 % slower)
-    // one_per_cu (round 3: fp32 bf16x3 products on 128 x 128 tiles with M <= 32 k rows, the shapes of the bottleneck level):
-    // 256 blocks - the producer / consumer kernel's fixed cost per block (first-load latency ~5 k cycles, slab store ~9 k) is
-    // a sixth of a 750-row chunk; measured 18 063 x 1024 x 256 49.7 -> 45.7 us, block weight gradients 69 -> 62 us, while the
-    // 60 k-row products lose 10 % with 256 blocks and keep 384
-    const int want = one_per_cu ? 256 : 384;
-    int64_t chunks = (want + tiles - 1) / tiles;
-    if (chunks > 8) chunks = (chunks + 7) / 8 * 8;          // whole rounds of 8 chunks (one per XCD, see the kernels' block map)
-    int64_t rows = (M + chunks - 1) / chunks;
-    if (rows < 4 * TN_R) rows = 4 * TN_R;
-    constexpr int max_rows = 128 * TN_R;
-    if (rows > max_rows) rows = max_rows;
-    rows = (rows + TN_R - 1) / TN_R * TN_R;
-    return (int)rows;
-}
-// bf16-storage TN: 256 x 256 tiles (k_gemm_tn_b16_tr<2, 4, 4, 2>) for the fat products.  STIN_TN_BIG = 0 | 1 forces (re-read per call;
-// the workspace bound covers both choices).
-inline bool tn_b16_big_tile(int Nc, int K) {
-    const char* e = getenv("STIN_TN_BIG");
-    if (e) return atoi(e) != 0 && Nc >= 256 && K >= 256;
-    return Nc >= 512 && K >= 512;
-}
-// bf16-storage TN, 128 x 128 tiles: the transposed-read kernel (k_gemm_tn_b16_tr); STIN_TN_TR=0 keeps the register-transpose
-// kernel (A/B switch, re-read per call).
-inline bool tn_b16_tr_enabled(int Nc, int K) {
-    const char* e = getenv("STIN_TN_TR");
-    if (e) return atoi(e) != 0;
-    // whole tiles only: with a ragged third tile (161 362 x 320 x 128, the level-0 product of the crop batches) the 64 KB of LDS
-    // (two blocks per CU instead of four) cost more than the transposes: 54.6 -> 68.6 us; whole-tile shapes gain 5-17 %
-    return Nc % 128 == 0 && K % 128 == 0;
-}
-inline bool tn_one_per_cu(int storage, int precision, int TI, int TJ, int64_t M) {
-    return storage == 0 && precision == STIN_GEMM_BF16X3 && TI == 128 && TJ == 128 && M <= 32768;
-}
-

@@ -214,12 +214,94 @@ struct stin_tn_batch {
     stin_tn_problem p[2];
     int n;
 };
-// stin_gemm.hip: geometry of one product (*ws_eligible = 1: the producer / consumer kernel of stin_wgrad.hip takes it);
-// stin_tn_slabs launches the product's TN kernel only (partial slabs, no reduction)
-int stin_tn_problem_init(stin_tn_problem* p, int storage, const void* G, int64_t ldg, const void* X, int64_t ldx, int64_t M,
-                         int Nc, int K, int ones_column, const void* row_w, int64_t ld_w, int precision, float* slab,
-                         int* ws_eligible);
-int stin_tn_slabs(const stin_tn_problem* p, int storage, int precision, stin_stream_t stream);
-// stin_wgrad.hip
-bool stin_tn_ws_enabled();
-int stin_tn_ws_launch(stin_tn_batch batch, stin_stream_t stream);
+// Block -> (row chunk, output tile) of every tiled TN kernel.  chunks >= 8: XCD x (blocks b = x mod 8; blockIdx % 8 is the observed
+// XCD round-robin) owns the row chunks x, x + 8, ... - its tiles re-read the same rows from its own L2; the grid is rounded up to
+// whole rounds of 8 chunks, false = a block past the last chunk (block-uniform).  Fewer chunks than XCDs (the wide layers: >= 64
+// output tiles): plain order, so that every XCD gets tiles of every chunk.
+__device__ __forceinline__ bool tn_block_map(int64_t b, int64_t chunks, int tiles, int64_t& chunk, int& tile) {
+    const int64_t xcd = b % 8, q = b / 8;
+    chunk = chunks >= 8 ? (q / tiles) * 8 + xcd : b / tiles;
+    tile = (int)(chunks >= 8 ? q % tiles : b % tiles);
+    return chunk < chunks;
+}
+
+// One chunk-lane's share of a fixed-order fold over `chunks` rows of stride `cs` floats: 16 chunk-lanes x 16 float4 groups per block,
+// lane ty of FN_KL walks rows ty, ty + FN_KL, ...; four running sums, merged (s0 + s1) + (s2 + s3); the caller adds the lanes in
+// order through LDS.  THE fold of k_reduce_slabs, k_wgrad_finalize and k_colsum_fold: one body, so all three give the same bits.
+constexpr int FN_COLS = 16, FN_KL = 16;
+__device__ __forceinline__ void add4(float4& a, const float4 b) { a.x += b.x; a.y += b.y; a.z += b.z; a.w += b.w; }
+__device__ __forceinline__ float4 fn_partial(const float* __restrict__ p, int64_t cs, int64_t chunks, int ty) {
+    float4 s0 = make_float4(0.f, 0.f, 0.f, 0.f), s1 = s0, s2 = s0, s3 = s0;
+    if (p != nullptr) {
+        int64_t c = ty;
+        // (round 4) sixteen slab loads in flight per thread where the chunk list is long (the first block's skinny product
+        // writes ~900 chunks: with four in flight this fold is 14-28 dependent trips to the fabric - 200 us at the very end of
+        // the backward pass under rocprofv3, 11 us now; stand-alone and in the un-profiled step the difference is small); the
+        // additions keep the order of the four-at-a-time loop below: bit-identical sums
+        for (; c + 15 * FN_KL < chunks; c += 16 * FN_KL) {
+            float4 v[16];
+#pragma unroll
+            for (int u = 0; u < 16; ++u) v[u] = ld4(p + (c + u * FN_KL) * cs);
+#pragma unroll
+            for (int u = 0; u < 16; u += 4) {
+                add4(s0, v[u]);
+                add4(s1, v[u + 1]);
+                add4(s2, v[u + 2]);
+                add4(s3, v[u + 3]);
+            }
+        }
+        for (; c + 3 * FN_KL < chunks; c += 4 * FN_KL) {
+            add4(s0, ld4(p + c * cs));
+            add4(s1, ld4(p + (c + FN_KL) * cs));
+            add4(s2, ld4(p + (c + 2 * FN_KL) * cs));
+            add4(s3, ld4(p + (c + 3 * FN_KL) * cs));
+        }
+        for (; c < chunks; c += FN_KL) add4(s0, ld4(p + c * cs));
+    }
+    add4(s0, s1);
+    add4(s2, s3);
+    add4(s0, s2);
+    return s0;
+}
+
+// ---- which kernel runs a TN product.  The records live here because two translation units use them; the rules are compiled once,
+// in stin_gemm.hip (csrc/gemm_tn_route.inc), and stin_wgrad.hip asks them through the functions below.
+struct TnSwitches {
+    bool pc;                   // STIN_TN_WS=0: never the producer / consumer kernel (the four-wave kernel on the tiles of the width rule)
+    int big, tr;               // STIN_TN_BIG / STIN_TN_TR = 0 | 1 force the 256 x 256 tile / the transposed-read kernel of bf16 rows, -1 (unset) = the rule
+};
+struct TnProblem {
+    int storage;               // 0 = fp32 rows, 1 = bf16 rows
+    int64_t M;
+    int Nc, K;
+    int64_t ldg, ldx;          // row pitches of G and X, in elements
+    int precision;             // STIN_GEMM_F32 / _BF16X3 / _BF16X6 (bf16 rows: _BF16X3)
+    bool ones_column;          // a bias-gradient column [X | w]
+    bool aligned16;            // the bases of G and X are 16-byte aligned
+    bool bn_tf;                // X is read as relu(bn(X)) (stin_gemm_tn_bn_f32) ...
+    bool bn_tf_aligned16;      // ... and its four vectors are 16-byte aligned
+    bool x_row_map;            // row m of X is X[x_row_map[m]] (stin_edgeconv_wgrad_map)
+};
+struct TnRoute {
+    int status;                // STIN_OK, or why this call cannot be served
+    int family;                // STIN_TN_FAMILY_* (stin_hip.h); _NONE: no rows, only the fold is launched
+    int TI, TJ;                // output tile of a block (0, 0: the skinny kernel, whose block owns all columns)
+    int tiles_i, tiles_j, rows_per_chunk;
+    int64_t chunks;            // row chunks = partial slabs
+    int Kq, vec;               // K rounded up to 4 (the slab's row pitch); 16-byte operand loads
+    int threads;
+    int64_t lds, grid;         // dynamic LDS bytes; blocks
+};
+// stin_gemm.hip.  stin_tn_setup: the argument checks of one product, its route and its kernel argument (xtf / x_row_map: the
+// optional transform of X and row map, NULL = none; they are part of what the route decides on).  stin_tn_slabs launches the TN
+// kernels of one product or of two (pb != NULL) - partial slabs, no reduction: both on the producer / consumer kernel -> ONE grid,
+// else one launch each.
+TnSwitches stin_tn_switches();
+TnRoute stin_tn_route(const TnProblem& p, const TnSwitches& sw);
+int stin_tn_setup(stin_tn_problem* p, TnRoute* r, const TnSwitches& sw, int storage, const void* G, int64_t ldg, const void* X,
+                  int64_t ldx, int64_t M, int Nc, int K, int ones_column, const void* row_w, int64_t ld_w, int precision, float* slab,
+                  const stin_bn_tf* xtf, const int32_t* x_row_map);
+int stin_tn_slabs(const stin_tn_problem* pa, const TnRoute* ra, const stin_tn_problem* pb, const TnRoute* rb, int precision,
+                  stin_stream_t stream);
+// stin_wgrad.hip: one or two (pb != NULL) products on the producer / consumer kernel, in one grid
+int stin_tn_ws_launch(const stin_tn_problem* pa, const TnRoute* ra, const stin_tn_problem* pb, const TnRoute* rb, stin_stream_t stream);

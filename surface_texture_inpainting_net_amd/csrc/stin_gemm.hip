@@ -48,8 +48,10 @@ __device__ __forceinline__ bool nt_block_tile(int64_t M, int Nc, int BM, int BN,
 #include "gemm_nt_resident.inc"   // NT products on fragment-order weights: resident strip, all-columns and balanced column-panel kernels (k_gemm_nt_strip / _wide / _panel)
 #include "gemm_tn.inc"   // TN (weight-gradient) products of fp32 rows: exact-fp32 and split-bf16 tilings (k_gemm_tn, k_gemm_tn_bf16s)
 #include "gemm_b16.inc"   // GEMMs of bf16-STORAGE rows: NT tiled / LDS-DMA, TN register-transpose / hardware-transposed reads
-#include "gemm_tn_skinny.inc"   // TN products with K <= 16 (k_gemm_tn_skinny), the slab reduction and the host-side tile / chunk rules
+#include "gemm_tn_skinny.inc"   // TN products with K <= 16 (k_gemm_tn_skinny) and the slab reduction (k_reduce_slabs)
+inline int stin_cu_count() { return stin_cu_count_dev(); }          // (per device: stin_common.h)
 #include "gemm_nt_route.inc"   // host only: which kernel runs an NT product - the switches, the rules, nt_route
+#include "gemm_tn_route.inc"   // host only: which kernel runs a TN product - the switches, the rules, tn_route
 }  // namespace
 
 // ------------------------------------------------------------------ NT products: route (gemm_nt_route.inc), then launch
@@ -69,11 +71,11 @@ inline int nt_parts(const float* bias, const float* row_mask, const float* resid
     return (bias ? STIN_NT_PART_BIAS : 0) | (row_mask ? STIN_NT_PART_ROW_MASK : 0) | (residual ? STIN_NT_PART_RESIDUAL : 0);
 }
 
-// THE launch of every NT kernel: raise the kernel's dynamic-LDS limit on this device where it needs more than 64 KB (max_lds > 0),
-// then launch.  One flag per kernel instantiation.
-struct NtLaunch { dim3 grid; int threads; int64_t lds; int max_lds; hipStream_t stream; };
+// THE launch of every NT and TN kernel of this file: raise the kernel's dynamic-LDS limit on this device where it needs more than
+// 64 KB (max_lds > 0), then launch.  One flag per kernel instantiation.
+struct KernelLaunch { dim3 grid; int threads; int64_t lds; int max_lds; hipStream_t stream; };
 template <auto KERNEL, typename... Args>
-void nt_launch(const NtLaunch& l, const std::tuple<Args...>& args) {
+void launch_kernel(const KernelLaunch& l, const std::tuple<Args...>& args) {
     if (l.max_lds > 0) {
         static stin_once_per_device raised;
         stin_raise_dynamic_lds(raised, (const void*)KERNEL, l.max_lds);
@@ -83,23 +85,23 @@ void nt_launch(const NtLaunch& l, const std::tuple<Args...>& args) {
 
 // ---- one launch table per family: the route's tile / parameter -> the template arguments
 template <int BM, int BN, int WM, int WN, typename Args>
-void nt_launch_tile(const NtRoute& r, int precision, bool wpre, const NtLaunch& l, const Args& a) {
+void nt_launch_tile(const NtRoute& r, int precision, bool wpre, const KernelLaunch& l, const Args& a) {
     if (wpre) {                                                     // (pre-split W: 16-byte rows, 64 x 64 and 128 x 128 only)
         if constexpr (BN != 32) {
-            if (precision == STIN_GEMM_BF16X3) nt_launch<k_gemm_nt_bf16s<BM, BN, WM, WN, 2, __bf16, true, true>>(l, a);
-            else nt_launch<k_gemm_nt_bf16s<BM, BN, WM, WN, 2, _Float16, true, true>>(l, a);
+            if (precision == STIN_GEMM_BF16X3) launch_kernel<k_gemm_nt_bf16s<BM, BN, WM, WN, 2, __bf16, true, true>>(l, a);
+            else launch_kernel<k_gemm_nt_bf16s<BM, BN, WM, WN, 2, _Float16, true, true>>(l, a);
         }
     } else if (precision == STIN_GEMM_F32)
-        r.vec ? nt_launch<k_gemm_nt<BM, BN, WM, WN, true>>(l, a) : nt_launch<k_gemm_nt<BM, BN, WM, WN, false>>(l, a);
+        r.vec ? launch_kernel<k_gemm_nt<BM, BN, WM, WN, true>>(l, a) : launch_kernel<k_gemm_nt<BM, BN, WM, WN, false>>(l, a);
     else if (precision == STIN_GEMM_BF16X3)
-        r.vec ? nt_launch<k_gemm_nt_bf16s<BM, BN, WM, WN, 2, __bf16, true>>(l, a) : nt_launch<k_gemm_nt_bf16s<BM, BN, WM, WN, 2, __bf16, false>>(l, a);
+        r.vec ? launch_kernel<k_gemm_nt_bf16s<BM, BN, WM, WN, 2, __bf16, true>>(l, a) : launch_kernel<k_gemm_nt_bf16s<BM, BN, WM, WN, 2, __bf16, false>>(l, a);
     else if (precision == STIN_GEMM_BF16X6)
-        r.vec ? nt_launch<k_gemm_nt_bf16s<BM, BN, WM, WN, 3, __bf16, true>>(l, a) : nt_launch<k_gemm_nt_bf16s<BM, BN, WM, WN, 3, __bf16, false>>(l, a);
+        r.vec ? launch_kernel<k_gemm_nt_bf16s<BM, BN, WM, WN, 3, __bf16, true>>(l, a) : launch_kernel<k_gemm_nt_bf16s<BM, BN, WM, WN, 3, __bf16, false>>(l, a);
     else
-        r.vec ? nt_launch<k_gemm_nt_bf16s<BM, BN, WM, WN, 2, _Float16, true>>(l, a) : nt_launch<k_gemm_nt_bf16s<BM, BN, WM, WN, 2, _Float16, false>>(l, a);
+        r.vec ? launch_kernel<k_gemm_nt_bf16s<BM, BN, WM, WN, 2, _Float16, true>>(l, a) : launch_kernel<k_gemm_nt_bf16s<BM, BN, WM, WN, 2, _Float16, false>>(l, a);
 }
 void nt_launch_tiled(const NtRoute& r, const NtProblem& p, int precision, const NtOperands& o, hipStream_t stream) {
-    const NtLaunch l = {dim3((unsigned)r.grid), BLOCK, 0, 0, stream};
+    const KernelLaunch l = {dim3((unsigned)r.grid), BLOCK, 0, 0, stream};
     const auto a = std::make_tuple(o.A, o.lda, o.W, o.ldw, o.bias, o.row_mask, o.ld_mask, o.residual, o.ld_res, p.M, p.Nc, p.K, o.C, o.ldc, o.tf);
     const bool wpre = (p.precision & STIN_GEMM_W_PRESPLIT) != 0;
     if (r.bn == 32) nt_launch_tile<128, 32, 4, 1>(r, precision, wpre, l, a);
@@ -108,14 +110,14 @@ void nt_launch_tiled(const NtRoute& r, const NtProblem& p, int precision, const 
 }
 
 template <int NT, int MODE, bool TF, typename Args>
-void nt_launch_stream_tiles(int precision, const NtLaunch& l, const Args& a) {
-    if (precision == STIN_GEMM_BF16X3) nt_launch<k_gemm_nt_stream<64, NT, 2, __bf16, MODE, TF>>(l, a);
-    else if (precision == STIN_GEMM_BF16X6) nt_launch<k_gemm_nt_stream<64, NT, 3, __bf16, MODE, TF>>(l, a);
-    else nt_launch<k_gemm_nt_stream<64, NT, 2, _Float16, MODE, TF>>(l, a);
+void nt_launch_stream_tiles(int precision, const KernelLaunch& l, const Args& a) {
+    if (precision == STIN_GEMM_BF16X3) launch_kernel<k_gemm_nt_stream<64, NT, 2, __bf16, MODE, TF>>(l, a);
+    else if (precision == STIN_GEMM_BF16X6) launch_kernel<k_gemm_nt_stream<64, NT, 3, __bf16, MODE, TF>>(l, a);
+    else launch_kernel<k_gemm_nt_stream<64, NT, 2, _Float16, MODE, TF>>(l, a);
 }
 template <int MODE, bool TF>
 void nt_launch_stream_mode(const NtRoute& r, const NtProblem& p, int precision, const NtOperands& o, hipStream_t stream) {
-    const NtLaunch l = {dim3((unsigned)r.grid, (unsigned)r.grid_y), BLOCK, r.lds, 160 * 1024, stream};
+    const KernelLaunch l = {dim3((unsigned)r.grid, (unsigned)r.grid_y), BLOCK, r.lds, 160 * 1024, stream};
     const auto a = std::make_tuple(o.A, o.lda, o.W, o.ldw, p.M, p.Nc, p.K, o.X, o.ldx, o.tf, o.P, o.Q, o.inv_n, o.stats, o.C, o.ldc, o.bias,
                                    o.row_mask, o.ld_mask, o.residual, o.ld_res, (p.precision & STIN_GEMM_W_PRESPLIT) ? 1 : 0);
     if (r.param == 2) nt_launch_stream_tiles<2, MODE, TF>(precision, l, a);
@@ -132,38 +134,38 @@ template <typename PT>
 void nt_launch_strip(const NtRoute& r, const NtProblem& p, const NtOperands& o, hipStream_t stream) {
     const int KC = p.K < 256 ? p.K : 256, P = (p.Nc + ST_PANEL - 1) / ST_PANEL;
     const int64_t units = ((p.M + r.bm - 1) / r.bm) * P;
-    const NtLaunch l = {dim3((unsigned)r.grid), r.param == 22 ? 512 : 256, r.lds, 160 * 1024, stream};
+    const KernelLaunch l = {dim3((unsigned)r.grid), r.param == 22 ? 512 : 256, r.lds, 160 * 1024, stream};
     const auto a = std::make_tuple(o.A, o.lda, o.W, o.bias, o.row_mask, o.ld_mask, o.residual, o.ld_res, p.M, p.Nc, p.K, o.C, o.ldc, KC, units,
                                    P, r.vec_out);
     switch (r.param) {
-        case 22: nt_launch<k_gemm_nt_strip<PT, 2, 2>>(l, a); break;
-        case 41: nt_launch<k_gemm_nt_strip<PT, 4, 1>>(l, a); break;
-        default: nt_launch<k_gemm_nt_strip<PT, 2, 1>>(l, a); break;
+        case 22: launch_kernel<k_gemm_nt_strip<PT, 2, 2>>(l, a); break;
+        case 41: launch_kernel<k_gemm_nt_strip<PT, 4, 1>>(l, a); break;
+        default: launch_kernel<k_gemm_nt_strip<PT, 2, 1>>(l, a); break;
     }
 }
 template <typename PT>
 void nt_launch_wide(const NtRoute& r, const NtProblem& p, const NtOperands& o, hipStream_t stream) {
-    const NtLaunch l = {dim3((unsigned)r.grid), p.Nc * r.param, 0, 0, stream};       // Nc / 64 column waves x param row waves x 64 lanes
+    const KernelLaunch l = {dim3((unsigned)r.grid), p.Nc * r.param, 0, 0, stream};       // Nc / 64 column waves x param row waves x 64 lanes
     const auto a = std::make_tuple(o.A, o.lda, o.W, o.bias, o.row_mask, o.ld_mask, o.residual, o.ld_res, p.M, p.K, o.C, o.ldc, o.stats, r.vec_out);
-    if (p.Nc == 128) nt_launch<k_gemm_nt_wide<PT, 2, 2>>(l, a);
-    else if (r.param == 2) nt_launch<k_gemm_nt_wide<PT, 4, 2>>(l, a);
-    else nt_launch<k_gemm_nt_wide<PT, 4, 1>>(l, a);
+    if (p.Nc == 128) launch_kernel<k_gemm_nt_wide<PT, 2, 2>>(l, a);
+    else if (r.param == 2) launch_kernel<k_gemm_nt_wide<PT, 4, 2>>(l, a);
+    else launch_kernel<k_gemm_nt_wide<PT, 4, 1>>(l, a);
 }
 template <typename PT>
 void nt_launch_panel(const NtRoute& r, const NtProblem& p, const NtOperands& o, hipStream_t stream) {
     const int P = p.Nc / 128, nrb = (int)((p.M + r.bm - 1) / r.bm);
-    const NtLaunch l = {dim3((unsigned)r.grid), 512, r.lds, 160 * 1024, stream};
+    const KernelLaunch l = {dim3((unsigned)r.grid), 512, r.lds, 160 * 1024, stream};
     const auto a = std::make_tuple(o.A, o.lda, o.W, o.bias, o.row_mask, o.ld_mask, o.residual, o.ld_res, p.M, p.Nc, p.K, o.C, o.ldc, o.stats, nrb,
                                    P, nrb >= 16 ? 1 : 0, o.de);
     switch (r.param) {                                              // 32-row tiles per block = MT0 + MT1
-        case 2: nt_launch<k_gemm_nt_panel<PT, 1, 1>>(l, a); break;
-        case 3: nt_launch<k_gemm_nt_panel<PT, 2, 1>>(l, a); break;
-        case 4: nt_launch<k_gemm_nt_panel<PT, 2, 2>>(l, a); break;
-        case 5: nt_launch<k_gemm_nt_panel<PT, 3, 2>>(l, a); break;
-        case 6: nt_launch<k_gemm_nt_panel<PT, 3, 3>>(l, a); break;
-        case 7: nt_launch<k_gemm_nt_panel<PT, 4, 3>>(l, a); break;
-        case 8: nt_launch<k_gemm_nt_panel<PT, 4, 4>>(l, a); break;
-        default: nt_launch<k_gemm_nt_panel<PT, 5, 4>>(l, a); break;
+        case 2: launch_kernel<k_gemm_nt_panel<PT, 1, 1>>(l, a); break;
+        case 3: launch_kernel<k_gemm_nt_panel<PT, 2, 1>>(l, a); break;
+        case 4: launch_kernel<k_gemm_nt_panel<PT, 2, 2>>(l, a); break;
+        case 5: launch_kernel<k_gemm_nt_panel<PT, 3, 2>>(l, a); break;
+        case 6: launch_kernel<k_gemm_nt_panel<PT, 3, 3>>(l, a); break;
+        case 7: launch_kernel<k_gemm_nt_panel<PT, 4, 3>>(l, a); break;
+        case 8: launch_kernel<k_gemm_nt_panel<PT, 4, 4>>(l, a); break;
+        default: launch_kernel<k_gemm_nt_panel<PT, 5, 4>>(l, a); break;
     }
 }
 
@@ -337,228 +339,180 @@ extern "C" int stin_gemm_nt_geometry(int storage, int64_t M, int Nc, int K, int 
     return STIN_OK;
 }
 
+// ------------------------------------------------------------------ TN products: route (gemm_tn_route.inc), then launch
+TnSwitches stin_tn_switches() { return tn_switches(); }
+TnRoute stin_tn_route(const TnProblem& p, const TnSwitches& sw) { return tn_route(p, sw); }
+
+// The slab workspace of a product of these four arguments: the largest chunks x tn_chunk_stride x 4 + 256 over the routes a caller can
+// reach with them - both storages, every precision, operands that are 16-byte vectors or not (row pitches beyond Nc / K add no
+// case: they only decide between these two), and the settings of the switches that move the geometry (STIN_TN_WS on fp32 rows,
+// STIN_TN_BIG on bf16 rows).  Asked of tn_route itself; at least one slab.
 extern "C" size_t stin_gemm_tn_workspace_bytes(int64_t M, int Nc, int K, int ones_column) {
     if (M < 0 || Nc <= 0 || K <= 0) return 0;
-    (void)ones_column;
-    const int TI = tn_tile(Nc), TJ = tn_tile(K);
-    const int tiles = ((Nc + TI - 1) / TI) * ((K + TJ - 1) / TJ);
     int64_t chunks = 1;
-    for (int rule = 0; rule < 2; ++rule) {                       // (the chunk rule depends on storage / precision: take the larger)
-        const int rows = tn_rows_per_chunk(M, tiles, rule == 1);
-        const int64_t c = (M + rows - 1) / rows;
-        if (c > chunks) chunks = c;
-    }
-    if (K <= 16) {                                               // k_gemm_tn_skinny's chunking (fp32 rows)
-        const int rows = tn_skinny_rows(M);
-        const int64_t c = (M + rows - 1) / rows;
-        if (c > chunks) chunks = c;
-    }
-    if (Nc >= 256 && K >= 256) {                                 // the 256 x 256 tiles of the bf16-storage products: fewer tiles, more chunks
-        const int rows = tn_rows_per_chunk(M, ((Nc + 255) / 256) * ((K + 255) / 256), true);
-        const int64_t c = (M + rows - 1) / rows;
-        if (c > chunks) chunks = c;
+    auto ask = [&](int storage, int precision, bool aligned16, const TnSwitches& sw) {
+        const TnProblem p = {storage, M, Nc, K, Nc, K, precision, ones_column != 0, aligned16, false, false, false};
+        const TnRoute r = tn_route(p, sw);
+        if (r.status == STIN_OK && r.chunks > chunks) chunks = r.chunks;
+    };
+    for (int aligned16 = 0; aligned16 < 2; ++aligned16) {
+        for (int precision : {STIN_GEMM_F32, STIN_GEMM_BF16X3, STIN_GEMM_BF16X6})
+            for (int pc = 0; pc < 2; ++pc) ask(0, precision, aligned16 != 0, TnSwitches{pc != 0, -1, -1});
+        for (int big = -1; big <= 1; ++big) ask(1, STIN_GEMM_BF16X3, aligned16 != 0, TnSwitches{true, big, -1});
     }
     return (size_t)chunks * (size_t)tn_chunk_stride(Nc, (K + 3) & ~3) * sizeof(float) + 256;
 }
 
-// Geometry of one TN product (shared with stin_wgrad.hip).  ws_eligible: fp32 storage, 2-piece bf16 split, 128 x 128 tiles,
-// 16-byte rows - what k_gemm_tn_ws is written for (STIN_TN_WS=0 keeps the four-wave kernel, A/B aid).
-int stin_tn_problem_init(stin_tn_problem* p, int storage, const void* G, int64_t ldg, const void* X, int64_t ldx, int64_t M,
-                         int Nc, int K, int ones_column, const void* row_w, int64_t ld_w, int precision, float* slab,
-                         int* ws_eligible) {
-    STIN_REQUIRE(M >= 0 && Nc > 0 && K > 0 && ldg >= Nc && ldx >= K, STIN_E_SIZE);
+// One TN product: its argument checks, its route and its kernel argument (shared with stin_wgrad.hip)
+int stin_tn_setup(stin_tn_problem* p, TnRoute* r, const TnSwitches& sw, int storage, const void* G, int64_t ldg, const void* X,
+                  int64_t ldx, int64_t M, int Nc, int K, int ones_column, const void* row_w, int64_t ld_w, int precision, float* slab,
+                  const stin_bn_tf* xtf, const int32_t* x_row_map) {
+    const bool tf16 = xtf != nullptr && stin_aligned16(xtf->mean) && stin_aligned16(xtf->rstd) && stin_aligned16(xtf->gamma) && stin_aligned16(xtf->beta);
+    const TnProblem q = {storage, M, Nc, K, ldg, ldx, precision, ones_column != 0, stin_aligned16(G) && stin_aligned16(X),
+                         xtf != nullptr, tf16, x_row_map != nullptr};
+    *r = tn_route(q, sw);
+    if (r->status == STIN_E_SIZE) return STIN_E_SIZE;
     STIN_REQUIRE(slab && (M == 0 || (G && X)), STIN_E_NULL);
-    p->xtf.mean = p->xtf.rstd = p->xtf.gamma = p->xtf.beta = nullptr;      // (set by the caller after init: stin_gemm_tn_bn_f32)
+    STIN_REQUIRE(xtf == nullptr || (xtf->mean && xtf->rstd && xtf->gamma && xtf->beta), STIN_E_NULL);
+    if (r->status != STIN_OK) return r->status;
+    p->xtf.mean = p->xtf.rstd = p->xtf.gamma = p->xtf.beta = nullptr;
+    if (xtf != nullptr) p->xtf = *xtf;
     p->G = static_cast<const float*>(G);
     p->X = static_cast<const float*>(X);
     p->row_w = static_cast<const float*>(row_w);
-    p->x_row_map = nullptr;                                        // (set by the caller after init: stin_edgeconv_wgrad_map)
     p->slab = slab;
-    p->ldg = ldg;
-    p->ldx = ldx;
-    p->ld_w = ld_w;
-    p->M = M;
-    p->Nc = Nc;
-    p->K = K;
-    const int a16 = storage ? 8 : 4;                               // elements per 16-byte vector
-    const bool vec16 = (Nc % a16 == 0) && (K % a16 == 0) && (ldg % a16 == 0) && (ldx % a16 == 0) && stin_aligned16(G) && stin_aligned16(X);
-    const bool big = storage == 1 && vec16 && tn_b16_big_tile(Nc, K);
-    p->TI = big ? 256 : tn_tile(Nc);
-    p->TJ = big ? 256 : tn_tile(K);
-    // (round 5) fp32 bf16x3 products whose narrow side is <= 64 columns (the level-0 dW2 = dagg^T h: 64 x 128; SingleConvMeshNet's
-    // per-edge dW2) ran on the four-wave kernel (its 64-wide tiles) at ~3 TB/s; on the producer / consumer kernel the same
-    // product is a 128 x 128 tile that is half or a quarter empty - the wasted MFMAs are free beside the operand stream
-    // (200 704 x 64 x 128: 50 -> 3x us; 1.2 M x 64 x 128: 267 -> 1xx us).  One tile either way: same chunks, same slabs.
-    if (!big && storage == 0 && precision == STIN_GEMM_BF16X3 && vec16 && M > 0 && Nc >= 32 && K >= 32 && stin_tn_ws_enabled()) {
-        p->TI = 128;
-        p->TJ = 128;
-    }
-    p->tiles_i = (Nc + p->TI - 1) / p->TI;
-    p->tiles_j = (K + p->TJ - 1) / p->TJ;
-    p->rows_per_chunk = tn_rows_per_chunk(M, p->tiles_i * p->tiles_j, big || tn_one_per_cu(storage, precision, p->TI, p->TJ, M));
-    if (tn_skinny_shape(storage, Nc, K, ldg, ldx, G, X)) {         // k_gemm_tn_skinny: a block owns all columns of its row chunk
-        p->TI = p->TJ = 0;
-        p->tiles_i = p->tiles_j = 1;
-        p->rows_per_chunk = tn_skinny_rows(M);
-    }
-    p->chunks = M > 0 ? (M + p->rows_per_chunk - 1) / p->rows_per_chunk : 0;
-    p->Kq = (K + 3) & ~3;
-    p->has_bias = ones_column ? 1 : 0;
+    p->ldg = ldg, p->ldx = ldx, p->ld_w = ld_w, p->M = M, p->chunks = r->chunks;
+    p->Nc = Nc, p->K = K, p->Kq = r->Kq, p->has_bias = ones_column ? 1 : 0, p->rows_per_chunk = r->rows_per_chunk;
+    p->tiles_i = r->tiles_i, p->tiles_j = r->tiles_j, p->vec = r->vec;
+    p->TI = (short)r->TI, p->TJ = (short)r->TJ;
     p->block0 = 0;
-    const int a = storage ? 8 : 4;                                 // elements per 16-byte vector
-    p->vec = (Nc % a == 0) && (K % a == 0) && (ldg % a == 0) && (ldx % a == 0) && stin_aligned16(G) && stin_aligned16(X);
-    if (ws_eligible)
-        *ws_eligible = (storage == 0 && precision == STIN_GEMM_BF16X3 && p->TI == 128 && p->TJ == 128 && p->vec && M > 0 &&
-                        stin_tn_ws_enabled()) ? 1 : 0;
+    p->x_row_map = x_row_map;
     return STIN_OK;
 }
 
-// The geometry stin_tn_problem_init gives a product of this shape, for tests and tools: which tile class (TI == 0: the skinny
-// kernel), how many row chunks = partial slabs, whether the 16-byte loads and the producer / consumer kernel apply.  Host only:
-// the placeholder operands (16-byte aligned or not) are never read through, nothing is launched, no device is touched.
+// The route a TN product of this shape takes, for tests and tools (stin_hip.h).  Host only: nothing is launched, no device is touched.
+// stin_gemm_tn_geometry keeps the eight values its callers have room for; stin_gemm_tn_route adds the kernel family and the grid.
+static int tn_query(int storage, int64_t M, int Nc, int K, int64_t ldg, int64_t ldx, int aligned16, int ones_column, int precision,
+                    int n, int32_t* out) {
+    STIN_REQUIRE(out != nullptr, STIN_E_NULL);
+    STIN_REQUIRE(storage == 0 || storage == 1, STIN_E_UNSUPPORTED);
+    const TnProblem p = {storage, M, Nc, K, ldg, ldx, precision, ones_column != 0, aligned16 != 0, false, false, false};
+    const TnRoute r = tn_route(p, tn_switches());
+    if (r.status != STIN_OK) return r.status;
+    const int64_t v[10] = {r.TI, r.TJ, r.tiles_i, r.tiles_j, r.rows_per_chunk, r.chunks, r.vec, r.family == STIN_TN_FAMILY_PC, r.family, r.grid};
+    for (int i = 0; i < n; ++i) out[i] = (int32_t)v[i];
+    return STIN_OK;
+}
 extern "C" int stin_gemm_tn_geometry(int storage, int64_t M, int Nc, int K, int64_t ldg, int64_t ldx, int aligned16, int ones_column,
                                      int precision, int32_t* out8) {
-    STIN_REQUIRE(out8 != nullptr, STIN_E_NULL);
-    STIN_REQUIRE(storage == 0 || storage == 1, STIN_E_UNSUPPORTED);
-    void* const some = reinterpret_cast<void*>(uintptr_t(aligned16 ? 256 : 260));
-    stin_tn_problem p;
-    int ws = 0;
-    const int rc = stin_tn_problem_init(&p, storage, some, ldg, some, ldx, M, Nc, K, ones_column, nullptr, 0, precision,
-                                        static_cast<float*>(some), &ws);
-    if (rc != STIN_OK) return rc;
-    out8[0] = p.TI;
-    out8[1] = p.TJ;
-    out8[2] = p.tiles_i;
-    out8[3] = p.tiles_j;
-    out8[4] = p.rows_per_chunk;
-    out8[5] = (int32_t)p.chunks;
-    out8[6] = p.vec;
-    out8[7] = ws;
-    return STIN_OK;
+    return tn_query(storage, M, Nc, K, ldg, ldx, aligned16, ones_column, precision, 8, out8);
+}
+extern "C" int stin_gemm_tn_route(int storage, int64_t M, int Nc, int K, int64_t ldg, int64_t ldx, int aligned16, int ones_column,
+                                  int precision, int32_t* out10) {
+    return tn_query(storage, M, Nc, K, ldg, ldx, aligned16, ones_column, precision, 10, out10);
 }
 
-// The TN kernel of one product: partial slabs only (k_reduce_slabs / k_wgrad_finalize add them).
-int stin_tn_slabs(const stin_tn_problem* p, int storage, int precision, stin_stream_t stream_) {
-    hipStream_t stream = (hipStream_t)stream_;
-    if (p->chunks <= 0) return STIN_OK;
-    const int64_t M = p->M, ldg = p->ldg, ldx = p->ldx, ld_weight = p->ld_w, chunks = p->chunks;
-    const int Nc = p->Nc, K = p->K, Kq = p->Kq, has_bias = p->has_bias, rows = p->rows_per_chunk, tiles_i = p->tiles_i,
-              tiles_j = p->tiles_j, TI = p->TI, TJ = p->TJ;
-    const bool vec = p->vec != 0;
-    float* slab = p->slab;
-    const int64_t blocks = (chunks >= 8 ? ((chunks + 7) / 8) * 8 : chunks) * (int64_t)tiles_i * tiles_j;   // 8 chunks (one per XCD) per round
-    if (storage == 1) {
-        const stin_bf16* G = reinterpret_cast<const stin_bf16*>(p->G);
-        const stin_bf16* X = reinterpret_cast<const stin_bf16*>(p->X);
-        const stin_bf16* row_weight = reinterpret_cast<const stin_bf16*>(p->row_w);
-#define STIN_TNK(TI_, TJ_)                                                                                            \
-    do {                                                                                                              \
-        if (vec) hipLaunchKernelGGL((k_gemm_tn_b16<TI_, TJ_, true>), dim3((unsigned)blocks), dim3(BLOCK), 0, stream, G, ldg, X, ldx, M, Nc, K, Kq, has_bias, row_weight, ld_weight, rows, tiles_i, tiles_j, chunks, slab); \
-        else hipLaunchKernelGGL((k_gemm_tn_b16<TI_, TJ_, false>), dim3((unsigned)blocks), dim3(BLOCK), 0, stream, G, ldg, X, ldx, M, Nc, K, Kq, has_bias, row_weight, ld_weight, rows, tiles_i, tiles_j, chunks, slab);    \
-    } while (0)
-#define STIN_TNTR(WI_, WJ_, MT_, NT_)                                                                                  \
-    do {                                                                                                              \
-        typedef TrGeom<WI_, WJ_, MT_, NT_> Geo_;                                                                      \
-        static stin_once_per_device raised;                                                                           \
-        stin_raise_dynamic_lds(raised, (const void*)k_gemm_tn_b16_tr<WI_, WJ_, MT_, NT_>, Geo_::LDS);                 \
-        hipLaunchKernelGGL((k_gemm_tn_b16_tr<WI_, WJ_, MT_, NT_>), dim3((unsigned)blocks), dim3(Geo_::THREADS), Geo_::LDS, stream, G, ldg, X, \
-                           ldx, M, Nc, K, Kq, has_bias, row_weight, ld_weight, rows, tiles_i, tiles_j, chunks, slab);  \
-    } while (0)
-        if (TI == 256 && TJ == 256) {
-            STIN_TNTR(2, 4, 4, 2);
-        } else if (TI == 128 && TJ == 128 && vec && Nc % 8 == 0 && K % 8 == 0 && tn_b16_tr_enabled(Nc, K)) {
-            STIN_TNTR(2, 2, 2, 2);
-        } else if (TI == 128 && TJ == 128) STIN_TNK(128, 128);
-        else if (TI == 128) STIN_TNK(128, 64);
-        else if (TJ == 128) STIN_TNK(64, 128);
-        else STIN_TNK(64, 64);
-#undef STIN_TNK
-#undef STIN_TNTR
-        return stin_launch_status();
+namespace {
+// ---- the launch table: the route's family and tile -> the template arguments
+template <typename F>
+void tn_with_tile(const TnRoute& r, F&& f) {                        // the four tiles of the four-wave kernels
+    typedef std::integral_constant<int, 64> c64;
+    typedef std::integral_constant<int, 128> c128;
+    if (r.TI == 128 && r.TJ == 128) f(c128(), c128());
+    else if (r.TI == 128) f(c128(), c64());
+    else if (r.TJ == 128) f(c64(), c128());
+    else f(c64(), c64());
+}
+template <typename T>
+auto tn_args(const stin_tn_problem& p) {                            // the arguments the tiled kernels share, operands as rows of T
+    return std::make_tuple(reinterpret_cast<const T*>(p.G), p.ldg, reinterpret_cast<const T*>(p.X), p.ldx, p.M, p.Nc, p.K, p.Kq, p.has_bias,
+                           reinterpret_cast<const T*>(p.row_w), p.ld_w, p.rows_per_chunk, p.tiles_i, p.tiles_j, p.chunks, p.slab);
+}
+int tn_launch(const stin_tn_problem& p, const TnRoute& r, int precision, hipStream_t stream) {
+    const KernelLaunch l = {dim3((unsigned)r.grid), r.threads, r.lds, r.family == STIN_TN_FAMILY_B16_TR ? (int)r.lds : 0, stream};
+    switch (r.family) {
+        case STIN_TN_FAMILY_NONE: return STIN_OK;
+        case STIN_TN_FAMILY_PC: return stin_tn_ws_launch(&p, &r, nullptr, nullptr, (stin_stream_t)stream);
+        case STIN_TN_FAMILY_SKINNY: {                               // KP = K: the shape rule admits 4, 8, 12, 16
+            const auto a = std::make_tuple(p.G, p.ldg, p.X, p.ldx, p.M, p.Nc, p.K, p.Kq, p.has_bias, p.row_w, p.ld_w, p.rows_per_chunk, p.slab);
+            switch (p.Kq) {
+                case 4: launch_kernel<k_gemm_tn_skinny<4>>(l, a); break;
+                case 8: launch_kernel<k_gemm_tn_skinny<8>>(l, a); break;
+                case 12: launch_kernel<k_gemm_tn_skinny<12>>(l, a); break;
+                default: launch_kernel<k_gemm_tn_skinny<16>>(l, a); break;
+            }
+            break;
+        }
+        case STIN_TN_FAMILY_F32:
+            tn_with_tile(r, [&](auto ti, auto tj) {
+                const auto a = std::tuple_cat(tn_args<float>(p), std::make_tuple(p.xtf));
+                r.vec ? launch_kernel<k_gemm_tn<ti(), tj(), true>>(l, a) : launch_kernel<k_gemm_tn<ti(), tj(), false>>(l, a);
+            });
+            break;
+        case STIN_TN_FAMILY_BF16S:
+            tn_with_tile(r, [&](auto ti, auto tj) {
+                const auto a = std::tuple_cat(tn_args<float>(p), std::make_tuple(p.xtf));
+                if (precision == STIN_GEMM_BF16X6)
+                    r.vec ? launch_kernel<k_gemm_tn_bf16s<ti(), tj(), 3, true>>(l, a) : launch_kernel<k_gemm_tn_bf16s<ti(), tj(), 3, false>>(l, a);
+                else
+                    r.vec ? launch_kernel<k_gemm_tn_bf16s<ti(), tj(), 2, true>>(l, a) : launch_kernel<k_gemm_tn_bf16s<ti(), tj(), 2, false>>(l, a);
+            });
+            break;
+        case STIN_TN_FAMILY_B16_REG:
+            tn_with_tile(r, [&](auto ti, auto tj) {
+                const auto a = tn_args<stin_bf16>(p);
+                r.vec ? launch_kernel<k_gemm_tn_b16<ti(), tj(), true>>(l, a) : launch_kernel<k_gemm_tn_b16<ti(), tj(), false>>(l, a);
+            });
+            break;
+        case STIN_TN_FAMILY_B16_TR:
+            if (r.TI == 256) launch_kernel<k_gemm_tn_b16_tr<2, 4, 4, 2>>(l, tn_args<stin_bf16>(p));
+            else launch_kernel<k_gemm_tn_b16_tr<2, 2, 2, 2>>(l, tn_args<stin_bf16>(p));
+            break;
     }
-    const float *G = p->G, *X = p->X, *row_weight = p->row_w;
-    if (TI == 0) {                                                 // skinny K (set by stin_tn_problem_init): exact fp32 on the VALU
-        const int kp = (K + 3) & ~3;
-        const size_t lds_x = (size_t)rows * (kp + 4) * sizeof(float), lds_o = (size_t)Nc * (kp + 1) * sizeof(float);
-        const size_t lds = lds_x > lds_o ? lds_x : lds_o;
-#define STIN_TNS(KP_)                                                                                                 \
-    hipLaunchKernelGGL((k_gemm_tn_skinny<KP_>), dim3((unsigned)chunks), dim3(BLOCK), lds, stream, G, ldg, X, ldx, M, Nc, K, Kq, has_bias, \
-                       row_weight, ld_weight, rows, slab)
-        if (K <= 4) STIN_TNS(4);
-        else if (K <= 8) STIN_TNS(8);
-        else if (K <= 12) STIN_TNS(12);
-        else STIN_TNS(16);
-#undef STIN_TNS
-        return stin_launch_status();
-    }
-    if (precision == STIN_GEMM_BF16X3 && TI == 128 && TJ == 128 && vec && stin_tn_ws_enabled()) {
-        stin_tn_batch batch;
-        batch.p[0] = *p;
-        batch.p[1] = *p;
-        batch.n = 1;
-        return stin_tn_ws_launch(batch, stream_);
-    }
-#define STIN_TN(TI_, TJ_)                                                                                            \
-    do {                                                                                                             \
-        if (vec) hipLaunchKernelGGL((k_gemm_tn<TI_, TJ_, true>), dim3((unsigned)blocks), dim3(BLOCK), 0, stream, G, ldg, X, ldx, M, Nc, K, Kq, has_bias, row_weight, ld_weight, rows, tiles_i, tiles_j, chunks, slab, p->xtf); \
-        else hipLaunchKernelGGL((k_gemm_tn<TI_, TJ_, false>), dim3((unsigned)blocks), dim3(BLOCK), 0, stream, G, ldg, X, ldx, M, Nc, K, Kq, has_bias, row_weight, ld_weight, rows, tiles_i, tiles_j, chunks, slab, p->xtf);    \
-    } while (0)
-#define STIN_TNB(TI_, TJ_, NS_)                                                                                      \
-    do {                                                                                                             \
-        if (vec) hipLaunchKernelGGL((k_gemm_tn_bf16s<TI_, TJ_, NS_, true>), dim3((unsigned)blocks), dim3(BLOCK), 0, stream, G, ldg, X, ldx, M, Nc, K, Kq, has_bias, row_weight, ld_weight, rows, tiles_i, tiles_j, chunks, slab, p->xtf); \
-        else hipLaunchKernelGGL((k_gemm_tn_bf16s<TI_, TJ_, NS_, false>), dim3((unsigned)blocks), dim3(BLOCK), 0, stream, G, ldg, X, ldx, M, Nc, K, Kq, has_bias, row_weight, ld_weight, rows, tiles_i, tiles_j, chunks, slab, p->xtf);    \
-    } while (0)
-#define STIN_TN_PICK(LAUNCH, ...)                                   \
-    do {                                                            \
-        if (TI == 128 && TJ == 128) LAUNCH(128, 128, ##__VA_ARGS__); \
-        else if (TI == 128) LAUNCH(128, 64, ##__VA_ARGS__);          \
-        else if (TJ == 128) LAUNCH(64, 128, ##__VA_ARGS__);          \
-        else LAUNCH(64, 64, ##__VA_ARGS__);                          \
-    } while (0)
-    if (precision == STIN_GEMM_BF16X3) STIN_TN_PICK(STIN_TNB, 2);
-    else if (precision == STIN_GEMM_BF16X6) STIN_TN_PICK(STIN_TNB, 3);
-    else STIN_TN_PICK(STIN_TN);
-#undef STIN_TN_PICK
-#undef STIN_TNB
-#undef STIN_TN
     return stin_launch_status();
 }
+}  // namespace
 
-static int gemm_tn_f32_impl(const float* G, int64_t ldg, const float* X, int64_t ldx, int64_t M, int Nc, int K,
-                           int ones_column, const float* row_weight, int64_t ld_weight, float* dW, int64_t lddw, float* db,
-                           int precision, void* workspace, size_t workspace_bytes, stin_stream_t stream_,
-                           const stin_bn_tf* xtf = nullptr) {
+// The TN kernels of one product or of two (pb != NULL): partial slabs only (k_reduce_slabs / k_wgrad_finalize add them).  Both
+// products on the producer / consumer kernel: ONE grid; else one launch each.
+int stin_tn_slabs(const stin_tn_problem* pa, const TnRoute* ra, const stin_tn_problem* pb, const TnRoute* rb, int precision,
+                  stin_stream_t stream_) {
+    hipStream_t stream = (hipStream_t)stream_;
+    if (pb != nullptr && ra->family == STIN_TN_FAMILY_PC && rb->family == STIN_TN_FAMILY_PC) return stin_tn_ws_launch(pa, ra, pb, rb, stream_);
+    int rc = tn_launch(*pa, *ra, precision, stream);
+    if (rc == STIN_OK && pb != nullptr) rc = tn_launch(*pb, *rb, precision, stream);
+    return rc;
+}
+
+// THE driver of the six stand-alone TN entry points: checks, slab alignment, route, launch, fold
+static int gemm_tn_impl(int storage, const void* G, int64_t ldg, const void* X, int64_t ldx, int64_t M, int Nc, int K, int ones_column,
+                        const void* row_weight, int64_t ld_weight, float* dW, int64_t lddw, float* db, int precision, void* workspace,
+                        size_t workspace_bytes, stin_stream_t stream_, const stin_bn_tf* xtf = nullptr) {
     stin_clear_stale_error();
     hipStream_t stream = (hipStream_t)stream_;
     const int Kp = K + ((ones_column && db == nullptr) ? 1 : 0);
     STIN_REQUIRE(M >= 0 && Nc > 0 && K > 0 && ldg >= Nc && ldx >= K && lddw >= Kp, STIN_E_SIZE);
     STIN_REQUIRE(dW && workspace && (M == 0 || (G && X)), STIN_E_NULL);
     STIN_REQUIRE(workspace_bytes >= stin_gemm_tn_workspace_bytes(M, Nc, K, ones_column), STIN_E_WORKSPACE);
-    STIN_REQUIRE(precision == STIN_GEMM_F32 || precision == STIN_GEMM_BF16X3 || precision == STIN_GEMM_BF16X6,
-                 STIN_E_UNSUPPORTED);
+    STIN_REQUIRE(precision == STIN_GEMM_F32 || precision == STIN_GEMM_BF16X3 || precision == STIN_GEMM_BF16X6, STIN_E_UNSUPPORTED);
     float* slab = reinterpret_cast<float*>((reinterpret_cast<uintptr_t>(workspace) + 255) & ~(uintptr_t)255);
     stin_tn_problem p;
-    int rc = stin_tn_problem_init(&p, 0, G, ldg, X, ldx, M, Nc, K, ones_column, row_weight, ld_weight, precision, slab, nullptr);
+    TnRoute r;
+    int rc = stin_tn_setup(&p, &r, tn_switches(), storage, G, ldg, X, ldx, M, Nc, K, ones_column, row_weight, ld_weight, precision, slab, xtf, nullptr);
     if (rc != STIN_OK) return rc;
-    // the slab the kernels will write must fit what the caller was told to allocate (tile choice and workspace bound are two functions)
-    STIN_REQUIRE((size_t)p.chunks * (size_t)tn_chunk_stride(Nc, p.Kq) * sizeof(float) + 256 <= workspace_bytes, STIN_E_WORKSPACE);
-    if (xtf != nullptr) {                     // X read as relu(bn(X)) per column (the tiled kernels and the producer / consumer kernel)
-        STIN_REQUIRE(xtf->mean && xtf->rstd && xtf->gamma && xtf->beta, STIN_E_NULL);
-        STIN_REQUIRE(p.TI != 0, STIN_E_UNSUPPORTED);                                      // (not the skinny-K kernel)
-        p.xtf = *xtf;
-        if (!(stin_aligned16(xtf->mean) && stin_aligned16(xtf->rstd) && stin_aligned16(xtf->gamma) && stin_aligned16(xtf->beta))) p.vec = 0;
-    }
-    rc = stin_tn_slabs(&p, 0, precision, stream_);
+    // the slab the kernels will write must fit what the caller was told to allocate
+    STIN_REQUIRE((size_t)r.chunks * (size_t)tn_chunk_stride(Nc, r.Kq) * sizeof(float) + 256 <= workspace_bytes, STIN_E_WORKSPACE);
+    rc = stin_tn_slabs(&p, &r, nullptr, nullptr, precision, stream_);
     if (rc != STIN_OK) return rc;
-    const int64_t n4 = (int64_t)Nc * p.Kq / 4 + (p.has_bias ? (Nc + 3) / 4 : 0);
-    hipLaunchKernelGGL(k_reduce_slabs, dim3((unsigned)((n4 + RS_COLS - 1) / RS_COLS)), dim3(BLOCK), 0, stream, slab, p.chunks, Nc, K,
-                       p.Kq, p.has_bias, dW, lddw, db);
+    const int64_t n4 = (int64_t)Nc * r.Kq / 4 + (p.has_bias ? (Nc + 3) / 4 : 0);
+    hipLaunchKernelGGL(k_reduce_slabs, dim3((unsigned)((n4 + FN_COLS - 1) / FN_COLS)), dim3(BLOCK), 0, stream, slab, r.chunks, Nc, K, r.Kq,
+                       p.has_bias, dW, lddw, db);
     return stin_launch_status();
 }
 extern "C" int stin_gemm_tn_f32(const float* G, int64_t ldg, const float* X, int64_t ldx, int64_t M, int Nc, int K,
                                 int ones_column, const float* row_weight, int64_t ld_weight, float* dW, int64_t lddw,
                                 int precision, void* workspace, size_t workspace_bytes, stin_stream_t stream_) {
-    return gemm_tn_f32_impl(G, ldg, X, ldx, M, Nc, K, ones_column, row_weight, ld_weight, dW, lddw, nullptr, precision, workspace,
+    return gemm_tn_impl(0, G, ldg, X, ldx, M, Nc, K, ones_column, row_weight, ld_weight, dW, lddw, nullptr, precision, workspace,
                             workspace_bytes, stream_);
 }
 // dW [Nc, K] = G^T relu(gamma ((X - mean) rstd) + beta): the weight gradient of SingleConvMeshNet's per-edge Linear from the
@@ -571,7 +525,7 @@ extern "C" int stin_gemm_tn_bn_f32(const float* G, int64_t ldg, const float* X, 
     tf.rstd = rstd;
     tf.gamma = gamma;
     tf.beta = beta;
-    return gemm_tn_f32_impl(G, ldg, X, ldx, M, Nc, K, 0, nullptr, 0, dW, lddw, nullptr, precision, workspace, workspace_bytes, stream_, &tf);
+    return gemm_tn_impl(0, G, ldg, X, ldx, M, Nc, K, 0, nullptr, 0, dW, lddw, nullptr, precision, workspace, workspace_bytes, stream_, &tf);
 }
 // weight gradient dW [Nc, K] (row pitch lddw >= K) and bias gradient db [Nc] as SEPARATE destinations - e.g. the views of an
 // nn.Linear's weight.grad / bias.grad in a flat gradient bucket: no [Nc, K + 1] intermediate and no slicing copies afterwards
@@ -579,17 +533,17 @@ extern "C" int stin_gemm_tn_wb_f32(const float* G, int64_t ldg, const float* X, 
                                    const float* row_weight, int64_t ld_weight, float* dW, int64_t lddw, float* db, int precision,
                                    void* workspace, size_t workspace_bytes, stin_stream_t stream_) {
     STIN_REQUIRE(db != nullptr, STIN_E_NULL);
-    return gemm_tn_f32_impl(G, ldg, X, ldx, M, Nc, K, 1, row_weight, ld_weight, dW, lddw, db, precision, workspace, workspace_bytes,
+    return gemm_tn_impl(0, G, ldg, X, ldx, M, Nc, K, 1, row_weight, ld_weight, dW, lddw, db, precision, workspace, workspace_bytes,
                             stream_);
 }
 
 // ------------------------------------------------------------------ bf16-storage entry points
 namespace {
 template <int BM, int BN, int WM, int WN, typename OUT, typename Args>
-void nt_launch_b16_tile(const NtRoute& r, bool wb, const NtLaunch& l, const Args& a) {
-    if (wb) nt_launch<k_gemm_nt_b16<BM, BN, WM, WN, OUT, true, true>>(l, a);
-    else if (r.vec) nt_launch<k_gemm_nt_b16<BM, BN, WM, WN, OUT, true>>(l, a);
-    else nt_launch<k_gemm_nt_b16<BM, BN, WM, WN, OUT, false>>(l, a);
+void nt_launch_b16_tile(const NtRoute& r, bool wb, const KernelLaunch& l, const Args& a) {
+    if (wb) launch_kernel<k_gemm_nt_b16<BM, BN, WM, WN, OUT, true, true>>(l, a);
+    else if (r.vec) launch_kernel<k_gemm_nt_b16<BM, BN, WM, WN, OUT, true>>(l, a);
+    else launch_kernel<k_gemm_nt_b16<BM, BN, WM, WN, OUT, false>>(l, a);
 }
 }  // namespace
 extern "C" int stin_gemm_nt_bf16(const stin_bf16_t* A_, int64_t lda, const float* W, int64_t ldw, const float* bias,
@@ -615,13 +569,13 @@ extern "C" int stin_gemm_nt_bf16(const stin_bf16_t* A_, int64_t lda, const float
         const auto tail = std::make_tuple(ldw, bias, row_mask, ld_mask, residual, ld_res, M, Nc, K, c, ldc, r.vec_out);
         if (r.family == STIN_NT_B16_GLDS) {
             const auto a = std::tuple_cat(head, std::make_tuple(reinterpret_cast<const stin_bf16*>(W)), tail);
-            const NtLaunch l = {dim3((unsigned)r.grid), r.bm == 256 ? 512 : 256, r.lds, (int)r.lds, stream};
-            if (r.bm == 256) nt_launch<k_gemm_nt_b16_glds<OUT, 2, 4, 4, 2>>(l, a);
-            else nt_launch<k_gemm_nt_b16_glds<OUT, 2, 2, 2, 2>>(l, a);
+            const KernelLaunch l = {dim3((unsigned)r.grid), r.bm == 256 ? 512 : 256, r.lds, (int)r.lds, stream};
+            if (r.bm == 256) launch_kernel<k_gemm_nt_b16_glds<OUT, 2, 4, 4, 2>>(l, a);
+            else launch_kernel<k_gemm_nt_b16_glds<OUT, 2, 2, 2, 2>>(l, a);
             return;
         }
         const auto a = std::tuple_cat(head, std::make_tuple(W), tail);
-        const NtLaunch l = {dim3((unsigned)r.grid), BLOCK, 0, 0, stream};
+        const KernelLaunch l = {dim3((unsigned)r.grid), BLOCK, 0, 0, stream};
         if (r.bn == 32) nt_launch_b16_tile<128, 32, 4, 1, OUT>(r, wb, l, a);
         else if (r.bm == 128) nt_launch_b16_tile<128, 64, 2, 2, OUT>(r, wb, l, a);
         else nt_launch_b16_tile<64, 64, 2, 2, OUT>(r, wb, l, a);
@@ -631,35 +585,16 @@ extern "C" int stin_gemm_nt_bf16(const stin_bf16_t* A_, int64_t lda, const float
     return stin_launch_status();
 }
 
-static int gemm_tn_bf16_impl(const stin_bf16_t* G_, int64_t ldg, const stin_bf16_t* X_, int64_t ldx, int64_t M, int Nc,
-                            int K, int ones_column, const stin_bf16_t* row_weight_, int64_t ld_weight, float* dW,
-                            int64_t lddw, float* db, void* workspace, size_t workspace_bytes, stin_stream_t stream_) {
-    stin_clear_stale_error();
-    hipStream_t stream = (hipStream_t)stream_;
-    const int Kp = K + ((ones_column && db == nullptr) ? 1 : 0);
-    STIN_REQUIRE(M >= 0 && Nc > 0 && K > 0 && ldg >= Nc && ldx >= K && lddw >= Kp, STIN_E_SIZE);
-    STIN_REQUIRE(dW && workspace && (M == 0 || (G_ && X_)), STIN_E_NULL);
-    STIN_REQUIRE(workspace_bytes >= stin_gemm_tn_workspace_bytes(M, Nc, K, ones_column), STIN_E_WORKSPACE);
-    float* slab = reinterpret_cast<float*>((reinterpret_cast<uintptr_t>(workspace) + 255) & ~(uintptr_t)255);
-    stin_tn_problem p;
-    int rc = stin_tn_problem_init(&p, 1, G_, ldg, X_, ldx, M, Nc, K, ones_column, row_weight_, ld_weight, STIN_GEMM_BF16X3, slab, nullptr);
-    if (rc != STIN_OK) return rc;
-    rc = stin_tn_slabs(&p, 1, STIN_GEMM_BF16X3, stream_);
-    if (rc != STIN_OK) return rc;
-    const int64_t n4 = (int64_t)Nc * p.Kq / 4 + (p.has_bias ? (Nc + 3) / 4 : 0);
-    hipLaunchKernelGGL(k_reduce_slabs, dim3((unsigned)((n4 + RS_COLS - 1) / RS_COLS)), dim3(BLOCK), 0, stream, slab, p.chunks, Nc, K,
-                       p.Kq, p.has_bias, dW, lddw, db);
-    return stin_launch_status();
-}
 extern "C" int stin_gemm_tn_bf16(const stin_bf16_t* G_, int64_t ldg, const stin_bf16_t* X_, int64_t ldx, int64_t M, int Nc,
                                  int K, int ones_column, const stin_bf16_t* row_weight_, int64_t ld_weight, float* dW,
                                  int64_t lddw, void* workspace, size_t workspace_bytes, stin_stream_t stream_) {
-    return gemm_tn_bf16_impl(G_, ldg, X_, ldx, M, Nc, K, ones_column, row_weight_, ld_weight, dW, lddw, nullptr, workspace,
-                             workspace_bytes, stream_);
+    return gemm_tn_impl(1, G_, ldg, X_, ldx, M, Nc, K, ones_column, row_weight_, ld_weight, dW, lddw, nullptr, STIN_GEMM_BF16X3, workspace,
+                        workspace_bytes, stream_);
 }
 extern "C" int stin_gemm_tn_wb_bf16(const stin_bf16_t* G_, int64_t ldg, const stin_bf16_t* X_, int64_t ldx, int64_t M, int Nc,
                                     int K, const stin_bf16_t* row_weight_, int64_t ld_weight, float* dW, int64_t lddw, float* db,
                                     void* workspace, size_t workspace_bytes, stin_stream_t stream_) {
     STIN_REQUIRE(db != nullptr, STIN_E_NULL);
-    return gemm_tn_bf16_impl(G_, ldg, X_, ldx, M, Nc, K, 1, row_weight_, ld_weight, dW, lddw, db, workspace, workspace_bytes, stream_);
+    return gemm_tn_impl(1, G_, ldg, X_, ldx, M, Nc, K, 1, row_weight_, ld_weight, dW, lddw, db, STIN_GEMM_BF16X3, workspace, workspace_bytes,
+                        stream_);
 }

@@ -95,12 +95,10 @@ __global__ __launch_bounds__(WS_THREADS) void k_gemm_tn_ws(const stin_tn_batch b
     const int tiles_j = batch.p[pi].tiles_j, tiles = batch.p[pi].tiles_i * tiles_j;
     const int rows_per_chunk = batch.p[pi].rows_per_chunk;
 
-    // block -> (row chunk, output tile): the map of k_gemm_tn_bf16s (chunks of one XCD share its L2)
-    const int64_t b = (int64_t)blockIdx.x - batch.p[pi].block0;
-    const int64_t xcd = b % 8, q = b / 8;
-    const int64_t chunk = chunks >= 8 ? (q / tiles) * 8 + xcd : b / tiles;
-    const int tile = (int)(chunks >= 8 ? q % tiles : b % tiles);
-    if (chunk >= chunks) return;                                  // (block-uniform; before any barrier)
+    // block -> (row chunk, output tile): the map of every tiled TN kernel (chunks of one XCD share its L2)
+    int64_t chunk;
+    int tile;
+    if (!tn_block_map((int64_t)blockIdx.x - batch.p[pi].block0, chunks, tiles, chunk, tile)) return;   // (block-uniform; before any barrier)
     const int tj = tile % tiles_j, ti = tile / tiles_j;
     const int i0 = ti * WS_T, j0 = tj * WS_T;
     const int64_t mb = chunk * rows_per_chunk;
@@ -369,7 +367,7 @@ __global__ __launch_bounds__(WS_THREADS) void k_gemm_tn_ws(const stin_tn_batch b
 // Sums the partial slabs of both products in the fixed order of k_reduce_slabs (16 chunk-lanes x 16 float4 groups per block:
 // each chunk-lane walks the chunk list with stride 16, four partial sums, then a fixed-order LDS reduction over the lanes)
 // and writes the sums where k_unpack would have put them: bit-identical to k_reduce_slabs + k_unpack.
-constexpr int FN_COLS = 16, FN_KL = 16, FN_BLOCK = 256;
+constexpr int FN_BLOCK = 256;                                  // (FN_COLS x FN_KL threads: fn_partial, stin_common.h)
 struct WgFinal {
     const float* slabA;      // dW2 product: [chunksA][Cout][KqA] + bias [Cout]
     const float* slabB;      // packed product: [chunksB][Yw][KqB] + bias [Yw]
@@ -379,42 +377,6 @@ struct WgFinal {
     const float* ti_colsum;  // compact trans-inv layout: [ti_rows][H] column partials of dA (stin_graph.hip k_edge_bwd_mask_ti) -> db1
     int64_t ti_rows;
 };
-__device__ __forceinline__ void add4(float4& a, const float4 b) { a.x += b.x; a.y += b.y; a.z += b.z; a.w += b.w; }
-
-// One chunk-lane's share of a fixed-order fold over `chunks` rows of stride `cs` floats (lane ty of FN_KL walks rows ty, ty + FN_KL, ...;
-// four running sums, merged (s0 + s1) + (s2 + s3)): shared by k_wgrad_finalize and k_colsum_fold so that both give the same bits.
-__device__ __forceinline__ float4 fn_partial(const float* __restrict__ p, int64_t cs, int64_t chunks, int ty) {
-        float4 s0 = make_float4(0.f, 0.f, 0.f, 0.f), s1 = s0, s2 = s0, s3 = s0;
-        if (p != nullptr) {
-            int64_t c = ty;
-            // (round 4) sixteen slab loads in flight per thread where the chunk list is long (the first block's skinny product
-            // writes ~900 chunks: with four in flight this fold is 14-28 dependent trips to the fabric - 200 us at the very end of
-            // the backward pass under rocprofv3, 11 us now; stand-alone and in the un-profiled step the difference is small); the additions keep the order of the four-at-a-time loop below: bit-identical sums
-            for (; c + 15 * FN_KL < chunks; c += 16 * FN_KL) {
-                float4 v[16];
-#pragma unroll
-                for (int u = 0; u < 16; ++u) v[u] = ld4(p + (c + u * FN_KL) * cs);
-#pragma unroll
-                for (int u = 0; u < 16; u += 4) {
-                    add4(s0, v[u]);
-                    add4(s1, v[u + 1]);
-                    add4(s2, v[u + 2]);
-                    add4(s3, v[u + 3]);
-                }
-            }
-            for (; c + 3 * FN_KL < chunks; c += 4 * FN_KL) {
-                add4(s0, ld4(p + c * cs));
-                add4(s1, ld4(p + (c + FN_KL) * cs));
-                add4(s2, ld4(p + (c + 2 * FN_KL) * cs));
-                add4(s3, ld4(p + (c + 3 * FN_KL) * cs));
-            }
-            for (; c < chunks; c += FN_KL) add4(s0, ld4(p + c * cs));
-        }
-        add4(s0, s1);
-        add4(s2, s3);
-        add4(s0, s2);
-        return s0;
-}
 
 // db1 of a compact trans-inv block from the edge stage's column partials [rows][H] alone (the per-op path; the whole-block path folds
 // them inside k_wgrad_finalize): same lanes, same order -> the same bits
@@ -514,24 +476,17 @@ inline size_t up256(size_t v) { return (v + 255) & ~(size_t)255; }
 
 }  // namespace
 
-// (re-read on every call: one process can A/B the four-wave and the producer / consumer kernel)
-bool stin_tn_ws_enabled() {
-    const char* e = getenv("STIN_TN_WS");
-    return e == nullptr || atoi(e) != 0;
-}
-
-int stin_tn_ws_launch(stin_tn_batch batch, stin_stream_t stream) {
+int stin_tn_ws_launch(const stin_tn_problem* pa, const TnRoute* ra, const stin_tn_problem* pb, const TnRoute* rb, stin_stream_t stream) {
     const int prio = 1;                                            // consumers (the MFMA-issuing waves) at raised priority
-    unsigned blocks = 0;
-    bool mapped = false;
-    for (int i = 0; i < batch.n; ++i) {
-        stin_tn_problem& p = batch.p[i];
-        mapped = mapped || p.x_row_map != nullptr;
-        blocks = (blocks + 7u) & ~7u;                              // every problem starts on an XCD round (blockIdx % 8 == XCD)
-        p.block0 = blocks;
-        blocks += (unsigned)((p.chunks >= 8 ? ((p.chunks + 7) / 8) * 8 : p.chunks) * (int64_t)p.tiles_i * p.tiles_j);
-    }
+    stin_tn_batch batch;
+    batch.p[0] = *pa;
+    batch.p[1] = pb != nullptr ? *pb : *pa;
+    batch.n = pb != nullptr ? 2 : 1;
+    const unsigned first = ((unsigned)ra->grid + 7u) & ~7u;        // every problem starts on an XCD round (blockIdx % 8 == XCD)
+    batch.p[1].block0 = first;
+    const unsigned blocks = pb != nullptr ? first + (unsigned)rb->grid : (unsigned)ra->grid;
     if (blocks == 0) return STIN_OK;
+    const bool mapped = pa->x_row_map != nullptr || (pb != nullptr && pb->x_row_map != nullptr);
     if (mapped) hipLaunchKernelGGL(k_gemm_tn_ws<true>, dim3(blocks), dim3(WS_THREADS), 0, (hipStream_t)stream, batch, prio);
     else hipLaunchKernelGGL(k_gemm_tn_ws<false>, dim3(blocks), dim3(WS_THREADS), 0, (hipStream_t)stream, batch, prio);
     return stin_launch_status();
@@ -539,8 +494,14 @@ int stin_tn_ws_launch(stin_tn_batch batch, stin_stream_t stream) {
 
 extern "C" size_t stin_edgeconv_wgrad_workspace_bytes(int64_t N, int Cp, int H, int Cout, int has_shortcut) {
     if (N < 0 || Cp <= 0 || H <= 0 || Cout <= 0) return 0;
-    const int Yw = 2 * H + (has_shortcut ? Cout : 0);
-    return up256(stin_gemm_tn_workspace_bytes(N, Cout, H, 1)) + up256(stin_gemm_tn_workspace_bytes(N, Yw, Cp, 1)) + 256;
+    // the packed product has Yw = 2 H (+ Cout) rows of dW, or H (+ Cout) in the compact trans-inv layout: the narrower product can
+    // take the route with MORE chunks (the skinny kernel up to 1024 columns), so slab B holds the larger of the two
+    size_t slab_b = 0;
+    for (int ti = 0; ti <= STIN_TI_COMPACT; ti += STIN_TI_COMPACT) {
+        const size_t b = stin_gemm_tn_workspace_bytes(N, stin_yw(H, Cout, has_shortcut, ti), Cp, 1);
+        if (b > slab_b) slab_b = b;
+    }
+    return up256(stin_gemm_tn_workspace_bytes(N, Cout, H, 1)) + up256(slab_b) + 256;
 }
 
 extern "C" int stin_edgeconv_wgrad(int storage, const void* dagg, int64_t ld_dagg, const void* hE, int64_t ldh, const void* dY,
@@ -571,51 +532,25 @@ static int wgrad_impl(int storage, const void* dagg, int64_t ld_dagg, const void
     STIN_REQUIRE(x_row_map == nullptr || (x_rows > 0 && stin_aligned16(x_row_map)), STIN_E_SIZE);
     char* p = reinterpret_cast<char*>((reinterpret_cast<uintptr_t>(workspace) + 255) & ~(uintptr_t)255);
     float* slabA = reinterpret_cast<float*>(p);
-    float* slabB = reinterpret_cast<float*>(p + up256(stin_gemm_tn_workspace_bytes(N, Cout, H, 1)));
+    const size_t offB = up256(stin_gemm_tn_workspace_bytes(N, Cout, H, 1));
+    float* slabB = reinterpret_cast<float*>(p + offB);
     const size_t es = storage ? 2 : 4;
     const void* row_w = static_cast<const char*>(hE) + (size_t)H * es;          // the [deg > 0] column of hE weights db2
+    const TnSwitches sw = stin_tn_switches();                    // (once for both products)
     stin_tn_problem pa, pb;
-    int wsa = 0, wsb = 0;
-    int rc = stin_tn_problem_init(&pa, storage, dagg, ld_dagg, hE, ldh, N, Cout, H, 1, row_w, ldh, precision, slabA, &wsa);
+    TnRoute ra, rb;
+    int rc = stin_tn_setup(&pa, &ra, sw, storage, dagg, ld_dagg, hE, ldh, N, Cout, H, 1, row_w, ldh, precision, slabA, nullptr, nullptr);
     if (rc != STIN_OK) return rc;
-    rc = stin_tn_problem_init(&pb, storage, dY, ldy, x, ldx, N, Yw, Cp, 1, nullptr, 0, precision, slabB, &wsb);
+    rc = stin_tn_setup(&pb, &rb, sw, storage, dY, ldy, x, ldx, N, Yw, Cp, 1, nullptr, 0, precision, slabB, nullptr, x_row_map);
     if (rc != STIN_OK) return rc;
-    if (x_row_map != nullptr && N > 0) {                          // only the producer / consumer kernel reads X through a map
-        STIN_REQUIRE(wsb, STIN_E_UNSUPPORTED);
-        pb.x_row_map = x_row_map;
-    }
-    if (wsa && wsb) {                                             // both products on the producer / consumer kernel: ONE grid
-        stin_tn_batch batch;
-        batch.p[0] = pa;
-        batch.p[1] = pb;
-        batch.n = 2;
-        rc = stin_tn_ws_launch(batch, stream);
-    } else {
-        rc = stin_tn_slabs(&pa, storage, precision, stream);
-        if (rc == STIN_OK) rc = stin_tn_slabs(&pb, storage, precision, stream);
-    }
+    // the slabs the kernels will write must fit what the caller was told to allocate: A in front of B, B to the end (256 bytes of
+    // alignment slack)
+    auto slab_bytes = [](const TnRoute& r, int Nc) { return (size_t)r.chunks * ((size_t)Nc * r.Kq + ((Nc + 3) & ~3)) * sizeof(float); };
+    STIN_REQUIRE(slab_bytes(ra, Cout) <= offB && offB + slab_bytes(rb, Yw) + 256 <= workspace_bytes, STIN_E_WORKSPACE);
+    rc = stin_tn_slabs(&pa, &ra, &pb, &rb, precision, stream);
     if (rc != STIN_OK) return rc;
-    WgFinal f;
-    f.slabA = slabA;
-    f.slabB = slabB;
-    f.chunksA = pa.chunks;
-    f.chunksB = pb.chunks;
-    f.KqA = pa.Kq;
-    f.KqB = pb.Kq;
-    f.Cin = Cin;
-    f.Cp = Cp;
-    f.H = H;
-    f.Cout = Cout;
-    f.has_shortcut = has_shortcut;
-    f.trans_inv = trans_inv;
-    f.dW1 = dW1;
-    f.db1 = db1;
-    f.dWs = dWs;
-    f.dbs = dbs;
-    f.dW2 = dW2;
-    f.db2 = db2;
-    f.ti_colsum = ti_colsum;
-    f.ti_rows = ti_rows;
+    const WgFinal f = {slabA, slabB, pa.chunks, pb.chunks, pa.Kq, pb.Kq, Cin, Cp, H, Cout, has_shortcut, trans_inv,
+                       dW1, db1, dWs, dbs, dW2, db2, ti_colsum, ti_rows};
     const int64_t groups = (int64_t)Cout * pa.Kq / 4 + (Cout + 3) / 4 + (int64_t)H * pb.Kq / 4 +
                            (has_shortcut ? (int64_t)Cout * pb.Kq / 4 : 0) + (Yw + 3) / 4 + ((compact && db1 != nullptr) ? H / 4 : 0);
     hipLaunchKernelGGL(k_wgrad_finalize, dim3((unsigned)((groups + FN_COLS - 1) / FN_COLS)), dim3(FN_BLOCK), 0, (hipStream_t)stream, f);
@@ -641,16 +576,13 @@ extern "C" int stin_edgeconv_wgrad_map(int storage, const void* dagg, int64_t ld
 }
 
 // 1 exactly where the packed product [dW1 ; dWs | db] = dY^T [x | 1] of such a block runs on the producer / consumer kernel (wide
-// layout, 16-byte aligned rows of Yw and Cp floats): ws_eligible of its stin_tn_problem_init, STIN_TN_WS honoured.  Host only.
+// layout, 16-byte aligned rows of Yw and Cp floats): the family of its route, STIN_TN_WS honoured.  Host only.
 extern "C" int stin_edgeconv_wgrad_map_supported(int64_t N, int Cp, int H, int Cout, int has_shortcut, int precision) {
     if (N <= 0 || Cp <= 0 || H <= 0 || Cout <= 0) return 0;
     const int Yw = stin_yw(H, Cout, has_shortcut, 0);
-    stin_tn_problem pb;
-    int wsb = 0;
-    void* const some = reinterpret_cast<void*>(uintptr_t(256));   // (geometry only: nothing is read through it)
-    if (stin_tn_problem_init(&pb, 0, some, Yw, some, Cp, N, Yw, Cp, 1, nullptr, 0, precision, static_cast<float*>(some), &wsb) != STIN_OK)
-        return 0;
-    return wsb;
+    const TnProblem pb = {0, N, Yw, Cp, Yw, Cp, precision, true, true, false, false, true};
+    const TnRoute rb = stin_tn_route(pb, stin_tn_switches());
+    return (rb.status == STIN_OK && rb.family == STIN_TN_FAMILY_PC) ? 1 : 0;
 }
 
 extern "C" int stin_edge_bwd_ti_colsum_fold_f32(const float* colsum, int64_t rows, int H, float* db1, stin_stream_t stream) {

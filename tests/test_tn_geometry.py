@@ -1,4 +1,4 @@
-"""The geometry of the weight-gradient products, asked of the host-only query stin_gemm_tn_geometry (no GPU): every point of the
+"""The geometry of the weight-gradient products, asked of the host-only query stin_gemm_tn_route (no GPU): every point of the
 sweep in tests/_tn_table.py must reach the tile class, chunk count, load width and kernel family its line names, and the
 workspace the caller is told to allocate must hold the slabs of that geometry.  tests/test_wgrad_exact.py runs the same table on
 the GPU; this file is the check that it aims where it says - a change of a tile or chunk rule shows up here first."""
@@ -11,6 +11,7 @@ _C = _lib.CONSTANTS
 
 
 def _check(lib, p, g):
+    assert g['family'] == p.family, (p.id, g)
     assert g['tile'] == p.tile, (p.id, g)
     assert g['chunks'] == p.chunks, (p.id, g)
     assert g['vec'] == p.vec and g['ws'] == p.ws, (p.id, g)
@@ -22,10 +23,15 @@ def _check(lib, p, g):
     assert g['chunks'] * g['rows'] >= p.M and (g['chunks'] - 1) * g['rows'] < max(p.M, 1)
     if p.tile != T.SKINNY:
         assert g['tiles'] == ((p.Nc + p.tile[0] - 1) // p.tile[0], (p.K + p.tile[1] - 1) // p.tile[1])
+    # the grid: nothing without rows | one block per chunk (skinny) | from 8 chunks on whole rounds of 8 chunks, times the tiles
+    rounds = g['chunks'] if g['chunks'] < 8 else (g['chunks'] + 7) // 8 * 8
+    assert g['grid'] == {T.NONE: 0, T.SKINNY_K: g['chunks']}.get(p.family, rounds * g['tiles'][0] * g['tiles'][1]), (p.id, g)
 
 
 def test_precision_constants_of_the_table():
     assert (T.F32, T.X3, T.X6) == (_C['STIN_GEMM_F32'], _C['STIN_GEMM_BF16X3'], _C['STIN_GEMM_BF16X6'])
+    assert (T.NONE, T.SKINNY_K, T.EXACT, T.FOUR_WAVE, T.PC, T.B16_REG, T.B16_TR) == tuple(
+        _C['STIN_TN_FAMILY_' + n] for n in ('NONE', 'SKINNY', 'F32', 'BF16S', 'PC', 'B16_REG', 'B16_TR'))
 
 
 @pytest.mark.parametrize('p', T.POINTS + T.BN_POINTS, ids=lambda p: p.id)
@@ -48,10 +54,61 @@ def test_sweep_covers_every_chunk_count_on_every_route():
         assert all(p.M - 128 * (p.chunks - 1) in (1, 128) for p in T.POINTS if p.id.startswith(name + '-c'))
     assert {p.tile for p in T.POINTS} == {(64, 64), (64, 128), (128, 64), (128, 128), (256, 256), T.SKINNY}
     assert {p.K for p in T.POINTS if p.tile == T.SKINNY} == {4, 8, 12, 16}
-    # (Not checked here, because the query cannot see them: the round-up of the grid to 8 chunks per XCD round - 9 chunks = 16 block
-    # slots of which 7 write nothing, stin_tn_slabs - and the trip thresholds of the slab fold - four in flight up to 64 chunks,
-    # sixteen from 241, k_reduce_slabs / fn_partial.  The counts 8, 9, 63 .. 65, 240, 241 are in the table for them; their
-    # protection is the equality on the GPU at those counts.)
+    assert {p.family for p in T.POINTS} == {T.NONE, T.SKINNY_K, T.EXACT, T.FOUR_WAVE, T.PC, T.B16_REG, T.B16_TR}
+    # (Not checked here, because the query cannot see them: the trip thresholds of the slab fold - four in flight up to 64 chunks,
+    # sixteen from 241, fn_partial.  The counts 63 .. 65, 240, 241 are in the table for them; their protection is the equality on
+    # the GPU at those counts.)
+
+
+def test_grid_blocks_at_seven_eight_and_nine_chunks(monkeypatch):
+    """128-row chunks (M = 128 c on at most 6 tiles): 7 chunks in plain order, 8 = one whole round of the 8 XCDs, 9 = two rounds
+    (16 block slots per tile, of which 7 write nothing); the skinny kernel has one block per chunk."""
+    lib = _lib.load()
+    T.set_env(monkeypatch, {})
+    for storage, prec, Nc, K, tiles, family in ((0, T.F32, 64, 64, 1, T.EXACT), (0, T.X3, 320, 128, 3, T.PC), (0, T.X6, 132, 260, 6, T.FOUR_WAVE),
+                                                (1, T.X3, 320, 128, 3, T.B16_REG), (1, T.X3, 512, 512, 4, T.B16_TR), (1, T.X3, 128, 128, 1, T.B16_TR)):
+        for chunks, slots in ((7, 7), (8, 8), (9, 16)):
+            g = T.geometry(lib, storage, 128 * chunks, Nc, K, Nc, K, 1, 1, prec)
+            assert (g['family'], g['chunks'], g['tiles'][0] * g['tiles'][1], g['grid']) == (family, chunks, tiles, slots * tiles), (Nc, K, g)
+    for chunks in (7, 8, 9):
+        g = T.geometry(lib, 0, 128 * chunks, 320, 12, 320, 12, 1, 1, T.X3)
+        assert (g['family'], g['chunks'], g['grid']) == (T.SKINNY_K, chunks, chunks)
+
+
+def test_the_eight_value_query_writes_eight_values_equal_to_the_route(monkeypatch):
+    """stin_gemm_tn_geometry keeps the contract its callers allocate for: eight int32 and not one more, the first eight of the route"""
+    import ctypes
+    lib = _lib.load()
+    T.set_env(monkeypatch, {})
+    for p in T.CLASS_POINTS:
+        g = T.point_geometry(lib, p)
+        out8 = (ctypes.c_int32 * 10)(*([-7] * 10))
+        assert lib.stin_gemm_tn_geometry(p.storage, p.M, p.Nc, p.K, p.Nc + p.padg, p.K + p.padx, int(p.off == 0), 1, p.prec, ctypes.addressof(out8)) == 0
+        if not p.env:
+            assert list(out8) == [*g['tile'], *g['tiles'], g['rows'], g['chunks'], g['vec'], g['ws'], -7, -7], p.id
+
+
+def test_block_workspace_holds_the_compact_layout_where_it_takes_more_chunks(monkeypatch):
+    """The compact trans-inv layout runs the packed product with Yw = H (+ Cout) rows inside the workspace of
+    stin_edgeconv_wgrad_workspace_bytes, which takes no layout.  With Cp <= 16 and H (+ Cout) <= 1024 < 2 H (+ Cout) the compact
+    product is the skinny kernel's (about 1024 chunks) and the wide one is not (about 384 / tiles): slab B must hold the larger of
+    the two, slab A (rounded up to 256 bytes) lies in front of it - what the entry points' guard requires."""
+    lib = _lib.load()
+    T.set_env(monkeypatch, {})
+    for N in (60211, 200704):
+        for Cp, H, Cout, sc in ((12, 768, 64, 0), (12, 512, 512, 1), (16, 520, 64, 0), (4, 1024, 64, 0), (12, 64, 32, 1)):
+            ws_bytes = lib.stin_edgeconv_wgrad_workspace_bytes(N, Cp, H, Cout, sc)
+            off_b = (lib.stin_gemm_tn_workspace_bytes(N, Cout, H, 1) + 255) // 256 * 256
+            ga = T.geometry(lib, 0, N, Cout, H, Cout, H + 4, 1, 1, T.X3)
+            assert ga['chunks'] * (Cout * H + Cout) * 4 <= off_b
+            chunks = {}
+            for ti in (0, 2):
+                yw = T.block_yw(H, Cout, sc, ti)
+                gb = T.geometry(lib, 0, N, yw, Cp, yw, Cp, 1, 1, T.X3)
+                chunks[ti] = gb['chunks']
+                assert off_b + gb['chunks'] * (yw * ((Cp + 3) & ~3) + ((yw + 3) & ~3)) * 4 + 256 <= ws_bytes, (N, Cp, H, Cout, sc, ti, gb)
+            if H == 768:
+                assert T.geometry(lib, 0, N, 768, Cp, 768, Cp, 1, 1, T.X3)['family'] == T.SKINNY_K and chunks[2] > 10 * chunks[0]
 
 
 def test_one_block_per_cu_rule_at_its_boundary(monkeypatch):
@@ -72,13 +129,17 @@ def test_one_block_per_cu_rule_at_its_boundary(monkeypatch):
 def test_query_argument_errors_and_no_write_on_error():
     import ctypes
     lib = _lib.load()
-    out = (ctypes.c_int32 * 8)(*([77] * 8))
+    out = (ctypes.c_int32 * 10)(*([77] * 10))
     at = ctypes.addressof(out)
+    assert lib.stin_gemm_tn_route(0, 100, 64, 64, 63, 64, 1, 0, T.X3, at) == _C['STIN_E_SIZE']             # ldg < Nc
+    assert lib.stin_gemm_tn_route(0, -1, 64, 64, 64, 64, 1, 0, T.X3, at) == _C['STIN_E_SIZE']
+    assert lib.stin_gemm_tn_route(2, 100, 64, 64, 64, 64, 1, 0, T.X3, at) == _C['STIN_E_UNSUPPORTED']
+    assert lib.stin_gemm_tn_route(0, 100, 64, 64, 64, 64, 1, 0, T.X3, None) == _C['STIN_E_NULL']
     assert lib.stin_gemm_tn_geometry(0, 100, 64, 64, 63, 64, 1, 0, T.X3, at) == _C['STIN_E_SIZE']          # ldg < Nc
     assert lib.stin_gemm_tn_geometry(0, -1, 64, 64, 64, 64, 1, 0, T.X3, at) == _C['STIN_E_SIZE']
     assert lib.stin_gemm_tn_geometry(2, 100, 64, 64, 64, 64, 1, 0, T.X3, at) == _C['STIN_E_UNSUPPORTED']
     assert lib.stin_gemm_tn_geometry(0, 100, 64, 64, 64, 64, 1, 0, T.X3, None) == _C['STIN_E_NULL']
-    assert list(out) == [77] * 8
+    assert list(out) == [77] * 10
 
 
 @pytest.mark.parametrize('case', list(T.block_cases()), ids=lambda c: '%s-sc%d-ti%d-st%d-p%d-n%d' % ('x'.join(map(str, c[0])), *c[1:]))

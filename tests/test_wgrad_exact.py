@@ -8,7 +8,7 @@ across a retiling; the bit-identity tests between two HIP routes (test_hip_parit
 test_mapped_weight_gradient_...) are expected to be replaced by one.
 
 Every case takes its geometry from tests/_tn_table.py (whose expectations tests/test_tn_geometry.py checks without a GPU) and
-asserts it again through stin_gemm_tn_geometry for the operands it really passes.  Operands are views with ld != width inside
+asserts it again through stin_gemm_tn_route for the operands it really passes.  Operands are views with ld != width inside
 buffers filled with 1e30, so a read outside an operand changes a sum instead of faulting; outputs lie inside buffers pre-filled
 with 7.0 that must stay 7.0 around the result.
 """
@@ -103,7 +103,7 @@ def tn_raw(G, X, ones, w, prec, wb=False):
 def check_geometry(p, G, X, ones=1):
     aligned = int(G.data_ptr() % 16 == 0 and X.data_ptr() % 16 == 0)
     g = T.geometry(_lib.load(), p.storage, p.M, p.Nc, p.K, G.stride(0), X.stride(0), aligned, ones, p.prec)
-    assert (g['tile'], g['chunks'], g['vec'], g['ws']) == (p.tile, p.chunks, p.vec, p.ws), (p.id, g)
+    assert (g['family'], g['tile'], g['chunks'], g['vec'], g['ws']) == (p.family, p.tile, p.chunks, p.vec, p.ws), (p.id, g)
 
 
 def operands(p, seed=0):
@@ -207,17 +207,23 @@ def test_bf16x3_keeps_three_of_the_four_piece_products(p, monkeypatch):
 
 
 # ---------------------------------------------------------------------------------------------- X read as relu(bn(X))
-@pytest.mark.parametrize('p', T.BN_POINTS, ids=lambda p: p.id)
-def test_tn_bn_product_of_integers_is_exact(p, monkeypatch):
+def bn_product_is_exact(p, tf_off=0):
     """stin_gemm_tn_bn_f32: dW = G^T relu(X s + t), s = gamma rstd, t = beta - mean s (the form stin_hip.h documents).  Integer
     mean, beta in {-2 .. 2}, gamma in {-2 .. 2}, rstd in {0.5, 1, 2}: s, t and relu(X s + t) <= 22 are exact half-integers of
-    at most 6 significant bits (one bf16 piece); |G X'| <= 66 in steps of 0.5 and 32 896 x 66 x 2 < 2^24: exact in any order."""
-    T.set_env(monkeypatch, p.env)
+    at most 6 significant bits (one bf16 piece); |G X'| <= 66 in steps of 0.5 and 32 896 x 66 x 2 < 2^24: exact in any order.
+    tf_off: the four transform vectors lie that many elements behind a 16-byte boundary, in buffers of POISON."""
     lib = _lib.load()
     G, X = ints((p.M, p.Nc), 3 * p.M + p.Nc), ints((p.M, p.K), 5 * p.M + p.K)
-    check_geometry(p, G, X, ones=0)
+    if tf_off == 0:
+        check_geometry(p, G, X, ones=0)
+    else:       # the query takes no transform: it answers for the aligned form, whose tile and chunks this route keeps
+        g = T.geometry(lib, 0, p.M, p.Nc, p.K, p.Nc, p.K, 1, 0, p.prec)
+        assert (g['tile'], g['chunks']) == (p.tile, p.chunks) and G.data_ptr() % 16 == 0 and X.data_ptr() % 16 == 0
     mean, beta, gamma = (ints((p.K,), 19 + i + p.K, lo=-2, hi=2) for i in range(3))
     rstd = torch.tensor([0.5, 1.0, 2.0], device=DEV)[ints((p.K,), 23 + p.K, lo=0, hi=2).long()]
+    if tf_off:
+        mean, beta, gamma, rstd = (strided(v[None, :], 4, tf_off)[0] for v in (mean, beta, gamma, rstd))
+        assert all(v.data_ptr() % 16 == 4 * tf_off and v.is_contiguous() for v in (mean, beta, gamma, rstd))
     s = gamma.double() * rstd.double()
     t = beta.double() - mean.double() * s
     Xn = torch.relu(X.double() * s + t)
@@ -231,6 +237,21 @@ def test_tn_bn_product_of_integers_is_exact(p, monkeypatch):
     assert untouched(buf, dW)
     assert torch.equal(dW.double(), want), p.id
     assert torch.equal(SCMN._gemm_tn_bn(G, X, mean, rstd, gamma, beta, p.prec), dW), p.id
+
+
+@pytest.mark.parametrize('p', T.BN_POINTS, ids=lambda p: p.id)
+def test_tn_bn_product_of_integers_is_exact(p, monkeypatch):
+    T.set_env(monkeypatch, p.env)
+    bn_product_is_exact(p)
+
+
+def test_tn_bn_product_with_unaligned_transform_vectors_is_exact(monkeypatch):
+    """bf16x3 on aligned operands whose transform vectors are no 16-byte vectors.  tn_route (csrc/gemm_tn_route.inc) gives this
+    the tile and chunks of the producer / consumer route on the four-wave kernel without 16-byte loads.  Asserted here: the exact
+    product, intact guards, and the tile and chunks of the aligned form.  NOT asserted: which kernel ran - the query takes no
+    transform; a kernel trace recorded it once (profiles/r24_tn_routes.md)."""
+    T.set_env(monkeypatch, {})
+    bn_product_is_exact(T.BN_UNALIGNED_TF_POINT, tf_off=1)
 
 
 def test_tn_bn_refuses_the_skinny_shape():
