@@ -984,6 +984,38 @@ int stin_coalesce_pairs_i64(const int64_t* a, const int64_t* b, const int64_t* m
                             int64_t* out_a, int64_t* out_b, int64_t* state, void* workspace, size_t workspace_bytes,
                             stin_stream_t stream);
 
+/* Mesh clustering: voxel clustering that keeps the result a TRIANGLE MESH, so that QEM levels can follow it - the step the
+ * reference shells out to vcglib's trimesh_clustering for (graph_level_generation.py, a --qem level that is no digit string).
+ * preprocessing.cluster_mesh drives the two entry points below.  A contract of this project's own, restated in numpy by
+ * tests/_meshcluster_oracle.py (bit-exact parity); it is NOT pinned against vcglib, and differs from it on purpose: the grid origin
+ * is 0 (as in the reference's own python vertex_clustering; vcglib anchors the grid on an inflated bounding box) and a cell's
+ * position is the unweighted mean of its members (vcglib weights by face corners).  Everything is fp64.
+ *   faces in    range-checked; faces that repeat a vertex are dropped at once (stin_qem_remap_faces_i64 with parent == NULL).
+ *   cells       bin = coords // cell_size per axis (numpy's floor division: the floor_div of stin_voxel_cluster_f64); cluster ids =
+ *               the ranks of the bin triples in lexicographic order (np.unique(bins, axis=0)); ALL N vertices are clustered,
+ *               referenced by a face or not: trace and Nc are those of stin_voxel_cluster_f64 bit for bit.
+ *   positions   per cluster the members' coordinates summed in ascending vertex id from 0.0, divided by the count (as a double)
+ *               with one IEEE division: stin_voxel_cluster_f64's value before its cast to fp32.
+ *   faces out   image = trace[face], corner order kept; images with two equal corners are dropped; among images with the same
+ *               vertex SET only the one of the lowest input face id survives, with that face's orientation (a fold makes most such
+ *               duplicates opposite in orientation); survivors keep their relative input order.
+ * Clusters that no surviving face references stay (they count in Nc and have no edges).  The result may be non-manifold (an edge
+ * with more than two faces).
+ * stin_voxel_cluster_mean_f64: stin_voxel_cluster_f64 with new_coords [N, 3] fp64 (the first Nc rows are written) - same state
+ *     words, same workspace (stin_voxel_cluster_workspace_bytes).
+ * stin_face_cluster_i64: faces [F, 3] int64, trace [N] int64 with values in [0, Nc) -> out_faces [F, 3] int64 (the first state[4]
+ *     rows are written).  One kernel forms image, degenerate flag and the key of the sorted triple (three 21-bit ids), a stable
+ *     radix sort of (key, face id), head flags by face id, a scan and a compaction follow - all inside the workspace
+ *     (>= stin_face_cluster_workspace_bytes(F)); nothing allocates or synchronises, no float atomics, identical from run to run.
+ *     state: 5 x int64 DEVICE words written by the call - state[3] bit 0: a face index outside [0, N) or a trace entry outside
+ *     [0, Nc) (checked before anything is read through it; that face is left out), bit 1: Nc > 2^21, three ids do not fit the key
+ *     and nothing else was done (the caller takes another route); state[4] = number of surviving faces. */
+int stin_voxel_cluster_mean_f64(const double* coords, int64_t N, double voxel, int64_t* trace, double* new_coords, int64_t* state,
+                                void* workspace, size_t workspace_bytes, stin_stream_t stream);
+size_t stin_face_cluster_workspace_bytes(int64_t F);
+int stin_face_cluster_i64(const int64_t* faces, int64_t F, const int64_t* trace, int64_t N, int64_t Nc, int64_t* out_faces,
+                          int64_t* state, void* workspace, size_t workspace_bytes, stin_stream_t stream);
+
 /* circle masks: the reference's circle inpainting masks (preprocessing/observed_texture_map_generation.py:530-603,
  * process_frame_circles) and the training transforms of the 3-D inpainting recipe, on the device.
  * stin_mask_adjacency_i64: both directions of every (src[e], dst[e]) pair -> int32 CSR rowptr [N + 1], col [2E] (order within a

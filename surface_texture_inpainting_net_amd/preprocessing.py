@@ -27,6 +27,12 @@
   stated in include/stin_hip.h and restated in numpy by the test suite (bit-exact parity); it is NOT pinned against vcglib.
   ``vertex_normals`` - open3d's documented ``compute_vertex_normals`` rule (unit face normals summed, normalised), for the levels it makes.
 
+* ``cluster_mesh``      - the mesh clustering the reference shells out to vcglib's ``trimesh_clustering`` for (a ``--qem`` level such
+  as ``0.04``): ``vertex_clustering``'s cells and trace with fp64 means (``stin_voxel_cluster_mean_f64``) and the faces carried along -
+  degenerate images dropped, one face per vertex set (``stin_face_cluster_i64``: a stable radix sort of the sorted cluster triples) - so
+  that QEM levels can follow (``['0.04', '30', '30', '30']`` from a mesh alone).  A contract of this project's own, NOT pinned against
+  vcglib (grid origin 0, unweighted means).
+
 * ``observe_vertices``  - ``preprocessing/observed_texture_map_generation.compute_observed_vertex_map`` (:159-251, ``generate_masks.sh
   observers``), which renders the mesh from every camera pose with PyTorch3D and keeps the face seen at each pixel: a depth-tested
   triangle rasteriser in HIP (``stin_observe_poses_f64``) that answers "which poses see vertex v" as one bit per (vertex, pose).
@@ -48,6 +54,7 @@ All take and return tensors in the reference's own formats.  Out of scope: readi
 here to pin a reader against: vertices, faces and colours are inputs), and the Matterport and S3DIS label paths.
 """
 import ctypes
+import re
 
 import torch
 
@@ -954,10 +961,112 @@ def decimate_qem(vertices, faces, percent=None, n_vertices=None, strict=False, p
     return v[alive], rank[f], trace, n_cur
 
 
+def _cluster_faces_torch(f, trace):
+    """cluster_mesh's faces without stin_face_cluster_i64 (more than 2^21 clusters: three ids do not fit its key) - the same rule
+    with torch's sorts, the same result."""
+    img = trace[f]
+    ids = torch.nonzero((img[:, 0] != img[:, 1]) & (img[:, 1] != img[:, 2]) & (img[:, 0] != img[:, 2])).reshape(-1)
+    if ids.numel() == 0:
+        return img[:0]
+    _, inverse = torch.unique(torch.sort(img[ids], dim=1).values, dim=0, return_inverse=True)
+    order = torch.sort(inverse, stable=True).indices                       # runs of one vertex set, ascending face id inside
+    run = inverse[order]
+    head = torch.ones_like(run, dtype=torch.bool)
+    head[1:] = run[1:] != run[:-1]
+    return img[torch.sort(ids[order[head]]).values]
+
+
+def cluster_mesh(vertices, faces, cell_size, profile=None, _torch_faces=False):
+    """Voxel clustering of a triangle mesh that keeps it a triangle mesh (csrc/stin_cluster.hip) - the step the reference shells out
+    to vcglib's trimesh_clustering for (a --qem level that is no digit string, `--level_params 0.04 30 30 30`) - so that QEM levels
+    can follow it.  vertices [N, >= 3] float, faces [F, 3] int (CUDA); cell_size finite and > 0.
+    -> (vertices' float64 [N', 3], faces' int64 [F', 3], trace int64 [N] onto [0, N'), N').
+
+    The contract (include/stin_hip.h, "Mesh clustering"; restated in numpy by the test suite, which this reproduces bit for bit) is
+    this project's own.  It is NOT pinned against vcglib, which is not available, and differs from it on purpose in two places: the
+    grid origin is 0, as in the reference's own python vertex_clustering (vcglib anchors the grid on an inflated bounding box), and
+    a cell's position is the unweighted mean of its members (vcglib averages with face-corner weights).  fp64 throughout:
+    * faces of the input are range-checked; those that repeat a vertex are dropped at once (as decimate_qem does).
+    * cells: the bin of a vertex is numpy's `coords // cell_size` per axis; cluster ids are the ranks of the bin triples in
+      lexicographic order (np.unique(bins, axis=0)).  ALL N vertices are clustered, referenced by a face or not, so trace and N' are
+      bitwise those of vertex_clustering(vertices, edges, cell_size).
+    * positions: per cluster the members' coordinates summed in ascending vertex id from 0.0 and divided by the count with one IEEE
+      division; vertices'.float() is bitwise vertex_clustering's new_coords.
+    * faces: the image of a face is trace[face], corner order kept; images with two equal corners are dropped; among images with
+      the same vertex SET only the one of the lowest input face id survives, with that face's orientation; survivors keep their
+      relative input order.
+    Clusters that no surviving face references stay: they count in N' and have no edges.  The result may be non-manifold (an edge
+    with more than two faces); decimate_qem's link condition leaves such edges alone.
+    TypeError for CPU input, IndexError for a face index outside [0, N) (a device status word, read before anything indexes with
+    it), ValueError for a non-finite coordinate, a cell_size that is not finite and > 0, or more than 2^21 cells along an axis.
+    With more than 2^21 clusters the faces go through torch's sorts instead of stin_face_cluster_i64 (the same result).
+    profile: a dict that receives the wall seconds per stage ('faces_in', 'cells', 'faces')."""
+    import math
+    v = _xyz64(vertices, 'vertices')
+    if not (torch.is_tensor(faces) and faces.is_cuda):
+        raise TypeError('faces must be a CUDA tensor (no CPU fallback exists)')
+    cell = float(cell_size)
+    if not (math.isfinite(cell) and cell > 0.0):
+        raise ValueError('cluster_mesh: cell_size must be finite and > 0')
+    lib = _lib.load()
+    n, dev, stream = int(v.shape[0]), v.device, _stream(v)
+    if n >= 2 ** 31:
+        raise ValueError('too many vertices')
+    stage = _Stages(profile)
+    stage('faces_in')
+    f = _checked_faces(faces, n, 'cluster_mesh')
+    stage('cells')
+    trace = torch.empty(n, dtype=torch.int64, device=dev)
+    means = torch.empty(max(n, 1), 3, dtype=torch.float64, device=dev)
+    state = torch.empty(5, dtype=torch.int64, device=dev)
+    ws_bytes = lib.stin_voxel_cluster_workspace_bytes(n)
+    ws = torch.empty(ws_bytes, dtype=torch.uint8, device=dev)
+    _lib.check(lib.stin_voxel_cluster_mean_f64(_ptr(v), n, cell, _ptr(trace), _ptr(means), _ptr(state), _ptr(ws), ws_bytes, stream),
+               'stin_voxel_cluster_mean_f64')
+    st = state.cpu()
+    if int(st[3]) != 0:
+        raise ValueError('cluster_mesh: non-finite coordinates or more than 2^21 cells along an axis')
+    nc = int(st[4])
+    stage('faces')
+    nf = int(f.shape[0])
+    if nf == 0:
+        out = f
+    elif _torch_faces:
+        out = _cluster_faces_torch(f, trace)
+    else:
+        out = torch.empty(nf, 3, dtype=torch.int64, device=dev)
+        ws_bytes = lib.stin_face_cluster_workspace_bytes(nf)
+        ws = torch.empty(ws_bytes, dtype=torch.uint8, device=dev)
+        _lib.check(lib.stin_face_cluster_i64(_ptr(f), nf, _ptr(trace), n, nc, _ptr(out), _ptr(state), _ptr(ws), ws_bytes, stream),
+                   'stin_face_cluster_i64')
+        st = state.cpu()
+        if int(st[3]) & 1:
+            raise RuntimeError('cluster_mesh: a checked face or the trace is out of range')
+        out = _cluster_faces_torch(f, trace) if int(st[3]) & 2 else out[:int(st[4])]
+    stage(None)
+    return means[:nc], out, trace, nc
+
+
 def _qem_percent(x):
     """The percentage of a decimator-mode level given as a digit string '1' .. '99', else None."""
     if isinstance(x, str) and x.isdigit() and 1 <= int(x) <= 99:
         return int(x)
+    return None
+
+
+_DECIMAL = re.compile(r'(\d+\.?\d*|\.\d+)([eE][+-]?\d+)?')
+
+
+def _cell_size(x):
+    """The cell size of a decimator-mode clustering level - a python float, or a decimal string that is not all digits ('0.04': the
+    reference's `not isdigit()` branch) - finite and > 0, else None."""
+    import math
+    if isinstance(x, str):
+        if x.isdigit() or not _DECIMAL.fullmatch(x):
+            return None
+        x = float(x)
+    if isinstance(x, float) and math.isfinite(x) and x > 0.0:
+        return x
     return None
 
 
@@ -973,7 +1082,10 @@ def graph_levels(mesh, levels, dilated_levels, dilation_dists, labels=None, refe
         first one the mesh itself) with `vertex_clustering`; runs fully on the GPU.
       * decimator mode (--qem): each entry is '100' (the plain current mesh with an identity trace: extract_plain_mesh), a digit
         string '1' .. '99' (decimate_qem of the current mesh to that percentage of its vertices, on the GPU: the trace is the
-        decimator's own, the level's normals are vertex_normals of the result - `['100', '30', '30', '30']` from a mesh alone), a dict
+        decimator's own, the level's normals are vertex_normals of the result - `['100', '30', '30', '30']` from a mesh alone), a
+        cell size - a decimal string that is not all digits ('0.04', the reference's `not isdigit()` branch) or a python float, finite
+        and > 0 - (cluster_mesh of the current mesh: the trace is the clustering's own membership trace onto the previous level, the
+        normals are vertex_normals of the result, the edges those of its faces - `['0.04', '30', '30', '30']` from a mesh alone), a dict
         (vertices [n, 3] float64, faces, csv = path or read_trace_csv tuple, normals) with a decimator's result for the current
         mesh (extract_qem_mesh: trace_from_csv against the previous level), or a dict without 'csv' - an externally clustered
         mesh (the trimesh_clustering branch) whose trace is nearest(ORIGINAL mesh vertices, its vertices), as the reference has
@@ -987,9 +1099,11 @@ def graph_levels(mesh, levels, dilated_levels, dilation_dists, labels=None, refe
     Differences from the reference: each level's edges come sorted by (row 0, row 1) instead of in CPython
     set order; and in vertex-clustering mode the normals of a dilated level are those of each coarse vertex's nearest original
     vertex - the reference walks with rows 0 .. N_l - 1 of the INPUT mesh's normals there because it never updates its current
-    mesh (reference_vc_normals=True reproduces that for file parity).
+    mesh (reference_vc_normals=True reproduces that for file parity); and a cell-size level's trace is the membership trace of the
+    clustering of the previous level, where the reference takes nearest(ORIGINAL mesh vertices, clustered vertices) whatever the
+    previous level was (the dict-without-'csv' branch keeps the reference's rule).
     Out of scope: reading mesh files and the Matterport / S3DIS label paths.  A dict level still takes the output of an external
-    decimator (vcglib's tridecimator in the reference) as it is."""
+    decimator (vcglib's tridecimator or trimesh_clustering in the reference) as it is."""
     if len(levels) != len(dilated_levels):
         raise ValueError('levels and dilated_levels need one entry per level')
     if len(levels) == 0:
@@ -1008,9 +1122,10 @@ def graph_levels(mesh, levels, dilated_levels, dilation_dists, labels=None, refe
         cols.append(torch.as_tensor(labels).to(dev).double().reshape(n, 1))
     original = torch.cat(cols, dim=1)
     vc_mode = all(isinstance(x, (int, float)) and not isinstance(x, bool) for x in levels)
-    if not vc_mode and any(not (isinstance(x, dict) or str(x) == '100' or _qem_percent(x) is not None) for x in levels):
-        raise ValueError("levels: all voxel sizes (vertex-clustering mode), or each '100', a percentage '1' .. '99' or a dict "
-                         "(decimator mode)")
+    if not vc_mode and any(not (isinstance(x, dict) or str(x) == '100' or _qem_percent(x) is not None or _cell_size(x) is not None)
+                           for x in levels):
+        raise ValueError("levels: all voxel sizes (vertex-clustering mode), or each '100', a percentage '1' .. '99', a cell size "
+                         "('0.04' or a float, finite and > 0) or a dict (decimator mode)")
     coords = [v64]
     edges, traces, level_normals = [], [], []
     cur = dict(vertices=v64, faces=faces0, normals=normals0)                          # the reference's curr_mesh
@@ -1039,6 +1154,11 @@ def graph_levels(mesh, levels, dilated_levels, dilation_dists, labels=None, refe
             nrm = cur['normals']
         elif _qem_percent(spec) is not None:                                      # the decimator itself: the trace comes with it
             c_l, f_l, tr, _ = decimate_qem(cur['vertices'], cur['faces'], percent=_qem_percent(spec))
+            e_l = _mesh_edges(f_l, c_l.shape[0])
+            cur = dict(vertices=c_l, faces=f_l, normals=vertex_normals(c_l, f_l))
+            nrm = cur['normals']
+        elif _cell_size(spec) is not None:                                        # mesh clustering: its own membership trace
+            c_l, f_l, tr, _ = cluster_mesh(cur['vertices'], cur['faces'], _cell_size(spec))
             e_l = _mesh_edges(f_l, c_l.shape[0])
             cur = dict(vertices=c_l, faces=f_l, normals=vertex_normals(c_l, f_l))
             nrm = cur['normals']
