@@ -1321,6 +1321,67 @@ int stin_frames_accumulate_f64(const double* vertices, int64_t N, const double* 
 int stin_frames_finish_f32(const int64_t* sum, const int32_t* count, int64_t N, float fill_r, float fill_g, float fill_b,
                            float* colors, uint8_t* observed, stin_stream_t stream);
 
+/* Render: colour, depth and face-id images of a vertex-coloured mesh from the camera poses of a scan (stin_render.hip) - the
+ * direction the two sections above lack, mesh -> images.  It stands in for what the reference shows in an Open3D window
+ * (utils/ColorCompletionVisualizer.py: unlit vertex colours, a screenshot key) on machines without a display; it is a contract of the
+ * project's own, NOT pinned against Open3D's renderer.  tests/_render_oracle.py restates it in numpy (per pose and per pixel over all
+ * faces) and agrees bit for bit.  Everything is fp64 and IEEE, the operations in the order written, nothing contracted; integers where
+ * stated.
+ *
+ *   poses     RT [P][12], valid [P]: preprocessing.pose_extrinsics' output (see "Observer masks").  An invalid pose renders the
+ *             background only.
+ *   view      xv = ((R00 x + R01 y) + R02 z) + t0, likewise yv, zv (the observers' expression).
+ *   screen    X = fx xv / zv + cx, Y = fy yv / zv + cy: the projection and the camera (fx, fy, cx, cy) of "Frame colours", a real
+ *             pinhole; pixel (row i, column j) is centred at (X, Y) = (j, i); the image is H x W, H != W allowed.
+ *   cull, coverage, depth key   those of "Observer masks", word for word, with (W - 1, H - 1) where it has S - 1: a face is skipped
+ *             for a pose when a corner has zv < z_near (DROPPED, not clipped), an index is outside [0, N), a screen coordinate is not
+ *             finite, or area2 = edge(a, b, c) is 0; wa = edge(b, c, pix), wb = edge(c, a, pix), wc = edge(a, b, pix), covered when all
+ *             three are >= 0 (area2 > 0) or all <= 0 (area2 < 0); la = wa / area2, lb, lc likewise;
+ *             zp = 1.0 / ((la / za + lb / zb) + lc / zc); key = bits(float32(zp)) << 32 | face id; the pixel keeps the MINIMUM key
+ *             (64-bit integer atomicMin).
+ *   resolve   per (pixel, pose), with the winning face: la, lb, lc, zp recomputed from the stored screen coordinates;
+ *     colour  qa = (la / za) zp, qb = (lb / zb) zp, qc = (lc / zc) zp (perspective-correct weights);
+ *             val_k = (qa Ca_k + qb Cb_k) + qc Cc_k, C = vertex colours float32 [N][K], 1 <= K <= 4, promoted to fp64;
+ *             color_f32 = float32(val_k); color_u8 = (uint8) rint(t 255.0), t = (double) color_f32, t = 0 when !(t > 0) (so NaN
+ *             gives 0), t = 1 when t > 1.
+ *     depth   uint16: mm = rint(zp depth_scale), stored when it is finite and 0 < mm < 65535, else 0 - the raw format "Frame
+ *             colours" reads.
+ *     face    int32: the winning face id, or -1.
+ *             A pixel nobody covers gets background[K] (floats, quantised by the same rule for color_u8), depth 0 and face -1.
+ * stin_render_poses_f64: poses in batches of `batch` (1 .. STIN_RENDER_MAX_BATCH) whose keys (batch H W 8 bytes, plus one resolve
+ *     tile) and screen coordinates (batch N 24 bytes) live in the workspace.  Per batch: clear, transform every vertex once, rasterise
+ *     with one thread per (face, pose) - the clamped box is formed first, a face outside the frustum costs six loads - and resolve.  A
+ *     face whose clamped box holds more than large_box centres (<= 0: STIN_RENDER_LARGE_BOX, measured in profiles/r26_render.md)
+ *     goes through a queue to a second rasteriser that spreads it over a wavefront; at a scan's frame sizes that is the main route.
+ *     The images depend neither on batch, nor on large_box, nor on how the work is split.  camera: HOST array of
+ *     STIN_RENDER_CAMERA_DOUBLES doubles (fx, fy, cx, cy); background: HOST array of K floats (both read during the call).
+ *     Outputs color_f32 [P][H][W][K], color_u8 [P][H][W][K], depth [P][H][W], face_ids [P][H][W]; every one may be NULL.  The
+ *     resolve pass stages 512 consecutive pixels of the flattened arrays per workgroup in LDS and streams them out 16 bytes per
+ *     lane where the array's base is 16-byte aligned (by element otherwise): 3- and 12-byte pixels need no alignment of their own.
+ *     stages: 0 = all; else a mask of STIN_RENDER_STAGE_* - only those kernels are launched, on what earlier calls left in the
+ *     workspace (for per-stage timing, profiles/render.py; the images are defined for 0 only).
+ *     H, W <= STIN_RENDER_MAX_SIZE, N, F, P < 2^31 - 1, z_near > 0, depth_scale > 0 (STIN_E_SIZE otherwise).  *status (device
+ *     int32, written): STIN_RENDER_BAD_INDEX - a face had an index outside [0, N) (it is skipped, the others are unaffected);
+ *     STIN_RENDER_LARGE_FACE - informational: a face went through the large-face rasteriser.  Null pointers are allowed where a
+ *     count is 0.  Nothing allocates or synchronises. */
+#define STIN_RENDER_BAD_INDEX 1
+#define STIN_RENDER_LARGE_FACE 2
+#define STIN_RENDER_LARGE_BOX 32
+#define STIN_RENDER_MAX_SIZE 4096
+#define STIN_RENDER_MAX_BATCH 1024
+#define STIN_RENDER_CAMERA_DOUBLES 4
+#define STIN_RENDER_STAGE_CLEAR 1
+#define STIN_RENDER_STAGE_TRANSFORM 2
+#define STIN_RENDER_STAGE_RASTER 4
+#define STIN_RENDER_STAGE_LARGE 8
+#define STIN_RENDER_STAGE_RESOLVE 16
+size_t stin_render_workspace_bytes(int64_t N, int64_t F, int H, int W, int batch);
+int stin_render_poses_f64(const double* vertices, int64_t N, const int64_t* faces, int64_t F, const float* colors, int K,
+                          const double* RT, const uint8_t* valid, int64_t P, const double* camera, int H, int W, double z_near,
+                          double depth_scale, const float* background, int batch, int64_t large_box, int stages, float* color_f32,
+                          uint8_t* color_u8, uint16_t* depth, int32_t* face_ids, int32_t* status, void* workspace,
+                          size_t workspace_bytes, stin_stream_t stream);
+
 /* ------------------------------------------------- 2-D image-graph inpainting experiment --
  * What the reference's ImageGraphTextureDataSet builds per item on CPU workers (datasets/imagegraph_dataloader.py:46-160) and what
  * the graph branch of its 2-D trainer reads back per step (trainers/inpainting2d_trainer.py:382-398, without lpips), stin_image.hip.
