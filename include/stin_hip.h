@@ -1150,6 +1150,51 @@ int stin_trace_check_i64(const int64_t* trace, int64_t n_old, const int64_t* row
 int stin_cluster_mean_f32(const float* coords, int64_t n, const int64_t* order, const int64_t* seg_ptr, int64_t n_seg, float* out,
                           stin_stream_t stream);
 
+/* k nearest neighbours: stin_nearest_f64 with k answers per query and a point set that can be restricted in place
+ * (stin_knn.hip) - the primitive under the fill of unseen vertices that Open3D's colour-map pipeline ends with (the reference's
+ * preprocessing/texture_map_optimization.py; see "Frame colours") and under a nearest-known-vertex inpainting baseline.  A
+ * contract of the project's own, NOT pinned against Open3D; tests/_knn_oracle.py restates it in numpy and agrees bit for bit.
+ * Everything is fp64 and IEEE, the operations in the order written, nothing contracted.
+ *   distance    d(q, p) = (dx dx + dy dy) + dz dz: the expression of stin_nearest_f64.
+ *   candidates  the points p with p_valid == NULL || p_valid[p] != 0 (p_valid: uint8 [P]).  An invalid point is skipped IN PLACE:
+ *               its index is never reported, its coordinates are never looked at (they may be non-finite), and every index is an
+ *               index into the full points array - nothing is compacted, so "the lowest index wins a tie" keeps its meaning
+ *               for a subset such as "seen vertices only".
+ *   answer      for query i the k smallest candidates under the total order (d, index), ascending: out_index[row][0 .. k) int64 and,
+ *               out_d2 != NULL, out_d2[row][0 .. k) fp64 (both [n_query_rows][k], dense).  Fewer than k candidates: the remaining
+ *               slots hold index -1 and d2 = +inf.  numpy: np.argsort(d[valid], kind='stable')[:k] mapped back through
+ *               np.flatnonzero(valid).  A candidate whose d is not < +inf (squares that overflow) is never reported, as in
+ *               stin_nearest_f64.  1 <= k <= STIN_KNN_MAX_K.
+ *   queries     q_index / q_count exactly as in stin_nearest_f64: query i is row q_index[i] (NULL: row i, Q <= n_query_rows) and its
+ *               answers go to output row q_index[i]; q_count (may be NULL) is a DEVICE word, only the first min(Q, *q_count) queries
+ *               are run; rows not listed are not written.
+ *   flags       the int64 DEVICE word and bits of stin_nearest_f64, OR-ed: 1 = non-finite query, 2 = non-finite VALID point,
+ *               4 = q_index entry outside [0, n_query_rows) (that query is skipped).
+ *   chunks      1 .. 64, stin_knn_chunks(Q, P, k) picks it; each chunk writes its k-list per query into the workspace
+ *               (stin_knn_workspace_bytes(Q, chunks, k); 0 for chunks <= 1), a second launch merges the lists in ascending chunk
+ *               order under (d, index).  The result does not depend on chunks.
+ *   sizes       Q == 0: nothing is done.  P == 0 is allowed (every listed row becomes -1 / +inf).  Negative sizes, k or chunks out
+ *               of range, Q > n_query_rows without q_index: STIN_E_SIZE; P >= 2^31 - 1: STIN_E_UNSUPPORTED; all before any launch.
+ * stin_knn_mean_f32: the mean of the neighbours' rows.  values float32 [P][C] (row pitch ld_values), idx int64 [n_rows][k] (what
+ *     stin_knn_f64 wrote), out float32 [n_rows][C] (row pitch ld_out), filled uint8 [n_rows] (may be NULL), q_index / q_count / Q as
+ *     above.  For a listed row with m >= 1 neighbours - the leading entries of its idx row that lie in [0, P) -
+ *       out[row][c] = (float)((((double)v1 + (double)v2) + ...) / (double)m),   the sum left to right in neighbour order,
+ *     and filled[row] = 1; a row with m == 0 is left untouched and gets filled[row] = 0; a row id outside [0, n_rows) is skipped.
+ *     1 <= C <= STIN_KNN_MAX_C.  values and out MAY BE THE SAME ARRAY provided no listed row is a neighbour of any listed row
+ *     (in the fill the listed rows are the unseen vertices and the candidates the seen ones: disjoint); otherwise they must not
+ *     overlap.
+ * Caller-owned buffers and workspace, the caller's stream; nothing allocates or synchronises. */
+#define STIN_KNN_MAX_K 16
+#define STIN_KNN_MAX_C 16
+int stin_knn_chunks(int64_t Q, int64_t P, int k);
+size_t stin_knn_workspace_bytes(int64_t Q, int chunks, int k);
+int stin_knn_f64(const double* queries, int64_t n_query_rows, const double* points, const uint8_t* p_valid, int64_t P,
+                 const int64_t* q_index, const int64_t* q_count, int64_t Q, int k, int chunks, int64_t* out_index, double* out_d2,
+                 int64_t* flags, void* workspace, size_t workspace_bytes, stin_stream_t stream);
+int stin_knn_mean_f32(const float* values, int64_t ld_values, int64_t P, int C, const int64_t* idx, int k, const int64_t* q_index,
+                      const int64_t* q_count, int64_t Q, int64_t n_rows, float* out, int64_t ld_out, uint8_t* filled,
+                      stin_stream_t stream);
+
 /* QEM: a deterministic, parallel quadric-error-metric edge-collapse decimator and vertex normals (stin_qem.hip) - the step the
  * reference shells out to vcglib's tridecimator for (graph_level_generation.py, --qem), with the fine -> coarse trace as a result
  * instead of a CSV.  preprocessing.decimate_qem drives it: a loop of rounds, per round the sorts on the host side (torch) and the
@@ -1286,7 +1331,11 @@ int stin_observe_mask_u32(const uint32_t* bits, int64_t N, int64_t words, const 
  *             result depends neither on the order of the poses, nor on the batching, nor on how the work is split over threads.
  *             q < 2^24: int64 cannot overflow below 2^31 poses.  Integer atomics only; no float atomics.
  *   finish    colour[v][c] = float32(sum[v][c] / (count[v] 16711680.0)) in [0, 1] (16711680 = 65536 * 255); observed[v] = count[v] > 0;
- *             a vertex with count 0 gets (fill_r, fill_g, fill_b).  Open3D's k-nearest-neighbour fill of unseen vertices is left out.
+ *             a vertex with count 0 gets (fill_r, fill_g, fill_b).  The k-nearest-neighbour fill of unseen vertices that Open3D's
+ *             pipeline ends with is a separate step on top of this one (preprocessing.fill_unseen_colors: stin_knn_f64 with
+ *             p_valid = count > 0, then stin_knn_mean_f32; see "k nearest neighbours") - the mean colour of the k nearest
+ *             coloured vertices, k = 3 being Open3D's default (invisible_vertex_color_knn) as far as we know; neither the default
+ *             nor Open3D's tie handling could be checked against a run of it.
  * stin_frames_depth_edges_u16: depth [B][Hd][Wd] -> edge bytes [B][Hd][Wd] (0 / 1), two passes: the gradient test into the
  *     workspace (stin_frames_edges_workspace_bytes), then the dilation (separable, through LDS).  half_kernel <=
  *     STIN_FRAMES_MAX_HALF_KERNEL, depth_scale > 0, sizes in [1, STIN_FRAMES_MAX_SIZE], B <= STIN_FRAMES_MAX_BATCH (STIN_E_SIZE).

@@ -48,7 +48,12 @@
   and depth frames and the camera trajectory to Open3D's colour-map pipeline with ``maximum_iteration=0``: per vertex and frame a
   visibility test (against the sensor's depth away from depth discontinuities, or ``observe_vertices``' bits), a projection and a
   bilinear colour sample, averaged in integers (``stin_frames_*``).  ``frame_intrinsics`` is its rescaled camera (:104-107).  A
-  contract of this project's own, NOT pinned against an Open3D run; no optimisation of the poses, no fill of unseen vertices.
+  contract of this project's own, NOT pinned against an Open3D run; no optimisation of the poses.
+
+* ``knn`` / ``fill_unseen_colors`` / ``knn_inpaint`` - exact fp64 k nearest neighbours with a validity mask on the points
+  (``stin_knn_f64``: ``nearest``'s tiled brute force with a k-list per query in registers) and the mean of the neighbours' rows
+  (``stin_knn_mean_f32``): the fill of unseen vertices that Open3D's pipeline ends with (``FrameColors.result(knn=3)``), and the
+  nearest-known-vertex baseline to put beside the network's l1 / psnr.
 
 All take and return tensors in the reference's own formats.  Out of scope: reading mesh files (neither open3d nor plyfile exists
 here to pin a reader against: vertices, faces and colours are inputs), and the Matterport and S3DIS label paths.
@@ -624,6 +629,130 @@ def nearest(queries, points, return_sq_dist=False, chunks=None):
         if word:
             raise ValueError('nearest: ' + _flag_text(word))
     return (out, d2) if return_sq_dist else out
+
+
+def _check_k(k, what):
+    kmax = _lib.CONSTANTS['STIN_KNN_MAX_K']
+    if isinstance(k, bool) or int(k) != k or not 1 <= int(k) <= kmax:
+        raise ValueError('%s: k must be an integer in [1, %d]' % (what, kmax))
+    return int(k)
+
+
+def _knn_launch(q64, p64, k, idx, d2, flags, p_valid=None, q_index=None, chunks=None):
+    """stin_knn_f64 on fp64 [., 3] tensors into idx int64 [rows, k] / d2 float64 [rows, k] (or None); nothing synchronises."""
+    lib = _lib.load()
+    nq = int(q64.shape[0]) if q_index is None else int(q_index.numel())
+    P = int(p64.shape[0])
+    if nq == 0:
+        return
+    c = int(chunks) if chunks is not None else int(lib.stin_knn_chunks(nq, P, k))
+    ws_bytes = lib.stin_knn_workspace_bytes(nq, c, k)
+    ws = torch.empty(max(ws_bytes, 1), dtype=torch.uint8, device=q64.device)
+    _lib.check(lib.stin_knn_f64(_ptr(q64), int(q64.shape[0]), _ptr(p64) if P else None, _ptr(p_valid), P, _ptr(q_index), None, nq, k, c,
+                                _ptr(idx), _ptr(d2), _ptr(flags), _ptr(ws), ws_bytes, _stream(q64)), 'stin_knn_f64')
+
+
+def _knn_mean_launch(values, idx, out, filled=None, q_index=None):
+    """stin_knn_mean_f32: values float32 [P, C] (rows may be strided), idx int64 [rows, k], out float32 [rows, C]."""
+    lib = _lib.load()
+    nq = int(idx.shape[0]) if q_index is None else int(q_index.numel())
+    _lib.check(lib.stin_knn_mean_f32(_ptr(values), int(values.stride(0)), int(values.shape[0]), int(values.shape[1]), _ptr(idx),
+                                     int(idx.shape[1]), _ptr(q_index), None, nq, int(idx.shape[0]), _ptr(out), int(out.stride(0)),
+                                     _ptr(filled), _stream(values)), 'stin_knn_mean_f32')
+
+
+def _point_valid(point_valid, n, device, what):
+    if point_valid is None:
+        return None
+    if not torch.is_tensor(point_valid) or not point_valid.is_cuda:
+        raise TypeError('%s must be a CUDA tensor (no CPU fallback exists)' % what)
+    if point_valid.dim() != 1 or int(point_valid.numel()) != n:
+        raise ValueError('%s needs one entry per point' % what)
+    return (point_valid != 0).to(device=device, dtype=torch.uint8).contiguous()
+
+
+def knn(queries, points, k, point_valid=None, query_index=None, return_sq_dist=False, chunks=None):
+    """Exact k nearest neighbours: for every row of queries [Q, >= 3] the indices (int64 [Q, k], CUDA) of its k nearest rows of
+    points [P, >= 3] by d = (dx dx + dy dy) + dz dz in fp64 (float32 input is promoted), ascending under (d, index): the lowest
+    index first among equal distances - np.argsort(d, kind='stable')[:k].  point_valid ([P], bool or integer, non-zero = a candidate):
+    the other points are skipped IN PLACE - their indices are never reported, their coordinates never read, and the indices stay
+    those of the full array.  Fewer than k candidates (P == 0 and no valid point included): the remaining slots hold -1 (and inf).
+    query_index (int64 [M]): only these rows are searched, the rows not listed hold -1 / inf.  return_sq_dist: also the squared
+    distances (float64 [Q, k]).  chunks: parts the points are cut into (default: from Q, k and the device's CU count; the result
+    does not depend on it).  Tiled brute force with the k-list in registers (stin_knn_f64; include/stin_hip.h, "k nearest
+    neighbours").  ValueError for k outside [1, STIN_KNN_MAX_K], non-finite queries or valid points, or a row id out of range."""
+    k = _check_k(k, 'knn')
+    q64, p64 = _xyz64(queries, 'queries'), _xyz64(points, 'points')
+    nq, dev = int(q64.shape[0]), q64.device
+    valid = _point_valid(point_valid, int(p64.shape[0]), dev, 'point_valid')
+    qi = None
+    if query_index is not None:
+        if not torch.is_tensor(query_index) or not query_index.is_cuda:
+            raise TypeError('query_index must be a CUDA tensor (no CPU fallback exists)')
+        qi = query_index.to(device=dev, dtype=torch.int64).reshape(-1).contiguous()
+    idx = torch.full((nq, k), -1, dtype=torch.int64, device=dev)        # (what a row that is not listed keeps)
+    d2 = torch.full((nq, k), float('inf'), dtype=torch.float64, device=dev) if return_sq_dist else None
+    if nq == 0 and qi is not None and qi.numel():
+        raise ValueError('knn: ' + _flag_text(4))
+    if nq:
+        flags = torch.zeros(1, dtype=torch.int64, device=dev)
+        _knn_launch(q64, p64, k, idx, d2, flags, p_valid=valid, q_index=qi, chunks=chunks)
+        word = int(flags.item())
+        if word:
+            raise ValueError('knn: ' + _flag_text(word))
+    return (idx, d2) if return_sq_dist else idx
+
+
+def fill_unseen_colors(vertices, colors, count, k=3, min_count=1, return_filled=False):
+    """The fill of unseen vertices that Open3D's colour-map pipeline ends with, as a step of its own: a vertex with count <
+    min_count gets the mean colour of its k nearest SEEN vertices (count >= min_count) - knn with point_valid = seen, then per
+    channel (float)((((double)c1 + (double)c2) + ...) / m) over the m <= k neighbours found, nearest first (stin_knn_mean_f32).
+    vertices [N, >= 3] float CUDA; colors float32 [N, C], C <= 16 (any value range); count [N] integer (FrameColors' count).
+    -> a new colours tensor whose seen rows are bit-identical to the input; return_filled: also bool [N], true for the rows that
+    were written.  No seen vertex: the input comes back unchanged (nothing is filled).  k = 3 is Open3D's default
+    (invisible_vertex_color_knn) to our knowledge; this is the project's own contract, not pinned against an Open3D run."""
+    k = _check_k(k, 'fill_unseen_colors')
+    v64 = _xyz64(vertices, 'vertices')
+    n, dev = int(v64.shape[0]), v64.device
+    if not torch.is_tensor(colors) or not colors.is_cuda or not torch.is_tensor(count) or not count.is_cuda:
+        raise TypeError('colors and count must be CUDA tensors (no CPU fallback exists)')
+    if colors.dtype != torch.float32:
+        raise TypeError('colors must be float32')
+    cmax = _lib.CONSTANTS['STIN_KNN_MAX_C']
+    if colors.dim() != 2 or int(colors.shape[0]) != n or not 1 <= int(colors.shape[1]) <= cmax:
+        raise ValueError('colors must be [N, C] with 1 <= C <= %d' % cmax)
+    if count.dim() != 1 or int(count.numel()) != n or count.dtype.is_floating_point:
+        raise ValueError('count must be an integer tensor with one entry per vertex')
+    out = colors.to(dev).clone(memory_format=torch.contiguous_format)
+    seen = count.to(dev) >= int(min_count)
+    filled = torch.zeros(n, dtype=torch.uint8, device=dev)
+    todo = torch.nonzero(~seen).reshape(-1)
+    if int(todo.numel()) and int(todo.numel()) < n:
+        idx = torch.empty(n, k, dtype=torch.int64, device=dev)
+        flags = torch.zeros(1, dtype=torch.int64, device=dev)
+        _knn_launch(v64, v64, k, idx, None, flags, p_valid=seen.to(torch.uint8), q_index=todo)
+        # in place: the listed rows (unseen) and the rows that are read (seen) are disjoint
+        _knn_mean_launch(out, idx, out, filled=filled, q_index=todo)
+        word = int(flags.item())
+        if word:
+            raise ValueError('fill_unseen_colors: ' + _flag_text(word))
+    return (out, filled.bool()) if return_filled else out
+
+
+def knn_inpaint(sample, k=3):
+    """The non-learned inpainting baseline: every masked vertex (mask > 0) of a training sample gets the mean colour of its k
+    nearest known vertices (mask == 0).  sample: the tuple (positions [N, >= 3], color [N, C], mask [N] or [N, 1]) of level 0, or a
+    training sample with `color`, `mask` and its positions in `pos` or, failing that, in x[:, 6:9] (the reference's feature
+    layout: rgb, normal, position, known; a uniform scale of the positions does not change who is nearest beyond rounding).
+    -> the composite float32 [N, C]: `color` itself outside the mask, bit for bit - what StepMetrics.update accepts as `out`
+    (composite=True and False alike), so the baseline's l1 / psnr stand beside the network's.  A few lines on fill_unseen_colors."""
+    if isinstance(sample, (tuple, list)):
+        pos, color, mask = sample
+    else:
+        pos = getattr(sample, 'pos', None)
+        pos, color, mask = (sample.x[:, 6:9] if pos is None else pos), sample.color, sample.mask
+    known = (mask.reshape(-1) == 0).to(torch.int32)
+    return fill_unseen_colors(pos, color.float(), known, k=k)
 
 
 def read_trace_csv(path):
@@ -1410,8 +1539,10 @@ class FrameColors:
     rounded to 1 / 65536 of a grey level and summed as integers - the result does not depend on the order or the batching.
 
     Not Open3D's result bit for bit and not pinned against a run of it.  Out of scope: reading image files and any resize (frames
-    arrive decoded, as everywhere here), Open3D's rigid / non-rigid optimisation (iterations > 0), its k-nearest-neighbour fill of
-    unseen vertices (they get `fill` and count 0), clipping at the near plane, and a CPU fallback."""
+    arrive decoded, as everywhere here), Open3D's rigid / non-rigid optimisation (iterations > 0), clipping at the near plane, and
+    a CPU fallback.  Unseen vertices get `fill` and count 0, or, with result(knn=k), the mean colour of their k nearest coloured
+    vertices (fill_unseen_colors: exact fp64 k-NN with a stated tie rule; k = 3 is Open3D's default to our knowledge, which - like
+    its tie handling - could not be checked against a run of it)."""
 
     def __init__(self, vertices, color_camera, depth_camera=None, *, depth_scale=1000.0, depth_trunc=3.0, max_depth=2.5,
                  depth_threshold=0.03, discontinuity_threshold=0.1, half_kernel=3, margin=10, z_near=0.01, num_poses=None):
@@ -1501,26 +1632,32 @@ class FrameColors:
                    'stin_frames_accumulate_f64')
         return self
 
-    def result(self, fill=(0, 0, 0)):
-        """-> (colors float32 [N, 3] in [0, 1], count int32 [N]): the mean of the samples; `fill` where count is 0."""
+    def result(self, fill=(0, 0, 0), knn=0):
+        """-> (colors float32 [N, 3] in [0, 1], count int32 [N]): the mean of the samples; `fill` where count is 0.  knn = k > 0:
+        a vertex with count 0 gets the mean colour of its k nearest coloured vertices instead (fill_unseen_colors; `fill` remains
+        only when no vertex was coloured at all); count is returned as it is - the honest mask of what was never observed."""
         lib = _lib.load()
         n = int(self.vertices.shape[0])
         f = tuple(float(v) for v in fill)
         if len(f) != 3:
             raise ValueError('fill must have three entries')
+        if int(knn) != 0:
+            _check_k(knn, 'FrameColors.result')
         colors = torch.empty(n, 3, dtype=torch.float32, device=self.vertices.device)
         _lib.check(lib.stin_frames_finish_f32(_ptr(self.sum), _ptr(self.count), n, f[0], f[1], f[2], _ptr(colors), None,
                                               _stream(self.vertices)), 'stin_frames_finish_f32')
+        if int(knn) != 0 and n:
+            colors = fill_unseen_colors(self.vertices, colors, self.count, k=int(knn))
         return colors, self.count
 
 
 def vertex_colors_from_frames(vertices, poses, color, depth=None, bits=None, batch=64, color_camera=None, depth_camera=None,
-                              fill=(0, 0, 0), return_seen=False, _route=None, **params):
+                              fill=(0, 0, 0), return_seen=False, _route=None, knn=0, **params):
     """FrameColors for frames that are all resident: poses [P, 4, 4], color uint8 [P, Hc, Wc, 3], depth uint16 [P, Hd, Wd] or bits
     (observe_vertices), added in batches of `batch` poses (the result does not depend on it) -> (colors float32 [N, 3], count int32
-    [N]), with return_seen=True also seen uint32 [N, ceil(P / 32)].  color_camera is required; the other keywords are FrameColors'.
-    Out of scope, as there: image files and resizing, optimisation of the poses, the fill of unseen vertices, near-plane clipping, a
-    CPU fallback."""
+    [N]), with return_seen=True also seen uint32 [N, ceil(P / 32)].  color_camera is required; knn = k > 0 fills the vertices no
+    frame coloured from their k nearest coloured ones (FrameColors.result); the other keywords are FrameColors'.
+    Out of scope, as there: image files and resizing, optimisation of the poses, near-plane clipping, a CPU fallback."""
     if color_camera is None:
         raise ValueError('color_camera = (fx, fy, cx, cy) is required')
     _frames_u(color, torch.uint8, (3,), 'color')
@@ -1535,5 +1672,5 @@ def vertex_colors_from_frames(vertices, poses, color, depth=None, bits=None, bat
     for p0 in range(0, P, step):
         p1 = min(p0 + step, P)
         fc.add(poses[p0:p1], color[p0:p1], None if depth is None else depth[p0:p1], bits, first_pose=p0, _route=_route)
-    colors, count = fc.result(fill)
+    colors, count = fc.result(fill, knn=knn)
     return (colors, count, fc.seen) if return_seen else (colors, count)
