@@ -1251,7 +1251,8 @@ int stin_qem_remap_faces_i64(int64_t* faces, int64_t F, const int64_t* parent, i
                              stin_stream_t stream);
 int stin_qem_trace_i64(const int64_t* parent, const int64_t* rank, int64_t N, int64_t* trace, int32_t* status, stin_stream_t stream);
 
-/* Observer masks: which vertices of a mesh does each camera pose of a scan see (stin_observe.hip) - the `observers` mode of the
+/* Observer masks: which vertices of a mesh does each camera pose of a scan see (stin_observe.hip; the rasteriser under it and
+ * under "Render" is stin_raster.hip: cull, coverage and depth below are its contract for both) - the `observers` mode of the
  * reference's preprocessing/observed_texture_map_generation.py (compute_observed_vertex_map :159-251, which renders the mesh with
  * PyTorch3D's MeshRasterizer at 256 x 256 and keeps pix_to_face; generate_mask_from_vertex_observing_poses :259-267), as a
  * depth-tested triangle rasteriser.  The projection below is what compute_projection_matrix (:117-133) composed with PyTorch3D's
@@ -1370,7 +1371,7 @@ int stin_frames_accumulate_f64(const double* vertices, int64_t N, const double* 
 int stin_frames_finish_f32(const int64_t* sum, const int32_t* count, int64_t N, float fill_r, float fill_g, float fill_b,
                            float* colors, uint8_t* observed, stin_stream_t stream);
 
-/* Render: colour, depth and face-id images of a vertex-coloured mesh from the camera poses of a scan (stin_render.hip) - the
+/* Render: colour, depth and face-id images of a vertex-coloured mesh from the camera poses of a scan (stin_render.hip on stin_raster.hip) - the
  * direction the two sections above lack, mesh -> images.  It stands in for what the reference shows in an Open3D window
  * (utils/ColorCompletionVisualizer.py: unlit vertex colours, a screenshot key) on machines without a display; it is a contract of the
  * project's own, NOT pinned against Open3D's renderer.  tests/_render_oracle.py restates it in numpy (per pose and per pixel over all

@@ -1,4 +1,4 @@
-"""Timing of the observer-mask path (csrc/stin_observe.hip, preprocessing.observe_vertices / observer_masks) on one GPU.
+"""Timing of the observer-mask path (csrc/stin_observe.hip on csrc/stin_raster.hip, preprocessing.observe_vertices / observer_masks) on one GPU.
 
     python profiles/observers.py [--out FILE] [--side 390] [--poses 256] [--reps 5] [--trace-only]
 
@@ -15,7 +15,7 @@ middle, the other half a walk-through 1.2 m above the surface looking ahead and 
   16 .. 4096 and with a threshold no box can exceed (the per-lane loop alone), alternating - the pair that justifies the
   threshold - and that the bits agree.
 --trace-only: 3 calls of the 256-pose set and 3 of the close-up set and nothing else, for a `rocprofv3 --kernel-trace --stats` run
-of its own (per-kernel times: k_observe_clear / _transform / _raster / _raster_large / _resolve).  Never reads the reference.
+of its own (per-kernel times: k_raster_clear / k_raster_transform / k_raster / k_raster_large / k_observe_resolve).  Never reads the reference.
 Prints one JSON line per measurement."""
 import argparse
 import json

@@ -1,4 +1,4 @@
-"""Timing of the render path (csrc/stin_render.hip, views.render_mesh) on one GPU.
+"""Timing of the render path (csrc/stin_render.hip on csrc/stin_raster.hip, views.render_mesh) on one GPU.
 
     python profiles/render.py [--out FILE] [--side 448] [--poses 16] [--reps 9] [--trace-only [--trace-size 480x640]]
 
@@ -14,7 +14,7 @@ its depth camera and 968 x 1296 through its colour camera, `poses` poses in one 
 * the yardstick: preprocessing.observe_vertices on the same scene and poses at S = 256, per pose, scaled by the pixel count;
 * what the images hold: the share of covered pixels and the covered centres per visible face (from the face ids: a statistic).
 --trace-only: 5 whole calls per size and nothing else, for a `rocprofv3 --kernel-trace --stats` run of its own (per-kernel times:
-k_render_clear / _transform / _raster / _raster_large / _resolve) at --trace-size (480x640 or 968x1296).
+k_raster_clear / k_raster_transform / k_raster / k_raster_large / k_render_resolve) at --trace-size (480x640 or 968x1296).
 Never reads the reference.  Prints one JSON line per measurement."""
 import argparse
 import ctypes

@@ -9,11 +9,10 @@
 
 namespace {
 
-inline size_t up256(size_t v) { return (v + 255) & ~(size_t)255; }
 inline char* align256(void* p) { return reinterpret_cast<char*>((reinterpret_cast<uintptr_t>(p) + 255) & ~(uintptr_t)255); }
 inline char* carve(char*& p, size_t bytes) {
     char* r = p;
-    p += up256(bytes);
+    p += stin_up256(bytes);
     return r;
 }
 #define STIN_TRY(expr)            \
@@ -46,7 +45,7 @@ inline BwdLayout bwd_layout(int64_t N, int H, int Cout, int has_shortcut, int B,
     size_t o = 0;
     auto take = [&o](size_t bytes) {
         const size_t r = o;
-        o += up256(bytes);
+        o += stin_up256(bytes);
         return r;
     };
     L.dagg = take((size_t)N * Cout * es);
@@ -114,15 +113,15 @@ extern "C" size_t stin_edgeconv_block_fwd_workspace_bytes(int Cin, int Cp, int H
     const size_t Yw = yw_wide(H, Cout, has_shortcut);
     (void)Cin;
     // wcat [Yw, Cp] + w2s [Cout, H] + bcat [Yw] (forward-only weight operands) + column-reduction workspace
-    return up256(Yw * Cp * 4) + up256((size_t)Cout * H * 4) + up256(Yw * 4) + up256(stin_colreduce_workspace_bytes(Cout, B)) + 256;
+    return stin_up256(Yw * Cp * 4) + stin_up256((size_t)Cout * H * 4) + stin_up256(Yw * 4) + stin_up256(stin_colreduce_workspace_bytes(Cout, B)) + 256;
 }
 
 extern "C" int stin_edgeconv_block_fwd_pack_offsets(int Cp, int H, int Cout, int has_shortcut, size_t* off_wcat, size_t* off_w2s,
                                                     size_t* off_bcat) {
     if (Cp <= 0 || H <= 0 || Cout <= 0 || !off_wcat || !off_w2s || !off_bcat) return STIN_E_SIZE;
     *off_wcat = 0;                                                  // the carve order of block_fwd
-    *off_w2s = up256(yw_wide(H, Cout, has_shortcut) * Cp * 4);
-    *off_bcat = *off_w2s + up256((size_t)Cout * H * 4);
+    *off_w2s = stin_up256(yw_wide(H, Cout, has_shortcut) * Cp * 4);
+    *off_bcat = *off_w2s + stin_up256((size_t)Cout * H * 4);
     return STIN_OK;
 }
 
@@ -130,7 +129,7 @@ extern "C" size_t stin_edgeconv_block_bwd_workspace_bytes(int64_t N, int Cp, int
                                                           int storage) {
     if (N < 0 || Cp <= 0 || H <= 0 || Cout <= 0 || B <= 0) return 0;
     // (sized for the wide layout; the compact trans-inv layout uses H of dY's 2 H columns and the slack pays for its dA column partials)
-    return bwd_layout(N, H, Cout, has_shortcut, B, storage).tn + up256(stin_edgeconv_wgrad_workspace_bytes(N, Cp, H, Cout, has_shortcut)) + 256;
+    return bwd_layout(N, H, Cout, has_shortcut, B, storage).tn + stin_up256(stin_edgeconv_wgrad_workspace_bytes(N, Cp, H, Cout, has_shortcut)) + 256;
 }
 
 // The unpool op `Un` in front of block `J` commutes with the block's first product (stin_net_op_t::y_from_src): the block reads
@@ -292,8 +291,8 @@ static int block_bwd(int storage, const stin_net_op_t& J, const void* g, int64_t
     int64_t ti_rows = 0;
     if (compact) {
         ti_rows = stin_edge_bwd_ti_colsum_rows(N, H);
-        ti_colsum = reinterpret_cast<float*>(static_cast<char*>(dY) + up256((size_t)N * Yw * 4));
-        STIN_REQUIRE(up256((size_t)N * Yw * 4) + (size_t)ti_rows * H * 4 <= up256((size_t)N * yw_wide(H, Cout, has_shortcut) * 4),
+        ti_colsum = reinterpret_cast<float*>(static_cast<char*>(dY) + stin_up256((size_t)N * Yw * 4));
+        STIN_REQUIRE(stin_up256((size_t)N * Yw * 4) + (size_t)ti_rows * H * 4 <= stin_up256((size_t)N * yw_wide(H, Cout, has_shortcut) * 4),
                      STIN_E_WORKSPACE);
     }
     float* coef[5];

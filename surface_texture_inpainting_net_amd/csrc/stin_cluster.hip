@@ -229,7 +229,6 @@ __global__ __launch_bounds__(T) void k_unique_out(const u64* __restrict__ keys, 
     out_b[o] = (int64_t)(keys[i] % (u64)n);
 }
 
-inline size_t up256(size_t v) { return (v + 255) & ~(size_t)255; }
 inline unsigned grid_for(int64_t n) { return (unsigned)((n + T - 1) / T); }
 
 size_t sort_temp_bytes(int64_t n, bool pairs) {
@@ -255,15 +254,15 @@ Layout layout(int64_t n, bool pairs) {
     Layout L;
     const size_t m = (size_t)(n > 0 ? n : 1);
     size_t off = 0;
-    L.keys0 = off; off += up256(m * 8);
-    L.keys1 = off; off += up256(m * 8);
-    L.ids0 = off;  off += pairs ? up256(m * 4) : 0;
-    L.ids1 = off;  off += pairs ? up256(m * 4) : 0;
-    L.head = off;  off += up256(m * 4);
-    L.scan = off;  off += up256(m * 4);
+    L.keys0 = off; off += stin_up256(m * 8);
+    L.keys1 = off; off += stin_up256(m * 8);
+    L.ids0 = off;  off += pairs ? stin_up256(m * 4) : 0;
+    L.ids1 = off;  off += pairs ? stin_up256(m * 4) : 0;
+    L.head = off;  off += stin_up256(m * 4);
+    L.scan = off;  off += stin_up256(m * 4);
     L.temp = off;
     const size_t a = sort_temp_bytes(n, pairs), b = scan_temp_bytes(n);
-    off += up256(a > b ? a : b);
+    off += stin_up256(a > b ? a : b);
     L.total = off + 256;
     return L;
 }

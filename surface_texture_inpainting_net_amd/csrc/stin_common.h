@@ -113,6 +113,8 @@ static inline void stin_raise_dynamic_lds(stin_once_per_device& raised, const vo
 }
 
 static inline bool stin_aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15u) == 0; }
+// workspace regions start on 256 bytes
+static inline size_t stin_up256(size_t v) { return (v + 255) & ~(size_t)255; }
 
 // Lanes that cooperate on one feature row: smallest power of two >= ceil(C/4), capped at a wave.
 static inline int stin_group_lanes(int c4) {

@@ -23,8 +23,6 @@ constexpr int KMAX = STIN_FRAMES_MAX_HALF_KERNEL;
 constexpr int SPLIT_MIN_POSES = 8;                        // poses per chunk of the split route, at least
 constexpr int64_t FILL_GROUPS = 1024;                     // workgroups that fill the chip (256 CUs x 4)
 
-inline size_t up256(size_t v) { return (v + 255) & ~(size_t)255; }
-
 // The largest raw value r with !((double)r / depth_scale > depth_trunc); -1: none stays, 65535: all stay (also for a NaN limit).
 int keep_max_raw(double depth_scale, double depth_trunc) {
     int lo = -1, hi = 65535;                              // predicate "stays" holds on [0, lo], fails above hi
@@ -217,7 +215,7 @@ inline bool frame_size_ok(int H, int W) { return H >= 1 && W >= 1 && H <= STIN_F
 
 extern "C" size_t stin_frames_edges_workspace_bytes(int B, int Hd, int Wd) {
     if (B < 0 || B > STIN_FRAMES_MAX_BATCH || !frame_size_ok(Hd, Wd)) return 0;
-    return up256((size_t)(B > 0 ? B : 1) * (size_t)Hd * (size_t)Wd);
+    return stin_up256((size_t)(B > 0 ? B : 1) * (size_t)Hd * (size_t)Wd);
 }
 
 extern "C" int stin_frames_depth_edges_u16(const uint16_t* depth, int B, int Hd, int Wd, double depth_scale, double depth_trunc,

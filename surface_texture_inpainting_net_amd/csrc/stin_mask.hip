@@ -25,8 +25,6 @@ constexpr int CTL_WORDS = 8;     // ticket, global-list count, ktot, status, bat
 constexpr int INFO_HEAD = 5;
 constexpr int MAX_SEEDED_GRAPHS = 64;     // per instance: batches, done, capped, masked, total; then sizes[max_iters], counts[max_iters]
 
-inline size_t up256(size_t v) { return (v + 255) & ~(size_t)255; }
-
 __device__ inline uint64_t mix64(uint64_t z) {
     z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ull;
     z = (z ^ (z >> 27)) * 0x94D049BB133111EBull;
@@ -427,12 +425,12 @@ MaskLayout mask_layout(int64_t N, int M, int B) {
     const size_t mn = (size_t)(N > 0 ? N : 1) * (size_t)M;
     const size_t I = (size_t)M * (size_t)B;
     size_t off = 0;
-    L.flag = off; off += up256(mn * 4);
-    L.list0 = off; off += up256(mn * 4);
-    L.list1 = off; off += up256(mn * 4);
-    L.ctl = off; off += up256((CTL_WORDS + I) * 8);
-    L.k = off; off += up256(I * 8);
-    L.kofs = off; off += up256((I + 1) * 8);
+    L.flag = off; off += stin_up256(mn * 4);
+    L.list0 = off; off += stin_up256(mn * 4);
+    L.list1 = off; off += stin_up256(mn * 4);
+    L.ctl = off; off += stin_up256((CTL_WORDS + I) * 8);
+    L.k = off; off += stin_up256(I * 8);
+    L.kofs = off; off += stin_up256((I + 1) * 8);
     L.total = off;
     return L;
 }
@@ -447,7 +445,7 @@ size_t adj_scan_bytes(int64_t n) {
 }  // namespace
 
 extern "C" size_t stin_mask_adjacency_workspace_bytes(int64_t N) {
-    return up256((size_t)(N + 1) * 4) * 2 + up256(adj_scan_bytes(N + 1));
+    return stin_up256((size_t)(N + 1) * 4) * 2 + stin_up256(adj_scan_bytes(N + 1));
 }
 
 extern "C" int stin_mask_adjacency_i64(const int64_t* src, const int64_t* dst, int64_t E, int64_t N, int32_t* rowptr, int32_t* col,
@@ -459,9 +457,9 @@ extern "C" int stin_mask_adjacency_i64(const int64_t* src, const int64_t* dst, i
     stin_clear_stale_error();
     char* w = (char*)workspace;
     int32_t* deg = (int32_t*)w;
-    int32_t* cursor = (int32_t*)(w + up256((size_t)(N + 1) * 4));
-    void* temp = w + 2 * up256((size_t)(N + 1) * 4);
-    size_t temp_bytes = up256(adj_scan_bytes(N + 1));
+    int32_t* cursor = (int32_t*)(w + stin_up256((size_t)(N + 1) * 4));
+    void* temp = w + 2 * stin_up256((size_t)(N + 1) * 4);
+    size_t temp_bytes = stin_up256(adj_scan_bytes(N + 1));
     (void)hipMemsetAsync(deg, 0, (size_t)(N + 1) * 4, stream);
     (void)hipMemsetAsync(bad, 0, 4, stream);
     const unsigned ge = (unsigned)((E + MB - 1) / MB);

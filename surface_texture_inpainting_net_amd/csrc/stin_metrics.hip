@@ -166,13 +166,12 @@ __global__ __launch_bounds__(64 * NQ) void k_metrics_final(const double* __restr
     if (threadIdx.x < 8) row_out[threadIdx.x] = vals[threadIdx.x];
 }
 
-inline size_t up256(size_t v) { return (v + 255) & ~(size_t)255; }
 inline int64_t n_blocks(int64_t N) { return (N + MB - 1) / MB; }
 }  // namespace
 
 extern "C" size_t stin_inpaint_metrics_workspace_bytes(int64_t N) {
     if (N <= 0) return 0;
-    return 256 + up256((size_t)NQ * (size_t)n_blocks(N) * sizeof(double)) + (size_t)N * sizeof(float4);
+    return 256 + stin_up256((size_t)NQ * (size_t)n_blocks(N) * sizeof(double)) + (size_t)N * sizeof(float4);
 }
 
 extern "C" int stin_inpaint_metrics_f32(const float* out, int64_t ldo, const float* color, const int64_t* mask,
@@ -187,7 +186,7 @@ extern "C" int stin_inpaint_metrics_f32(const float* out, int64_t ldo, const flo
     const int64_t blocks = n_blocks(N);
     char* base = reinterpret_cast<char*>((reinterpret_cast<uintptr_t>(workspace) + 255) & ~(uintptr_t)255);
     double* partial = reinterpret_cast<double*>(base);
-    float4* stage = reinterpret_cast<float4*>(base + up256((size_t)NQ * (size_t)blocks * sizeof(double)));
+    float4* stage = reinterpret_cast<float4*>(base + stin_up256((size_t)NQ * (size_t)blocks * sizeof(double)));
     hipStream_t stream = (hipStream_t)stream_;
     const dim3 grid((unsigned)blocks), block(MB);
 #define STIN_METRICS_ROWS(C_, ONE_)                                                                                              \

@@ -136,13 +136,11 @@ size_t sort_temp_bytes(int64_t n) {
     return bytes;
 }
 
-inline size_t up256(size_t v) { return (v + 255) & ~(size_t)255; }
-
 }  // namespace
 
 extern "C" size_t stin_vertex_order_workspace_bytes(int64_t n_max) {
     if (n_max <= 0) return 0;
-    return 256 + 4 * up256((size_t)n_max * 4) + 256 + up256(sort_temp_bytes(n_max)) + 256;
+    return 256 + 4 * stin_up256((size_t)n_max * 4) + 256 + stin_up256(sort_temp_bytes(n_max)) + 256;
 }
 
 extern "C" int stin_vertex_order_f32(const float* pos, int64_t ld_pos, const stin_order_level_t* levels, int n_levels,
@@ -158,14 +156,14 @@ extern "C" int stin_vertex_order_f32(const float* pos, int64_t ld_pos, const sti
     }
     STIN_REQUIRE(workspace != nullptr && workspace_bytes >= stin_vertex_order_workspace_bytes(n_max), STIN_E_WORKSPACE);
     char* p = reinterpret_cast<char*>((reinterpret_cast<uintptr_t>(workspace) + 255) & ~(uintptr_t)255);
-    const size_t arr = up256((size_t)n_max * 4);
+    const size_t arr = stin_up256((size_t)n_max * 4);
     unsigned* keys_in = reinterpret_cast<unsigned*>(p);
     unsigned* keys_out = reinterpret_cast<unsigned*>(p + arr);
     int32_t* vals_in = reinterpret_cast<int32_t*>(p + 2 * arr);
     int32_t* vals_out = reinterpret_cast<int32_t*>(p + 3 * arr);
     unsigned* mm = reinterpret_cast<unsigned*>(p + 4 * arr);
     void* temp = p + 4 * arr + 256;
-    size_t temp_bytes = up256(sort_temp_bytes(n_max));
+    size_t temp_bytes = stin_up256(sort_temp_bytes(n_max));
 
     // ---- level 0: bounding box, Morton keys, stable sort
     const int64_t n0 = levels[0].n;

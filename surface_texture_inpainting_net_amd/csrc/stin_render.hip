@@ -1,24 +1,16 @@
 // Result views on the device: a vertex-coloured mesh through a pinhole camera from every pose -> colour, depth and face-id images
 // (what the reference's utils/ColorCompletionVisualizer.py shows in an Open3D window, unlit, and what its `P` key saves).
 // Contract: include/stin_hip.h ("Render"); tests/_render_oracle.py restates it in numpy, pixel-major, and agrees bit for bit.
-// The cull, coverage and depth-key arithmetic is stin_observe.hip's, copied: that file stays as it is.
 //
-//   faces:     int64 -> int32 once, a face with an index outside [0, N) becomes (-1, -1, -1) and sets STIN_RENDER_BAD_INDEX.
-//   per batch of poses (keys and screen coordinates of a batch live in the workspace):
-//   clear:     every key of the batch = all ones ("no face"), 16 bytes per lane; the large-face queue emptied.
-//   transform: one thread per (vertex, pose): view space, then the pinhole -> (X, Y, zv), 24 bytes (one record, not three planes:
-//              planes left the cull where it was and cost the resolve, which reads all nine numbers of a face, 40 %).
-//   raster:    one thread per (face, pose).  The clamped box of the three corners comes FIRST: at a scan's frame sizes most faces of
-//              a scene lie outside the frustum of a pose, and a face that covers no centre costs six loads and no division.  A box of
-//              at most `large_box` centres is looped by its lane; a larger one goes to the queue.
-//   large:     one wavefront per queue entry, lane k takes the centres k, k + 64, ... of the box.  At 480 x 640 and above this is
+//   faces, and per batch of poses clear, transform, raster, large: the shared rasteriser (stin_raster.hip) with the pinhole screen;
+//              keys and screen coordinates of a batch live in the workspace.  At 480 x 640 and above the large-face kernel is
 //              where most of the covered pixels come from (profiles/r26_render.md).
 //   resolve:   a workgroup owns 512 consecutive pixels of the [P][H][W] arrays (two per thread: one 16-byte key load), recomputes
 //              the winner's barycentrics, interpolates the colour perspective-correctly and stages colour / depth / face id in LDS;
 //              the workgroup then streams each array out with 16-byte stores.  The pixel index is GLOBAL over the poses, so the 3-
 //              and 12-byte pixels need no alignment beyond the array's own: 512 pixels are a multiple of 16 bytes in every format.
 // Integer min only: the images do not depend on the schedule, the batch size or `large_box`.
-#include "stin_common.h"
+#include "stin_raster.h"
 
 #include <cmath>
 
@@ -26,188 +18,13 @@ namespace {
 
 constexpr int RB = 256;                                   // threads per workgroup
 constexpr int RES_PIX = 512;                              // pixels of a resolve workgroup
-constexpr unsigned long long NO_FACE = ~0ull;
-constexpr int64_t QUEUE_CAP = (int64_t)1 << 22;           // large-face queue entries per batch; beyond it a lane loops its own face
-constexpr int LARGE_GRID = 2048;                          // workgroups of the large-face kernel (4 waves each, entries strided)
-constexpr int ALL_STAGES = STIN_RENDER_STAGE_CLEAR | STIN_RENDER_STAGE_TRANSFORM | STIN_RENDER_STAGE_RASTER | STIN_RENDER_STAGE_LARGE |
-                           STIN_RENDER_STAGE_RESOLVE;
+constexpr unsigned long long NO_FACE = STIN_RASTER_NO_FACE;
+constexpr int LARGE_GRID = 2048;                          // workgroups of the large-face kernel (r26_render.md)
+constexpr int ALL_STAGES = STIN_RASTER_ALL_STAGES | STIN_RENDER_STAGE_RESOLVE;
 
-inline size_t up256(size_t v) { return (v + 255) & ~(size_t)255; }
-
-struct RenderLayout {
-    size_t faces, coords, keys, queue, ctl, total;
-    int64_t queue_cap;
-};
-RenderLayout render_layout(int64_t N, int64_t F, int H, int W, int batch) {
-    RenderLayout L;
-    size_t off = 0;
-    L.faces = off; off += up256((size_t)(F > 0 ? F : 1) * 3 * 4);
-    L.coords = off; off += up256((size_t)batch * (size_t)(N > 0 ? N : 1) * 3 * 8);
-    // the keys of a batch start at its first pixel's GLOBAL index modulo RES_PIX, so that a resolve workgroup's keys are aligned
-    L.keys = off; off += up256(((size_t)batch * (size_t)H * (size_t)W + RES_PIX) * 8);
-    const int64_t pairs = (int64_t)batch * (F > 0 ? F : 1);
-    L.queue_cap = pairs < QUEUE_CAP ? pairs : QUEUE_CAP;
-    L.queue = off; off += up256((size_t)L.queue_cap * 8);
-    L.ctl = off; off += 256;
-    L.total = off;
-    return L;
-}
-
-__global__ void k_render_faces(const int64_t* __restrict__ faces, int64_t F, int64_t N, int32_t* __restrict__ f32,
-                               int32_t* __restrict__ status) {
-    const int64_t f = (int64_t)blockIdx.x * RB + threadIdx.x;
-    if (f >= F) return;
-    int64_t a = faces[3 * f], b = faces[3 * f + 1], c = faces[3 * f + 2];
-    if (a < 0 || a >= N || b < 0 || b >= N || c < 0 || c >= N) {
-        atomicOr(status, STIN_RENDER_BAD_INDEX);
-        a = b = c = -1;
-    }
-    f32[3 * f] = (int32_t)a;
-    f32[3 * f + 1] = (int32_t)b;
-    f32[3 * f + 2] = (int32_t)c;
-}
-
-// pairs of keys: the buffer is 256-byte aligned and holds an even number of them
-__global__ void k_render_clear(ulonglong2* __restrict__ keys2, int64_t pairs, unsigned* __restrict__ qcount) {
-    const int64_t i = (int64_t)blockIdx.x * RB + threadIdx.x;
-    if (i < pairs) keys2[i] = make_ulonglong2(NO_FACE, NO_FACE);
-    if (i == 0) *qcount = 0u;
-}
-
-struct Camera {
-    double fx, fy, cx, cy;
-};
-
-// coords[b][v] = (X, Y, zv) of vertex v seen from pose p0 + b
-__global__ void k_render_transform(const double* __restrict__ vertices, int64_t N, const double* __restrict__ RT,
-                                   const uint8_t* __restrict__ valid, int64_t p0, Camera cam, double* __restrict__ coords) {
-    const int64_t v = (int64_t)blockIdx.x * RB + threadIdx.x;
-    const int64_t p = p0 + blockIdx.y;
-    if (v >= N || !valid[p]) return;
-    const double* m = RT + p * 12;
-    const double x = vertices[3 * v], y = vertices[3 * v + 1], z = vertices[3 * v + 2];
-    const double xv = ((m[0] * x + m[1] * y) + m[2] * z) + m[3];
-    const double yv = ((m[4] * x + m[5] * y) + m[6] * z) + m[7];
-    const double zv = ((m[8] * x + m[9] * y) + m[10] * z) + m[11];
-    double* o = coords + ((int64_t)blockIdx.y * N + v) * 3;
-    o[0] = cam.fx * xv / zv + cam.cx;
-    o[1] = cam.fy * yv / zv + cam.cy;
-    o[2] = zv;
-}
-
-struct Tri {
-    double ax, ay, az, bx, by, bz, cx, cy, cz, area2;
-    int x0, x1, y0, y1;
-};
-
-__device__ inline bool finite3(double a, double b, double c) { return isfinite(a) && isfinite(b) && isfinite(c); }
-
-// The box of centres that can be covered, then the cull tests of the contract; false: the face is skipped for this pose.  The tests
-// are a conjunction, so their order is free: the box goes first because it is what rejects most (face, pose) pairs.  fmin / fmax pass
-// over a NaN, so a non-finite corner may survive the box; the finite test behind it drops the face, and nothing becomes an int before.
-__device__ inline bool tri_setup(const int32_t* __restrict__ f32, int64_t f, const double* __restrict__ c, double z_near, int H, int W,
-                                 Tri& t) {
-    const int32_t ia = f32[3 * f], ib = f32[3 * f + 1], ic = f32[3 * f + 2];
-    if (ia < 0) return false;                              // an index outside [0, N)
-    t.ax = c[3 * (int64_t)ia];
-    t.bx = c[3 * (int64_t)ib];
-    t.cx = c[3 * (int64_t)ic];
-    const double xlo = fmax(ceil(fmin(t.ax, fmin(t.bx, t.cx))), 0.0), xhi = fmin(floor(fmax(t.ax, fmax(t.bx, t.cx))), (double)(W - 1));
-    if (xlo > xhi) return false;
-    t.ay = c[3 * (int64_t)ia + 1];
-    t.by = c[3 * (int64_t)ib + 1];
-    t.cy = c[3 * (int64_t)ic + 1];
-    const double ylo = fmax(ceil(fmin(t.ay, fmin(t.by, t.cy))), 0.0), yhi = fmin(floor(fmax(t.ay, fmax(t.by, t.cy))), (double)(H - 1));
-    if (ylo > yhi) return false;
-    t.az = c[3 * (int64_t)ia + 2];
-    t.bz = c[3 * (int64_t)ib + 2];
-    t.cz = c[3 * (int64_t)ic + 2];
-    if (t.az < z_near || t.bz < z_near || t.cz < z_near) return false;
-    if (!finite3(t.ax, t.bx, t.cx) || !finite3(t.ay, t.by, t.cy)) return false;
-    t.area2 = (t.bx - t.ax) * (t.cy - t.ay) - (t.by - t.ay) * (t.cx - t.ax);
-    if (!(t.area2 > 0.0) && !(t.area2 < 0.0)) return false;   // zero (or not a number: no centre could pass the sign tests)
-    t.x0 = (int)xlo;
-    t.x1 = (int)xhi;
-    t.y0 = (int)ylo;
-    t.y1 = (int)yhi;
-    return true;
-}
-
-// One centre: coverage (inclusive edges), perspective-correct depth, the key, atomicMin.
-__device__ inline void tri_centre(const Tri& t, int px, int py, unsigned long long* __restrict__ keys, int W, uint32_t face) {
-    const double X = (double)px, Y = (double)py;
-    const double wa = (t.cx - t.bx) * (Y - t.by) - (t.cy - t.by) * (X - t.bx);
-    const double wb = (t.ax - t.cx) * (Y - t.cy) - (t.ay - t.cy) * (X - t.cx);
-    const double wc = (t.bx - t.ax) * (Y - t.ay) - (t.by - t.ay) * (X - t.ax);
-    const bool in = t.area2 > 0.0 ? (wa >= 0.0 && wb >= 0.0 && wc >= 0.0) : (wa <= 0.0 && wb <= 0.0 && wc <= 0.0);
-    if (!in) return;
-    const double la = wa / t.area2, lb = wb / t.area2, lc = wc / t.area2;
-    const double zp = 1.0 / ((la / t.az + lb / t.bz) + lc / t.cz);
-    const unsigned long long key = ((unsigned long long)__float_as_uint((float)zp) << 32) | face;
-    unsigned long long* k = keys + (int64_t)py * W + px;
-    if (*k > key) atomicMin(k, key);                       // keys only fall: a stale look can cost an atomic, never lose one
-}
-
-// keys: the batch's first key (pose b at keys + b H W)
-__global__ __launch_bounds__(RB) void k_render_raster(const int32_t* __restrict__ f32, int64_t F, const double* __restrict__ coords,
-                                                      int64_t N, const uint8_t* __restrict__ valid, int64_t p0, double z_near, int H,
-                                                      int W, int64_t large_box, unsigned long long* __restrict__ keys,
-                                                      unsigned long long* __restrict__ queue, unsigned queue_cap,
-                                                      unsigned* __restrict__ qcount) {
-    __shared__ unsigned s_n, s_base;
-    const int64_t f = (int64_t)blockIdx.x * RB + threadIdx.x;
-    const int b = blockIdx.y;
-    if (!valid[p0 + b]) return;                            // (workgroup-uniform)
-    if (threadIdx.x == 0) s_n = 0u;
-    __syncthreads();
-    Tri t;
-    const bool live = f < F && tri_setup(f32, f, coords + (int64_t)b * N * 3, z_near, H, W, t);
-    const bool large = live && (int64_t)(t.x1 - t.x0 + 1) * (t.y1 - t.y0 + 1) > large_box;
-    // queue slots: ranks inside the workgroup through LDS, then ONE add on the global counter per workgroup - every (face, pose)
-    // that reaches the image at a scan's frame sizes is large, and one word takes only so many returning atomics a microsecond
-    const unsigned rank = large ? atomicAdd(&s_n, 1u) : 0u;
-    __syncthreads();
-    if (threadIdx.x == 0 && s_n != 0u) s_base = atomicAdd(qcount, s_n);
-    __syncthreads();
-    if (!live) return;
-    if (large && s_base + rank < queue_cap) {
-        queue[s_base + rank] = ((unsigned long long)b << 32) | (unsigned long long)f;
-        return;
-    }                                                      // (queue full: rasterise it here, the keys come out the same)
-    unsigned long long* kp = keys + (int64_t)b * H * W;
-    for (int py = t.y0; py <= t.y1; ++py)
-        for (int px = t.x0; px <= t.x1; ++px) tri_centre(t, px, py, kp, W, (uint32_t)f);
-}
-
-__global__ __launch_bounds__(RB) void k_render_raster_large(const int32_t* __restrict__ f32, const double* __restrict__ coords, int64_t N,
-                                                            double z_near, int H, int W, unsigned long long* __restrict__ keys,
-                                                            const unsigned long long* __restrict__ queue, unsigned queue_cap,
-                                                            const unsigned* __restrict__ qcount, int32_t* __restrict__ status) {
-    const unsigned n = *qcount < queue_cap ? *qcount : queue_cap;
-    const int lane = threadIdx.x & (STIN_WAVE - 1);
-    const unsigned waves = gridDim.x * (RB / STIN_WAVE);
-    for (unsigned e = blockIdx.x * (RB / STIN_WAVE) + threadIdx.x / STIN_WAVE; e < n; e += waves) {
-        const unsigned long long entry = queue[e];
-        const int b = (int)(entry >> 32);
-        const int64_t f = (int64_t)(entry & 0xffffffffull);
-        Tri t;
-        if (!tri_setup(f32, f, coords + (int64_t)b * N * 3, z_near, H, W, t)) continue;   // (it passed in k_render_raster)
-        unsigned long long* kp = keys + (int64_t)b * H * W;
-        const int w = t.x1 - t.x0 + 1, h = t.y1 - t.y0 + 1;
-        // centre k = (row k / w, column k % w) of the box; one division per face, then steps of 64 = dq rows and dr columns
-        const int dq = STIN_WAVE / w, dr = STIN_WAVE % w;
-        int row = lane / w, col = lane % w;
-        while (row < h) {
-            tri_centre(t, t.x0 + col, t.y0 + row, kp, W, (uint32_t)f);
-            row += dq;
-            col += dr;
-            if (col >= w) {
-                col -= w;
-                ++row;
-            }
-        }
-        if (lane == 0 && !(*status & STIN_RENDER_LARGE_FACE)) atomicOr(status, STIN_RENDER_LARGE_FACE);
-    }
+// the keys of a batch start at its first pixel's GLOBAL index modulo RES_PIX, so that a resolve workgroup's keys are aligned
+RasterLayout render_layout(int64_t N, int64_t F, int H, int W, int batch) {
+    return stin_raster_layout(N, F, batch, (size_t)batch * (size_t)H * (size_t)W + RES_PIX);
 }
 
 struct Background {
@@ -361,16 +178,10 @@ extern "C" int stin_render_poses_f64(const double* vertices, int64_t N, const in
     STIN_REQUIRE(workspace != nullptr && workspace_bytes >= stin_render_workspace_bytes(N, F, H, W, batch), STIN_E_WORKSPACE);
     hipStream_t stream = (hipStream_t)stream_;
     stin_clear_stale_error();
-    const RenderLayout L = render_layout(N, F, H, W, batch);
-    char* w = (char*)workspace;
-    int32_t* f32 = (int32_t*)(w + L.faces);
-    double* coords = (double*)(w + L.coords);
-    unsigned long long* keys = (unsigned long long*)(w + L.keys);
-    unsigned long long* queue = (unsigned long long*)(w + L.queue);
-    unsigned* qcount = (unsigned*)(w + L.ctl);
-    if (large_box <= 0) large_box = STIN_RENDER_LARGE_BOX;
+    RasterCall c = {vertices, N, F, RT, valid, {STIN_RASTER_PINHOLE, {camera[0], camera[1], camera[2], camera[3]}}, H, W, z_near,
+                    large_box > 0 ? large_box : STIN_RENDER_LARGE_BOX, LARGE_GRID, status};
+    stin_raster_bind(c, render_layout(N, F, H, W, batch), workspace);
     if (stages <= 0) stages = ALL_STAGES;
-    const Camera cam = {camera[0], camera[1], camera[2], camera[3]};
     Background bg = {};
     for (int k = 0; k < K; ++k) {
         bg.f[k] = background[k];
@@ -381,28 +192,15 @@ extern "C" int stin_render_poses_f64(const double* vertices, int64_t N, const in
               (stin_aligned16(face_ids) ? 8 : 0);
     (void)hipMemsetAsync(status, 0, 4, stream);
     if (P == 0) return stin_launch_status();
-    const unsigned gf = (unsigned)((F + RB - 1) / RB), gv = (unsigned)((N + RB - 1) / RB);
     const int64_t HW = (int64_t)H * W;
-    const bool geometry = N > 0 && F > 0;                  // else every pixel is background
-    if (F > 0) hipLaunchKernelGGL(k_render_faces, dim3(gf), dim3(RB), 0, stream, faces, F, N, f32, status);
+    stin_raster_faces(c, faces, stream);
     for (int64_t p0 = 0; p0 < P; p0 += batch) {
         const unsigned nb = (unsigned)(P - p0 < batch ? P - p0 : batch);
         const int64_t g_lo = p0 * HW, g_hi = g_lo + (int64_t)nb * HW, g_base = g_lo & ~(int64_t)(RES_PIX - 1);
-        unsigned long long* batch_keys = keys + (g_lo - g_base);
-        const int64_t pairs = (g_hi - g_base + 1) / 2;
-        if (stages & STIN_RENDER_STAGE_CLEAR)
-            hipLaunchKernelGGL(k_render_clear, dim3((unsigned)((pairs + RB - 1) / RB)), dim3(RB), 0, stream, (ulonglong2*)keys, pairs, qcount);
-        if (geometry && (stages & STIN_RENDER_STAGE_TRANSFORM))
-            hipLaunchKernelGGL(k_render_transform, dim3(gv, nb), dim3(RB), 0, stream, vertices, N, RT, valid, p0, cam, coords);
-        if (geometry && (stages & STIN_RENDER_STAGE_RASTER))
-            hipLaunchKernelGGL(k_render_raster, dim3(gf, nb), dim3(RB), 0, stream, f32, F, coords, N, valid, p0, z_near, H, W, large_box,
-                               batch_keys, queue, (unsigned)L.queue_cap, qcount);
-        if (geometry && (stages & STIN_RENDER_STAGE_LARGE))
-            hipLaunchKernelGGL(k_render_raster_large, dim3(LARGE_GRID), dim3(RB), 0, stream, f32, coords, N, z_near, H, W, batch_keys, queue,
-                               (unsigned)L.queue_cap, qcount, status);
+        stin_raster_batch(c, p0, nb, g_hi - g_base, g_lo - g_base, stages, stream);      // (no geometry: every pixel is background)
         if (stages & STIN_RENDER_STAGE_RESOLVE)
-            hipLaunchKernelGGL(k_render_resolve, dim3((unsigned)((g_hi - g_base + RES_PIX - 1) / RES_PIX)), dim3(RB), 0, stream, keys, f32,
-                               coords, N, colors, K, g_base, g_lo, g_hi, p0, H, W, depth_scale, bg, out);
+            hipLaunchKernelGGL(k_render_resolve, dim3((unsigned)((g_hi - g_base + RES_PIX - 1) / RES_PIX)), dim3(RB), 0, stream, c.keys, c.f32,
+                               c.coords, N, colors, K, g_base, g_lo, g_hi, p0, H, W, depth_scale, bg, out);
     }
     return stin_launch_status();
 }

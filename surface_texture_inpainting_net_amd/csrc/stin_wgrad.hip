@@ -472,8 +472,6 @@ __global__ __launch_bounds__(FN_BLOCK) void k_wgrad_finalize(const WgFinal f) {
     }
 }
 
-inline size_t up256(size_t v) { return (v + 255) & ~(size_t)255; }
-
 }  // namespace
 
 int stin_tn_ws_launch(const stin_tn_problem* pa, const TnRoute* ra, const stin_tn_problem* pb, const TnRoute* rb, stin_stream_t stream) {
@@ -501,7 +499,7 @@ extern "C" size_t stin_edgeconv_wgrad_workspace_bytes(int64_t N, int Cp, int H, 
         const size_t b = stin_gemm_tn_workspace_bytes(N, stin_yw(H, Cout, has_shortcut, ti), Cp, 1);
         if (b > slab_b) slab_b = b;
     }
-    return up256(stin_gemm_tn_workspace_bytes(N, Cout, H, 1)) + up256(slab_b) + 256;
+    return stin_up256(stin_gemm_tn_workspace_bytes(N, Cout, H, 1)) + stin_up256(slab_b) + 256;
 }
 
 extern "C" int stin_edgeconv_wgrad(int storage, const void* dagg, int64_t ld_dagg, const void* hE, int64_t ldh, const void* dY,
@@ -532,7 +530,7 @@ static int wgrad_impl(int storage, const void* dagg, int64_t ld_dagg, const void
     STIN_REQUIRE(x_row_map == nullptr || (x_rows > 0 && stin_aligned16(x_row_map)), STIN_E_SIZE);
     char* p = reinterpret_cast<char*>((reinterpret_cast<uintptr_t>(workspace) + 255) & ~(uintptr_t)255);
     float* slabA = reinterpret_cast<float*>(p);
-    const size_t offB = up256(stin_gemm_tn_workspace_bytes(N, Cout, H, 1));
+    const size_t offB = stin_up256(stin_gemm_tn_workspace_bytes(N, Cout, H, 1));
     float* slabB = reinterpret_cast<float*>(p + offB);
     const size_t es = storage ? 2 : 4;
     const void* row_w = static_cast<const char*>(hE) + (size_t)H * es;          // the [deg > 0] column of hE weights db2

@@ -144,6 +144,41 @@ def test_boxes_just_below_and_just_above_the_threshold(nx, ny):
     assert status & LARGE
 
 
+# ------------------------------------------------------------------------------------------------------- the shared rasteriser
+@functools.lru_cache(maxsize=None)
+def sphere_from_five_sides(S):
+    """The jittered icosphere from the first five outside poses of sphere_poses() (heights 0, 0.5, -0.7, 0, 0.5); the restatement
+    once per size."""
+    V, F = QO.icosphere(2, 3)
+    poses = sphere_poses()[:5]
+    return V, F, poses, OO.observe(V, F, poses, image_size=S, **CAM)
+
+
+@pytest.mark.parametrize('S', [1, 15, 33])
+def test_odd_key_counts_under_the_paired_clear(S):
+    """The keys are cleared 16 bytes at a time; nb S S is odd for an odd S and an odd number of poses in the batch, so the last
+    pair reaches one key into the region's padding.  Background and covered keys are both in play: a pose covers 93 - 96 of 225
+    pixels at S = 15, 458 - 468 of 1089 at S = 33, the one pixel of S = 1."""
+    V, F, poses, want = sphere_from_five_sides(S)
+    covered = (want[2] >= 0).reshape(5, -1).sum(axis=1)
+    print('S = %d: covered pixels per pose %s of %d' % (S, covered.tolist(), S * S))
+    assert OO.unpack(want[0], 5).any(axis=0).all() and (covered > 0).all()       # every pose observes something
+    assert (covered < S * S).all() or S == 1
+    runs = [check_parity(V, F, poses, S, want=want, batch=b)[0] for b in (1, 2, 5)]
+    assert runs[0].tobytes() == runs[1].tobytes() == runs[2].tobytes()
+
+
+def test_the_queue_route_over_a_whole_mesh():
+    """large_box = 1: every face that reaches a centre with a box of two or more is queued, workgroups hold queued, looped and
+    culled lanes side by side; large_box = 2^40: no face is queued.  Same bits, the oracle's."""
+    V, F, poses, want = sphere_from_five_sides(33)
+    queued, status = check_parity(V, F, poses, 33, want=want, large_box=1)
+    assert status & LARGE and not status & BAD
+    looped, status = check_parity(V, F, poses, 33, want=want, large_box=2 ** 40)
+    assert not status & LARGE and not status & BAD
+    assert queued.tobytes() == looped.tobytes() and queued.any()
+
+
 # ------------------------------------------------------------------------------------------------------- culling
 def test_poses_looking_away_see_nothing():
     V, F = QO.icosphere(1, 5)
