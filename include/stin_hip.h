@@ -1371,6 +1371,62 @@ int stin_frames_accumulate_f64(const double* vertices, int64_t N, const double* 
 int stin_frames_finish_f32(const int64_t* sum, const int32_t* count, int64_t N, float fill_r, float fill_g, float fill_b,
                            float* colors, uint8_t* observed, stin_stream_t stream);
 
+/* Colour-map optimisation: the photometric normal equations of every camera pose (stin_colormap.hip) - the hot part of the rigid
+ * optimiser that Open3D's colour-map pipeline runs with maximum_iteration > 0 (Zhou & Koltun 2014), on top of "Frame colours":
+ * preprocessing.optimize_poses_rigid refines the poses from the frames before the colours are averaged.  A contract of the
+ * project's own, NOT a port of Open3D and NOT pinned against a run of it; tests/_colormap_oracle.py restates it in numpy (per pose
+ * over all vertices) and agrees byte for byte.  Everything is fp64 and IEEE, the operations in the order written, nothing
+ * contracted; integers where stated.  The non-rigid optimiser (per-camera warp grids) is not built.
+ *
+ *   inputs    vertices fp64 [N][3]; poses RT [B][12], valid [B], first_pose and the view (xv, yv, zv) as in "Frame colours"; colour
+ *             frames uint8 [B][H][W][3]; ONE camera (fx, fy, cx, cy), the colour camera; bits uint32 [N][words], the FIXED
+ *             visibility in stin_observe_poses_f64's / seen's layout; z_near > 0; integer margin >= 1.
+ *   images    per pixel, int32: G = 299 R + 587 G + 114 B (<= 255000), and gx, gy = the two Sobel expressions that "Frame colours"
+ *             writes for r under `edges`, on G, with row and column indices clamped to the image (|value| <= 1 020 000).  Stored as
+ *             one 16-byte pixel (G, gx, gy, 0): int32 [B][H][W][4].  Intensity in [0, 1] is G / 255000.0; the derivative per pixel
+ *             is gx / 2040000.0 (the Sobel response / 8: Gauss-Newton needs the true derivative), likewise gy.
+ *   pairs     (v, p) contributes when pose p is valid, bit p of bits[v] is set, !(zv < z_near), u = fx xv / zv + cx and v = fy yv /
+ *             zv + cy are finite, margin <= u <= W - 1 - margin and margin <= v <= H - 1 - margin: the test of
+ *             stin_frames_accumulate_f64's bits mode, word for word.  The bits stay fixed over an optimisation; the projection moves.
+ *   proxy     from the sums of stin_frames_accumulate_f64 in bits mode AT THE SAME POSES (sum, count zeroed first):
+ *             num = 299 sum[v][0] + 587 sum[v][1] + 114 sum[v][2] (int64); proxy[v] = (double) num / ((double) count[v]
+ *             16711680000.0) (= 65536 * 255 * 1000), 0 where count[v] is 0.  The pair set is the same: a contributing pair has count >= 1.
+ *   per pair  sI, sX, sY = the `sample` expression of "Frame colours" (x0, y0, a, b, x1, y1, val) on G, gx, gy promoted to fp64;
+ *             I = sI / 255000.0, dIdx = sX / 2040000.0, dIdy = sY / 2040000.0; r = I - proxy[v]; iz = 1.0 / zv;
+ *             v0 = (dIdx fx) iz, v1 = (dIdy fy) iz, v2 = -((v0 xv + v1 yv) iz);
+ *             J = ((-zv v1) + yv v2, zv v0 - xv v2, (-yv v0) + xv v1, v0, v1, v2): rotation x, y, z and translation x, y, z of an
+ *             increment multiplied from the LEFT onto the extrinsic.
+ *   per pose  one row of STIN_COLORMAP_ROW_DOUBLES = 28 doubles: A[i][j] += J_i J_j for i <= j in row-major order of the upper
+ *             triangle (21), b[i] += J_i r (6), e += r r (1); and an int32 count n += 1.
+ *   order     vertices are cut into consecutive tiles of 256 STIN_COLORMAP_U ids.  Lane l (0 .. 255) of a tile starts at +0.0 and
+ *             adds its terms for the vertices base + l + 256 i, i = 0 .. STIN_COLORMAP_U - 1 ascending (a pair that does not
+ *             contribute adds +0.0, i.e. nothing); the 256 lane sums x[] are folded by the halving tree, for s = 128, 64, .. 1:
+ *             x[i] += x[i + s] for i < s; the tile sums x[0] are added in ascending tile order, starting at +0.0.  A function of N
+ *             alone: the result depends neither on B, nor on first_pose, nor on how poses are split over launches or grid
+ *             dimensions, nor on the run.  No float atomics.  A tile without a contributing pair for a pose may skip the tree: its
+ *             sum is +0.0 either way (no lane sum can be -0.0).  Visible pairs are NOT compacted: that would move terms in the tree.
+ *   update    on the host (preprocessing.optimize_poses_rigid): x = solve(A, -b) per pose on the symmetrised 6 x 6;
+ *             D(x) = [[Rz(x2) Ry(x1) Rx(x0), x[3:6]], [0 0 0 1]]; E' = D(x) E.
+ * stin_colormap_gradients_u8: colour [B][H][W][3] -> images int32 [B][H][W][4] (16-byte aligned), one workgroup per 64 x 16 tile
+ *     through LDS.  16 bytes per pixel: 4.9 MB per 480 x 640 frame.  Sizes and B as for the frame kernels (STIN_E_SIZE).
+ * stin_colormap_proxy_f64: sum int64 [N][3], count int32 [N] -> proxy fp64 [N].
+ * stin_colormap_normal_f64: one batch of poses -> rows fp64 [B][28], counts int32 [B] (written, not accumulated), in two kernels:
+ *     per (tile, chunk of poses) the tile sums into the workspace (stin_colormap_workspace_bytes: tiles x B x 116 bytes, rounded),
+ *     then one thread per (pose, value) over the tiles.  images: those of the batch's B frames.  camera: HOST array of
+ *     STIN_COLORMAP_CAMERA_DOUBLES doubles (read during the call).  words >= ceil((first_pose + B) / 32), margin >= 1, z_near > 0,
+ *     N < 2^31 - 1, B <= STIN_FRAMES_MAX_BATCH, sizes in [1, STIN_FRAMES_MAX_SIZE] (STIN_E_SIZE otherwise).  N = 0: rows of +0.0.
+ * Null pointers are allowed where a count is 0.  Nothing allocates or synchronises. */
+#define STIN_COLORMAP_ROW_DOUBLES 28
+#define STIN_COLORMAP_U 4
+#define STIN_COLORMAP_CAMERA_DOUBLES 4
+int stin_colormap_gradients_u8(const uint8_t* color, int B, int H, int W, int32_t* images, stin_stream_t stream);
+int stin_colormap_proxy_f64(const int64_t* sum, const int32_t* count, int64_t N, double* proxy, stin_stream_t stream);
+size_t stin_colormap_workspace_bytes(int64_t N, int B);
+int stin_colormap_normal_f64(const double* vertices, int64_t N, const double* RT, const uint8_t* valid, int B, int64_t first_pose,
+                             const int32_t* images, int H, int W, const double* camera, double z_near, const uint32_t* bits,
+                             int64_t words, int margin, const double* proxy, double* rows, int32_t* counts, void* workspace,
+                             size_t workspace_bytes, stin_stream_t stream);
+
 /* Render: colour, depth and face-id images of a vertex-coloured mesh from the camera poses of a scan (stin_render.hip on stin_raster.hip) - the
  * direction the two sections above lack, mesh -> images.  It stands in for what the reference shows in an Open3D window
  * (utils/ColorCompletionVisualizer.py: unlit vertex colours, a screenshot key) on machines without a display; it is a contract of the

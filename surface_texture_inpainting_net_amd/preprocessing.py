@@ -48,7 +48,12 @@
   and depth frames and the camera trajectory to Open3D's colour-map pipeline with ``maximum_iteration=0``: per vertex and frame a
   visibility test (against the sensor's depth away from depth discontinuities, or ``observe_vertices``' bits), a projection and a
   bilinear colour sample, averaged in integers (``stin_frames_*``).  ``frame_intrinsics`` is its rescaled camera (:104-107).  A
-  contract of this project's own, NOT pinned against an Open3D run; no optimisation of the poses.
+  contract of this project's own, NOT pinned against an Open3D run.
+
+* ``optimize_poses_rigid`` - the rigid optimisation the same pipeline runs with ``maximum_iteration > 0`` (Zhou & Koltun 2014): per
+  iteration the proxy intensities from ``FrameColors``' sums, the photometric residual and 6-DoF Jacobian of every visible (vertex,
+  pose) pair, the normal equations of every pose summed in a fixed order (``stin_colormap_*``), and one Gauss-Newton step per free pose
+  on the host (``rigid_update``, ``rigid_increment``).  A contract of this project's own, NOT pinned against Open3D; no non-rigid step.
 
 * ``knn`` / ``fill_unseen_colors`` / ``knn_inpaint`` - exact fp64 k nearest neighbours with a validity mask on the points
   (``stin_knn_f64``: ``nearest``'s tiled brute force with a k-list per query in registers) and the mean of the neighbours' rows
@@ -1539,8 +1544,8 @@ class FrameColors:
     rounded to 1 / 65536 of a grey level and summed as integers - the result does not depend on the order or the batching.
 
     Not Open3D's result bit for bit and not pinned against a run of it.  Out of scope: reading image files and any resize (frames
-    arrive decoded, as everywhere here), Open3D's rigid / non-rigid optimisation (iterations > 0), clipping at the near plane, and
-    a CPU fallback.  Unseen vertices get `fill` and count 0, or, with result(knn=k), the mean colour of their k nearest coloured
+    arrive decoded, as everywhere here), Open3D's non-rigid optimisation (its rigid one, iterations > 0, is optimize_poses_rigid: run it
+    first and average with the poses it returns), clipping at the near plane, and a CPU fallback.  Unseen vertices get `fill` and count 0, or, with result(knn=k), the mean colour of their k nearest coloured
     vertices (fill_unseen_colors: exact fp64 k-NN with a stated tie rule; k = 3 is Open3D's default to our knowledge, which - like
     its tie handling - could not be checked against a run of it)."""
 
@@ -1598,14 +1603,12 @@ class FrameColors:
             raise ValueError('poses %d .. %d lie outside [0, num_poses)' % (first, first + B))
         if B > _lib.CONSTANTS['STIN_FRAMES_MAX_BATCH']:
             raise ValueError('at most %d poses per batch' % _lib.CONSTANTS['STIN_FRAMES_MAX_BATCH'])
-        lib = _lib.load()
+        _lib.load()
         d = edge = b = None
-        Hd = Wd = words = 0
         if depth is not None:
             d = _frames_u(depth, torch.uint16, (), 'depth')
             if int(d.shape[0]) != B:
                 raise ValueError('%d poses but %d depth frames' % (B, int(d.shape[0])))
-            Hd, Wd = int(d.shape[1]), int(d.shape[2])
         else:
             if not (torch.is_tensor(bits) and bits.is_cuda):
                 raise TypeError('bits must be a CUDA tensor (no CPU fallback exists)')
@@ -1621,14 +1624,26 @@ class FrameColors:
         if d is not None:
             edge = self.depth_edges(d)
         rt_d, valid_d = torch.from_numpy(RT).to(dev), torch.from_numpy(valid).to(dev)
+        return self._add_extrinsics(rt_d, valid_d, c, first, depth=d, edge=edge, bits=b, seen=self.seen, route=_route)
+
+    def _add_extrinsics(self, rt_d, valid_d, color, first_pose, depth=None, edge=None, bits=None, seen=None, route=None):
+        """The launch under add(), for extrinsics that are already on the device (rt_d fp64 [B, 12], valid_d uint8 [B],
+        pose_extrinsics' rows) and arguments as add() has checked them; optimize_poses_rigid repeats it in bits mode at the poses of
+        every iteration."""
+        n, B = int(self.vertices.shape[0]), int(rt_d.shape[0])
+        if B == 0 or n == 0:
+            return self
         cameras = (ctypes.c_double * _lib.CONSTANTS['STIN_FRAMES_CAMERA_DOUBLES'])(*(self.color_camera + self.depth_camera))
         params = (ctypes.c_double * _lib.CONSTANTS['STIN_FRAMES_PARAM_DOUBLES'])(self.depth_scale, self.depth_trunc, self.max_depth,
                                                                                  self.depth_threshold, self.z_near)
-        _lib.check(lib.stin_frames_accumulate_f64(_ptr(self.vertices), n, _ptr(rt_d), _ptr(valid_d), B, first, _ptr(c), int(c.shape[1]),
-                                                  int(c.shape[2]), _ptr(d), _ptr(edge), Hd, Wd, cameras, params, _ptr(b), words,
-                                                  self.margin, _lib.CONSTANTS['STIN_FRAMES_ROUTE_AUTO'] if _route is None else int(_route),
-                                                  _ptr(self.sum), _ptr(self.count), _ptr(self.seen),
-                                                  0 if self.seen is None else int(self.seen.shape[1]), _stream(self.vertices)),
+        Hd, Wd = (int(depth.shape[1]), int(depth.shape[2])) if depth is not None else (0, 0)
+        _lib.check(_lib.load().stin_frames_accumulate_f64(_ptr(self.vertices), n, _ptr(rt_d), _ptr(valid_d), B, int(first_pose),
+                                                          _ptr(color), int(color.shape[1]), int(color.shape[2]), _ptr(depth), _ptr(edge),
+                                                          Hd, Wd, cameras, params, _ptr(bits), 0 if bits is None else int(bits.shape[1]),
+                                                          self.margin,
+                                                          _lib.CONSTANTS['STIN_FRAMES_ROUTE_AUTO'] if route is None else int(route),
+                                                          _ptr(self.sum), _ptr(self.count), _ptr(seen),
+                                                          0 if seen is None else int(seen.shape[1]), _stream(self.vertices)),
                    'stin_frames_accumulate_f64')
         return self
 
@@ -1657,7 +1672,8 @@ def vertex_colors_from_frames(vertices, poses, color, depth=None, bits=None, bat
     (observe_vertices), added in batches of `batch` poses (the result does not depend on it) -> (colors float32 [N, 3], count int32
     [N]), with return_seen=True also seen uint32 [N, ceil(P / 32)].  color_camera is required; knn = k > 0 fills the vertices no
     frame coloured from their k nearest coloured ones (FrameColors.result); the other keywords are FrameColors'.
-    Out of scope, as there: image files and resizing, optimisation of the poses, near-plane clipping, a CPU fallback."""
+    Out of scope, as there: image files and resizing, the non-rigid optimisation (the rigid one is optimize_poses_rigid, whose poses go
+    in here), near-plane clipping, a CPU fallback."""
     if color_camera is None:
         raise ValueError('color_camera = (fx, fy, cx, cy) is required')
     _frames_u(color, torch.uint8, (3,), 'color')
@@ -1674,3 +1690,192 @@ def vertex_colors_from_frames(vertices, poses, color, depth=None, bits=None, bat
         fc.add(poses[p0:p1], color[p0:p1], None if depth is None else depth[p0:p1], bits, first_pose=p0, _route=_route)
     colors, count = fc.result(fill, knn=knn)
     return (colors, count, fc.seen) if return_seen else (colors, count)
+
+
+# ------------------------------------------------------------------------------------------------- colour-map optimisation
+COLORMAP_NOT_FREE, COLORMAP_INVALID, COLORMAP_FEW_PAIRS, COLORMAP_SINGULAR = 1, 2, 4, 8      # bits of info['status']
+
+
+def rigid_increment(x):
+    """x = (rotation x, y, z in radians, translation x, y, z) -> D(x) float64 [4, 4] = [[Rz(x2) Ry(x1) Rx(x0), x[3:6]], [0 0 0 1]],
+    the increment the rigid optimiser multiplies onto an extrinsic from the left (include/stin_hip.h, "Colour-map optimisation")."""
+    import numpy as np
+    x = np.asarray(x, dtype=np.float64).reshape(6)
+    c, s = np.cos(x[:3]), np.sin(x[:3])
+    D = np.zeros((4, 4), dtype=np.float64)
+    D[0, 0], D[0, 1], D[0, 2] = c[2] * c[1], (c[2] * s[1]) * s[0] - s[2] * c[0], (c[2] * s[1]) * c[0] + s[2] * s[0]
+    D[1, 0], D[1, 1], D[1, 2] = s[2] * c[1], (s[2] * s[1]) * s[0] + c[2] * c[0], (s[2] * s[1]) * c[0] - c[2] * s[0]
+    D[2, 0], D[2, 1], D[2, 2] = -s[1], c[1] * s[0], c[1] * c[0]
+    D[:3, 3] = x[3:6]
+    D[3, 3] = 1.0
+    return D
+
+
+def rigid_update(E, valid, free, rows, counts, min_pairs, status):
+    """One Gauss-Newton update on the host: E float64 [P, 4, 4] extrinsics (changed in place), rows [P, 28] and counts [P] as
+    stin_colormap_normal_f64 writes them, status int32 [P] (bits COLORMAP_FEW_PAIRS / COLORMAP_SINGULAR are OR-ed in).  A pose moves
+    when it is free, valid, has counts >= min_pairs and np.linalg.solve on its symmetrised 6 x 6 gives a finite x: E' = D(x) E.
+    -> bool [P]: which poses moved."""
+    import numpy as np
+    iu = np.triu_indices(6)
+    moved = np.zeros(E.shape[0], dtype=bool)
+    for p in range(E.shape[0]):
+        if not (free[p] and valid[p]):
+            continue
+        if int(counts[p]) < min_pairs:
+            status[p] |= COLORMAP_FEW_PAIRS
+            continue
+        A = np.zeros((6, 6), dtype=np.float64)
+        A[iu] = rows[p, :21]
+        A.T[iu] = rows[p, :21]
+        try:
+            x = np.linalg.solve(A, -rows[p, 21:27])
+        except np.linalg.LinAlgError:
+            x = None
+        if x is None or not np.isfinite(x).all():
+            status[p] |= COLORMAP_SINGULAR
+            continue
+        E[p] = rigid_increment(x) @ np.ascontiguousarray(E[p])
+        moved[p] = True
+    return moved
+
+
+def _colormap_gradients(color, images=None):
+    """color uint8 [B, H, W, 3] (CUDA, contiguous) -> the intensity and gradient images int32 [B, H, W, 4] = (G, gx, gy, 0)."""
+    B, H, W = (int(s) for s in color.shape[:3])
+    if images is None:
+        images = torch.empty(B, H, W, 4, dtype=torch.int32, device=color.device)
+    _lib.check(_lib.load().stin_colormap_gradients_u8(_ptr(color), B, H, W, _ptr(images), _stream(color)), 'stin_colormap_gradients_u8')
+    return images
+
+
+def _colormap_proxy(total, count, proxy=None):
+    """sum int64 [N, 3], count int32 [N] of FrameColors -> the proxy intensity fp64 [N]."""
+    n = int(count.shape[0])
+    if proxy is None:
+        proxy = torch.empty(n, dtype=torch.float64, device=count.device)
+    _lib.check(_lib.load().stin_colormap_proxy_f64(_ptr(total), _ptr(count), n, _ptr(proxy), _stream(count)), 'stin_colormap_proxy_f64')
+    return proxy
+
+
+def _colormap_workspace(n, batch, device):
+    ws_bytes = _lib.load().stin_colormap_workspace_bytes(n, batch)
+    if ws_bytes == 0:
+        raise ValueError('%d vertices in batches of %d poses are outside what the normal-equation kernel supports' % (n, batch))
+    return torch.empty(ws_bytes, dtype=torch.uint8, device=device)
+
+
+def _colormap_normal(v64, rt_d, valid_d, first_pose, images, camera, z_near, bits, margin, proxy, rows, counts, ws):
+    """One batch of poses -> rows fp64 [B, 28], counts int32 [B] (written in place): stin_colormap_normal_f64 on device arrays."""
+    n, B = int(v64.shape[0]), int(rt_d.shape[0])
+    cam = (ctypes.c_double * _lib.CONSTANTS['STIN_COLORMAP_CAMERA_DOUBLES'])(*camera)
+    _lib.check(_lib.load().stin_colormap_normal_f64(_ptr(v64), n, _ptr(rt_d), _ptr(valid_d), B, int(first_pose), _ptr(images),
+                                                    int(images.shape[1]), int(images.shape[2]), cam, float(z_near),
+                                                    _ptr(bits) if n else None, int(bits.shape[1]), int(margin), _ptr(proxy), _ptr(rows),
+                                                    _ptr(counts), _ptr(ws), int(ws.numel()), _stream(v64)), 'stin_colormap_normal_f64')
+
+
+def optimize_poses_rigid(vertices, poses, color, depth=None, bits=None, *, color_camera=None, depth_camera=None, iterations=30,
+                         free=None, min_pairs=16, batch=64, **params):
+    """The rigid colour-map optimisation (Zhou & Koltun 2014; what Open3D's colour-map pipeline does with maximum_iteration > 0
+    before it averages colours): refine the camera poses photometrically, so that the frames agree on the mesh's intensities, on the
+    GPU (csrc/stin_colormap.hip).  vertices [N, >= 3] float, color uint8 [P, H, W, 3] and either depth uint16 [P, Hd, Wd] or bits
+    (observe_vertices' uint32 [N, words]) - CUDA tensors, checked as FrameColors.add checks them; poses [P, 4, 4] camera-to-world
+    (array or tensor); color_camera (required), depth_camera and **params are FrameColors'; margin must be >= 1.
+    -> (poses float64 [P, 4, 4] camera-to-world numpy, info): info['residual'] float64 and info['pairs'] int64, both
+    [iterations + 1, P] - the sum of squared intensity residuals and the number of (vertex, pose) pairs of every pose before each
+    update and after the last; info['status'] int32 [P], bits COLORMAP_NOT_FREE, COLORMAP_INVALID, COLORMAP_FEW_PAIRS (fewer than
+    min_pairs pairs in some iteration: not moved in it), COLORMAP_SINGULAR (its 6 x 6 could not be solved in some iteration).
+
+    Visibility is established ONCE, at the given poses: in depth mode by one FrameColors pass whose `seen` becomes the bits, in
+    bits mode by the caller's bits; only the projection moves afterwards.  Per iteration (the count is fixed, there is no early
+    stop: the result is a pure function of the inputs): the proxy intensity of every vertex from the integer colour sums at the
+    current poses; per pair the residual between the frame's intensity and the proxy and its Jacobian for a rigid increment of the
+    extrinsic; per pose the 6 x 6 normal equations, summed in a fixed order; the P x 29 numbers are read back (the only
+    synchronisation) and every free, valid pose with at least min_pairs pairs takes one Gauss-Newton step on the host.  The contract
+    is in include/stin_hip.h ("Colour-map optimisation"); the test suite restates it in numpy and this reproduces it byte for byte.
+    free: bool [P], default all.  A held pose takes part in the proxy but never moves - anchor keyframes with it: with every pose
+    free the cameras settle on a consensus, which need not be the truth.  A pose that never moved (held, invalid, too few pairs)
+    comes back exactly as given.  Memory: the intensity and gradient images of ALL P frames are built once, 16 bytes per pixel
+    (4.9 MB per 480 x 640 frame); the rows are computed in batches of `batch` poses (the result does not depend on it).
+
+    The recipe: poses, info = optimize_poses_rigid(vertices, poses, color, depth, color_camera=cam); then
+    vertex_colors_from_frames(vertices, poses, color, depth, color_camera=cam) with the returned poses.
+    Not Open3D's result and not pinned against a run of it; the non-rigid optimisation (per-camera warp grids) is not built."""
+    import numpy as np
+    if color_camera is None:
+        raise ValueError('color_camera = (fx, fy, cx, cy) is required')
+    if (depth is None) == (bits is None):
+        raise ValueError('exactly one of depth and bits must be given')
+    margin, iters, step, min_pairs = int(params.get('margin', 10)), int(iterations), int(batch), int(min_pairs)
+    if margin < 1:
+        raise ValueError('margin must be >= 1: the gradient is sampled like the colour')
+    if iters < 0 or step < 1:
+        raise ValueError('iterations must be >= 0 and batch positive')
+    P = len(poses)
+    free = np.ones(P, dtype=bool) if free is None else np.asarray(free.detach().cpu().numpy() if torch.is_tensor(free) else free)
+    if free.dtype != np.bool_ or free.shape != (P,):
+        raise ValueError('free must be bool [%d], one entry per pose' % P)
+    c = _frames_u(color, torch.uint8, (3,), 'color')
+    if int(c.shape[0]) != P:
+        raise ValueError('%d poses but %d colour frames' % (P, int(c.shape[0])))
+    fc = FrameColors(vertices, color_camera, depth_camera, num_poses=P if depth is not None else None, **params)
+    v, n, dev = fc.vertices, int(fc.vertices.shape[0]), fc.vertices.device
+    step = max(1, min(step, P, _lib.CONSTANTS['STIN_FRAMES_MAX_BATCH']))
+    words = (P + 31) // 32
+    if depth is not None:
+        d = _frames_u(depth, torch.uint16, (), 'depth')
+        if int(d.shape[0]) != P:
+            raise ValueError('%d poses but %d depth frames' % (P, int(d.shape[0])))
+    else:
+        if not (torch.is_tensor(bits) and bits.is_cuda):
+            raise TypeError('bits must be a CUDA tensor (no CPU fallback exists)')
+        if bits.dtype != torch.uint32 or bits.dim() != 2 or int(bits.shape[0]) != n:
+            raise TypeError('bits must be uint32 [N, words], as observe_vertices returns it')
+        if int(bits.shape[1]) < words:
+            raise ValueError('bits has %d words per vertex, %d poses need %d' % (int(bits.shape[1]), P, words))
+        vis = bits.contiguous()
+    if P and 0 in c.shape:
+        raise ValueError('empty frames')
+    RT, valid = pose_extrinsics(poses)
+    given = np.array(poses.detach().cpu().numpy() if torch.is_tensor(poses) else poses, dtype=np.float64).reshape(P, 4, 4)
+    status = np.where(free, 0, COLORMAP_NOT_FREE).astype(np.int32) | np.where(valid != 0, 0, COLORMAP_INVALID).astype(np.int32)
+    residual, pairs = np.zeros((iters + 1, P), dtype=np.float64), np.zeros((iters + 1, P), dtype=np.int64)
+    info = dict(residual=residual, pairs=pairs, status=status)
+    if P == 0:
+        return given, info
+    if depth is not None:                                              # visibility, once, at the given poses
+        for p0 in range(0, P, step):
+            fc.add(given[p0:p0 + step], c[p0:p0 + step], depth=d[p0:p0 + step], first_pose=p0)
+        vis = fc.seen
+    H, W = int(c.shape[1]), int(c.shape[2])
+    images = torch.empty(P, H, W, 4, dtype=torch.int32, device=dev)
+    for p0 in range(0, P, step):
+        _colormap_gradients(c[p0:p0 + step], images[p0:p0 + step])
+    proxy = torch.empty(n, dtype=torch.float64, device=dev)
+    rows = torch.empty(P, _lib.CONSTANTS['STIN_COLORMAP_ROW_DOUBLES'], dtype=torch.float64, device=dev)
+    counts = torch.empty(P, dtype=torch.int32, device=dev)
+    ws = _colormap_workspace(n, step, dev)
+    valid_d = torch.from_numpy(valid).to(dev)
+    E = np.zeros((P, 4, 4), dtype=np.float64)
+    E[:, :3, :] = RT.reshape(P, 3, 4)
+    E[:, 3, 3] = 1.0
+    ever = np.zeros(P, dtype=bool)
+    for it in range(iters + 1):
+        rt_d = torch.from_numpy(np.ascontiguousarray(E[:, :3, :]).reshape(P, 12)).to(dev)
+        fc.sum.zero_()
+        fc.count.zero_()
+        for p0 in range(0, P, step):
+            fc._add_extrinsics(rt_d[p0:p0 + step], valid_d[p0:p0 + step], c[p0:p0 + step], p0, bits=vis)
+        _colormap_proxy(fc.sum, fc.count, proxy)
+        for p0 in range(0, P, step):
+            _colormap_normal(v, rt_d[p0:p0 + step], valid_d[p0:p0 + step], p0, images[p0:p0 + step], fc.color_camera, fc.z_near, vis,
+                             margin, proxy, rows[p0:p0 + step], counts[p0:p0 + step], ws)
+        r, k = rows.cpu().numpy(), counts.cpu().numpy()
+        residual[it], pairs[it] = r[:, 27], k
+        if it < iters:
+            ever |= rigid_update(E, valid, free, r, k, min_pairs, status)
+    out = given.copy()
+    for p in np.flatnonzero(ever):
+        out[p] = np.linalg.inv(E[p])
+    return out, info
