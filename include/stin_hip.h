@@ -93,7 +93,8 @@ int stin_csr_pair_from_edges_i64(const int64_t* src, const int64_t* dst, int64_t
  * A job = one CSR grouped by a[] with the value b[] (b == NULL: the pair id itself, e.g. the children of every coarse vertex
  * of hierarchy_trace_index_l) or, with pair != 0, both CSRs of one directed edge set (a = edge_index[1] = targets,
  * b = edge_index[0] = sources; outputs as stin_csr_pair_from_edges_i64).  narrow_out (may be NULL): the int32 copy of a[]
- * (0 where out of range) - the `trace` the pool / unpool kernels gather with, written by the counting pass.
+ * (0 where the PAIR is left out: a[] out of range, or - with a value array - b[] out of range) - the `trace` the pool / unpool
+ * kernels gather with, written by the first pass over the pairs.
  * jobs: HOST array (copied into the kernel arguments); out-of-range pairs set *bad and are left out, as above.
  * workspace >= stin_plan_build_workspace_bytes(sum of E, sum over jobs of (pair ? 2 : 1) * N + 1). */
 #define STIN_PLAN_MAX_JOBS 16
