@@ -1533,6 +1533,48 @@ int stin_image_metrics_f32(const float* out, int64_t ldo, const float* color, co
                            int composite, float data_range, const float* loss, float* row_out, void* workspace,
                            size_t workspace_bytes, stin_stream_t stream);
 
+/* ------------------------------------------------------------------------------- Image resize --
+ * What the reference asks cv2.resize for: colour frames to the depth size (preprocessing/texture_map_optimization.py:93, the
+ * default = bilinear) and Rescale of the 2-D experiment (datasets/imagegraph_dataloader.py:215, INTER_AREA), stin_resize.hip.
+ *
+ * Images are uint8, row-major [H, W, C], C = 1, 3 or 4.  A source H x W becomes h x w; every side lies in
+ * [1, STIN_RESIZE_MAX_SIDE].  Integer arithmetic only: the result does not depend on batching, tiling or route.
+ *
+ * STIN_RESIZE_LINEAR: bilinear with half-pixel centres and 11-bit coefficients, for enlarging and for reducing (no
+ *     antialiasing).  Per axis, for output index d of n_out from n_in:
+ *         num = (2 d + 1) n_in - n_out,  den = 2 n_out,  s = floor(num / den) (floor also for num < 0),  r = num - s den,
+ *         b = (4096 r + den) / (2 den) (integer division: round(2048 frac), halves up),  a = 2048 - b;
+ *         s < 0: s = 0, b = 0;   s >= n_in - 1: s = n_in - 1, b = 0;   second tap = min(s + 1, n_in - 1).
+ *     With (sy, ay, by) of the row, (sx, ax, bx) of the column and v00 .. v11 the four taps (first index: row tap):
+ *         out = (ay (ax v00 + bx v01) + by (ax v10 + bx v11) + 2^21) >> 22
+ *     - one rounding; every term fits in int32.  Equal sizes give the input back byte for byte.
+ *     |out - exact bilinear| <= 0.5 + 255 (2^-12 + 2^-12 + 2^-24) < 0.625: within one grey level of any correctly rounded
+ *     bilinear resize with half-pixel centres.  That is what cv2.resize does on 8-bit images to our knowledge; it is NOT pinned
+ *     against a run of cv2.
+ * STIN_RESIZE_AREA: the exact area average; h <= H and w <= W (cv2 switches to a bilinear variant when enlarging, which is not
+ *     restated: such a job is unsupported - see below for what the library, which sees the table on the device only, does).  With ox(j, x) = max(0, min((x + 1) w, (j + 1) W) - max(x w, j W)) the overlap of
+ *     source column x with output column j in units of 1 / w of a source pixel, oy(i, y) the same with h, H:
+ *         S = sum_y sum_x oy(i, y) ox(j, x) v[y, x],   out = (2 S + W H) / (2 W H)   (integer division: halves up)
+ *     S reaches 255 * 2^28: the sums are 64-bit.  Not pinned against cv2.INTER_AREA either.
+ * The reference applies Rescale after Normalize, on float32; here it runs on the bytes, which differs by at most half a grey level.
+ *
+ * stin_resize_u8: J jobs in one launch.  jobs: int64 [J][STIN_RESIZE_JOB_WORDS] on the device = src_off, H, W, dst_off, h, w:
+ *     the source image starts at byte src_off of `src` (src_bytes long), the result at byte dst_off of `dst` (dst_bytes long); any
+ *     alignment, the jobs may be of different sizes (a pool of images) or equal (a [B, H, W, C] batch).  The table is read on the
+ *     device only: a job with a side outside [1, STIN_RESIZE_MAX_SIDE], an image that does not lie inside its buffer, or AREA with
+ *     h > H or w > W writes NOTHING (the host wrappers raise before the launch); no byte outside [dst_off, dst_off + h w C) of a job
+ *     is written and no byte outside `src` is read.  Results of jobs must not overlap each other or `src`.
+ *     Source rows are staged through LDS with 16-byte loads, results leave as 16-byte stores where the address allows; the
+ *     per-column coefficients / overlaps are formed once per block and column, the per-row ones once per block and row.  A
+ *     footprint of any size (2000 rows to 3) is a loop over source rows and column chunks.  No workspace, no allocation, no
+ *     synchronisation, no float, no atomics.  J <= 0, channels not in {1, 3, 4}, an unknown mode: STIN_E_SIZE. */
+#define STIN_RESIZE_MAX_SIDE 16384
+#define STIN_RESIZE_JOB_WORDS 6
+#define STIN_RESIZE_LINEAR 0
+#define STIN_RESIZE_AREA 1
+int stin_resize_u8(const uint8_t* src, int64_t src_bytes, uint8_t* dst, int64_t dst_bytes, const int64_t* jobs, int J, int channels,
+                   int mode, stin_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

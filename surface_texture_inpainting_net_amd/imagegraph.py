@@ -9,14 +9,17 @@ bytes, the graph and its plan are built once per batch size, and ONE launch per 
     grid_levels        the graph tensors under the reference's keys (one launch, stin_grid_levels_i64)
     draw_image_params  the reference's random draws of one item, in its order, from its generators
     build_samples      x / color / mask of a batch from the resident byte pool
+    rescale_size       the size the reference's Rescale gives an image
     ImageGraphLoader   epochs of HierarchicalBatch objects with a resident, shared GraphPlan
     (metrics.ImageStepMetrics: the 2-D trainer's step metrics as rows of a device table)
 
 Every function takes CPU tensors too and then runs a torch / numpy path with the same semantics.
 
-Out of scope: `Rescale` (cv2.INTER_AREA - there is nothing here to compare a resampler against): an image must already have
-min(h, w) == img_size, as the reference's images have after its Rescale(img_size, img_size); PNG decoding (the caller's business:
-`images` are uint8 arrays).  The edge ORDER is defined here (the reference iterates a Python set): image-major, then the source
+`Rescale` (cv2.INTER_AREA) is ImageGraphLoader(..., rescale=True): every larger image is area-resized to rescale_size once, at
+construction, in one launch (preprocessing.resize_pool_u8: the exact area average in integers, include/stin_hip.h "Image resize",
+not pinned against cv2; on the bytes, where the reference runs it after Normalize on float32 - at most half a grey level apart).
+Without it an image must already have min(h, w) == img_size, as the reference's images have after its Rescale(img_size, img_size).
+Out of scope: PNG decoding (the caller's business: `images` are uint8 arrays).  The edge ORDER is defined here (the reference iterates a Python set): image-major, then the source
 vertex in row-major order, then its neighbours up, left, right, down.
 """
 import collections
@@ -125,6 +128,17 @@ def draw_image_params(py_rng, np_rng, img_size, crop_half_width, circle_radius, 
     return k, flip, starts
 
 
+def rescale_size(h, w, img_size):
+    """(new_h, new_w) of the reference's Rescale(img_size, img_size).__call__ for an h x w image (imagegraph_dataloader.py:197-209):
+    the shorter side becomes img_size, the longer one int(img_size * longer / shorter) - Python's true division, then truncation."""
+    h, w, output_size = int(h), int(w), int(img_size)
+    if h > w:
+        new_h, new_w = output_size * h / w, output_size
+    else:
+        new_h, new_w = output_size, output_size * w / h
+    return int(new_h), int(new_w)
+
+
 def circle_template(circle_radius):
     """bool [2R, 2R]: (r - R)^2 + (c - R)^2 <= R^2 (imagegraph_dataloader.py:35-39)."""
     R = int(circle_radius)
@@ -139,8 +153,8 @@ def _check_records(pool_bytes, records, S, R):
     nc = len(records[0].starts)
     for r in records:
         if min(int(r.h), int(r.w)) != S:
-            raise ValueError('image of %d x %d: min(h, w) must equal img_size %d (Rescale is out of scope: resize the images first)'
-                             % (r.h, r.w, S))
+            raise ValueError('image of %d x %d: min(h, w) must equal img_size %d (resize it first: ImageGraphLoader(rescale=True) or '
+                             'preprocessing.resize_u8)' % (r.h, r.w, S))
         if int(r.offset) < 0 or int(r.offset) + int(r.h) * int(r.w) * 3 > pool_bytes:
             raise ValueError('image at offset %d (%d x %d x 3 bytes) lies outside the pool of %d bytes' % (r.offset, r.h, r.w, pool_bytes))
         if int(r.k) not in (0, 1, 2, 3):
@@ -184,7 +198,7 @@ def _pack_records(records, nc):
 def build_samples(pool, records, img_size, circle_radius):
     """x [B S S, 4] f32, color [B S S, 3] f32, mask [B S S, 1] bool of the items `records` (ImageRecord or the same tuples) whose raw
     uint8 images lie in `pool` (1-D uint8 tensor).  A GPU pool: the records travel in one non-blocking copy from pinned memory, ONE
-    launch builds the batch, nothing synchronises.  ValueError: min(h, w) != img_size (Rescale is out of scope), an image outside the
+    launch builds the batch, nothing synchronises.  ValueError: min(h, w) != img_size (Rescale happens before: ImageGraphLoader(rescale=True)), an image outside the
     pool, a circle window outside the image (the reference would fail with a shape mismatch, or wrap a negative index)."""
     S, R = int(img_size), int(circle_radius)
     if pool.dtype != torch.uint8 or pool.dim() != 1 or not pool.is_contiguous():
@@ -213,7 +227,10 @@ def build_samples(pool, records, img_size, circle_radius):
 class ImageGraphLoader:
     """Epochs of image-graph batches, resident on `device`: ``for sample in loader.epoch(e): loss = step(sample)``.
 
-    images: list of uint8 H x W x 3 arrays with min(H, W) == img_size, uploaded once into one byte pool.  The graph tensors and
+    images: list of uint8 H x W x 3 arrays with min(H, W) == img_size, uploaded once into one byte pool.  rescale=True is the
+    reference's Rescale(img_size, img_size): an image with min(H, W) > img_size is area-resized to rescale_size(H, W, img_size) on
+    the device, all images in one launch into the resident pool (an image of the right size is copied, a smaller one is a
+    ValueError); the default keeps refusing every other size.  The graph tensors and
     the GraphPlan built from them are made once per distinct batch size (the last batch of an epoch may be smaller) and shared by
     every batch of that size through `_plan_cache`, the way loader.SceneLoader keeps a scene's plan resident.  Sharding over ranks:
     loader.shard_indices.  An item's rotation, flip and circle positions come from generators seeded by (seed, epoch, item index)
@@ -221,7 +238,7 @@ class ImageGraphLoader:
     Per batch: one small non-blocking copy of the records, one kernel launch, no host synchronisation."""
 
     def __init__(self, images, device, img_size, end_level, batch_size, circle_radius, crop_half_width, num_circles=4, is_train=True,
-                 random_mask=False, random_augmentation=False, shuffle=True, seed=0, rank=0, world_size=1, model=None):
+                 random_mask=False, random_augmentation=False, shuffle=True, seed=0, rank=0, world_size=1, model=None, rescale=False):
         self.device = torch.device(device)
         # model (optional): the network the batches are for - the resident plan takes its instance-norm convention
         # (compat_linspace_norm) from it, as surfacetextureinpaintingnet.build_plan does; None = the network's default
@@ -230,21 +247,32 @@ class ImageGraphLoader:
         self.circle_radius, self.crop_half_width, self.num_circles = int(circle_radius), crop_half_width, int(num_circles)
         self.is_train, self.random_mask, self.random_augmentation = bool(is_train), bool(random_mask), bool(random_augmentation)
         self.shuffle, self.seed, self.rank, self.world_size = bool(shuffle), int(seed), int(rank), int(world_size)
-        self.items, parts, at = [], [], 0
+        self.items, parts, jobs, at, raw_at = [], [], [], 0, 0
         for img in images:
             img = np.ascontiguousarray(img)
             if img.dtype != np.uint8 or img.ndim != 3 or img.shape[2] != 3:
                 raise TypeError('images must be uint8 arrays of shape H x W x 3')
-            h, w = int(img.shape[0]), int(img.shape[1])
+            H, W = int(img.shape[0]), int(img.shape[1])
+            h, w = H, W
+            if rescale and min(H, W) > self.img_size:
+                h, w = rescale_size(H, W, self.img_size)
             if min(h, w) != self.img_size:
-                raise ValueError('image of %d x %d: min(h, w) must equal img_size %d (Rescale is out of scope: resize the images '
-                                 'first)' % (h, w, self.img_size))
+                raise ValueError('image of %d x %d: min(h, w) must %s img_size %d%s' % (
+                    H, W, 'be at least' if rescale else 'equal', self.img_size,
+                    '' if rescale else ' (rescale=True resizes larger images as the reference\'s Rescale does)'))
             self.items.append((at, h, w))
+            jobs.append((raw_at, H, W, at, h, w))
             parts.append(img.reshape(-1))
-            at += img.size
+            at += h * w * 3
+            raw_at += img.size
         if not self.items:
             raise ValueError('no images')
         self.pool = torch.from_numpy(np.concatenate(parts)).to(self.device)
+        if rescale and at != raw_at:
+            # one launch over every image (those of the right size are copied: equal sizes are the identity); the raw upload is
+            # released when this returns
+            from . import preprocessing
+            self.pool = preprocessing.resize_pool_u8(self.pool, jobs, at, channels=3, mode='area')
         self._graphs = {}                                    # batch size -> (graph tensors, host num_vertices, GraphPlan or None)
 
     def __len__(self):

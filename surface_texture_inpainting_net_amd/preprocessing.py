@@ -60,6 +60,11 @@
   (``stin_knn_mean_f32``): the fill of unseen vertices that Open3D's pipeline ends with (``FrameColors.result(knn=3)``), and the
   nearest-known-vertex baseline to put beside the network's l1 / psnr.
 
+* ``resize_u8`` / ``resize_pool_u8`` / ``scan_vertex_colors`` - the two ``cv2.resize`` calls of the reference: colour frames to the
+  depth size (``texture_map_optimization.py:93``, bilinear) and ``Rescale`` of the 2-D experiment (``INTER_AREA``), in integers, one
+  launch for a batch or a ragged pool of images (``stin_resize_u8``); ``scan_vertex_colors`` is ``load_dataset`` plus the averaging,
+  from a scan directory.  A contract of this project's own (include/stin_hip.h, "Image resize"), NOT pinned against cv2.
+
 All take and return tensors in the reference's own formats.  Out of scope: reading mesh files (neither open3d nor plyfile exists
 here to pin a reader against: vertices, faces and colours are inputs), and the Matterport and S3DIS label paths.
 """
@@ -1543,8 +1548,9 @@ class FrameColors:
     observe_vertices' bit says so.  The sample: bilinear in the uint8 colour frame, required to lie `margin` pixels inside it,
     rounded to 1 / 65536 of a grey level and summed as integers - the result does not depend on the order or the batching.
 
-    Not Open3D's result bit for bit and not pinned against a run of it.  Out of scope: reading image files and any resize (frames
-    arrive decoded, as everywhere here), Open3D's non-rigid optimisation (its rigid one, iterations > 0, is optimize_poses_rigid: run it
+    Not Open3D's result bit for bit and not pinned against a run of it.  Frames arrive here decoded and at their final size: resize_u8
+    brings colour frames to the depth size on the device, scene_io.read_frames reads a scan's files, and scan_vertex_colors does
+    both from a scan directory.  Out of scope: Open3D's non-rigid optimisation (its rigid one, iterations > 0, is optimize_poses_rigid: run it
     first and average with the poses it returns), clipping at the near plane, and a CPU fallback.  Unseen vertices get `fill` and count 0, or, with result(knn=k), the mean colour of their k nearest coloured
     vertices (fill_unseen_colors: exact fp64 k-NN with a stated tie rule; k = 3 is Open3D's default to our knowledge, which - like
     its tie handling - could not be checked against a run of it)."""
@@ -1672,8 +1678,9 @@ def vertex_colors_from_frames(vertices, poses, color, depth=None, bits=None, bat
     (observe_vertices), added in batches of `batch` poses (the result does not depend on it) -> (colors float32 [N, 3], count int32
     [N]), with return_seen=True also seen uint32 [N, ceil(P / 32)].  color_camera is required; knn = k > 0 fills the vertices no
     frame coloured from their k nearest coloured ones (FrameColors.result); the other keywords are FrameColors'.
-    Out of scope, as there: image files and resizing, the non-rigid optimisation (the rigid one is optimize_poses_rigid, whose poses go
-    in here), near-plane clipping, a CPU fallback."""
+    Frames of another size go through resize_u8 first; scan_vertex_colors reads, resizes and adds a scan directory batch by batch.
+    Out of scope, as there: the non-rigid optimisation (the rigid one is optimize_poses_rigid, whose poses go in here), near-plane
+    clipping, a CPU fallback."""
     if color_camera is None:
         raise ValueError('color_camera = (fx, fy, cx, cy) is required')
     _frames_u(color, torch.uint8, (3,), 'color')
@@ -1690,6 +1697,181 @@ def vertex_colors_from_frames(vertices, poses, color, depth=None, bits=None, bat
         fc.add(poses[p0:p1], color[p0:p1], None if depth is None else depth[p0:p1], bits, first_pose=p0, _route=_route)
     colors, count = fc.result(fill, knn=knn)
     return (colors, count, fc.seen) if return_seen else (colors, count)
+
+
+# -------------------------------------------------------------------------------------------------------------- image resize
+RESIZE_MODES = {'linear': 'STIN_RESIZE_LINEAR', 'area': 'STIN_RESIZE_AREA'}
+
+
+def _resize_job(job, pool_bytes, out_bytes, channels, mode):
+    """One (src_off, H, W, dst_off, h, w) row, checked the way the kernel checks it (which then writes nothing): raised here."""
+    if len(job) != _lib.CONSTANTS['STIN_RESIZE_JOB_WORDS']:
+        raise ValueError('a resize job is (src_off, H, W, dst_off, h, w)')
+    so, H, W, do, h, w = (int(v) for v in job)
+    top = _lib.CONSTANTS['STIN_RESIZE_MAX_SIDE']
+    if min(H, W, h, w) < 1:
+        raise ValueError('resize %d x %d -> %d x %d: every side must be at least 1' % (H, W, h, w))
+    if max(H, W, h, w) > top:
+        raise ValueError('resize %d x %d -> %d x %d: a side above %d' % (H, W, h, w, top))
+    if mode == 'area' and (h > H or w > W):
+        raise ValueError('resize %d x %d -> %d x %d: the area mode does not enlarge (use mode="linear")' % (H, W, h, w))
+    if so < 0 or so + H * W * channels > pool_bytes:
+        raise ValueError('image at offset %d (%d x %d x %d bytes) lies outside the pool of %d bytes' % (so, H, W, channels, pool_bytes))
+    if do < 0 or do + h * w * channels > out_bytes:
+        raise ValueError('result at offset %d (%d x %d x %d bytes) lies outside the %d output bytes' % (do, h, w, channels, out_bytes))
+    return so, H, W, do, h, w
+
+
+def _linear_axis_np(n_in, n_out):
+    import numpy as np
+    d = np.arange(n_out, dtype=np.int64)
+    num, den = (2 * d + 1) * n_in - n_out, 2 * n_out
+    s = num // den
+    b = (4096 * (num - s * den) + den) // (2 * den)
+    edge = (s < 0) | (s >= n_in - 1)
+    s = np.clip(s, 0, n_in - 1)
+    b = np.where(edge, 0, b).astype(np.int32)
+    return s, np.minimum(s + 1, n_in - 1), b
+
+
+def _area_axis_np(v, n_out):
+    """v float64 [n_in, M] (integers) -> [n_out, M]: the overlap-weighted sums along axis 0, exact while they stay below 2^53; the
+    overlap matrix is formed for 256 outputs at a time, over the inputs they touch."""
+    import numpy as np
+    n_in = v.shape[0]
+    out = np.empty((n_out, v.shape[1]), dtype=np.float64)
+    for j0 in range(0, n_out, 256):
+        j1 = min(j0 + 256, n_out)
+        x0, x1 = j0 * n_in // n_out, -(-(j1 * n_in) // n_out)
+        j, x = np.arange(j0, j1, dtype=np.int64)[:, None], np.arange(x0, x1, dtype=np.int64)[None, :]
+        o = np.maximum(0, np.minimum((x + 1) * n_out, (j + 1) * n_in) - np.maximum(x * n_out, j * n_in))
+        out[j0:j1] = o.astype(np.float64) @ v[x0:x1]
+    return out
+
+
+def _resize_np(img, h, w, mode):
+    """The CPU path: uint8 numpy [H, W, C] -> [h, w, C], the bytes of the contract (include/stin_hip.h, "Image resize")."""
+    import numpy as np
+    H, W, C = img.shape
+    if mode == 'linear':
+        sx, tx, bx = _linear_axis_np(W, w)
+        sy, ty, by = _linear_axis_np(H, h)
+        v = img.astype(np.int32)
+        bx = bx[None, :, None]
+        rows = (2048 - bx) * v[:, sx] + bx * v[:, tx]                                   # [H, w, C], < 2^19
+        by = by[:, None, None]
+        return (((2048 - by) * rows[sy] + by * rows[ty] + (1 << 21)) >> 22).astype(np.uint8)
+    part = _area_axis_np(img.reshape(H, W * C).astype(np.float64), h).reshape(h, W, C)
+    S = _area_axis_np(np.ascontiguousarray(part.transpose(1, 0, 2)).reshape(W, h * C), w).reshape(w, h, C).transpose(1, 0, 2)
+    S = np.rint(S).astype(np.int64)
+    return ((2 * S + W * H) // (2 * W * H)).astype(np.uint8)
+
+
+def resize_pool_u8(pool, jobs, out_bytes, channels=3, mode='linear', out=None):
+    """The ragged form under resize_u8: `pool` is a contiguous 1-D uint8 tensor that holds row-major H x W x channels images at any
+    byte offsets, jobs = [(src_off, H, W, dst_off, h, w), ...]: image at byte src_off becomes h x w at byte dst_off of the result, a
+    uint8 tensor of out_bytes bytes on the pool's device (`out`: write into this tensor instead of a new one; bytes that no job
+    covers keep their value, in a new tensor they are 0).  The contract is include/stin_hip.h, "Image resize".  A CUDA pool: the
+    table travels in one non-blocking copy from pinned memory and ONE launch serves every job (stin_resize_u8); a CPU pool takes a
+    numpy path with the same bytes.  Results must not overlap each other.  TypeError / ValueError as resize_u8, and for an image or
+    a result outside its buffer."""
+    if mode not in RESIZE_MODES:
+        raise ValueError('mode must be one of %s' % ', '.join(sorted(RESIZE_MODES)))
+    channels, out_bytes = int(channels), int(out_bytes)
+    if channels not in (1, 3, 4):
+        raise ValueError('channels must be 1, 3 or 4')
+    if not torch.is_tensor(pool) or pool.dtype != torch.uint8 or pool.dim() != 1 or not pool.is_contiguous():
+        raise TypeError('pool must be a contiguous 1-D uint8 tensor')
+    if out is None:
+        out = torch.zeros(max(out_bytes, 0), dtype=torch.uint8, device=pool.device)
+    elif (not torch.is_tensor(out) or out.dtype != torch.uint8 or out.dim() != 1 or not out.is_contiguous()
+          or out.device != pool.device or out.numel() != out_bytes):
+        raise TypeError('out must be a contiguous 1-D uint8 tensor of out_bytes bytes on the pool\'s device')
+    rows = [_resize_job(job, pool.numel(), out_bytes, channels, mode) for job in jobs]
+    if not rows:
+        return out
+    if not pool.is_cuda:
+        src, dst = pool.numpy(), out.numpy()
+        for so, H, W, do, h, w in rows:
+            img = src[so:so + H * W * channels].reshape(H, W, channels)
+            dst[do:do + h * w * channels] = _resize_np(img, h, w, mode).reshape(-1)
+        return out
+    words = _lib.CONSTANTS['STIN_RESIZE_JOB_WORDS']
+    host = torch.empty(len(rows), words, dtype=torch.int64, pin_memory=True)
+    host.copy_(torch.tensor(rows, dtype=torch.int64))
+    table = host.to(pool.device, non_blocking=True)
+    with torch.cuda.device(pool.device):
+        _lib.check(_lib.load().stin_resize_u8(_ptr(pool), pool.numel(), _ptr(out), out_bytes, _ptr(table), len(rows), channels,
+                                              _lib.CONSTANTS[RESIZE_MODES[mode]], _stream(pool)), 'stin_resize_u8')
+    return out
+
+
+def resize_u8(images, size, mode='linear'):
+    """uint8 images [B, H, W, C] or [H, W, C] (C = 1, 3 or 4) -> the same rank at size = (h, w).  mode 'linear': bilinear with
+    half-pixel centres and 11-bit coefficients, enlarging or reducing, no antialiasing - what cv2.resize does by default on 8-bit
+    images to our knowledge, within one grey level of any correctly rounded bilinear resize (|out - exact| < 0.625).  mode 'area':
+    the exact area average (cv2.INTER_AREA's meaning when reducing); it does not enlarge.  Integer arithmetic with one rounding:
+    the contract is include/stin_hip.h, "Image resize", restated in numpy by the test suite; equal sizes return the bytes
+    unchanged; NEITHER mode is pinned against a run of cv2.  The reference's Rescale runs after Normalize, on float32; this runs
+    on the bytes, which differs by at most half a grey level.  CUDA tensors: one launch for the batch (stin_resize_u8, no
+    synchronisation); CPU tensors: a numpy path with the same bytes.  TypeError: not a uint8 tensor; ValueError: another rank or
+    C, an empty side, a side above STIN_RESIZE_MAX_SIDE, 'area' asked to enlarge."""
+    if not torch.is_tensor(images) or images.dtype != torch.uint8:
+        raise TypeError('images must be a uint8 tensor')
+    if images.dim() not in (3, 4) or int(images.shape[-1]) not in (1, 3, 4):
+        raise ValueError('images must be [B, H, W, C] or [H, W, C] with C = 1, 3 or 4')
+    if mode not in RESIZE_MODES:
+        raise ValueError('mode must be one of %s' % ', '.join(sorted(RESIZE_MODES)))
+    try:
+        h, w = (int(v) for v in size)
+    except (TypeError, ValueError):
+        raise ValueError('size must be (h, w)') from None
+    batch = images if images.dim() == 4 else images[None]
+    B, H, W, C = (int(s) for s in batch.shape)
+    rows = [(b * H * W * C, H, W, b * h * w * C, h, w) for b in range(B)]
+    if not rows:
+        _resize_job((0, H, W, 0, h, w), H * W * C, h * w * C, C, mode)                 # the checks, for an empty batch too
+    out = resize_pool_u8(batch.contiguous().view(-1), rows, B * max(h, 0) * max(w, 0) * C, C, mode)
+    out = out.view(B, h, w, C)
+    return out if images.dim() == 4 else out[0]
+
+
+def scan_vertex_colors(vertices, scan_dir, width=640, height=480, trajectory_slice=slice(None, None, 10), batch=32, knn=0,
+                       **frame_colors_options):
+    """Per-vertex colours of a mesh straight from a scan directory: the reference's load_dataset (texture_map_optimization.py:48-123)
+    plus FrameColors' averaging -> (colors float32 [N, 3], count int32 [N]).  scan_dir holds color/*.jpg, depth/*.png, pose/*.txt
+    (scene_io.scan_frame_files: natural order for all three) and intrinsic/intrinsic_color.txt; every trajectory_slice-th frame is
+    used.  Per batch of `batch` frames: the files are read (scene_io.read_frames) and uploaded, the colour frames are resized to
+    (height, width) on the device (resize_u8, 'linear': the reference's cv2.resize), the depth frames must already have that size
+    (the reference asserts it), and FrameColors.add takes them with the camera of frame_intrinsics (original size: the first colour
+    frame's).  knn: FrameColors.result's fill of unseen vertices; further keywords are FrameColors'.  vertices: a CUDA tensor - the
+    mesh is the caller's business, as everywhere here."""
+    import os
+    import numpy as np
+    from . import scene_io
+    width, height, step = int(width), int(height), int(batch)
+    if step < 1:
+        raise ValueError('batch must be positive')
+    files = scene_io.scan_frame_files(scan_dir)
+    color_files, depth_files, pose_files = (files[k][trajectory_slice] for k in ('color', 'depth', 'pose'))
+    if not (len(color_files) == len(depth_files) == len(pose_files)):
+        raise ValueError('%d colour frames, %d depth frames and %d poses' % (len(color_files), len(depth_files), len(pose_files)))
+    if not color_files:
+        raise ValueError('no frames in %s' % scan_dir)
+    intrinsic = np.loadtxt(os.path.join(scan_dir, 'intrinsic', 'intrinsic_color.txt'), dtype=np.float64)
+    fc, dev = None, vertices.device
+    for p0 in range(0, len(color_files), step):
+        p1 = min(p0 + step, len(color_files))
+        color, depth = scene_io.read_frames(color_files[p0:p1], depth_files[p0:p1])
+        if tuple(depth.shape[1:]) != (height, width):
+            raise ValueError('depth frames are %d x %d, not height x width = %d x %d' % (depth.shape[1], depth.shape[2], height, width))
+        if fc is None:
+            camera = frame_intrinsics(intrinsic, int(color.shape[2]), int(color.shape[1]), width, height)
+            fc = FrameColors(vertices, camera, **frame_colors_options)
+        poses = np.stack([np.loadtxt(name, dtype=np.float64).reshape(4, 4) for name in pose_files[p0:p1]])
+        small = resize_u8(torch.from_numpy(color).to(dev), (height, width), 'linear')
+        fc.add(poses, small, torch.from_numpy(depth).to(dev), first_pose=p0)
+    return fc.result(knn=knn)
 
 
 # ------------------------------------------------------------------------------------------------- colour-map optimisation

@@ -305,6 +305,61 @@ def load_scan_config(path, scan_name, cpp_sens_reader=True):
             'colorintrinsic': intrinsic}
 
 
+# --------------------------------------------------------------------------------------------------------------- scan frames
+def _natural_key(name):
+    """Runs of digits compare as numbers, everything between them as text; the leading text run (possibly empty) keeps the two
+    kinds at the same positions of every key."""
+    import re
+    parts = re.findall(r'\d+|\D+', name)
+    if parts and parts[0][0].isdigit():
+        parts.insert(0, '')
+    return [int(p) if p[0:1].isdigit() else p for p in parts]
+
+
+def scan_frame_files(scan_dir):
+    """The frame files of an exported scan -> {'color': [...], 'depth': [...], 'pose': [...]}: color/*.jpg, depth/*.png and
+    pose/*.txt of scan_dir as full paths, each list in natural (alphanumeric) order - 2.jpg before 10.jpg - which is what the
+    reference's sorted_alphanum gives its colour and depth lists (texture_map_optimization.py:52-76).  The reference sorts its pose
+    files lexicographically (:101-102), which pairs them with the wrong frames once the ids are not zero-padded; here all three lists
+    are in natural order, so that entry i of each belongs to frame i."""
+    import os
+    out = {}
+    for kind, ext in (('color', '.jpg'), ('depth', '.png'), ('pose', '.txt')):
+        folder = os.path.join(str(scan_dir), kind)
+        names = [f for f in os.listdir(folder) if os.path.isfile(os.path.join(folder, f)) and os.path.splitext(f)[1] == ext]
+        out[kind] = [os.path.join(folder, f) for f in sorted(names, key=_natural_key)]
+    return out
+
+
+def read_frames(color_files, depth_files):
+    """Decoded frames of a scan -> (color uint8 [B, Hc, Wc, 3] RGB, depth uint16 [B, Hd, Wd]) numpy arrays, with depth == 65535 set
+    to 0 as the reference does (texture_map_optimization.py:86-92); every colour file must have one size and every depth file one
+    size.  What preprocessing.resize_u8 and FrameColors.add take after torch.from_numpy(...).to(device).  Decoding is Pillow's,
+    imported here and only here: the package does not depend on it, and a missing Pillow is an ImportError that says so."""
+    try:
+        from PIL import Image
+    except ImportError as e:
+        raise ImportError('read_frames decodes JPEG and PNG files with Pillow (PIL), which is not installed') from e
+    colors, depths = [], []
+    for name in color_files:
+        with Image.open(name) as im:
+            colors.append(np.asarray(im.convert('RGB'), dtype=np.uint8))
+    for name in depth_files:
+        with Image.open(name) as im:
+            d = np.asarray(im)
+        if d.ndim != 2 or d.min(initial=0) < 0 or d.max(initial=0) > 65535:
+            raise ValueError('%s is not a 16-bit single-channel depth image' % name)
+        d = d.astype(np.uint16)
+        d[d == 65535] = 0
+        depths.append(d)
+    for what, frames in (('colour', colors), ('depth', depths)):
+        if len({f.shape for f in frames}) > 1:
+            raise ValueError('%s frames of different sizes' % what)
+    color = np.stack(colors) if colors else np.zeros((0, 0, 0, 3), dtype=np.uint8)
+    depth = np.stack(depths) if depths else np.zeros((0, 0, 0), dtype=np.uint16)
+    return color, depth
+
+
 def write_observers(path, bits, valid_pose_ids, num_poses):
     """The per-scene cache the reference keeps under observers_per_vert/<scene>.npz (:489-507), as plain arrays instead of a pickled
     dict of lists: bits (uint32 [N, words], preprocessing.observe_vertices), valid_pose_ids (int64), num_poses.  -> path."""
