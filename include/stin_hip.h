@@ -1377,7 +1377,8 @@ int stin_frames_finish_f32(const int64_t* sum, const int32_t* count, int64_t N, 
  * preprocessing.optimize_poses_rigid refines the poses from the frames before the colours are averaged.  A contract of the
  * project's own, NOT a port of Open3D and NOT pinned against a run of it; tests/_colormap_oracle.py restates it in numpy (per pose
  * over all vertices) and agrees byte for byte.  Everything is fp64 and IEEE, the operations in the order written, nothing
- * contracted; integers where stated.  The non-rigid optimiser (per-camera warp grids) is not built.
+ * contracted; integers where stated.  The non-rigid optimiser (per-camera warp grids) builds on this one: see "Non-rigid
+ * colour-map optimisation" below.
  *
  *   inputs    vertices fp64 [N][3]; poses RT [B][12], valid [B], first_pose and the view (xv, yv, zv) as in "Frame colours"; colour
  *             frames uint8 [B][H][W][3]; ONE camera (fx, fy, cx, cy), the colour camera; bits uint32 [N][words], the FIXED
@@ -1427,6 +1428,71 @@ int stin_colormap_normal_f64(const double* vertices, int64_t N, const double* RT
                              const int32_t* images, int H, int W, const double* camera, double z_near, const uint32_t* bits,
                              int64_t words, int margin, const double* proxy, double* rows, int32_t* counts, void* workspace,
                              size_t workspace_bytes, stin_stream_t stream);
+
+/* Non-rigid colour-map optimisation: a low-resolution warp lattice per frame on top of the rigid optimiser (stin_nonrigid.hip) -
+ * Zhou & Koltun 2014, section 5, the step the reference's preprocessing/texture_map_optimization.py actually asks of Open3D
+ * (run_non_rigid_optimizer); preprocessing.optimize_poses_nonrigid.  It removes what a rigid pose cannot: rolling shutter, lens
+ * distortion, a depth/colour misregistration that differs across the frame.  A contract of the project's own, NOT a port of Open3D
+ * and NOT pinned against a run of it; tests/_nonrigid_oracle.py restates it in numpy (per pose over all vertices, every cell summed
+ * by a plain loop) and agrees byte for byte.  Everything is fp64 and IEEE, the operations in the order written, nothing contracted;
+ * integers where stated.  Inputs, images, the view and the projection (u, v) are those of "Colour-map optimisation".
+ *
+ *   lattice   step S, a positive integer in pixels of the colour frame (H, W >= 2).  Aw = ceil((W - 1) / S) + 1 and Ah = ceil((H -
+ *             1) / S) + 1 anchors at the pixel coordinates (j S, i S); cells = (Ah - 1)(Aw - 1), cell (ci, cj) numbered ci (Aw - 1) +
+ *             cj.  flow fp64 [P][Ah][Aw][2]: the x, then the y offset of every anchor in pixels; zero at the start.
+ *   cell      gu = u / (double) S, cj = min((int) floor(gu), Aw - 2), a = gu - (double) cj; likewise gv, ci, b from v.
+ *             w00 = (1 - a)(1 - b), w01 = a (1 - b), w10 = (1 - a) b, w11 = a b: the weights of the anchors (ci, cj), (ci, cj + 1),
+ *             (ci + 1, cj), (ci + 1, cj + 1) with the flows f00 .. f11.  A point on a lattice line belongs to the cell it opens
+ *             (a = 0), on the last line to the last cell (a = 1).
+ *   warp      u' = u + ((w00 f00x + w01 f01x) + (w10 f10x + w11 f11x)); v' likewise with the y offsets.
+ *   pairs     (v, p) contributes under the test of "Colour-map optimisation", word for word, on (u, v), and when in addition u', v'
+ *             are finite, margin <= u' <= W - 1 - margin and margin <= v' <= H - 1 - margin.  The visibility bits stay fixed.
+ *   sums      stin_nonrigid_accumulate_f64 = stin_frames_accumulate_f64 in bits mode with the colour frame sampled at (u', v'): the
+ *             same q, int64 sum, int32 count, optional seen; both routes, identical bits, independent of batching and order.  With a
+ *             zero flow it equals stin_frames_accumulate_f64 byte for byte (margin >= 0 here too).  The proxy is
+ *             stin_colormap_proxy_f64 on these sums, unchanged.
+ *   per pair  sI, sX, sY sampled from the (G, gx, gy, 0) images at (u', v'); I, dIdx, dIdy, r, iz, v0, v1, v2 and J[0 .. 5] exactly
+ *             as in "Colour-map optimisation", with xv, yv, zv UNWARPED; J[6 + 2 k] = dIdx w_k, J[7 + 2 k] = dIdy w_k for k = 00, 01,
+ *             10, 11: STIN_NONRIGID_LOCAL = 14 local unknowns, the pose's six and the x, y offsets of the cell's four anchors.
+ *   per (pose, cell)  one block of STIN_NONRIGID_BLOCK_DOUBLES = 120 doubles: J_i J_j for i <= j in row-major order of the upper
+ *             triangle (105), J_i r (14), r r (1); and an int32 pair count.
+ *   order     the terms of a (pose, cell) are added one after another in ASCENDING VERTEX ID, starting at +0.0: a function of the
+ *             inputs alone, not of B, first_pose, the split of the poses over launches, or the run.  A cell without pairs is 120 x
+ *             +0.0.  No float atomics.
+ *   update    on the host (preprocessing.nonrigid_update), per free, valid pose whose pair count n_p (the sum of its cells' counts)
+ *             is >= min_pairs: unknown k < 6 is the pose's, unknown 6 + 2 (i Aw + j) + c the offset c (0: x, 1: y) of anchor (i, j).
+ *             The (6 + 2 Ah Aw)^2 system A, b is assembled from the blocks, cells ascending, every entry starting at +0.0; every
+ *             anchor unknown k is regularised with wgt = (anchor_weight (double) n_p) / (double) N: A[k][k] += wgt wgt, b[k] += (wgt
+ *             wgt) f_k.  That is the shape of Open3D's non_rigid_anchor_point_weight term (default 0.316) as far as we know; it
+ *             could NOT be checked against Open3D here.  x = solve(A, -b) on the symmetrised A; E' = D(x[0:6]) E with the D of
+ *             "Colour-map optimisation"; f += x[6:].  An anchor that no pair touches keeps f = 0 through the regulariser alone; with
+ *             wgt = 0 the system is then singular and the pose does not move (COLORMAP_SINGULAR, as in the rigid update).
+ * stin_nonrigid_accumulate_f64: one batch of poses into sum / count / seen (ACCUMULATED INTO); flow: the batch's [B][Ah][Aw][2];
+ *     camera: HOST array of STIN_COLORMAP_CAMERA_DOUBLES doubles; route as for stin_frames_accumulate_f64.
+ * stin_nonrigid_keys_f64 + a sort + stin_nonrigid_normal_f64: one batch of poses -> blocks fp64 [B][cells][120], counts int32
+ *     [B][cells] (written, not accumulated).  The key kernel writes one int64 per (pose, vertex) into `keys` (at least
+ *     stin_nonrigid_workspace_bytes = 8 N B bytes, exactly): (b cells + cell) << 31 | vertex for a contributing pair, INT64_MAX
+ *     otherwise.  The CALLER sorts the B N keys ascending (any sort: the keys are distinct) and hands them to
+ *     stin_nonrigid_normal_f64 with the same poses, flow and sizes: one workgroup of 128 threads per (pose, cell) finds its run of
+ *     keys by binary search, stages up to 128 pairs' (J, r) in LDS at a time, one pair per thread, and 120 threads add one product
+ *     each over the staged pairs in order.  B cells < 2^31 - 1, H, W in [2, STIN_FRAMES_MAX_SIZE], lattice_step >= 1, margin >= 1
+ *     (>= 0 for the accumulate), z_near > 0, N < 2^31 - 1, B <= STIN_FRAMES_MAX_BATCH (STIN_E_SIZE otherwise; the workspace size is
+ *     0 then).  N = 0: blocks of +0.0.  Keys that were not made from the same inputs give unspecified sums, never a wild access.
+ * Null pointers are allowed where a count is 0.  Nothing allocates or synchronises. */
+#define STIN_NONRIGID_BLOCK_DOUBLES 120
+#define STIN_NONRIGID_LOCAL 14
+int stin_nonrigid_accumulate_f64(const double* vertices, int64_t N, const double* RT, const uint8_t* valid, int B, int64_t first_pose,
+                                 const uint8_t* color, int H, int W, const double* flow, int lattice_step, const double* camera,
+                                 double z_near, const uint32_t* bits, int64_t words, int margin, int route, int64_t* sum,
+                                 int32_t* count, uint32_t* seen, int64_t seen_words, stin_stream_t stream);
+size_t stin_nonrigid_workspace_bytes(int64_t N, int B, int H, int W, int lattice_step);
+int stin_nonrigid_keys_f64(const double* vertices, int64_t N, const double* RT, const uint8_t* valid, int B, int64_t first_pose,
+                           int H, int W, const double* flow, int lattice_step, const double* camera, double z_near,
+                           const uint32_t* bits, int64_t words, int margin, void* keys, size_t keys_bytes, stin_stream_t stream);
+int stin_nonrigid_normal_f64(const double* vertices, int64_t N, const double* RT, const uint8_t* valid, int B, int64_t first_pose,
+                             const int32_t* images, int H, int W, const double* flow, int lattice_step, const double* camera,
+                             double z_near, int margin, const double* proxy, const void* sorted_keys, size_t keys_bytes,
+                             double* blocks, int32_t* counts, stin_stream_t stream);
 
 /* Render: colour, depth and face-id images of a vertex-coloured mesh from the camera poses of a scan (stin_render.hip on stin_raster.hip) - the
  * direction the two sections above lack, mesh -> images.  It stands in for what the reference shows in an Open3D window

@@ -53,7 +53,12 @@
 * ``optimize_poses_rigid`` - the rigid optimisation the same pipeline runs with ``maximum_iteration > 0`` (Zhou & Koltun 2014): per
   iteration the proxy intensities from ``FrameColors``' sums, the photometric residual and 6-DoF Jacobian of every visible (vertex,
   pose) pair, the normal equations of every pose summed in a fixed order (``stin_colormap_*``), and one Gauss-Newton step per free pose
-  on the host (``rigid_update``, ``rigid_increment``).  A contract of this project's own, NOT pinned against Open3D; no non-rigid step.
+  on the host (``rigid_update``, ``rigid_increment``).  A contract of this project's own, NOT pinned against Open3D.
+
+* ``optimize_poses_nonrigid`` - the non-rigid optimisation, the call the reference actually makes (``run_non_rigid_optimizer``;
+  Zhou & Koltun 2014, section 5): a low-resolution warp lattice per frame beside its pose.  The normal equations are summed per
+  (pose, lattice cell) in ascending vertex id (``stin_nonrigid_*``: keys, a sort, one workgroup per cell), the colours are sampled at
+  the warped positions, and the host solves one (6 + 2 anchors) system per free pose (``nonrigid_update``).  NOT pinned against Open3D.
 
 * ``knn`` / ``fill_unseen_colors`` / ``knn_inpaint`` - exact fp64 k nearest neighbours with a validity mask on the points
   (``stin_knn_f64``: ``nearest``'s tiled brute force with a k-list per query in registers) and the mean of the neighbours' rows
@@ -1550,8 +1555,8 @@ class FrameColors:
 
     Not Open3D's result bit for bit and not pinned against a run of it.  Frames arrive here decoded and at their final size: resize_u8
     brings colour frames to the depth size on the device, scene_io.read_frames reads a scan's files, and scan_vertex_colors does
-    both from a scan directory.  Out of scope: Open3D's non-rigid optimisation (its rigid one, iterations > 0, is optimize_poses_rigid: run it
-    first and average with the poses it returns), clipping at the near plane, and a CPU fallback.  Unseen vertices get `fill` and count 0, or, with result(knn=k), the mean colour of their k nearest coloured
+    both from a scan directory.  Open3D's optimisers are optimize_poses_rigid (iterations > 0) and optimize_poses_nonrigid (warp
+    lattices per frame): run one first and average with what it returns.  Out of scope: clipping at the near plane, and a CPU fallback.  Unseen vertices get `fill` and count 0, or, with result(knn=k), the mean colour of their k nearest coloured
     vertices (fill_unseen_colors: exact fp64 k-NN with a stated tie rule; k = 3 is Open3D's default to our knowledge, which - like
     its tie handling - could not be checked against a run of it)."""
 
@@ -1593,13 +1598,18 @@ class FrameColors:
                    'stin_frames_depth_edges_u16')
         return edge
 
-    def add(self, poses, color, depth=None, bits=None, first_pose=0, _route=None):
+    def add(self, poses, color, depth=None, bits=None, first_pose=0, _route=None, flow=None, lattice_step=None):
         """One batch: poses [B, 4, 4] camera-to-world (array or tensor; inverted on the host), color uint8 [B, Hc, Wc, 3] RGB and
         either depth uint16 [B, Hd, Wd] or bits (observe_vertices' uint32 [N, words], indexed by first_pose + b) - CUDA tensors.
         first_pose: the scan-wide id of the batch's first pose (for bits and seen).  Batches arrive in any order and any size.
-        _route (tests): STIN_FRAMES_ROUTE_OWNER / _SPLIT instead of the host's choice from N and B."""
+        _route (tests): STIN_FRAMES_ROUTE_OWNER / _SPLIT instead of the host's choice from N and B.
+        flow, lattice_step: the warp lattices of optimize_poses_nonrigid for these poses, float64 [B, Ah, Aw, 2] (array or tensor),
+        and their step - the colour frame is then sampled at the warped position (stin_nonrigid_accumulate_f64).  Bits mode only:
+        the depth test knows no warp."""
         if (depth is None) == (bits is None):
             raise ValueError('exactly one of depth and bits must be given')
+        if flow is not None and depth is not None:
+            raise ValueError('flow needs bits mode: the depth test knows no warp (vertex_colors_from_frames makes the two passes)')
         c = _frames_u(color, torch.uint8, (3,), 'color')
         RT, valid = pose_extrinsics(poses)
         B, n, dev, first = int(RT.shape[0]), int(self.vertices.shape[0]), self.vertices.device, int(first_pose)
@@ -1623,6 +1633,8 @@ class FrameColors:
             b, words = bits.contiguous(), int(bits.shape[1])
             if words < (first + B + 31) // 32:
                 raise ValueError('bits has %d words per vertex, poses up to %d need %d' % (words, first + B, (first + B + 31) // 32))
+        if flow is not None:
+            flow, lattice_step = _nonrigid_flow(flow, lattice_step, B, int(c.shape[1]), int(c.shape[2]))
         if B == 0 or n == 0:
             return self
         if 0 in c.shape or (d is not None and 0 in d.shape):
@@ -1630,14 +1642,28 @@ class FrameColors:
         if d is not None:
             edge = self.depth_edges(d)
         rt_d, valid_d = torch.from_numpy(RT).to(dev), torch.from_numpy(valid).to(dev)
-        return self._add_extrinsics(rt_d, valid_d, c, first, depth=d, edge=edge, bits=b, seen=self.seen, route=_route)
+        if flow is not None:
+            flow = flow.to(dev)
+        return self._add_extrinsics(rt_d, valid_d, c, first, depth=d, edge=edge, bits=b, seen=self.seen, route=_route, flow=flow,
+                                    lattice_step=lattice_step)
 
-    def _add_extrinsics(self, rt_d, valid_d, color, first_pose, depth=None, edge=None, bits=None, seen=None, route=None):
+    def _add_extrinsics(self, rt_d, valid_d, color, first_pose, depth=None, edge=None, bits=None, seen=None, route=None, flow=None,
+                        lattice_step=None):
         """The launch under add(), for extrinsics that are already on the device (rt_d fp64 [B, 12], valid_d uint8 [B],
         pose_extrinsics' rows) and arguments as add() has checked them; optimize_poses_rigid repeats it in bits mode at the poses of
-        every iteration."""
+        every iteration; flow (fp64 [B, Ah, Aw, 2] on the device, bits mode): optimize_poses_nonrigid's warped pass."""
         n, B = int(self.vertices.shape[0]), int(rt_d.shape[0])
         if B == 0 or n == 0:
+            return self
+        route = _lib.CONSTANTS['STIN_FRAMES_ROUTE_AUTO'] if route is None else int(route)
+        if flow is not None:
+            cam = (ctypes.c_double * _lib.CONSTANTS['STIN_COLORMAP_CAMERA_DOUBLES'])(*self.color_camera)
+            _lib.check(_lib.load().stin_nonrigid_accumulate_f64(_ptr(self.vertices), n, _ptr(rt_d), _ptr(valid_d), B, int(first_pose),
+                                                                _ptr(color), int(color.shape[1]), int(color.shape[2]), _ptr(flow),
+                                                                int(lattice_step), cam, self.z_near, _ptr(bits), int(bits.shape[1]),
+                                                                self.margin, route, _ptr(self.sum), _ptr(self.count), _ptr(seen),
+                                                                0 if seen is None else int(seen.shape[1]), _stream(self.vertices)),
+                       'stin_nonrigid_accumulate_f64')
             return self
         cameras = (ctypes.c_double * _lib.CONSTANTS['STIN_FRAMES_CAMERA_DOUBLES'])(*(self.color_camera + self.depth_camera))
         params = (ctypes.c_double * _lib.CONSTANTS['STIN_FRAMES_PARAM_DOUBLES'])(self.depth_scale, self.depth_trunc, self.max_depth,
@@ -1646,8 +1672,7 @@ class FrameColors:
         _lib.check(_lib.load().stin_frames_accumulate_f64(_ptr(self.vertices), n, _ptr(rt_d), _ptr(valid_d), B, int(first_pose),
                                                           _ptr(color), int(color.shape[1]), int(color.shape[2]), _ptr(depth), _ptr(edge),
                                                           Hd, Wd, cameras, params, _ptr(bits), 0 if bits is None else int(bits.shape[1]),
-                                                          self.margin,
-                                                          _lib.CONSTANTS['STIN_FRAMES_ROUTE_AUTO'] if route is None else int(route),
+                                                          self.margin, route,
                                                           _ptr(self.sum), _ptr(self.count), _ptr(seen),
                                                           0 if seen is None else int(seen.shape[1]), _stream(self.vertices)),
                    'stin_frames_accumulate_f64')
@@ -1673,14 +1698,18 @@ class FrameColors:
 
 
 def vertex_colors_from_frames(vertices, poses, color, depth=None, bits=None, batch=64, color_camera=None, depth_camera=None,
-                              fill=(0, 0, 0), return_seen=False, _route=None, knn=0, **params):
+                              fill=(0, 0, 0), return_seen=False, _route=None, knn=0, flow=None, lattice_step=None, **params):
     """FrameColors for frames that are all resident: poses [P, 4, 4], color uint8 [P, Hc, Wc, 3], depth uint16 [P, Hd, Wd] or bits
     (observe_vertices), added in batches of `batch` poses (the result does not depend on it) -> (colors float32 [N, 3], count int32
     [N]), with return_seen=True also seen uint32 [N, ceil(P / 32)].  color_camera is required; knn = k > 0 fills the vertices no
     frame coloured from their k nearest coloured ones (FrameColors.result); the other keywords are FrameColors'.
     Frames of another size go through resize_u8 first; scan_vertex_colors reads, resizes and adds a scan directory batch by batch.
-    Out of scope, as there: the non-rigid optimisation (the rigid one is optimize_poses_rigid, whose poses go in here), near-plane
-    clipping, a CPU fallback."""
+    flow float64 [P, Ah, Aw, 2] and lattice_step: the warp lattices that optimize_poses_nonrigid returns with its poses - the colour
+    frames are sampled at the warped positions.  In bits mode that is one warped pass; in depth mode one UNWARPED pass establishes
+    which frames see which vertex (the depth test knows no warp, as in the optimiser) and a second, warped pass in bits mode fills
+    fresh sums under that visibility.  Without flow every path is what it was, to the byte.
+    Out of scope, as there: near-plane clipping, a CPU fallback (the optimisers are optimize_poses_rigid and
+    optimize_poses_nonrigid, whose poses go in here)."""
     if color_camera is None:
         raise ValueError('color_camera = (fx, fy, cx, cy) is required')
     _frames_u(color, torch.uint8, (3,), 'color')
@@ -1689,12 +1718,22 @@ def vertex_colors_from_frames(vertices, poses, color, depth=None, bits=None, bat
         raise ValueError('batch must be positive')
     if len(poses) != P:
         raise ValueError('%d poses but %d colour frames' % (len(poses), P))
-    fc = FrameColors(vertices, color_camera, depth_camera, num_poses=P if return_seen else None, **params)
+    two_passes = flow is not None and depth is not None
+    fc = FrameColors(vertices, color_camera, depth_camera, num_poses=P if return_seen or two_passes else None, **params)
     if (depth is None) == (bits is None):
         raise ValueError('exactly one of depth and bits must be given')
+    if flow is not None:
+        flow, lattice_step = _nonrigid_flow(flow, lattice_step, P, int(color.shape[1]), int(color.shape[2]))
     for p0 in range(0, P, step):
         p1 = min(p0 + step, P)
-        fc.add(poses[p0:p1], color[p0:p1], None if depth is None else depth[p0:p1], bits, first_pose=p0, _route=_route)
+        fc.add(poses[p0:p1], color[p0:p1], None if depth is None else depth[p0:p1], bits, first_pose=p0, _route=_route,
+               flow=None if flow is None or two_passes else flow[p0:p1], lattice_step=lattice_step)
+    if two_passes:                                                     # the visibility of the unwarped pass, the colours of a warped one
+        bits = fc.seen
+        fc = FrameColors(vertices, color_camera, depth_camera, num_poses=P if return_seen else None, **params)
+        for p0 in range(0, P, step):
+            p1 = min(p0 + step, P)
+            fc.add(poses[p0:p1], color[p0:p1], bits=bits, first_pose=p0, _route=_route, flow=flow[p0:p1], lattice_step=lattice_step)
     colors, count = fc.result(fill, knn=knn)
     return (colors, count, fc.seen) if return_seen else (colors, count)
 
@@ -1837,7 +1876,7 @@ def resize_u8(images, size, mode='linear'):
 
 
 def scan_vertex_colors(vertices, scan_dir, width=640, height=480, trajectory_slice=slice(None, None, 10), batch=32, knn=0,
-                       **frame_colors_options):
+                       nonrigid_iterations=0, **frame_colors_options):
     """Per-vertex colours of a mesh straight from a scan directory: the reference's load_dataset (texture_map_optimization.py:48-123)
     plus FrameColors' averaging -> (colors float32 [N, 3], count int32 [N]).  scan_dir holds color/*.jpg, depth/*.png, pose/*.txt
     (scene_io.scan_frame_files: natural order for all three) and intrinsic/intrinsic_color.txt; every trajectory_slice-th frame is
@@ -1845,7 +1884,11 @@ def scan_vertex_colors(vertices, scan_dir, width=640, height=480, trajectory_sli
     (height, width) on the device (resize_u8, 'linear': the reference's cv2.resize), the depth frames must already have that size
     (the reference asserts it), and FrameColors.add takes them with the camera of frame_intrinsics (original size: the first colour
     frame's).  knn: FrameColors.result's fill of unseen vertices; further keywords are FrameColors'.  vertices: a CUDA tensor - the
-    mesh is the caller's business, as everywhere here."""
+    mesh is the caller's business, as everywhere here.
+    nonrigid_iterations = k > 0: what the reference asks of Open3D (run_non_rigid_optimizer) - the frames are then all kept on the
+    device (0.9 MB per 480 x 640 colour frame, 0.6 MB per depth frame, 4.9 MB of gradient images), optimize_poses_nonrigid runs k
+    iterations on them in depth mode at its defaults, and the colours are averaged with its poses and warp lattices
+    (vertex_colors_from_frames).  0, the default: no optimisation, batch by batch, as before."""
     import os
     import numpy as np
     from . import scene_io
@@ -1860,6 +1903,8 @@ def scan_vertex_colors(vertices, scan_dir, width=640, height=480, trajectory_sli
         raise ValueError('no frames in %s' % scan_dir)
     intrinsic = np.loadtxt(os.path.join(scan_dir, 'intrinsic', 'intrinsic_color.txt'), dtype=np.float64)
     fc, dev = None, vertices.device
+    resident = int(nonrigid_iterations) > 0
+    kept = ([], [], [])
     for p0 in range(0, len(color_files), step):
         p1 = min(p0 + step, len(color_files))
         color, depth = scene_io.read_frames(color_files[p0:p1], depth_files[p0:p1])
@@ -1870,7 +1915,17 @@ def scan_vertex_colors(vertices, scan_dir, width=640, height=480, trajectory_sli
             fc = FrameColors(vertices, camera, **frame_colors_options)
         poses = np.stack([np.loadtxt(name, dtype=np.float64).reshape(4, 4) for name in pose_files[p0:p1]])
         small = resize_u8(torch.from_numpy(color).to(dev), (height, width), 'linear')
+        if resident:
+            for k, x in zip(kept, (poses, small, torch.from_numpy(depth).to(dev))):
+                k.append(x)
+            continue
         fc.add(poses, small, torch.from_numpy(depth).to(dev), first_pose=p0)
+    if resident:
+        poses, small, depth = np.concatenate(kept[0]), torch.cat(kept[1]), torch.cat(kept[2])
+        poses, flow, info = optimize_poses_nonrigid(vertices, poses, small, depth=depth, color_camera=camera,
+                                                    iterations=int(nonrigid_iterations), batch=step, **frame_colors_options)
+        return vertex_colors_from_frames(vertices, poses, small, depth=depth, batch=step, color_camera=camera, knn=knn, flow=flow,
+                                         lattice_step=info['lattice_step'], **frame_colors_options)
     return fc.result(knn=knn)
 
 
@@ -1957,39 +2012,16 @@ def _colormap_normal(v64, rt_d, valid_d, first_pose, images, camera, z_near, bit
                                                     _ptr(counts), _ptr(ws), int(ws.numel()), _stream(v64)), 'stin_colormap_normal_f64')
 
 
-def optimize_poses_rigid(vertices, poses, color, depth=None, bits=None, *, color_camera=None, depth_camera=None, iterations=30,
-                         free=None, min_pairs=16, batch=64, **params):
-    """The rigid colour-map optimisation (Zhou & Koltun 2014; what Open3D's colour-map pipeline does with maximum_iteration > 0
-    before it averages colours): refine the camera poses photometrically, so that the frames agree on the mesh's intensities, on the
-    GPU (csrc/stin_colormap.hip).  vertices [N, >= 3] float, color uint8 [P, H, W, 3] and either depth uint16 [P, Hd, Wd] or bits
-    (observe_vertices' uint32 [N, words]) - CUDA tensors, checked as FrameColors.add checks them; poses [P, 4, 4] camera-to-world
-    (array or tensor); color_camera (required), depth_camera and **params are FrameColors'; margin must be >= 1.
-    -> (poses float64 [P, 4, 4] camera-to-world numpy, info): info['residual'] float64 and info['pairs'] int64, both
-    [iterations + 1, P] - the sum of squared intensity residuals and the number of (vertex, pose) pairs of every pose before each
-    update and after the last; info['status'] int32 [P], bits COLORMAP_NOT_FREE, COLORMAP_INVALID, COLORMAP_FEW_PAIRS (fewer than
-    min_pairs pairs in some iteration: not moved in it), COLORMAP_SINGULAR (its 6 x 6 could not be solved in some iteration).
-
-    Visibility is established ONCE, at the given poses: in depth mode by one FrameColors pass whose `seen` becomes the bits, in
-    bits mode by the caller's bits; only the projection moves afterwards.  Per iteration (the count is fixed, there is no early
-    stop: the result is a pure function of the inputs): the proxy intensity of every vertex from the integer colour sums at the
-    current poses; per pair the residual between the frame's intensity and the proxy and its Jacobian for a rigid increment of the
-    extrinsic; per pose the 6 x 6 normal equations, summed in a fixed order; the P x 29 numbers are read back (the only
-    synchronisation) and every free, valid pose with at least min_pairs pairs takes one Gauss-Newton step on the host.  The contract
-    is in include/stin_hip.h ("Colour-map optimisation"); the test suite restates it in numpy and this reproduces it byte for byte.
-    free: bool [P], default all.  A held pose takes part in the proxy but never moves - anchor keyframes with it: with every pose
-    free the cameras settle on a consensus, which need not be the truth.  A pose that never moved (held, invalid, too few pairs)
-    comes back exactly as given.  Memory: the intensity and gradient images of ALL P frames are built once, 16 bytes per pixel
-    (4.9 MB per 480 x 640 frame); the rows are computed in batches of `batch` poses (the result does not depend on it).
-
-    The recipe: poses, info = optimize_poses_rigid(vertices, poses, color, depth, color_camera=cam); then
-    vertex_colors_from_frames(vertices, poses, color, depth, color_camera=cam) with the returned poses.
-    Not Open3D's result and not pinned against a run of it; the non-rigid optimisation (per-camera warp grids) is not built."""
+def _colormap_inputs(vertices, poses, color, depth, bits, color_camera, depth_camera, iterations, free, batch, params):
+    """The argument checks that the colour-map optimisers share, and the visibility both keep fixed: in depth mode one FrameColors
+    pass at the given poses whose `seen` becomes the bits, in bits mode the caller's bits.
+    -> (fc, color, bits, free bool [P], RT, valid, poses float64 [P, 4, 4], status int32 [P], batch, margin)"""
     import numpy as np
     if color_camera is None:
         raise ValueError('color_camera = (fx, fy, cx, cy) is required')
     if (depth is None) == (bits is None):
         raise ValueError('exactly one of depth and bits must be given')
-    margin, iters, step, min_pairs = int(params.get('margin', 10)), int(iterations), int(batch), int(min_pairs)
+    margin, iters, step = int(params.get('margin', 10)), int(iterations), int(batch)
     if margin < 1:
         raise ValueError('margin must be >= 1: the gradient is sampled like the colour')
     if iters < 0 or step < 1:
@@ -2022,14 +2054,50 @@ def optimize_poses_rigid(vertices, poses, color, depth=None, bits=None, *, color
     RT, valid = pose_extrinsics(poses)
     given = np.array(poses.detach().cpu().numpy() if torch.is_tensor(poses) else poses, dtype=np.float64).reshape(P, 4, 4)
     status = np.where(free, 0, COLORMAP_NOT_FREE).astype(np.int32) | np.where(valid != 0, 0, COLORMAP_INVALID).astype(np.int32)
-    residual, pairs = np.zeros((iters + 1, P), dtype=np.float64), np.zeros((iters + 1, P), dtype=np.int64)
-    info = dict(residual=residual, pairs=pairs, status=status)
-    if P == 0:
-        return given, info
     if depth is not None:                                              # visibility, once, at the given poses
         for p0 in range(0, P, step):
             fc.add(given[p0:p0 + step], c[p0:p0 + step], depth=d[p0:p0 + step], first_pose=p0)
         vis = fc.seen
+    return fc, c, vis, free, RT, valid, given, status, step, margin
+
+
+def optimize_poses_rigid(vertices, poses, color, depth=None, bits=None, *, color_camera=None, depth_camera=None, iterations=30,
+                         free=None, min_pairs=16, batch=64, **params):
+    """The rigid colour-map optimisation (Zhou & Koltun 2014; what Open3D's colour-map pipeline does with maximum_iteration > 0
+    before it averages colours): refine the camera poses photometrically, so that the frames agree on the mesh's intensities, on the
+    GPU (csrc/stin_colormap.hip).  vertices [N, >= 3] float, color uint8 [P, H, W, 3] and either depth uint16 [P, Hd, Wd] or bits
+    (observe_vertices' uint32 [N, words]) - CUDA tensors, checked as FrameColors.add checks them; poses [P, 4, 4] camera-to-world
+    (array or tensor); color_camera (required), depth_camera and **params are FrameColors'; margin must be >= 1.
+    -> (poses float64 [P, 4, 4] camera-to-world numpy, info): info['residual'] float64 and info['pairs'] int64, both
+    [iterations + 1, P] - the sum of squared intensity residuals and the number of (vertex, pose) pairs of every pose before each
+    update and after the last; info['status'] int32 [P], bits COLORMAP_NOT_FREE, COLORMAP_INVALID, COLORMAP_FEW_PAIRS (fewer than
+    min_pairs pairs in some iteration: not moved in it), COLORMAP_SINGULAR (its 6 x 6 could not be solved in some iteration).
+
+    Visibility is established ONCE, at the given poses: in depth mode by one FrameColors pass whose `seen` becomes the bits, in
+    bits mode by the caller's bits; only the projection moves afterwards.  Per iteration (the count is fixed, there is no early
+    stop: the result is a pure function of the inputs): the proxy intensity of every vertex from the integer colour sums at the
+    current poses; per pair the residual between the frame's intensity and the proxy and its Jacobian for a rigid increment of the
+    extrinsic; per pose the 6 x 6 normal equations, summed in a fixed order; the P x 29 numbers are read back (the only
+    synchronisation) and every free, valid pose with at least min_pairs pairs takes one Gauss-Newton step on the host.  The contract
+    is in include/stin_hip.h ("Colour-map optimisation"); the test suite restates it in numpy and this reproduces it byte for byte.
+    free: bool [P], default all.  A held pose takes part in the proxy but never moves - anchor keyframes with it: with every pose
+    free the cameras settle on a consensus, which need not be the truth.  A pose that never moved (held, invalid, too few pairs)
+    comes back exactly as given.  Memory: the intensity and gradient images of ALL P frames are built once, 16 bytes per pixel
+    (4.9 MB per 480 x 640 frame); the rows are computed in batches of `batch` poses (the result does not depend on it).
+
+    The recipe: poses, info = optimize_poses_rigid(vertices, poses, color, depth, color_camera=cam); then
+    vertex_colors_from_frames(vertices, poses, color, depth, color_camera=cam) with the returned poses.
+    Not Open3D's result and not pinned against a run of it; the non-rigid optimisation (per-camera warp grids) is
+    optimize_poses_nonrigid, which runs this loop first when asked to."""
+    import numpy as np
+    fc, c, vis, free, RT, valid, given, status, step, margin = _colormap_inputs(vertices, poses, color, depth, bits, color_camera,
+                                                                                depth_camera, iterations, free, batch, params)
+    P, iters, min_pairs = len(given), int(iterations), int(min_pairs)
+    v, n, dev = fc.vertices, int(fc.vertices.shape[0]), fc.vertices.device
+    residual, pairs = np.zeros((iters + 1, P), dtype=np.float64), np.zeros((iters + 1, P), dtype=np.int64)
+    info = dict(residual=residual, pairs=pairs, status=status)
+    if P == 0:
+        return given, info
     H, W = int(c.shape[1]), int(c.shape[2])
     images = torch.empty(P, H, W, 4, dtype=torch.int32, device=dev)
     for p0 in range(0, P, step):
@@ -2061,3 +2129,208 @@ def optimize_poses_rigid(vertices, poses, color, depth=None, bits=None, *, color
     for p in np.flatnonzero(ever):
         out[p] = np.linalg.inv(E[p])
     return out, info
+
+
+# --------------------------------------------------------------------------------------- non-rigid colour-map optimisation
+def nonrigid_lattice(height, width, lattice_step):
+    """-> (Ah, Aw): the anchors of a warp lattice of step lattice_step over a height x width frame, at the pixels (j S, i S):
+    ceil((height - 1) / S) + 1 rows and ceil((width - 1) / S) + 1 columns (include/stin_hip.h, "Non-rigid colour-map optimisation")."""
+    S = int(lattice_step)
+    if S < 1:
+        raise ValueError('lattice_step must be >= 1')
+    if int(height) < 2 or int(width) < 2:
+        raise ValueError('a warp lattice needs frames of at least 2 x 2 pixels')
+    return -(-(int(height) - 1) // S) + 1, -(-(int(width) - 1) // S) + 1
+
+
+def _nonrigid_flow(flow, lattice_step, P, H, W):
+    """flow as a caller gives it (array or tensor) -> (float64 tensor [P, Ah, Aw, 2], contiguous, where it was; lattice_step)"""
+    import numpy as np
+    if lattice_step is None:
+        raise ValueError('flow needs its lattice_step')
+    Ah, Aw = nonrigid_lattice(H, W, lattice_step)
+    t = flow if torch.is_tensor(flow) else torch.from_numpy(np.ascontiguousarray(flow))
+    if t.dtype != torch.float64 or tuple(t.shape) != (P, Ah, Aw, 2):
+        raise ValueError('flow must be float64 [%d, %d, %d, 2] for %d frames of %d x %d and lattice_step %d'
+                         % (P, Ah, Aw, P, H, W, int(lattice_step)))
+    return t.contiguous(), int(lattice_step)
+
+
+_NONRIGID_TRI = tuple((i, j) for i in range(14) for j in range(i, 14))
+
+
+def nonrigid_update(E, flow, valid, free, blocks, counts, n_vertices, anchor_weight, min_pairs, status):
+    """One Gauss-Newton update of poses and warp lattices on the host: E float64 [P, 4, 4] extrinsics and flow float64
+    [P, Ah, Aw, 2] (both changed in place), blocks [P, cells, 120] and counts [P, cells] as stin_nonrigid_normal_f64 writes them,
+    status int32 [P] (COLORMAP_FEW_PAIRS / COLORMAP_SINGULAR are OR-ed in).  Per free, valid pose with n_p = counts.sum() >=
+    min_pairs: the (6 + 2 Ah Aw)^2 system from the blocks, cells ascending; every anchor unknown regularised with wgt =
+    anchor_weight n_p / n_vertices (A[k][k] += wgt^2, b[k] += wgt^2 f_k); x = np.linalg.solve(A, -b); E' = D(x[:6]) E, flow += x[6:].
+    A pose whose system is singular or whose x is not finite does not move.  -> bool [P]: which poses moved."""
+    import numpy as np
+    P, Ah, Aw = (int(s) for s in flow.shape[:3])
+    n = 6 + 2 * Ah * Aw
+    # the unknowns of every cell's 14 local ones, ascending within a cell (so that the triangle of a block lands in the upper triangle),
+    # and from them the targets of every block entry, cell-major: np.add.at adds in the order of its index array - cells ascending
+    ti, tj = (np.array(k) for k in zip(*_NONRIGID_TRI))
+    cell = np.arange((Ah - 1) * (Aw - 1))
+    anchors = ((cell // (Aw - 1)) * Aw + cell % (Aw - 1))[:, None] + np.array([0, 1, Aw, Aw + 1])
+    g = np.concatenate([np.broadcast_to(np.arange(6), (len(cell), 6)), 6 + (2 * anchors[:, :, None] + np.arange(2)).reshape(len(cell), 8)], axis=1)
+    gi, gj, gb = g[:, ti].reshape(-1), g[:, tj].reshape(-1), g.reshape(-1)
+    moved = np.zeros(P, dtype=bool)
+    for p in range(P):
+        if not (free[p] and valid[p]):
+            continue
+        n_p = int(counts[p].sum())
+        if n_p < min_pairs:
+            status[p] |= COLORMAP_FEW_PAIRS
+            continue
+        A, b = np.zeros((n, n), dtype=np.float64), np.zeros(n, dtype=np.float64)
+        np.add.at(A, (gi, gj), np.ascontiguousarray(blocks[p, :, :105]).reshape(-1))
+        np.add.at(b, gb, np.ascontiguousarray(blocks[p, :, 105:119]).reshape(-1))
+        with np.errstate(all='ignore'):
+            wgt = (np.float64(anchor_weight) * np.float64(n_p)) / np.float64(n_vertices)
+        anchor = np.arange(6, n)
+        A[anchor, anchor] += wgt * wgt
+        b[6:] += (wgt * wgt) * flow[p].reshape(-1)
+        lower = A.T.copy()                                              # A is upper triangular so far: mirror it
+        np.fill_diagonal(lower, 0.0)
+        A += lower
+        try:
+            x = np.linalg.solve(A, -b)
+        except np.linalg.LinAlgError:
+            x = None
+        if x is None or not np.isfinite(x).all():
+            status[p] |= COLORMAP_SINGULAR
+            continue
+        E[p] = rigid_increment(x[:6]) @ np.ascontiguousarray(E[p])
+        flow[p] += x[6:].reshape(Ah, Aw, 2)
+        moved[p] = True
+    return moved
+
+
+def _nonrigid_workspace(n, batch, H, W, lattice_step, device):
+    """The key buffer of one batch: int64 [batch * n] on the device (stin_nonrigid_workspace_bytes)."""
+    ws_bytes = _lib.load().stin_nonrigid_workspace_bytes(n, batch, H, W, int(lattice_step))
+    if ws_bytes == 0:
+        raise ValueError('%d vertices, batches of %d poses and a lattice of step %d over %d x %d frames are outside what the '
+                         'non-rigid kernels support' % (n, batch, int(lattice_step), H, W))
+    return torch.empty(ws_bytes // 8, dtype=torch.int64, device=device)
+
+
+def _nonrigid_keys(v64, rt_d, valid_d, first_pose, H, W, flow_d, lattice_step, camera, z_near, bits, margin, keys):
+    """One batch of poses -> keys int64 [B * N] (the head of `keys`, written in place): stin_nonrigid_keys_f64 on device arrays."""
+    n, B = int(v64.shape[0]), int(rt_d.shape[0])
+    cam = (ctypes.c_double * _lib.CONSTANTS['STIN_COLORMAP_CAMERA_DOUBLES'])(*camera)
+    _lib.check(_lib.load().stin_nonrigid_keys_f64(_ptr(v64), n, _ptr(rt_d), _ptr(valid_d), B, int(first_pose), int(H), int(W),
+                                                  _ptr(flow_d), int(lattice_step), cam, float(z_near), _ptr(bits) if n else None,
+                                                  int(bits.shape[1]), int(margin), _ptr(keys), int(keys.numel()) * 8, _stream(v64)),
+               'stin_nonrigid_keys_f64')
+    return keys[:B * n]
+
+
+def _nonrigid_blocks(v64, rt_d, valid_d, first_pose, images, flow_d, lattice_step, camera, z_near, margin, proxy, ordered, blocks, counts):
+    """One batch of poses and its SORTED keys -> blocks fp64 [B, cells, 120], counts int32 [B, cells] (written in place)."""
+    n, B = int(v64.shape[0]), int(rt_d.shape[0])
+    cam = (ctypes.c_double * _lib.CONSTANTS['STIN_COLORMAP_CAMERA_DOUBLES'])(*camera)
+    _lib.check(_lib.load().stin_nonrigid_normal_f64(_ptr(v64), n, _ptr(rt_d), _ptr(valid_d), B, int(first_pose), _ptr(images),
+                                                    int(images.shape[1]), int(images.shape[2]), _ptr(flow_d), int(lattice_step), cam,
+                                                    float(z_near), int(margin), _ptr(proxy), _ptr(ordered), int(ordered.numel()) * 8,
+                                                    _ptr(blocks), _ptr(counts), _stream(v64)), 'stin_nonrigid_normal_f64')
+
+
+def _nonrigid_normal(v64, rt_d, valid_d, first_pose, images, flow_d, lattice_step, camera, z_near, bits, margin, proxy, blocks, counts, keys):
+    """One batch of poses -> blocks fp64 [B, cells, 120], counts int32 [B, cells] (written in place): the key kernel, the sort of the
+    B N keys (rocPRIM through torch.sort), and one workgroup per (pose, cell) over its run of sorted keys."""
+    made = _nonrigid_keys(v64, rt_d, valid_d, first_pose, images.shape[1], images.shape[2], flow_d, lattice_step, camera, z_near, bits,
+                          margin, keys)
+    ordered = torch.sort(made)[0] if made.numel() else keys
+    _nonrigid_blocks(v64, rt_d, valid_d, first_pose, images, flow_d, lattice_step, camera, z_near, margin, proxy, ordered, blocks, counts)
+
+
+def optimize_poses_nonrigid(vertices, poses, color, depth=None, bits=None, *, color_camera=None, depth_camera=None, iterations=30,
+                            rigid_iterations=0, lattice_step=None, vertical_anchors=16, anchor_weight=0.316, free=None, min_pairs=16,
+                            batch=64, **params):
+    """The non-rigid colour-map optimisation (Zhou & Koltun 2014, section 5; Open3D's run_non_rigid_optimizer, the call the
+    reference's texture_map_optimization.py makes): beside its pose every frame gets a low-resolution warp lattice - an (x, y) offset
+    in pixels at anchors every lattice_step pixels, interpolated bilinearly - and both are refined photometrically on the GPU
+    (csrc/stin_nonrigid.hip).  The lattice absorbs what no rigid pose can: rolling shutter, lens distortion, a depth/colour
+    misregistration that differs across the frame.  Arguments as optimize_poses_rigid's; margin must be >= 1.
+    -> (poses float64 [P, 4, 4] camera-to-world numpy, flow float64 [P, Ah, Aw, 2] numpy, info).  info['residual'], info['pairs'],
+    info['status'] as the rigid optimiser's; info['flow_norm'] float64 [iterations + 1, P]: the largest |offset| of every pose's
+    lattice, in pixels, beside each residual; info['lattice_step']; info['rigid']: the rigid loop's info when rigid_iterations > 0.
+
+    The iteration is the rigid one's: visibility is established ONCE, at the given poses (depth mode: one unwarped FrameColors pass;
+    the depth test knows no warp), the iteration count is fixed, there is one read-back per iteration (P x cells x 121 numbers), and
+    the result is a pure function of the inputs, independent of `batch`.  Per iteration: the colour sums at the warped positions,
+    the proxy, per (pose, lattice cell) the normal equations of the 14 unknowns a pair touches - the pose's six and its cell's four
+    anchors - summed in ascending vertex id, and on the host one Gauss-Newton step per free, valid pose with at least min_pairs
+    pairs (nonrigid_update).  Every anchor is pulled towards zero with weight anchor_weight n_p / N (n_p pairs of the pose, N
+    vertices): the shape of Open3D's non_rigid_anchor_point_weight term as far as we know, 0.316 being its default; NOT checked
+    against Open3D.  A held pose takes part in the proxy, never moves and keeps a zero flow.
+    rigid_iterations = k > 0: optimize_poses_rigid runs k iterations first, under the same visibility, and this loop starts from its
+    poses.  lattice_step: default ceil((H - 1) / (vertical_anchors - 1)) - 32 pixels at 480 rows, 16 x 21 anchors and 678 unknowns
+    per frame, the size the paper uses.  A finer lattice is allowed; the host solve is dense, O((6 + 2 Ah Aw)^3) per free pose and
+    iteration (678 unknowns: about 0.1 Gflop and 3.7 MB; step 8 at 480 x 640: 9 888 unknowns, 0.3 Tflop and 0.8 GB per pose).
+
+    The recipe: poses, flow, info = optimize_poses_nonrigid(vertices, poses, color, depth, color_camera=cam); then
+    vertex_colors_from_frames(vertices, poses, color, depth, color_camera=cam, flow=flow, lattice_step=info['lattice_step']).
+    The contract is in include/stin_hip.h ("Non-rigid colour-map optimisation"); the test suite restates it in numpy and this
+    reproduces it byte for byte.  Not Open3D's result and not pinned against a run of it; warp-aware depth visibility and a solve
+    on the device are not built."""
+    import numpy as np
+    if int(rigid_iterations) < 0 or int(vertical_anchors) < 2:
+        raise ValueError('rigid_iterations must be >= 0 and vertical_anchors >= 2')
+    if lattice_step is not None and int(lattice_step) < 1:
+        raise ValueError('lattice_step must be >= 1')
+    fc, c, vis, free, RT, valid, given, status, step, margin = _colormap_inputs(vertices, poses, color, depth, bits, color_camera,
+                                                                                depth_camera, iterations, free, batch, params)
+    P, iters, min_pairs = len(given), int(iterations), int(min_pairs)
+    v, n, dev = fc.vertices, int(fc.vertices.shape[0]), fc.vertices.device
+    H, W = int(c.shape[1]), int(c.shape[2])
+    S = -(-(H - 1) // (int(vertical_anchors) - 1)) if lattice_step is None else int(lattice_step)
+    Ah, Aw = nonrigid_lattice(H, W, max(S, 1))
+    cells = (Ah - 1) * (Aw - 1)
+    residual, pairs = np.zeros((iters + 1, P), dtype=np.float64), np.zeros((iters + 1, P), dtype=np.int64)
+    flow_norm = np.zeros((iters + 1, P), dtype=np.float64)
+    flow = np.zeros((P, Ah, Aw, 2), dtype=np.float64)
+    info = dict(residual=residual, pairs=pairs, status=status, flow_norm=flow_norm, lattice_step=S)
+    if P == 0:
+        return given, flow, info
+    if int(rigid_iterations) > 0:                                      # the rigid loop first, under the same visibility
+        given, info['rigid'] = optimize_poses_rigid(v, given, c, bits=vis, color_camera=fc.color_camera, iterations=int(rigid_iterations),
+                                                    free=free, min_pairs=min_pairs, batch=step, **params)
+        status |= info['rigid']['status']
+        RT, valid = pose_extrinsics(given)
+    keys = _nonrigid_workspace(n, step, H, W, S, dev)
+    images = torch.empty(P, H, W, 4, dtype=torch.int32, device=dev)
+    for p0 in range(0, P, step):
+        _colormap_gradients(c[p0:p0 + step], images[p0:p0 + step])
+    proxy = torch.empty(n, dtype=torch.float64, device=dev)
+    blocks = torch.empty(P, cells, _lib.CONSTANTS['STIN_NONRIGID_BLOCK_DOUBLES'], dtype=torch.float64, device=dev)
+    counts = torch.empty(P, cells, dtype=torch.int32, device=dev)
+    valid_d = torch.from_numpy(valid).to(dev)
+    E = np.zeros((P, 4, 4), dtype=np.float64)
+    E[:, :3, :] = RT.reshape(P, 3, 4)
+    E[:, 3, 3] = 1.0
+    ever = np.zeros(P, dtype=bool)
+    for it in range(iters + 1):
+        rt_d = torch.from_numpy(np.ascontiguousarray(E[:, :3, :]).reshape(P, 12)).to(dev)
+        flow_d = torch.from_numpy(flow).to(dev)
+        fc.sum.zero_()
+        fc.count.zero_()
+        for p0 in range(0, P, step):
+            fc._add_extrinsics(rt_d[p0:p0 + step], valid_d[p0:p0 + step], c[p0:p0 + step], p0, bits=vis, flow=flow_d[p0:p0 + step],
+                               lattice_step=S)
+        _colormap_proxy(fc.sum, fc.count, proxy)
+        for p0 in range(0, P, step):
+            _nonrigid_normal(v, rt_d[p0:p0 + step], valid_d[p0:p0 + step], p0, images[p0:p0 + step], flow_d[p0:p0 + step], S,
+                             fc.color_camera, fc.z_near, vis, margin, proxy, blocks[p0:p0 + step], counts[p0:p0 + step], keys)
+        blk, k = blocks.cpu().numpy(), counts.cpu().numpy()
+        residual[it] = np.cumsum(blk[:, :, 119], axis=1)[:, -1]           # cells ascending
+        pairs[it], flow_norm[it] = k.sum(axis=1), np.abs(flow).reshape(P, -1).max(axis=1)
+        if it < iters:
+            ever |= nonrigid_update(E, flow, valid, free, blk, k, n, anchor_weight, min_pairs, status)
+    out = given.copy()
+    for p in np.flatnonzero(ever):
+        out[p] = np.linalg.inv(E[p])
+    return out, flow, info
