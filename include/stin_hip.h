@@ -1459,7 +1459,8 @@ int stin_colormap_normal_f64(const double* vertices, int64_t N, const double* RT
  *   order     the terms of a (pose, cell) are added one after another in ASCENDING VERTEX ID, starting at +0.0: a function of the
  *             inputs alone, not of B, first_pose, the split of the poses over launches, or the run.  A cell without pairs is 120 x
  *             +0.0.  No float atomics.
- *   update    on the host (preprocessing.nonrigid_update), per free, valid pose whose pair count n_p (the sum of its cells' counts)
+ *   update    on the host (preprocessing.nonrigid_update; its linear solve alone on the device: "Non-rigid solve" below, a second
+ *             solver with its own bytes), per free, valid pose whose pair count n_p (the sum of its cells' counts)
  *             is >= min_pairs: unknown k < 6 is the pose's, unknown 6 + 2 (i Aw + j) + c the offset c (0: x, 1: y) of anchor (i, j).
  *             The (6 + 2 Ah Aw)^2 system A, b is assembled from the blocks, cells ascending, every entry starting at +0.0; every
  *             anchor unknown k is regularised with wgt = (anchor_weight (double) n_p) / (double) N: A[k][k] += wgt wgt, b[k] += (wgt
@@ -1493,6 +1494,77 @@ int stin_nonrigid_normal_f64(const double* vertices, int64_t N, const double* RT
                              const int32_t* images, int H, int W, const double* flow, int lattice_step, const double* camera,
                              double z_near, int margin, const double* proxy, const void* sorted_keys, size_t keys_bytes,
                              double* blocks, int32_t* counts, stin_stream_t stream);
+
+/* Non-rigid solve: the update's linear solve on the device (stin_nonrigid_solve.hip) - one banded-arrow Cholesky per pose on the
+ * blocks that stin_nonrigid_normal_f64 wrote, so that an iteration reads back x instead of the blocks; preprocessing.nonrigid_solve,
+ * optimize_poses_nonrigid(solver='banded').  A SECOND solver beside the host's np.linalg.solve ('dense', the default, unchanged):
+ * the two agree to rounding, not in bytes, hence a contract of its own.  tests/_nonrigid_solve_oracle.py restates it in numpy
+ * (dense storage, left-looking, plain loops) and agrees byte for byte.  Everything is fp64 and IEEE, every operation in the order
+ * and association written, nothing contracted and no fma; `/` and sqrt are the correctly rounded operations, never a multiplication
+ * by a reciprocal; integers where stated.
+ *
+ *   inputs    per pose p: blocks[p] fp64 [cells][120] and counts[p] int32 [cells] as stin_nonrigid_normal_f64 writes them; flow[p]
+ *             fp64 [Ah][Aw][2]; valid[p], free[p] bytes; the scalars n_vertices (int64), anchor_weight (fp64), min_pairs (int64).
+ *   poses     pairs[p] = the integer sum of counts[p] (int64).  residual[p] = ((+0.0 + blocks[p][0][119]) + blocks[p][1][119]) + ..,
+ *             cells ascending - written for EVERY pose.  A pose is SOLVED iff free && valid && pairs >= min_pairs; free && valid but
+ *             pairs < min_pairs: status STIN_NONRIGID_FEW_PAIRS.  A pose that is not solved gets an x row of +0.0.
+ *   assembly  that of "Non-rigid colour-map optimisation", update: unknown k < 6 the pose's, 6 + 2 (i Aw + j) + c the offset c of
+ *             anchor (i, j); a cell's 14 local unknowns are the pose's six and the offsets of its anchors (ci, cj), (ci, cj + 1),
+ *             (ci + 1, cj), (ci + 1, cj + 1); entry t of a block, t < 105, is the t-th pair (a, b), a <= b, of the row-major upper
+ *             triangle of the 14 x 14 and is added to A[g(a)][g(b)] (g ascending in a cell: the upper triangle), entry 105 + a to
+ *             b[g(a)]; every target starts at +0.0 and takes its cells in ASCENDING cell number: acc = acc + entry.  Then
+ *             wgt = (anchor_weight (double) pairs) / (double) n_vertices, w2 = wgt wgt, and for every anchor unknown k (f_k its
+ *             offset in flow[p], flattened): A[k][k] = A[k][k] + w2, b[k] = b[k] + w2 f_k.  A is symmetric: A[j][i] = A[i][j].
+ *             These are the numbers the host update builds, bit for bit.  On the device a GATHER: one thread per stored entry
+ *             adds the at most four cells that hold both its anchors, the 21 + 6 pose entries add all cells; no atomics.
+ *   ordering  the pose LAST: q = [6 .. n - 1, 0 .. 5], M[i][j] = A[q_i][q_j], r_i = -b[q_i] (a negation: -(+0.0) is -0.0).
+ *             m = 2 Ah Aw, n = m + 6, w = 2 Aw + 3.  Envelope: lo(i) = max(0, i - w) for i < m, lo(i) = 0 for the six border rows:
+ *             anchors that share a cell differ by at most Aw + 1, their unknowns by at most w, so M is zero outside it.
+ *   factor    M = L L^T over the envelope.  For i ascending, j = lo(i) .. i ascending:
+ *                 t = M[i][j];  for k = max(lo(i), lo(j)) .. j - 1 ascending: t = t - L[i][k] L[j][k];
+ *                 j < i: L[i][j] = t / L[j][j];   j = i: !(t > 0) -> the pose is STIN_NONRIGID_SINGULAR, else L[i][i] = sqrt(t).
+ *             Structural zeros inside the envelope take part like every other entry (that fixes the signs of zeros).  A
+ *             right-looking factorisation gives every entry the same subtractions in the same ascending pivot order: the kernel is
+ *             right-looking, the restatement left-looking, the bytes are the same.
+ *   forward   y: t = r_i; for k = lo(i) .. i - 1 ascending: t = t - L[i][k] y_k; y_i = t / L[i][i] - the arithmetic of one more
+ *             border row, and implemented as one.
+ *   backward  for i descending: t = y_i; for k = n - 1 down to i + 1, those with lo(k) <= i: t = t - L[k][i] x_k;
+ *             x_i = t / L[i][i] - what a column-oriented sweep produces.
+ *   finish    x is un-permuted (x[q_i] = x_i).  Any component not finite: STIN_NONRIGID_SINGULAR.  A SINGULAR pose's x row is +0.0.
+ *             No loop bound and no barrier depends on a data value: on the device a failed pivot sets a flag and the arithmetic
+ *             runs on; a NaN or infinite block ends as SINGULAR like any other input and leaves the other poses alone.
+ *   versus 'dense'   LAPACK's LU moves a pose whose matrix is indefinite but non-singular, Cholesky reports it SINGULAR; J^T J plus
+ *             a non-negative diagonal is never indefinite in exact arithmetic.  An anchor that no pair touches under anchor_weight = 0
+ *             is SINGULAR under both (the pivot is exactly 0).
+ * stin_nonrigid_solve_f64: B poses in three launches - per pose the pair count, residual and status; the gather into band storage
+ *     [B][m][w + 1] (row i, column c: M[i][i - w + c]) and border storage [B][7][n] (the pose's six rows of M, then r); one
+ *     workgroup of 256 threads per pose that factors and solves in place through a window of w + 1 band rows and the border's 7 rows
+ *     over the same columns in LDS: ((w + 1)(w + 8) + 42 + w + 7) doubles, 19.8 KB at Aw = 21 and 63.5 KB at Aw = 41, within the
+ *     64 KB a workgroup gets without raising a limit - hence Aw <= STIN_NONRIGID_SOLVE_MAX_AW = 41 (step 16 at 640 pixels); Ah is
+ *     free (the window does not grow with it).  Outputs: x fp64 [B][n] in the ORIGINAL order of the unknowns, residual fp64 [B],
+ *     pairs int64 [B], status int32 [B] (WRITTEN: FEW_PAIRS / SINGULAR of this call only).  The workspace
+ *     (stin_nonrigid_solve_workspace_bytes; 8-byte aligned) holds the factor afterwards.  Ah >= 2, 2 <= Aw <= 41, Ah Aw < 2^22,
+ *     0 <= B <= STIN_NONRIGID_SOLVE_MAX_BATCH: otherwise the workspace size is 0 and the call returns STIN_E_SIZE.  B = 0: nothing
+ *     is launched.  Nothing allocates or synchronises.
+ * stin_nonrigid_solve_stages_f64: the same with `stages`, 0 = all, else a mask of STIN_NONRIGID_SOLVE_STAGE_*: only those kernels
+ *     are launched, on what earlier calls left in the workspace (for per-stage timing, profiles/nonrigid_solve.py; the outputs are
+ *     defined for 0 only.  No kernel's loop bounds depend on the values, so a stage's time is its time in a whole call). */
+#define STIN_NONRIGID_FEW_PAIRS 4
+#define STIN_NONRIGID_SINGULAR 8
+#define STIN_NONRIGID_SOLVE_MAX_AW 41
+#define STIN_NONRIGID_SOLVE_MAX_BATCH 65535
+#define STIN_NONRIGID_SOLVE_STAGE_STATS 1
+#define STIN_NONRIGID_SOLVE_STAGE_ASSEMBLE 2
+#define STIN_NONRIGID_SOLVE_STAGE_FACTOR 4
+size_t stin_nonrigid_solve_workspace_bytes(int B, int Ah, int Aw);
+int stin_nonrigid_solve_f64(const double* blocks, const int32_t* counts, const double* flow, const uint8_t* valid,
+                            const uint8_t* free_, int B, int Ah, int Aw, int64_t n_vertices, double anchor_weight, int64_t min_pairs,
+                            double* x, double* residual, int64_t* pairs, int32_t* status, void* workspace, size_t workspace_bytes,
+                            stin_stream_t stream);
+int stin_nonrigid_solve_stages_f64(const double* blocks, const int32_t* counts, const double* flow, const uint8_t* valid,
+                                   const uint8_t* free_, int B, int Ah, int Aw, int64_t n_vertices, double anchor_weight,
+                                   int64_t min_pairs, double* x, double* residual, int64_t* pairs, int32_t* status, void* workspace,
+                                   size_t workspace_bytes, int stages, stin_stream_t stream);
 
 /* Render: colour, depth and face-id images of a vertex-coloured mesh from the camera poses of a scan (stin_render.hip on stin_raster.hip) - the
  * direction the two sections above lack, mesh -> images.  It stands in for what the reference shows in an Open3D window

@@ -58,7 +58,9 @@
 * ``optimize_poses_nonrigid`` - the non-rigid optimisation, the call the reference actually makes (``run_non_rigid_optimizer``;
   Zhou & Koltun 2014, section 5): a low-resolution warp lattice per frame beside its pose.  The normal equations are summed per
   (pose, lattice cell) in ascending vertex id (``stin_nonrigid_*``: keys, a sort, one workgroup per cell), the colours are sampled at
-  the warped positions, and the host solves one (6 + 2 anchors) system per free pose (``nonrigid_update``).  NOT pinned against Open3D.
+  the warped positions, and the host solves one (6 + 2 anchors) system per free pose (``nonrigid_update``) - or, with
+  ``solver='banded'``, the device does: ``nonrigid_solve``, a banded-arrow Cholesky per pose (``stin_nonrigid_solve_f64``).  NOT
+  pinned against Open3D.
 
 * ``knn`` / ``fill_unseen_colors`` / ``knn_inpaint`` - exact fp64 k nearest neighbours with a validity mask on the points
   (``stin_knn_f64``: ``nearest``'s tiled brute force with a k-list per query in registers) and the mean of the neighbours' rows
@@ -1876,7 +1878,7 @@ def resize_u8(images, size, mode='linear'):
 
 
 def scan_vertex_colors(vertices, scan_dir, width=640, height=480, trajectory_slice=slice(None, None, 10), batch=32, knn=0,
-                       nonrigid_iterations=0, **frame_colors_options):
+                       nonrigid_iterations=0, nonrigid_solver='dense', **frame_colors_options):
     """Per-vertex colours of a mesh straight from a scan directory: the reference's load_dataset (texture_map_optimization.py:48-123)
     plus FrameColors' averaging -> (colors float32 [N, 3], count int32 [N]).  scan_dir holds color/*.jpg, depth/*.png, pose/*.txt
     (scene_io.scan_frame_files: natural order for all three) and intrinsic/intrinsic_color.txt; every trajectory_slice-th frame is
@@ -1888,13 +1890,16 @@ def scan_vertex_colors(vertices, scan_dir, width=640, height=480, trajectory_sli
     nonrigid_iterations = k > 0: what the reference asks of Open3D (run_non_rigid_optimizer) - the frames are then all kept on the
     device (0.9 MB per 480 x 640 colour frame, 0.6 MB per depth frame, 4.9 MB of gradient images), optimize_poses_nonrigid runs k
     iterations on them in depth mode at its defaults, and the colours are averaged with its poses and warp lattices
-    (vertex_colors_from_frames).  0, the default: no optimisation, batch by batch, as before."""
+    (vertex_colors_from_frames).  0, the default: no optimisation, batch by batch, as before.  nonrigid_solver: the optimiser's
+    `solver`, 'dense' (the host's, the default) or 'banded' (on the device)."""
     import os
     import numpy as np
     from . import scene_io
     width, height, step = int(width), int(height), int(batch)
     if step < 1:
         raise ValueError('batch must be positive')
+    if nonrigid_solver not in NONRIGID_SOLVERS:
+        raise ValueError("nonrigid_solver must be 'dense' or 'banded', not %r" % (nonrigid_solver,))
     files = scene_io.scan_frame_files(scan_dir)
     color_files, depth_files, pose_files = (files[k][trajectory_slice] for k in ('color', 'depth', 'pose'))
     if not (len(color_files) == len(depth_files) == len(pose_files)):
@@ -1923,7 +1928,8 @@ def scan_vertex_colors(vertices, scan_dir, width=640, height=480, trajectory_sli
     if resident:
         poses, small, depth = np.concatenate(kept[0]), torch.cat(kept[1]), torch.cat(kept[2])
         poses, flow, info = optimize_poses_nonrigid(vertices, poses, small, depth=depth, color_camera=camera,
-                                                    iterations=int(nonrigid_iterations), batch=step, **frame_colors_options)
+                                                    iterations=int(nonrigid_iterations), batch=step, solver=nonrigid_solver,
+                                                    **frame_colors_options)
         return vertex_colors_from_frames(vertices, poses, small, depth=depth, batch=step, color_camera=camera, knn=knn, flow=flow,
                                          lattice_step=info['lattice_step'], **frame_colors_options)
     return fc.result(knn=knn)
@@ -2247,9 +2253,70 @@ def _nonrigid_normal(v64, rt_d, valid_d, first_pose, images, flow_d, lattice_ste
     _nonrigid_blocks(v64, rt_d, valid_d, first_pose, images, flow_d, lattice_step, camera, z_near, margin, proxy, ordered, blocks, counts)
 
 
+def _dev_array(t, dtype, shape, name):
+    if not (torch.is_tensor(t) and t.is_cuda):
+        raise ValueError('%s must be a CUDA tensor' % name)
+    if t.dtype != dtype or tuple(t.shape) != tuple(shape):
+        raise ValueError('%s must be %s %s' % (name, str(dtype).replace('torch.', ''), list(shape)))
+    return t.contiguous()
+
+
+def nonrigid_solve(blocks, counts, flow, valid, free, n_vertices, anchor_weight, min_pairs):
+    """The linear solve of one non-rigid update on the device (csrc/stin_nonrigid_solve.hip; include/stin_hip.h, "Non-rigid solve"):
+    per pose the (6 + 2 Ah Aw) system is gathered from the blocks into band storage, pose last, and factored by a banded-arrow
+    Cholesky in one workgroup - about (2 Ah Aw)(2 Aw + 3)^2 multiply-adds where the dense solve spends (6 + 2 Ah Aw)^3 / 3.
+    blocks float64 [P, cells, 120] and counts int32 [P, cells] as stin_nonrigid_normal_f64 writes them, flow float64 [P, Ah, Aw, 2],
+    valid and free uint8 or bool [P]: CUDA tensors.  -> (x float64 [P, 6 + 2 Ah Aw] in the order of the unknowns - the pose's six,
+    then the anchors' offsets -, residual float64 [P], pairs int64 [P], status int32 [P]) on the device.  status holds
+    COLORMAP_FEW_PAIRS / COLORMAP_SINGULAR of THIS call; a pose that is held, invalid, short of min_pairs or singular has an x row
+    of +0.0.  residual and pairs are those of every pose.  A lattice of more than 41 columns is not supported (ValueError: use
+    solver='dense').  The workspace (the band factors: 8 (2 Ah Aw (2 Aw + 4) + 7 (6 + 2 Ah Aw)) bytes per pose) is allocated here.
+    The test suite restates the contract in numpy and this reproduces it byte for byte; it agrees with np.linalg.solve to rounding,
+    and reports COLORMAP_SINGULAR where a pivot is not positive."""
+    if not (torch.is_tensor(flow) and flow.dim() == 4 and int(flow.shape[3]) == 2):
+        raise ValueError('flow must be a float64 CUDA tensor [P, Ah, Aw, 2]')
+    P, Ah, Aw = (int(s) for s in flow.shape[:3])
+    if Ah < 2 or Aw < 2:
+        raise ValueError('a warp lattice has at least 2 x 2 anchors')
+    cells = (Ah - 1) * (Aw - 1)
+    flow = _dev_array(flow, torch.float64, (P, Ah, Aw, 2), 'flow')
+    blocks = _dev_array(blocks, torch.float64, (P, cells, _lib.CONSTANTS['STIN_NONRIGID_BLOCK_DOUBLES']), 'blocks')
+    counts = _dev_array(counts, torch.int32, (P, cells), 'counts')
+    flags = []
+    for name, t in (('valid', valid), ('free', free)):
+        if torch.is_tensor(t) and t.dtype == torch.bool:
+            t = t.to(torch.uint8)
+        flags.append(_dev_array(t, torch.uint8, (P,), name))
+    if int(n_vertices) < 0 or int(min_pairs) < 0:
+        raise ValueError('n_vertices and min_pairs must be >= 0')
+    if Aw > _lib.CONSTANTS['STIN_NONRIGID_SOLVE_MAX_AW']:
+        raise ValueError("a lattice of %d columns is wider than the %d the banded solve supports: use solver='dense'"
+                         % (Aw, _lib.CONSTANTS['STIN_NONRIGID_SOLVE_MAX_AW']))
+    dev, n = flow.device, 6 + 2 * Ah * Aw
+    x = torch.empty(P, n, dtype=torch.float64, device=dev)
+    residual = torch.empty(P, dtype=torch.float64, device=dev)
+    pairs = torch.empty(P, dtype=torch.int64, device=dev)
+    status = torch.empty(P, dtype=torch.int32, device=dev)
+    lib, step = _lib.load(), _lib.CONSTANTS['STIN_NONRIGID_SOLVE_MAX_BATCH']
+    for p0 in range(0, P, step):
+        B = min(step, P - p0)
+        ws_bytes = lib.stin_nonrigid_solve_workspace_bytes(B, Ah, Aw)
+        if ws_bytes == 0:
+            raise ValueError("a lattice of %d x %d anchors is outside what the banded solve supports: use solver='dense'" % (Ah, Aw))
+        ws = torch.empty(ws_bytes, dtype=torch.uint8, device=dev)
+        _lib.check(lib.stin_nonrigid_solve_f64(_ptr(blocks[p0:]), _ptr(counts[p0:]), _ptr(flow[p0:]), _ptr(flags[0][p0:]),
+                                               _ptr(flags[1][p0:]), B, Ah, Aw, int(n_vertices), float(anchor_weight), int(min_pairs),
+                                               _ptr(x[p0:]), _ptr(residual[p0:]), _ptr(pairs[p0:]), _ptr(status[p0:]), _ptr(ws),
+                                               ws_bytes, _stream(flow)), 'stin_nonrigid_solve_f64')
+    return x, residual, pairs, status
+
+
+NONRIGID_SOLVERS = ('dense', 'banded')
+
+
 def optimize_poses_nonrigid(vertices, poses, color, depth=None, bits=None, *, color_camera=None, depth_camera=None, iterations=30,
                             rigid_iterations=0, lattice_step=None, vertical_anchors=16, anchor_weight=0.316, free=None, min_pairs=16,
-                            batch=64, **params):
+                            batch=64, solver='dense', **params):
     """The non-rigid colour-map optimisation (Zhou & Koltun 2014, section 5; Open3D's run_non_rigid_optimizer, the call the
     reference's texture_map_optimization.py makes): beside its pose every frame gets a low-resolution warp lattice - an (x, y) offset
     in pixels at anchors every lattice_step pixels, interpolated bilinearly - and both are refined photometrically on the GPU
@@ -2271,13 +2338,21 @@ def optimize_poses_nonrigid(vertices, poses, color, depth=None, bits=None, *, co
     poses.  lattice_step: default ceil((H - 1) / (vertical_anchors - 1)) - 32 pixels at 480 rows, 16 x 21 anchors and 678 unknowns
     per frame, the size the paper uses.  A finer lattice is allowed; the host solve is dense, O((6 + 2 Ah Aw)^3) per free pose and
     iteration (678 unknowns: about 0.1 Gflop and 3.7 MB; step 8 at 480 x 640: 9 888 unknowns, 0.3 Tflop and 0.8 GB per pose).
+    solver: 'dense' (the default) is that host solve, np.linalg.solve on the blocks read back.  'banded' solves on the device
+    (nonrigid_solve: a banded-arrow Cholesky per pose, one call per iteration on all P poses) and reads back x, the residuals, pair
+    counts and status instead of the blocks - P (6 + 2 Ah Aw) numbers for P cells 121; the poses and lattices are then updated on
+    the host by the code the dense path uses, so the two solvers differ in x only: to rounding, not in bytes, which is why 'dense'
+    stays the default and 'banded' has a contract and a restatement of its own ("Non-rigid solve").  Cholesky reports a pose whose
+    system is not positive definite as COLORMAP_SINGULAR where LU may still move it.  'banded' supports lattices of up to 41 columns
+    (step 16 at 640 pixels; ValueError beyond).  info['solver'] names the solver.
 
     The recipe: poses, flow, info = optimize_poses_nonrigid(vertices, poses, color, depth, color_camera=cam); then
     vertex_colors_from_frames(vertices, poses, color, depth, color_camera=cam, flow=flow, lattice_step=info['lattice_step']).
     The contract is in include/stin_hip.h ("Non-rigid colour-map optimisation"); the test suite restates it in numpy and this
-    reproduces it byte for byte.  Not Open3D's result and not pinned against a run of it; warp-aware depth visibility and a solve
-    on the device are not built."""
+    reproduces it byte for byte.  Not Open3D's result and not pinned against a run of it; warp-aware depth visibility is not built."""
     import numpy as np
+    if solver not in NONRIGID_SOLVERS:
+        raise ValueError("solver must be 'dense' or 'banded', not %r" % (solver,))
     if int(rigid_iterations) < 0 or int(vertical_anchors) < 2:
         raise ValueError('rigid_iterations must be >= 0 and vertical_anchors >= 2')
     if lattice_step is not None and int(lattice_step) < 1:
@@ -2293,7 +2368,10 @@ def optimize_poses_nonrigid(vertices, poses, color, depth=None, bits=None, *, co
     residual, pairs = np.zeros((iters + 1, P), dtype=np.float64), np.zeros((iters + 1, P), dtype=np.int64)
     flow_norm = np.zeros((iters + 1, P), dtype=np.float64)
     flow = np.zeros((P, Ah, Aw, 2), dtype=np.float64)
-    info = dict(residual=residual, pairs=pairs, status=status, flow_norm=flow_norm, lattice_step=S)
+    info = dict(residual=residual, pairs=pairs, status=status, flow_norm=flow_norm, lattice_step=S, solver=solver)
+    if solver == 'banded' and Aw > _lib.CONSTANTS['STIN_NONRIGID_SOLVE_MAX_AW']:
+        raise ValueError("a lattice of %d columns is wider than the %d the banded solve supports: use solver='dense'"
+                         % (Aw, _lib.CONSTANTS['STIN_NONRIGID_SOLVE_MAX_AW']))
     if P == 0:
         return given, flow, info
     if int(rigid_iterations) > 0:                                      # the rigid loop first, under the same visibility
@@ -2309,6 +2387,7 @@ def optimize_poses_nonrigid(vertices, poses, color, depth=None, bits=None, *, co
     blocks = torch.empty(P, cells, _lib.CONSTANTS['STIN_NONRIGID_BLOCK_DOUBLES'], dtype=torch.float64, device=dev)
     counts = torch.empty(P, cells, dtype=torch.int32, device=dev)
     valid_d = torch.from_numpy(valid).to(dev)
+    free_d = torch.from_numpy(free.astype(np.uint8)).to(dev) if solver == 'banded' else None
     E = np.zeros((P, 4, 4), dtype=np.float64)
     E[:, :3, :] = RT.reshape(P, 3, 4)
     E[:, 3, 3] = 1.0
@@ -2325,6 +2404,16 @@ def optimize_poses_nonrigid(vertices, poses, color, depth=None, bits=None, *, co
         for p0 in range(0, P, step):
             _nonrigid_normal(v, rt_d[p0:p0 + step], valid_d[p0:p0 + step], p0, images[p0:p0 + step], flow_d[p0:p0 + step], S,
                              fc.color_camera, fc.z_near, vis, margin, proxy, blocks[p0:p0 + step], counts[p0:p0 + step], keys)
+        if solver == 'banded':                                         # the solve on the device: x comes back, not the blocks
+            x, e, k, st = (t.cpu().numpy() for t in nonrigid_solve(blocks, counts, flow_d, valid_d, free_d, n, anchor_weight, min_pairs))
+            residual[it], pairs[it], flow_norm[it] = e, k, np.abs(flow).reshape(P, -1).max(axis=1)
+            if it < iters:
+                status |= st
+                for p in np.flatnonzero((st == 0) & free & (valid != 0)):
+                    E[p] = rigid_increment(x[p, :6]) @ np.ascontiguousarray(E[p])
+                    flow[p] += x[p, 6:].reshape(Ah, Aw, 2)
+                    ever[p] = True
+            continue
         blk, k = blocks.cpu().numpy(), counts.cpu().numpy()
         residual[it] = np.cumsum(blk[:, :, 119], axis=1)[:, -1]           # cells ascending
         pairs[it], flow_norm[it] = k.sum(axis=1), np.abs(flow).reshape(P, -1).max(axis=1)
