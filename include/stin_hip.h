@@ -1713,6 +1713,79 @@ int stin_image_metrics_f32(const float* out, int64_t ldo, const float* color, co
 int stin_resize_u8(const uint8_t* src, int64_t src_bytes, uint8_t* dst, int64_t dst_bytes, const int64_t* jobs, int J, int channels,
                    int mode, stin_stream_t stream);
 
+/* ------------------------------------------------------------------------------- Surface samples --
+ * Area-uniform points on a triangle mesh, thinned to a minimum spacing, as centres of the circle masks (stin_surface.hip): the
+ * sampler the reference's process_frame_circles planned (preprocessing/observed_texture_map_generation.py:545-562, "TODO: Sample
+ * using poisson disk") and replaced by a uniform draw over vertex ids.  A contract of the project's own: NOT pinned against Open3D's
+ * sample_points_poisson_disk (weighted sample elimination); spacing is Euclidean, not geodesic.  tests/_surface_oracle.py restates
+ * it in numpy and agrees bit for bit.  All arithmetic is fp64, every product and sum rounded once (no contraction).
+ *
+ * Face weights (stin_surface_weights_f64).  vertices [N, 3] fp64, faces [F, 3] int64, F <= STIN_SURFACE_MAX_FACES.  e1 = b - a, e2 = c - a;
+ *     nx = e1y e2z - e1z e2y, ny = e1z e2x - e1x e2z, nz = e1x e2y - e1y e2x;  A2 = sqrt((nx nx + ny ny) + nz nz) (IEEE sqrt).
+ *     A face with an index outside [0, N) (flag bit 0; nothing is read through it) or a non-finite A2 (flag bit 1: a non-finite
+ *     vertex, or an overflow) has A2 = 0.  Amax = max A2 (an integer maximum of bit patterns: order-free), (_, e) = frexp(Amax),
+ *     W_f = (int64) floor(ldexp(A2_f, 40 - e)) < 2^40; all W = 0 when Amax = 0.  cum [F] int64 = the inclusive scan of W (integers:
+ *     the same bytes on any schedule), T = cum[F - 1] < 2^62.  A face that repeats a vertex has e1, e2 or e1 - e2 = 0,
+ *     hence A2 = 0 exactly: it is never drawn, which is the rule of stin_qem_remap_faces_i64 (such faces are dropped).
+ *     state: 4 x int64 DEVICE words written by the call: [0] bits of Amax, [1] flags, [2] T, [3] 0.
+ *     Workspace >= stin_surface_weights_workspace_bytes(F).
+ * Samples (stin_surface_sample_f64).  With mix64 the finaliser of the circle masks' hash (splitmix64), G = 0x9E3779B97F4A7C15 and
+ *     uint64 wrap arithmetic:  base = mix64(seed + G),  r_k = mix64(base + (3 (first + i) + k) G), k = 0, 1, 2.
+ *         face   u = (r_0 T) >> 64 (the high word of the 128-bit product), f = the first face with cum[f] > u
+ *         point  x1 = (r_1 >> 11) 2^-53, x2 = (r_2 >> 11) 2^-53, s = sqrt(x1);  b0 = 1 - s, b1 = s (1 - x2), b2 = s x2;
+ *                p = (b0 a + b1 b) + b2 c per component
+ *     Sample i depends on (seed, first + i) only: a stream can be extended or split over launches with the same bytes.  Outputs:
+ *     points [n, 3] fp64, face [n] int64, bary [n, 3] fp64.  T = 0 (no positive weight): flag bit 2 is OR-ed into state[1] and
+ *     nothing is written.  state is the array stin_surface_weights_f64 wrote.
+ *
+ * Poisson-disk subset in index order.  Candidate i of points [C, 3] fp64 is accepted iff no accepted j < i has
+ *     d2(i, j) = (dx dx + dy dy) + dz dz < r2 = r r (strict).  The accepted set is the unique sequential-greedy one, and every
+ *     prefix of it is the result for the same prefix of candidates.
+ *     Grid (stin_poisson_grid_f64): origin o = the component-wise minimum, cell edge h = r (1 + 2^-20), cell = floor((p - o) / h)
+ *     per axis, three 21-bit cells in one key (x highest), a stable radix sort of (key, index): order [C] int32 = the indices in
+ *     key order, ascending inside a cell.  runs [C][18] int32: for candidate i the nine ranges [beg, end) of `order` that hold the
+ *     cells (cx + dx, cy + dy, cz - 1 .. cz + 1), dx, dy in {-1, 0, 1} (three consecutive keys each).  decided [C] bytes = 0.
+ *     state: 8 x int64 DEVICE words: [0..2] / [3..5] the minimum / maximum per axis as order-preserving integer keys (sign bit
+ *     flipped for v >= 0, all bits for v < 0), [6] flags: bit 0 a non-finite candidate, bit 1 more than 2^21 cells along an axis;
+ *     with a flag set the runs are empty and the caller must not go on.  Workspace >= stin_poisson_grid_workspace_bytes(C).
+ *     Why the 27 cells suffice, i.e. why the grid cannot change the result: a pair with computed d2 < r2 has dx dx < r2 (1 + 2 eps),
+ *     so the exact |p_i - p_j| < r (1 + 4 eps) on each axis, eps = 2^-53, allowing for the rounding of dx itself.  The exact
+ *     quotients (p - o) / h of the two therefore differ by less than (1 + 4 eps) / (1 + 2^-20) < 1 - 2^-21.  A computed quotient
+ *     (one rounded subtraction, one rounded division) is off by at most 2 eps q <= 2^21 2^-52 = 2^-31 for q < 2^21.  The computed
+ *     quotients hence differ by less than 1 - 2^-21 + 2^-30 < 1, and their floors by at most 1.
+ *     Rounds (stin_poisson_rounds_f64): `rounds` (1 .. 64) launches of one decision round.  decided[i]: 0 undecided, 1 accepted,
+ *     2 rejected.  An undecided i scans its conflicting j < i: one accepted -> rejected; else one undecided -> i waits; else
+ *     accepted.  States only move from undecided to the value they have in the greedy set, so a thread may read states written in the
+ *     same round (relaxed agent-scope byte loads and stores): that changes how many rounds are needed, never the result.
+ *     remaining [rounds] int64 DEVICE words: the candidates still undecided after each round.  The lowest undecided index always
+ *     decides, so C rounds are enough for any input; the host loops until a remaining count is 0.  No kernel waits for another
+ *     workgroup.
+ *
+ * stin_first_occurrence_i64: keep[i] = 1 iff i is the lowest position with the value ids[i] (ids [n] int64 in [0, N); an integer
+ *     atomicMin per value into first_pos [N] int64, then one compare): a stream of vertex ids without its repeats, in stream order.
+ *     *bad (device int32) = 1 when an id lies outside [0, N) (keep = 0 there).
+ *
+ * Circle masks on surface samples (preprocessing.circle_masks_on_surface; host loop over the calls above, stin_nearest_f64 and
+ *     stin_circle_mask_run with given centres): mask m draws its centre stream with the seed
+ *         seed_m = mix64(mix64(seed + G) + (m + 1) G)
+ *     and runs the batch rule of stin_circle_mask_run (10 centres, then k = int(total (frac / cur - 1)) until cur >= frac or
+ *     k <= 0), each batch taking the next k entries of the stream; a stream with fewer than k entries left gives what it has
+ *     and the mask ends `exhausted`.  Radii are hop counts, as before. */
+#define STIN_SURFACE_MAX_FACES 4194304
+size_t stin_surface_weights_workspace_bytes(int64_t F);
+int stin_surface_weights_f64(const double* vertices, int64_t N, const int64_t* faces, int64_t F, int64_t* cum, int64_t* state,
+                             void* workspace, size_t workspace_bytes, stin_stream_t stream);
+int stin_surface_sample_f64(const double* vertices, int64_t N, const int64_t* faces, int64_t F, const int64_t* cum, int64_t n,
+                            uint64_t seed, uint64_t first, double* points, int64_t* face, double* bary, int64_t* state,
+                            stin_stream_t stream);
+size_t stin_poisson_grid_workspace_bytes(int64_t C);
+int stin_poisson_grid_f64(const double* points, int64_t C, double radius, int32_t* order, int32_t* runs, uint8_t* decided,
+                          int64_t* state, void* workspace, size_t workspace_bytes, stin_stream_t stream);
+int stin_poisson_rounds_f64(const double* points, int64_t C, double radius, const int32_t* order, const int32_t* runs,
+                            uint8_t* decided, int rounds, int64_t* remaining, stin_stream_t stream);
+int stin_first_occurrence_i64(const int64_t* ids, int64_t n, int64_t N, int64_t* first_pos, uint8_t* keep, int32_t* bad,
+                              stin_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -112,6 +112,14 @@ static inline void stin_raise_dynamic_lds(stin_once_per_device& raised, const vo
     raised.publish();
 }
 
+// splitmix64's finaliser: the counter-based hash of the circle masks' centres (stin_mask.hip) and of the surface samples
+// (stin_surface.hip).  The constants are part of both contracts (include/stin_hip.h).
+__device__ inline uint64_t stin_mix64(uint64_t z) {
+    z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ull;
+    z = (z ^ (z >> 27)) * 0x94D049BB133111EBull;
+    return z ^ (z >> 31);
+}
+
 static inline bool stin_aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15u) == 0; }
 // workspace regions start on 256 bytes
 static inline size_t stin_up256(size_t v) { return (v + 255) & ~(size_t)255; }

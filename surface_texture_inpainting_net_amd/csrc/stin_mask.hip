@@ -25,17 +25,11 @@ constexpr int CTL_WORDS = 8;     // ticket, global-list count, ktot, status, bat
 constexpr int INFO_HEAD = 5;
 constexpr int MAX_SEEDED_GRAPHS = 64;     // per instance: batches, done, capped, masked, total; then sizes[max_iters], counts[max_iters]
 
-__device__ inline uint64_t mix64(uint64_t z) {
-    z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ull;
-    z = (z ^ (z >> 27)) * 0x94D049BB133111EBull;
-    return z ^ (z >> 31);
-}
-
 // centre i of batch b of mask m, drawn from [0, n) (with replacement): a counter-based hash, no state
 __device__ inline int64_t draw_centre(uint64_t seed, int m, int b, int64_t i, int64_t n) {
-    uint64_t h = mix64(seed + 0x9E3779B97F4A7C15ull);
-    h = mix64(h ^ ((uint64_t)(uint32_t)m << 32 | (uint32_t)b));
-    h = mix64(h + (uint64_t)i * 0x9E3779B97F4A7C15ull);
+    uint64_t h = stin_mix64(seed + 0x9E3779B97F4A7C15ull);
+    h = stin_mix64(h ^ ((uint64_t)(uint32_t)m << 32 | (uint32_t)b));
+    h = stin_mix64(h + (uint64_t)i * 0x9E3779B97F4A7C15ull);
     return (int64_t)(((h >> 32) * (uint64_t)n) >> 32);
 }
 

@@ -72,6 +72,13 @@
   launch for a batch or a ragged pool of images (``stin_resize_u8``); ``scan_vertex_colors`` is ``load_dataset`` plus the averaging,
   from a scan directory.  A contract of this project's own (include/stin_hip.h, "Image resize"), NOT pinned against cv2.
 
+* ``sample_surface`` / ``poisson_disk`` / ``surface_centres`` / ``circle_masks_on_surface`` - the sampler ``process_frame_circles``
+  planned and left as a TODO (:545-562, "Sample using poisson disk"; it draws centres over vertex ids instead, which ``circle_masks``
+  reproduces): area-uniform points on the mesh with exact integer face weights, a Poisson-disk subset in index order (uniform grid,
+  decision rounds), the nearest vertices without repeats, and the reference's batch loop over that stream (``stin_surface_*``,
+  ``stin_poisson_*``, ``stin_first_occurrence_i64``).  A contract of this project's own (include/stin_hip.h, "Surface samples"),
+  NOT pinned against Open3D's ``sample_points_poisson_disk``; Euclidean spacing, hop-count radii.
+
 All take and return tensors in the reference's own formats.  Out of scope: reading mesh files (neither open3d nor plyfile exists
 here to pin a reader against: vertices, faces and colours are inputs), and the Matterport and S3DIS label paths.
 """
@@ -2423,3 +2430,254 @@ def optimize_poses_nonrigid(vertices, poses, color, depth=None, bits=None, *, co
     for p in np.flatnonzero(ever):
         out[p] = np.linalg.inv(E[p])
     return out, flow, info
+
+
+# ------------------------------------------------------------------------------------------------------------ surface samples
+_GOLDEN, _M64 = 0x9E3779B97F4A7C15, (1 << 64) - 1
+SURFACE_MAX_CANDIDATES = 1 << 20     # upper end of circle_masks_on_surface's default candidate count
+_POISSON_GROUP = 4                   # decision rounds per host read of poisson_disk
+
+
+def _mix64(z):
+    """The hash finaliser of the circle masks and the surface samples (csrc: mix64) on Python integers."""
+    z &= _M64
+    z = ((z ^ (z >> 30)) * 0xBF58476D1CE4E5B9) & _M64
+    z = ((z ^ (z >> 27)) * 0x94D049BB133111EB) & _M64
+    return z ^ (z >> 31)
+
+
+def surface_stream_seed(seed, m):
+    """Seed of mask m's centre stream in circle_masks_on_surface: mix64(mix64(seed + G) + (m + 1) G) (include/stin_hip.h)."""
+    return _mix64(_mix64(int(seed) + _GOLDEN) + (int(m) + 1) * _GOLDEN)
+
+
+def _surface_mesh(vertices, faces, what):
+    """-> (fp64 vertices, int64 faces as given, cum int64 [F], state int64 [4] on the host): checked faces (IndexError), face
+    weights and their scan (stin_surface_weights_f64); ValueError for a non-finite vertex of a face or no positive weight."""
+    v = _xyz64(vertices, 'vertices')
+    if not (torch.is_tensor(faces) and faces.is_cuda):
+        raise TypeError('faces must be a CUDA tensor (no CPU fallback exists)')
+    lib = _lib.load()
+    n = int(v.shape[0])
+    _checked_faces(faces, n, what)                                      # the range check; a face that repeats a vertex has weight 0
+    f = faces.long().reshape(-1, 3).contiguous()
+    nf = int(f.shape[0])
+    if nf > _lib.CONSTANTS['STIN_SURFACE_MAX_FACES']:
+        raise ValueError('%s: more than %d faces' % (what, _lib.CONSTANTS['STIN_SURFACE_MAX_FACES']))
+    cum = torch.empty(max(nf, 1), dtype=torch.int64, device=v.device)[:nf]
+    state = torch.empty(4, dtype=torch.int64, device=v.device)
+    ws_bytes = lib.stin_surface_weights_workspace_bytes(nf)
+    ws = torch.empty(max(ws_bytes, 1), dtype=torch.uint8, device=v.device)
+    _lib.check(lib.stin_surface_weights_f64(_ptr(v), n, _ptr(f) if nf else None, nf, _ptr(cum) if nf else None, _ptr(state), _ptr(ws),
+                                            ws_bytes, _stream(v)), 'stin_surface_weights_f64')
+    st = state.cpu()
+    if int(st[1]) & 1:
+        raise IndexError('%s: a face refers to a vertex outside [0, %d)' % (what, n))
+    if int(st[1]) & 2:
+        raise ValueError('%s: a vertex of a face is not finite (or its area overflows)' % what)
+    if int(st[2]) <= 0:
+        raise ValueError('%s: the mesh has no face of positive area' % what)
+    return v, f, cum, state, st
+
+
+def _surface_area(st):
+    """The area the integer weights stand for: T 2^(e - 40) / 2 with (_, e) = frexp(Amax) - the same on every run."""
+    import math
+    amax = float(st[0:1].numpy().view('float64')[0])
+    return math.ldexp(float(int(st[2])), math.frexp(amax)[1] - 40) / 2.0
+
+
+def _surface_draw(v, f, cum, state, n, seed, first):
+    lib = _lib.load()
+    n, dev = int(n), v.device
+    points = torch.empty(max(n, 1), 3, dtype=torch.float64, device=dev)[:n]
+    face = torch.empty(max(n, 1), dtype=torch.int64, device=dev)[:n]
+    bary = torch.empty(max(n, 1), 3, dtype=torch.float64, device=dev)[:n]
+    if n:
+        _lib.check(lib.stin_surface_sample_f64(_ptr(v), int(v.shape[0]), _ptr(f), int(f.shape[0]), _ptr(cum), n, int(seed) & _M64,
+                                               int(first) & _M64, _ptr(points), _ptr(face), _ptr(bary), _ptr(state), _stream(v)),
+                   'stin_surface_sample_f64')
+    return points, face, bary
+
+
+def sample_surface(vertices, faces, n, seed=0, first=0):
+    """Area-weighted uniform points on a triangle mesh (vertices [N, >= 3] float, faces [F, 3] int; CUDA) ->
+    (points float64 [n, 3], face int64 [n] - ids into `faces` as given -, bary float64 [n, 3]).  Sample i depends on
+    (seed, first + i) only, so ``sample_surface(v, f, n, seed, first=k)`` is the tail of a longer draw.  Integer face weights
+    (exact in any summation order), a counter hash per sample, a binary search and the square-root map: include/stin_hip.h,
+    "Surface samples" (csrc/stin_surface.hip).  A face of zero area - one that repeats a vertex included - is never drawn.
+    IndexError for a face index out of range; ValueError for a non-finite vertex of a face or a mesh without positive area."""
+    if int(n) < 0 or int(first) < 0:
+        raise ValueError('sample_surface: n and first must be >= 0')
+    v, f, cum, state, _ = _surface_mesh(vertices, faces, 'sample_surface')
+    return _surface_draw(v, f, cum, state, n, seed, first)
+
+
+def _ordered_bits_to_float(k):
+    import numpy as np
+    k &= _M64
+    b = (k & ~(1 << 63)) if k >> 63 else (~k & _M64)
+    return float(np.array([b], dtype=np.uint64).view(np.float64)[0])
+
+
+def poisson_disk(points, radius, return_info=False):
+    """The Poisson-disk subset of `points` ([C, >= 3] float, CUDA) in index order: candidate i is kept iff no kept j < i has
+    (dx dx + dy dy) + dz dz < radius radius in fp64 (strict) -> the kept indices, int64 ascending.  The unique sequential-greedy
+    set; every prefix of the result is the result for the same prefix of candidates.  On the device: a uniform grid of cell edge
+    radius (1 + 2^-20) (stin_poisson_grid_f64), then decision rounds until nobody is undecided (stin_poisson_rounds_f64; the
+    host reads one count per %d rounds).  The grid and the schedule do not change the result (include/stin_hip.h).
+    ValueError for radius <= 0, a non-finite point or more than 2^21 cells along an axis.
+    return_info=True: also a dict with 'rounds' (decision rounds until the last candidate was settled), 'launched' (rounds
+    launched), 'grid' (cells per axis) and 'cell' (the cell edge).""" % _POISSON_GROUP
+    import math
+    p = _xyz64(points, 'points')
+    r = float(radius)
+    if not (r > 0.0 and math.isfinite(r)):
+        raise ValueError('poisson_disk: radius must be positive and finite')
+    lib = _lib.load()
+    C, dev = int(p.shape[0]), p.device
+    if C == 0:
+        out = torch.empty(0, dtype=torch.int64, device=dev)
+        return (out, dict(rounds=0, launched=0, grid=(0, 0, 0), cell=r * (1.0 + 2.0 ** -20))) if return_info else out
+    order = torch.empty(C, dtype=torch.int32, device=dev)
+    runs = torch.empty(C, 18, dtype=torch.int32, device=dev)
+    decided = torch.empty(C, dtype=torch.uint8, device=dev)
+    state = torch.empty(8, dtype=torch.int64, device=dev)
+    ws_bytes = lib.stin_poisson_grid_workspace_bytes(C)
+    ws = torch.empty(max(ws_bytes, 1), dtype=torch.uint8, device=dev)
+    _lib.check(lib.stin_poisson_grid_f64(_ptr(p), C, r, _ptr(order), _ptr(runs), _ptr(decided), _ptr(state), _ptr(ws), ws_bytes,
+                                         _stream(p)), 'stin_poisson_grid_f64')
+    st = [int(x) for x in state.cpu()]
+    if st[6] & 1:
+        raise ValueError('poisson_disk: a point is not finite')
+    if st[6] & 2:
+        raise ValueError('poisson_disk: more than 2^21 cells of edge %g along an axis' % r)
+    del ws
+    remaining = torch.empty(_POISSON_GROUP, dtype=torch.int64, device=dev)
+    rounds = launched = 0
+    while True:
+        if launched >= C + _POISSON_GROUP:                              # (the lowest undecided index decides in every round)
+            raise RuntimeError('poisson_disk: %d candidates still undecided after %d rounds' % (int(left[-1]), launched))
+        _lib.check(lib.stin_poisson_rounds_f64(_ptr(p), C, r, _ptr(order), _ptr(runs), _ptr(decided), _POISSON_GROUP,
+                                               _ptr(remaining), _stream(p)), 'stin_poisson_rounds_f64')
+        left = remaining.cpu().tolist()
+        launched += _POISSON_GROUP
+        if 0 in left:
+            rounds += left.index(0) + 1
+            break
+        rounds += _POISSON_GROUP
+    out = torch.nonzero(decided == 1).reshape(-1)
+    if not return_info:
+        return out
+    h = r * (1.0 + 2.0 ** -20)
+    lo, hi = [_ordered_bits_to_float(k) for k in st[0:3]], [_ordered_bits_to_float(k) for k in st[3:6]]
+    grid = tuple(int(math.floor((b - a) / h)) + 1 for a, b in zip(lo, hi))
+    return out, dict(rounds=rounds, launched=launched, grid=grid, cell=h)
+
+
+def first_occurrences(ids, num_values):
+    """`ids` (int64, CUDA, values in [0, num_values)) without its repeats, every value at its first position, order kept: an integer
+    atomicMin of the stream position per value, then one compare (stin_first_occurrence_i64)."""
+    if not (torch.is_tensor(ids) and ids.is_cuda):
+        raise TypeError('ids must be a CUDA tensor (no CPU fallback exists)')
+    lib = _lib.load()
+    s = ids.long().reshape(-1).contiguous()
+    n, N, dev = int(s.numel()), int(num_values), s.device
+    if n == 0:
+        return s
+    pos = torch.empty(max(N, 1), dtype=torch.int64, device=dev)
+    keep = torch.empty(n, dtype=torch.uint8, device=dev)
+    bad = torch.empty(1, dtype=torch.int32, device=dev)
+    _lib.check(lib.stin_first_occurrence_i64(_ptr(s), n, N, _ptr(pos), _ptr(keep), _ptr(bad), _stream(s)), 'stin_first_occurrence_i64')
+    if int(bad.item()) != 0:
+        raise IndexError('first_occurrences: a value lies outside [0, %d)' % N)
+    return s[keep.bool()]
+
+
+def _surface_centres(v, f, cum, state, candidates, seed, spacing):
+    pts, _, _ = _surface_draw(v, f, cum, state, candidates, seed, 0)
+    if spacing is not None:
+        pts = pts[poisson_disk(pts, spacing)]
+    if pts.shape[0] == 0:
+        return torch.empty(0, dtype=torch.int64, device=v.device)
+    return first_occurrences(nearest(pts, v), int(v.shape[0]))
+
+
+def surface_centres(vertices, faces, candidates, seed=0, spacing=None):
+    """Vertex ids (int64, CUDA) spread over the SURFACE of a mesh, in stream order: ``sample_surface(candidates, seed)``, thinned by
+    ``poisson_disk(spacing)`` when spacing is given (Euclidean, in the units of the vertices), snapped to the nearest vertex
+    (``nearest``), repeats removed keeping the first occurrence.  Every prefix of the result is a well-spread set."""
+    if int(candidates) < 0:
+        raise ValueError('surface_centres: candidates must be >= 0')
+    v, f, cum, state, _ = _surface_mesh(vertices, faces, 'surface_centres')
+    return _surface_centres(v, f, cum, state, int(candidates), seed, spacing)
+
+
+def default_surface_candidates(area, num_vertices, spacing=None):
+    """The candidate count circle_masks_on_surface uses when none is given: with a spacing, ceil(4 area / spacing^2) - about five
+    darts for every point a saturated Poisson-disk set of that spacing can hold (~0.7 area / spacing^2) -, else the number of
+    vertices (no more centres than that exist); clamped to [1024, SURFACE_MAX_CANDIDATES]."""
+    import math
+    c = int(num_vertices) if spacing is None else int(math.ceil(4.0 * float(area) / (float(spacing) * float(spacing))))
+    return min(max(c, 1024), SURFACE_MAX_CANDIDATES)
+
+
+def circle_masks_on_surface(vertices, faces, radius=16, frac_masked_vertices=0.25, num_masks=1, seed=0, spacing=None, candidates=None,
+                            edge_index=None, max_iters=32, return_centres=False):
+    """Circle masks whose centres are spread over the surface instead of over the vertex ids: int64 [num_masks, N], mask[v] =
+    max(0, R - hop distance to the nearest centre), ready for ``scene_io.write_circle_masks``.  The reference's loop
+    (``circle_masks``; that function stays the way to reproduce the reference's files) with the sampler its TODO asks for: mask m
+    draws ``surface_centres(candidates, surface_stream_seed(seed, m), spacing)`` once and every batch - 10 centres, then
+    k = int(total * (frac / cur - 1)) more until cur >= frac or k <= 0 - takes the next k entries of that stream.  A stream with
+    fewer than k entries left gives what it has; the mask is then reported `exhausted` and the loop stops.  Hop distances
+    (``circle_mask_from_centres``' pass) run on the mesh's own edges, or on `edge_index` when given.  candidates=None:
+    ``default_surface_candidates(area, N, spacing)``.  One host read per batch (an offline path).  Spacing is Euclidean, radii are
+    hop counts; NOT pinned against Open3D's sample_points_poisson_disk.
+    return_centres=True: also a dict in circle_masks' shape (one graph): 'centres'[m][0] (one int64 tensor per batch), 'sizes' /
+    'counts' (int64 [M, 1, max_iters]), 'batches', 'masked' ([M, 1]), 'capped' and 'exhausted' (bool [M, 1]), 'candidates'."""
+    v, f, cum, state, st = _surface_mesh(vertices, faces, 'circle_masks_on_surface')
+    n, dev, M, it = int(v.shape[0]), v.device, int(num_masks), int(max_iters)
+    frac = float(frac_masked_vertices)
+    if int(radius) < 1 or M < 1 or it < 1:
+        raise ValueError('circle_masks_on_surface: radius, num_masks and max_iters must be >= 1')
+    cand = int(candidates) if candidates is not None else default_surface_candidates(_surface_area(st), n, spacing)
+    ei = edge_index.to(dev) if edge_index is not None else edges_from_faces(f, n)
+    adj = mask_adjacency(ei, n)
+    masks = torch.zeros(M, n, dtype=torch.int64, device=dev)
+    sizes, counts = torch.zeros(M, 1, it, dtype=torch.int64), torch.zeros(M, 1, it, dtype=torch.int64)
+    batches, masked_out = torch.zeros(M, 1, dtype=torch.int64), torch.zeros(M, 1, dtype=torch.int64)
+    capped, exhausted = torch.zeros(M, 1, dtype=torch.bool), torch.zeros(M, 1, dtype=torch.bool)
+    centres = []
+    for m in range(M):
+        stream = _surface_centres(v, f, cum, state, cand, surface_stream_seed(seed, m), spacing)
+        pos, total, k, masked, done, per_batch = 0, 0, 10, 0, False, []
+        for b in range(it):
+            take = stream[pos:pos + k]
+            got = int(take.numel())
+            if got:
+                _, mk, info, _ = _circle_dist(adj, n, radius, 0.0, 1, 0, None, 1, centres=take, want_mask=True)
+                torch.maximum(masks[m], mk[0], out=masks[m])
+                masked = int((masks[m] > 0).sum())
+                if int(info[-1]) != 0:
+                    raise RuntimeError('circle_masks_on_surface: the overflow drain did not finish (status %d)' % int(info[-1]))
+            pos, total = pos + got, total + got
+            per_batch.append(take)
+            sizes[m, 0, b], counts[m, 0, b], batches[m, 0] = got, masked, b + 1
+            if got < k:
+                exhausted[m, 0] = done = True
+                break
+            cur = masked / n
+            if cur >= frac:
+                done = True
+                break
+            k = min(int(total * (frac / cur - 1)), n)
+            if k <= 0:
+                done = True
+                break
+        capped[m, 0] = not done
+        masked_out[m, 0] = masked
+        centres.append([per_batch])
+    if not return_centres:
+        return masks
+    return masks, dict(centres=centres, sizes=sizes, counts=counts, batches=batches, masked=masked_out, capped=capped,
+                       exhausted=exhausted, candidates=cand)
