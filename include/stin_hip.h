@@ -1786,6 +1786,54 @@ int stin_poisson_rounds_f64(const double* points, int64_t C, double radius, cons
 int stin_first_occurrence_i64(const int64_t* ids, int64_t n, int64_t N, int64_t* first_pos, uint8_t* keep, int32_t* bad,
                               stin_stream_t stream);
 
+/* --------------------------------------------------------------------------- Geodesic distances --
+ * Circle masks whose radius is a length along the surface in the units of the vertices, not a hop count (stin_geodesic.hip):
+ * shortest paths over the mesh EDGES weighted by their Euclidean length, from many centres at once, cut off at the radius.  This is
+ * the Dijkstra metric of the edge graph, NOT the exact polyhedral geodesic (which crosses faces); it is never shorter than that.
+ * A contract of the project's own; tests/_geodesic_oracle.py restates it (heap Dijkstra, and Bellman-Ford sweeps) and the device
+ * agrees bit for bit.  All arithmetic is fp64, every product and sum rounded once (no contraction), division and sqrt are IEEE.
+ *
+ * Edge length (stin_geodesic_lengths_f64).  vertices [N, 3] fp64 (float32 input is promoted first); rowptr [N + 1], col [E2] the
+ *     int32 CSR of stin_mask_adjacency_i64 (E2 = 2E slots, reused as it is; its row order is unspecified and nothing depends on
+ *     it).  length [E2] fp64, slot e of row u with v = col[e]:  d = pos[u] - pos[v],  len = sqrt((dx dx + dy dy) + dz dz).
+ *     Symmetric bit for bit (d only changes sign).  flags: one int64 DEVICE word written by the call - bit 0: a length is not
+ *     finite (a non-finite vertex, or an overflow), bit 1: col[e] outside [0, N) (nothing is read through it, the slot gets +inf).
+ *     A slot whose length is not finite is never relaxed.  One pass, no workspace.
+ * Distance.  Instance m with the source set S_m and a cut-off cap > 0 (+inf allowed): D[m][v] = the minimum, over all edge paths
+ *     from any source of S_m to v, of the path's length folded from the source outward, ((0 + l1) + l2) + ...  This is the unique
+ *     fixed point of D[s] = 0, D[v] = min_u fl(D[u] + len(u, v)) (fp64 addition of non-negative numbers is monotone), so heap
+ *     Dijkstra and ANY order of relaxations reach the same bits.  Result: dist[m][v] = D[m][v] where D < cap (strict), +inf
+ *     elsewhere - a vertex at exactly cap, an unreachable and an isolated vertex all give +inf.  (Prefix sums are monotone, so not
+ *     expanding a vertex with D >= cap changes nothing below cap.)  Duplicate edges, self loops, zero-length edges (coincident
+ *     vertices) and repeated sources are legal.
+ *     stin_geodesic_begin_f64: dist [M][N] = +inf, then 0 at sources[i] of instance source_instance[i] (int32 [S], or NULL: all
+ *         instance 0), which are listed for round 0.  Writes state and prepares the workspace
+ *         (>= stin_geodesic_workspace_bytes(N, M); needs M * max(N, 1) < 2^31).
+ *     stin_geodesic_rounds_f64: `rounds` (1 .. 4096) launches, rounds first_round, first_round + 1, ... of the call sequence that
+ *         stin_geodesic_begin_f64 started (same dist, state, workspace, cap; first_round = rounds launched so far).  A round takes
+ *         the vertices listed for it, relaxes their edges (64-bit integer atomicMin on the bit patterns; no float atomics) and
+ *         lists every vertex it lowered for the next round (once: a stamp word per (m, v)); a workgroup follows the vertices it
+ *         lowered itself for up to `levels` (1 .. 64) levels in LDS before it lists them.  `levels` changes the number of rounds
+ *         and the work, never the result.  A round whose list is empty returns at once.  No host synchronisation, no kernel waits
+ *         for another workgroup (one last-arrival ticket per round), every in-kernel loop is bounded by its arguments.  N rounds are
+ *         enough for any input (a shortest path has fewer than N edges).
+ *     state: 4 x int64 DEVICE words - [0] flags: bit 1 a source or instance index out of range (left out), bit 2 the worklist is
+ *         not empty after the last round run (= not converged yet); [1] vertices waiting for the next round; [2] rounds that found
+ *         work; [3] directed edges relaxed so far (fl(D[u] + len) formed), the schedule's work.
+ * Mask value (stin_geodesic_mask_f64).  rings >= 1, 0 < radius < inf, ring = radius / rings:  mask[i] = 0 if dist[i] >= radius,
+ *     else min(rings, (int64) ceil((radius - dist[i]) / ring)): a centre gets `rings`, the rim 1, everything outside 0.
+ * Circle masks (preprocessing.circle_masks_geodesic; a host loop): circle_masks_on_surface's centre streams, batch rule and info,
+ *     with batch b of ALL masks still running in one distance call (one instance per mask) and cap = radius. */
+int stin_geodesic_lengths_f64(const double* vertices, int64_t N, const int32_t* rowptr, const int32_t* col, int64_t E2, double* length,
+                              int64_t* flags, stin_stream_t stream);
+size_t stin_geodesic_workspace_bytes(int64_t N, int num_instances);
+int stin_geodesic_begin_f64(const int64_t* sources, const int32_t* source_instance, int64_t S, int64_t N, int num_instances,
+                            double* dist, int64_t* state, void* workspace, size_t workspace_bytes, stin_stream_t stream);
+int stin_geodesic_rounds_f64(const int32_t* rowptr, const int32_t* col, const double* length, int64_t N, int64_t E2,
+                             int num_instances, double cap, double* dist, int first_round, int rounds, int levels, int64_t* state,
+                             void* workspace, size_t workspace_bytes, stin_stream_t stream);
+int stin_geodesic_mask_f64(const double* dist, int64_t count, double radius, int rings, int64_t* mask, stin_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -79,6 +79,12 @@
   ``stin_poisson_*``, ``stin_first_occurrence_i64``).  A contract of this project's own (include/stin_hip.h, "Surface samples"),
   NOT pinned against Open3D's ``sample_points_poisson_disk``; Euclidean spacing, hop-count radii.
 
+* ``geodesic_adjacency`` / ``geodesic_distance`` / ``circle_mask_from_centres_geodesic`` / ``circle_masks_geodesic`` - the same
+  masks with a radius that is a LENGTH in the units of the vertices: bounded multi-source shortest paths over the mesh edges
+  weighted by their Euclidean length (``stin_geodesic_*``: frontier rounds, 64-bit integer atomicMin on fp64 bit patterns), the
+  same bytes on every schedule and equal to heap Dijkstra's.  The Dijkstra metric of the edge graph, NOT the exact polyhedral
+  geodesic.  A contract of this project's own (include/stin_hip.h, "Geodesic distances").
+
 All take and return tensors in the reference's own formats.  Out of scope: reading mesh files (neither open3d nor plyfile exists
 here to pin a reader against: vertices, faces and colours are inputs), and the Matterport and S3DIS label paths.
 """
@@ -2677,6 +2683,243 @@ def circle_masks_on_surface(vertices, faces, radius=16, frac_masked_vertices=0.2
         capped[m, 0] = not done
         masked_out[m, 0] = masked
         centres.append([per_batch])
+    if not return_centres:
+        return masks
+    return masks, dict(centres=centres, sizes=sizes, counts=counts, batches=batches, masked=masked_out, capped=capped,
+                       exhausted=exhausted, candidates=cand)
+
+
+# -------------------------------------------------------------------------------------------------------- geodesic circle masks
+GEODESIC_LEVELS = 4                  # LDS levels a workgroup follows inside one round (changes rounds and work, never the result)
+_GEODESIC_GROUP = 16                 # rounds per host read of geodesic_distance (max_rounds=None)
+_GEODESIC_CALL = 4096                # rounds per stin_geodesic_rounds_f64 call (its upper bound)
+
+
+def _geodesic_edges(n, dev, edge_index, faces, what):
+    if edge_index is not None:
+        return edge_index.to(dev)
+    if faces is None:
+        raise ValueError('%s: give edge_index, faces or adjacency' % what)
+    if not (torch.is_tensor(faces) and faces.is_cuda):
+        raise TypeError('faces must be a CUDA tensor (no CPU fallback exists)')
+    return edges_from_faces(_checked_faces(faces, n, what), n)
+
+
+def geodesic_adjacency(vertices, edge_index=None, faces=None, check=True):
+    """The weighted CSR of the geodesic pass: ``mask_adjacency``'s (rowptr [N + 1], col [2E]) as it is, plus length float64 [2E],
+    the Euclidean length of every slot's edge in fp64: sqrt((dx dx + dy dy) + dz dz), symmetric bit for bit
+    (``stin_geodesic_lengths_f64``).  vertices [N, >= 3] float (float32 is promoted first); the edges are edge_index [2, E] taken as
+    undirected, or the sides of `faces`.  check=True reads one status word: ValueError for a length that is not finite (a
+    non-finite vertex of an edge), IndexError for an endpoint outside [0, N).  Unchecked, such an edge is simply never walked."""
+    v = _xyz64(vertices, 'vertices')
+    lib = _lib.load()
+    n, dev = int(v.shape[0]), v.device
+    ei = _geodesic_edges(n, dev, edge_index, faces, 'geodesic_adjacency')
+    rowptr, col = mask_adjacency(ei, n, check=check)
+    e2 = 2 * int(ei.shape[1])
+    col = col[:e2]
+    length = torch.empty(max(e2, 1), dtype=torch.float64, device=dev)[:e2]
+    flags = torch.empty(1, dtype=torch.int64, device=dev)
+    _lib.check(lib.stin_geodesic_lengths_f64(_ptr(v), n, _ptr(rowptr), _ptr(col), e2, _ptr(length), _ptr(flags), _stream(v)),
+               'stin_geodesic_lengths_f64')
+    if check:
+        fl = int(flags.item())
+        if fl & 2:
+            raise IndexError('geodesic_adjacency: an edge refers to a vertex outside [0, %d)' % n)
+        if fl & 1:
+            raise ValueError('geodesic_adjacency: the length of an edge is not finite (a non-finite vertex)')
+    return rowptr, col, length
+
+
+def _geodesic_adjacency_arg(adjacency, n, what):
+    rowptr, col, length = adjacency
+    if not (rowptr.is_cuda and rowptr.dtype == torch.int32 and col.dtype == torch.int32 and length.dtype == torch.float64):
+        raise TypeError('%s: adjacency must be what geodesic_adjacency returns (int32, int32, float64 on the GPU)' % what)
+    if int(rowptr.numel()) != n + 1 or int(col.numel()) != int(length.numel()):
+        raise ValueError('%s: adjacency does not belong to %d vertices' % (what, n))
+    return rowptr.contiguous(), col.contiguous(), length.contiguous()
+
+
+def _geodesic_run(adj, n, sources, inst, M, cap, max_rounds, levels, what):
+    """-> (dist float64 [M, n], state int64 [4] on the device, rounds launched).  max_rounds=None: until the worklist is empty."""
+    lib = _lib.load()
+    rowptr, col, length = adj
+    dev = rowptr.device
+    e2 = int(col.numel())
+    if M * max(n, 1) >= (1 << 31) - 1:
+        raise ValueError('%s: num_instances * N must stay below 2^31' % what)
+    dist = torch.empty(M, max(n, 1), dtype=torch.float64, device=dev)[:, :n]
+    state = torch.zeros(4, dtype=torch.int64, device=dev)
+    ws_bytes = lib.stin_geodesic_workspace_bytes(n, M)
+    ws = torch.empty(max(ws_bytes, 1), dtype=torch.uint8, device=dev)
+    S = int(sources.numel())
+    _lib.check(lib.stin_geodesic_begin_f64(_ptr(sources) if S else None, _ptr(inst) if inst is not None and S else None, S, n, M,
+                                           _ptr(dist) if n else None, _ptr(state), _ptr(ws), ws_bytes, _stream(rowptr)),
+               'stin_geodesic_begin_f64')
+    launched = 0
+
+    def rounds(k):
+        nonlocal launched
+        while k > 0:
+            step = min(k, _GEODESIC_CALL)
+            _lib.check(lib.stin_geodesic_rounds_f64(_ptr(rowptr), _ptr(col), _ptr(length), n, e2, M, cap, _ptr(dist) if n else None,
+                                                    launched, step, int(levels), _ptr(state), _ptr(ws), ws_bytes, _stream(rowptr)),
+                       'stin_geodesic_rounds_f64')
+            launched, k = launched + step, k - step
+
+    if max_rounds is not None:
+        rounds(int(max_rounds))
+        return dist, state, launched
+    while True:
+        st = state.tolist()
+        if st[0] & 2:
+            raise IndexError('%s: a source lies outside [0, %d) or its instance outside [0, %d)' % (what, n, M))
+        if st[1] == 0:
+            return dist, state, launched
+        if launched >= n + _GEODESIC_GROUP:                                 # (a shortest path has fewer than N edges)
+            raise RuntimeError('%s: %d vertices still listed after %d rounds' % (what, st[1], launched))
+        rounds(_GEODESIC_GROUP)
+
+
+def _geodesic_sources(sources, source_instance, num_instances, n, dev, what):
+    s = torch.as_tensor(sources, dtype=torch.int64).reshape(-1).to(dev).contiguous()
+    M = int(num_instances)
+    if M < 1:
+        raise ValueError('%s: num_instances must be >= 1' % what)
+    inst = None
+    if source_instance is not None:
+        inst = torch.as_tensor(source_instance).reshape(-1).to(device=dev, dtype=torch.int32).contiguous()
+        if inst.numel() != s.numel():
+            raise ValueError('%s: one instance per source' % what)
+    return s, inst, M
+
+
+def geodesic_distance(vertices, sources, edge_index=None, faces=None, max_distance=None, source_instance=None, num_instances=1,
+                      adjacency=None, max_rounds=None, levels=None, return_info=False):
+    """Distances along the mesh EDGES, weighted by their Euclidean length in the units of the vertices, to the nearest of `sources`:
+    float64 [N] (CUDA), or [num_instances, N] when `source_instance` (one int per source) spreads the sources over several
+    independent instances that run in the same launches.  The Dijkstra metric of the edge graph - NOT the exact polyhedral geodesic,
+    which crosses faces - cut off at max_distance: D[v] where D[v] < max_distance (strict), +inf elsewhere and for unreachable
+    vertices (None: no cut-off).  D is the minimum over all edge paths of the length folded from the source outward in fp64, the
+    same bytes on every schedule and equal to heap Dijkstra's (include/stin_hip.h, "Geodesic distances"; csrc/stin_geodesic.hip:
+    frontier rounds, 64-bit integer atomicMin on the bit patterns).  Edges: edge_index, the sides of `faces`, or a ready
+    `adjacency` from ``geodesic_adjacency``.  Runs on the GPU only.  IndexError for a source outside [0, N); no sources: all +inf.
+    max_rounds=None: rounds are launched %d at a time and one count is read per group until the worklist is empty (RuntimeError
+    after N rounds, which no input needs).  max_rounds=k: exactly k round launches and NO host synchronisation; returns
+    (dist, status) with status int64 [4] on the device: [0] flags (bit 1: a source out of range, bit 2: not converged), [1]
+    vertices still listed, [2] rounds that found work, [3] directed edges relaxed.
+    levels: LDS levels per round (default GEODESIC_LEVELS; changes rounds and work, never the result).  return_info=True (with
+    max_rounds=None): also a dict with 'rounds', 'launched' and 'relaxed'.""" % _GEODESIC_GROUP
+    import math
+    what = 'geodesic_distance'
+    v = _xyz64(vertices, 'vertices')
+    n, dev = int(v.shape[0]), v.device
+    cap = math.inf if max_distance is None else float(max_distance)
+    if not cap > 0.0:
+        raise ValueError('%s: max_distance must be > 0' % what)
+    if max_rounds is not None and int(max_rounds) < 1:
+        raise ValueError('%s: max_rounds must be >= 1' % what)
+    s, inst, M = _geodesic_sources(sources, source_instance, num_instances, n, dev, what)
+    adj = (_geodesic_adjacency_arg(adjacency, n, what) if adjacency is not None
+           else geodesic_adjacency(v, edge_index=edge_index, faces=faces))
+    dist, state, launched = _geodesic_run(adj, n, s, inst, M, cap, max_rounds, levels or GEODESIC_LEVELS, what)
+    out = dist if source_instance is not None or M > 1 else dist[0]
+    if max_rounds is not None:
+        return out, state
+    if return_info:
+        st = state.tolist()
+        return out, dict(rounds=st[2], launched=launched, relaxed=st[3])
+    return out
+
+
+def _geodesic_mask_values(dist, radius, rings):
+    lib = _lib.load()
+    d = dist.contiguous()
+    mask = torch.empty(d.shape, dtype=torch.int64, device=d.device)
+    _lib.check(lib.stin_geodesic_mask_f64(_ptr(d) if d.numel() else None, int(d.numel()), float(radius), int(rings),
+                                          _ptr(mask) if d.numel() else None, _stream(d)), 'stin_geodesic_mask_f64')
+    return mask
+
+
+def _geodesic_radius(radius, rings, what):
+    import math
+    r = float(radius)
+    if not (r > 0.0 and math.isfinite(r)):
+        raise ValueError('%s: radius must be positive and finite' % what)
+    if int(rings) < 1:
+        raise ValueError('%s: rings must be >= 1' % what)
+    return r, int(rings)
+
+
+def circle_mask_from_centres_geodesic(vertices, centres, radius, rings=16, edge_index=None, faces=None, adjacency=None):
+    """``circle_mask_from_centres`` with a metric radius: int64 [N] (CUDA), mask[v] = 0 where the edge-path distance D[v] from the
+    nearest centre (``geodesic_distance``, cut off at `radius`) is >= radius, else min(rings, ceil((radius - D[v]) / (radius /
+    rings))): a centre gets `rings`, the rim 1.  With rings = 16 the loss weight 0.99^mask spans the range of the hop masks.
+    radius is a length in the units of the vertices; the metric is Dijkstra's on the edge graph, not the polyhedral geodesic."""
+    what = 'circle_mask_from_centres_geodesic'
+    r, rings = _geodesic_radius(radius, rings, what)
+    dist = geodesic_distance(vertices, centres, edge_index=edge_index, faces=faces, max_distance=r, adjacency=adjacency)
+    return _geodesic_mask_values(dist, r, rings)
+
+
+def circle_masks_geodesic(vertices, faces, radius, frac_masked_vertices=0.25, num_masks=1, seed=0, rings=16, spacing=None,
+                          candidates=None, edge_index=None, max_iters=32, return_centres=False):
+    """``circle_masks_on_surface`` with a metric radius: int64 [num_masks, N], ready for ``scene_io.write_circle_masks``.  The same
+    centre streams (``surface_centres(candidates, surface_stream_seed(seed, m), spacing)``), the same batch rule (10 centres, then
+    k = int(total * (frac / cur - 1)) more until cur >= frac or k <= 0; a short stream ends the mask `exhausted`) and the same info
+    dict; the value is ``circle_mask_from_centres_geodesic``'s, so a hole has the same physical size whatever the local
+    tessellation and on every hierarchy of a scan.  Batch b of ALL masks still running is ONE distance call (one instance per
+    mask); one host read per batch (an offline path).  Distances run on the mesh's own edges, or on `edge_index` when given.
+    Dijkstra's metric on the edge graph, not the polyhedral geodesic; the Poisson-disk `spacing` stays Euclidean."""
+    what = 'circle_masks_geodesic'
+    r, rings = _geodesic_radius(radius, rings, what)
+    v, f, cum, state, st = _surface_mesh(vertices, faces, what)
+    n, dev, M, it = int(v.shape[0]), v.device, int(num_masks), int(max_iters)
+    frac = float(frac_masked_vertices)
+    if M < 1 or it < 1:
+        raise ValueError('%s: num_masks and max_iters must be >= 1' % what)
+    cand = int(candidates) if candidates is not None else default_surface_candidates(_surface_area(st), n, spacing)
+    adj = geodesic_adjacency(v, edge_index=edge_index.to(dev) if edge_index is not None else edges_from_faces(f, n))
+    masks = torch.zeros(M, n, dtype=torch.int64, device=dev)
+    sizes, counts = torch.zeros(M, 1, it, dtype=torch.int64), torch.zeros(M, 1, it, dtype=torch.int64)
+    batches, masked_out = torch.zeros(M, 1, dtype=torch.int64), torch.zeros(M, 1, dtype=torch.int64)
+    capped, exhausted = torch.ones(M, 1, dtype=torch.bool), torch.zeros(M, 1, dtype=torch.bool)
+    streams = [_surface_centres(v, f, cum, state, cand, surface_stream_seed(seed, m), spacing) for m in range(M)]
+    centres = [[[]] for _ in range(M)]
+    pos, total, k, masked = [0] * M, [0] * M, [10] * M, [0] * M
+    running = list(range(M))
+    for b in range(it):
+        if not running:
+            break
+        takes = [streams[m][pos[m]:pos[m] + k[m]] for m in running]
+        if sum(int(t.numel()) for t in takes):
+            inst = torch.cat([torch.full((int(t.numel()),), j, dtype=torch.int32, device=dev) for j, t in enumerate(takes)])
+            dist = geodesic_distance(v, torch.cat(takes), max_distance=r, source_instance=inst, num_instances=len(running),
+                                     adjacency=adj)
+            idx = torch.as_tensor(running, device=dev)
+            masks[idx] = torch.maximum(masks[idx], _geodesic_mask_values(dist, r, rings))
+            for m, c in zip(running, (masks[idx] > 0).sum(dim=1).tolist()):
+                masked[m] = int(c)
+        still = []
+        for m, take in zip(running, takes):
+            got = int(take.numel())
+            pos[m], total[m] = pos[m] + got, total[m] + got
+            centres[m][0].append(take)
+            sizes[m, 0, b], counts[m, 0, b], batches[m, 0] = got, masked[m], b + 1
+            if got < k[m]:
+                exhausted[m, 0], capped[m, 0] = True, False
+                continue
+            cur = masked[m] / n
+            if cur >= frac:
+                capped[m, 0] = False
+                continue
+            k[m] = min(int(total[m] * (frac / cur - 1)), n)
+            if k[m] <= 0:
+                capped[m, 0] = False
+                continue
+            still.append(m)
+        running = still
+    masked_out[:, 0] = torch.as_tensor(masked)
     if not return_centres:
         return masks
     return masks, dict(centres=centres, sizes=sizes, counts=counts, batches=batches, masked=masked_out, capped=capped,
