@@ -463,7 +463,8 @@ int stin_linear_tanh_bwd_f32(const float* g, const float* y, const float* x, int
                              float* dx, int64_t lddx, float* dW, float* db, void* workspace, size_t workspace_bytes,
                              stin_stream_t stream);
 
-/* dst[n, c] += alpha * src[n, c] * [rowptr[n + 1] > rowptr[n]] for c in [c0, c1), in place: the translation-invariant SAGE
+/* dst[n, c] += alpha * src[n, c] * [rowptr[n + 1] > rowptr[n]] for c in [c0, c1), in place (fl(dst + fl(alpha src)); bf16 rows: the
+ * same in fp32, rounded once to bf16; rows without an in-edge and the other columns are not written): the translation-invariant SAGE
  * message of models/modules/sage_conv_filter.py:87-90 (x_j[:, 3:9] -= x_i[:, 3:9]) under the mean aggregation, applied to the
  * aggregated rows (alpha = -1, rowptr = destination CSR) and, in the backward pass, to the input gradient. */
 int stin_cols_axpy_rowmask_f32(float* dst, int64_t ldd, const float* src, int64_t lds, const int32_t* rowptr, int64_t N, int c0,
@@ -529,9 +530,10 @@ int stin_bn_running_stats_f32(const float* mean, const float* rstd, int C, float
  * stin_scmn_unpack_f32: dwcat [2 h2, cin] -> dW1 in the reference layout (d/dWa = top, d/dWb = bottom - top; trans_inv: bottom - top).
  * stin_bn_affine_res_fwd_f32: y = [relu](res + [rowptr[r + 1] > rowptr[r]] (gamma ((x - mean) rstd) + beta)) over N rows - the
  *   BatchNorm affine of the aggregated rows, the "vertex has an in-edge" mask, the ResBlock's `x + f(x)` and its ReLU
- *   (singleconvmeshnet.py:60-66) in one pass; rowptr / res may be NULL.
+ *   (singleconvmeshnet.py:60-66) in one pass; rowptr / res may be NULL.  Every operation is rounded on its own, in this order:
+ *   gamma * ((x - mean) * rstd) + beta, times 1.0 or 0.0 (the mask IS a multiplication: 0 * inf = NaN), res + ., relu = (z > 0 ? z : +0).
  * stin_relu_mask_bwd_f32: g_eff = g [y > 0] (relu != 0; else g), g_in = g_eff [row has an in-edge]; g_eff may be NULL; both
- *   outputs are [N, C] with pitch C. */
+ *   outputs are [N, C] with pitch C.  A y of +0, -0 or NaN fails y > 0 and gives +0; y is not read when relu == 0. */
 /* The per-EDGE Linear of that layer with the BatchNorm1d + ReLU of its input applied while the operand rows are staged
  * (edge_conv_filter.py:36-40: Lin -> BN -> ReLU -> Lin): the normalised [E, 2 cout] matrix is never written.
  *   stin_gemm_nt_bn_f32: C [M, Nc] = relu(gamma ((A - mean) rstd) + beta) W^T, W plain fp32 [Nc, K] (no pre-split flags);
@@ -597,10 +599,18 @@ int stin_concat_unpool_f32(const float* skip, int64_t ld_skip, const float* coar
  * (stin_edge_relu_mean_fwd_ti_f32: mode 1's values up to one ulp of A) and the backward pass carries D = dB - dA in H columns
  * (stin_edge_relu_mean_bwd_mask_ti_f32) - half the first Linear's GEMM work in every direction.  fp32 rows with a saved-mask
  * width H; unpack then takes dW1 = rows [0, H) as they are and leaves db1 to the caller (the column sums of dA).
- * unpack: dwb [Yw, Cin+1] (gemm_tn output: weight grad | bias grad) -> dW1, db1, dWs, dbs; and
- *   dw2b [Cout, H+1] (optional) -> contiguous dW2 [Cout, H], db2 [Cout].
+ * unpack: dwb [Yw, Cp + 1] (gemm_tn output over the padded rows: Cp weight-gradient columns, of which the first Cin are used, and
+ *   the bias gradient in column Cp) -> dW1, db1, dWs, dbs; and dw2b [Cout, H+1] (optional) -> contiguous dW2 [Cout, H], db2 [Cout].
+ *   dWa = the top H rows, dWb = bottom - top (one fp32 subtraction; trans_inv 1: dW1 = bottom - top); db1 / dbs / db2 may be NULL;
+ *   outputs the mode does not have (db1 in COMPACT mode, dWs / dbs without a shortcut, dW2 / db2 without dw2b) are left alone.
+ * pack, to the bit: Wa - Wb is one fp32 subtraction, -W1 a sign flip, the padding columns Cin .. Cp - 1 are +0, a NULL b1 / bs counts
+ *   as zeros; w2s is written when it is passed (required with a fwd_split).  Storage STIN_GEMM_W_BF16 rounds each value to bf16
+ *   (nearest even) into [rows][cols] bf16 at the START of the operand's buffer; the second half of the buffer is not written.
+ *   The two pieces of a split precision are hi = rn16(s v), lo = rn16(s v - hi) with s = 64 for fp16 pieces and 1 for bf16 pieces
+ *   (rn16: round to nearest even into the 16-bit format; the subtraction in fp32), in the k-group or fragment layout above.
  * (models/modules/edge_conv_filter.py:46-52, models/surfacetextureinpaintingnet.py:505-506)
- * norm_bwd_coef: k = -rstd^3 T1 inv_cnt, m = -rstd S0 inv_cnt for stin_norm_act_bwd_f32.
+ * norm_bwd_coef: k = -rstd^3 T1 inv_cnt, m = -rstd S0 inv_cnt for stin_norm_act_bwd_f32; evaluated in fp32 as
+ *   k = ((-((rstd rstd) rstd)) T1) inv_cnt[b] and m = (-(rstd S0)) inv_cnt[b], operands [B, C], inv_cnt [B].
  * fwd_split / bwd_split (0, STIN_GEMM_F16X3 or STIN_GEMM_BF16X3, optionally | STIN_GEMM_W_FRAG): write the forward
  * operands (wcat, and a copy w2s [Cout, H] of W2) / the backward operands (wcatT, w2T) directly in the
  * STIN_GEMM_W_PRESPLIT form of that precision (each operand in fragment order where its shape allows, see W_FRAG).
@@ -625,7 +635,8 @@ int stin_edgeconv_unpack_grads_f32(const float* dwb, const float* dw2b, int Cin,
 int stin_norm_bwd_coef_f32(const float* T1, const float* S0, const float* rstd, const float* inv_cnt, int B, int C,
                            float* k, float* m, stin_stream_t stream);
 /* linspace-slice quirk of FastInstanceNorm (fastinstancenorm.py:53-82): m = -(rstd S0 + U) inv_cnt, where
- * U = stin_colreduce(STIN_RED_COEF_XC, coef = k) - the second coefficient of stin_norm_act_bwd_* when slices != graphs. */
+ * U = stin_colreduce(STIN_RED_COEF_XC, coef = k) - the second coefficient of stin_norm_act_bwd_* when slices != graphs; evaluated
+ * as (-((rstd S0) + U)) inv_cnt[b], every operation rounded on its own. */
 int stin_norm_bwd_coef_m_quirk_f32(const float* S0, const float* U, const float* rstd, const float* inv_cnt, int B, int C,
                                    float* m, stin_stream_t stream);
 
@@ -634,9 +645,19 @@ int stin_norm_bwd_coef_m_quirk_f32(const float* S0, const float* U, const float*
  * (trainers/inpainting3d_trainer.py:127-137): pred = mask > 0 ? out : color,
  * loss = mean |pred - color| * 0.99^mask (use_weight = trainer.use_mask_weighted_loss),
  * grad = dloss/dout.  fp64 block partials summed in a fixed order.  mask: int64 [N].
+ *   To the bit: inv = fl(1 / (float)(N C)); on a row with mask > 0, d = out - color, grad = (sign(d) w) inv with w = powf(0.99f,
+ *   (float)mask) or 1, and the element's term is (double)(|d| w); other rows give grad = +0 and term 0.  Element t belongs to block
+ *   t / 256; a block adds its 256 terms in a pairwise tree (for s = 128, 64 .. 1: term[i] += term[i + s], i < s); the finaliser's
+ *   thread i adds the block sums i, i + 256, i + 512 .. in that order, the 256 results go through the same tree, and
+ *   loss = (float)(sum * (double)inv).  stin_total_variation_f32 folds its per-row sums the same way (row r in block r / 256).
  * adam: torch.optim.Adam(amsgrad) on ONE flat parameter/gradient/state buffer (the reference's
  * optimizer, experiments/3d_inpainting/config/...json:95-102), step = 1-based update count; the hyper-parameters are
  * doubles (python floats in torch) and the bias corrections 1 - beta^step are formed in double on the host, as torch does.
+ *   To the bit: the scalars -(lr / (1 - beta1^step)), 1 - beta1, beta2, 1 - beta2, eps, weight_decay and sqrt(1 - beta2^step) are
+ *   formed in double and cast once to fp32; per element, every operation rounded on its own: g' = g + wd p (only when wd != 0),
+ *   m' = m + (1 - beta1) (g' - m), v' = beta2 v + ((1 - beta2) g') g', vh = amsgrad ? max(vmax, v') : v' (vmax' = vh),
+ *   p' = p + (nss m') / (sqrt(vh) / bc2s + eps).  amsgrad = 0: vmax may be NULL and is not touched.  Bases that are all 16-byte
+ *   aligned take a four-wide kernel, others a scalar one: same bits.
  */
 size_t stin_masked_l1_workspace_bytes(int64_t N, int C);
 int stin_masked_l1_loss_f32(const float* out, const float* color, const int64_t* mask, int64_t N, int C,
@@ -667,13 +688,15 @@ int stin_seg_ce_bwd_f32(const float* logits, int64_t ld, const int64_t* target, 
                         stin_stream_t stream);
 /* graph total variation, the per-step smoothness metric of the trainer (utils/metrics/graph_metrics.py:34-38,
  * trainers/inpainting3d_trainer.py:254-263): out[0] = sum_e sum_c |x[src_e, c] - x[dst_e, c]| / (N * C) over the
- * destination CSR the forward pass has built (rowptr_dst / col_dst), fp64 partial sums in a fixed order. */
+ * destination CSR the forward pass has built (rowptr_dst / col_dst), fp64 partial sums in a fixed order: per destination row an
+ * fp64 sum over its CSR entries, in order, of the fp32 channel sum (c = 0 .. C - 1, from 0) of |x[col[e], c] - x[row, c]|; the rows
+ * are folded as the loss folds its elements, with inv = fl(1 / fl((float)N (float)C)). */
 size_t stin_total_variation_workspace_bytes(int64_t N);
 int stin_total_variation_f32(const float* x, int64_t ldx, const int32_t* rowptr_dst, const int32_t* col_dst, int64_t N, int C,
                              float* out, void* workspace, size_t workspace_bytes, stin_stream_t stream);
 /* graph Laplace of the same metrics module (utils/metrics/graph_metrics.py:6-16, GraphLaplaceOperator: propagate [1 | x] with
  * aggr = 'add', then prop[:, 1:] - prop[:, 0:1] * x): out[i, c] = sum_{j in N(i)} x[j, c] - deg_i x[i, c] over the destination CSR,
- * fp32 adds in edge order - the numbers of the reference's composition, bit for bit. */
+ * fp32 adds in edge order - the numbers of the reference's composition, bit for bit: s - fl((float)deg_i x[i, c]), s summed from 0. */
 int stin_graph_laplace_f32(const float* x, int64_t ldx, const int32_t* rowptr_dst, const int32_t* col_dst, int64_t N, int C,
                            float* out, int64_t ldo, stin_stream_t stream);
 /* the trainer's seven per-step metrics in one call (trainers/inpainting3d_trainer.py:254-271: loss, l1, mse, graph_tv, graph_lap_var,

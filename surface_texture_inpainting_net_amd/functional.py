@@ -996,7 +996,7 @@ class EdgeConvBlockFn(torch.autograd.Function):
             edge_relu_mean_bwd_src(A, B, dhE, edges.inv_deg, edges.by_src, dY[:, H:2 * H])
         if ctx.has_shortcut:
             dY[:, oS:].copy_(g)                     # (the whole-block C call lets this ride on the edge launch)
-        dwb = gemm_tn(dY, x, ones_column=True, precision=PREC_BWD)           # [Yw, Cin + 1]: packed weight grad | bias grad
+        dwb = gemm_tn(dY, x, ones_column=True, precision=PREC_BWD)           # [Yw, Cp + 1]: packed weight grad (Cin columns used) | bias grad in column Cp
         # dx = dY Wcat (+ g: the identity-residual path, added in the GEMM epilogue); skipped when the block input
         # needs no gradient (the network input of the first block)
         dx = None
