@@ -1857,6 +1857,68 @@ int stin_geodesic_rounds_f64(const int32_t* rowptr, const int32_t* col, const do
                              void* workspace, size_t workspace_bytes, stin_stream_t stream);
 int stin_geodesic_mask_f64(const double* dist, int64_t count, double radius, int rings, int64_t* mask, stin_stream_t stream);
 
+/* --------------------------------------------------------------------------------- Harmonic fill --
+ * Harmonic (diffusion, Laplace) inpainting on a graph (stin_harmonic.hip): every masked vertex becomes the weighted mean of its
+ * neighbours with the known vertices as boundary values - the zero of the graph Laplacian on the hole, the minimiser of
+ * sum_edges w (x_i - x_j)^2 - by Jacobi-preconditioned conjugate gradients in a FIXED order of operations.  A contract of the
+ * project's own; tests/_harmonic_oracle.py restates it in numpy and the device agrees bit for bit.  A graph Laplacian with uniform
+ * or given (e.g. inverse-length) weights, NOT cotangent weights; one global solve for all holes, zero start.
+ * All arithmetic is fp64 and IEEE: every product and every sum is rounded once (no contraction), `/` is the correctly rounded
+ * division.  "fold" = a plain left-to-right sum that starts from +0.0.
+ *
+ * Inputs.  rowptr [N + 1], col [E2] int32: stin_mask_adjacency_i64's CSR as it is (slot order is part of the input: the folds
+ *     below follow it).  weight [E2] fp64 aligned with col, or NULL = every weight is exactly 1.0.  values [N, C] float32
+ *     (contiguous), 1 <= C <= STIN_HARMONIC_MAX_C, promoted to fp64.  masked [N] uint8, non-zero = to be filled.
+ *     A slot with col == row is skipped everywhere; a duplicate slot counts as often as it occurs.  A slot whose col lies outside
+ *     [0, N), or a row whose rowptr range is not inside [0, E2], is skipped and sets status bit 2 (nothing is read through it).
+ * Reached.  A masked vertex is reached if it has a slot to a known (unmasked) vertex or to a reached masked vertex: the least fixed
+ *     point.  stin_harmonic_reach_u8 computes it in rounds over one byte per vertex (0 known, 1 masked, 2 reached; a byte only ever
+ *     goes 1 -> 2, so a round may see flags set in the same launch: the fixed point is the same).  first_round == 0 initialises
+ *     the bytes and the state table; every round is one ordinary launch, `rounds` (1 .. 64) of them per call; the caller reads
+ *     state[3] (vertices reached by the LAST round of the call) and stops when it is 0.  Masked vertices that are never reached
+ *     (an isolated vertex, a masked component with no known vertex on its rim) take no part in the solve and receive `fill`.
+ * System.  The unknowns are the reached vertices in ascending vertex id, u = 0 .. n_U - 1.  Over the slots of row i in ascending
+ *     slot order (self slots skipped):  d_i = fold of w;  b_i = fold of w * v_j over the slots whose j is known;
+ *     (A p)_i = d_i * p_i - acc,  acc = fold of w * p_j over the slots whose j is an unknown.  Status bit 0: a weight of a slot of an
+ *     unknown's row is not finite or not > 0; bit 1: a known value next to an unknown is not finite (any channel).
+ * Inner products.  <a, b>: tile t holds the products a_u * b_u of the unknowns [256 t, 256 t + 256), missing entries +0.0; inside
+ *     a tile s[j] += s[j + h] for h = 128, 64, ..., 1 (j < h); the tile sums s[0] are folded in ascending t.  Independent of the
+ *     launch geometry.
+ * Iteration.  Every channel runs on its own scalars, x = 0 at the start:
+ *         r = b,  z = r / d,  p = z,  rz = <r, z>,  bb = <b, b>,  rr = bb;      bb == 0: the channel is DONE with 0 iterations
+ *     iteration k:  q = A p,  pq = <p, q>;  if not (pq > 0): the channel STOPS (flag bit 1, breakdown), nothing else changes;
+ *         alpha = rz / pq,  x = x + alpha * p,  r = r - alpha * q,  rr = <r, r>,  iterations += 1;
+ *         if rr <= (tol * tol) * bb: DONE (flag bit 0);
+ *         else  z = r / d,  rzn = <r, z>,  beta = rzn / rz,  p = z + beta * p,  rz = rzn.
+ *     A channel that is done or stopped is frozen on the device: later iterations change none of its bytes, so the result does not
+ *     depend on how many iterations are launched after it, nor on how they are grouped into calls.
+ *     Kernels: two ordinary launches per iteration over one workgroup per tile - the product (forms the new p of a row and of its
+ *     neighbours on the fly from z and the old p, ping-pong p buffers, writes the <p, q> tile sums) and the update (x, r, z and the
+ *     <r, r>, <r, z> tile sums); every workgroup folds the tile sums itself in the fixed order, so there are no atomics, no
+ *     cooperative launch and no grid-wide wait.  stin_harmonic_iterate_f64 launches iterations first_iteration ..
+ *     first_iteration + count - 1 (count 1 .. 4096) of the sequence stin_harmonic_setup_f64 started and then refreshes the state
+ *     table; no host synchronisation.
+ * Output (stin_harmonic_finish_f32).  out [N, C] float32: known rows = the input bit for bit, reached rows = (float) x, unreached
+ *     masked rows = fill.  Channels that are neither done nor stopped get flag bit 2 (not converged); their current x is the result.
+ * state: STIN_HARMONIC_STATE int64 DEVICE words.  [0] status bits (above); [1] n_U; [2] masked vertices never reached (written
+ *     by finish); [3] vertices reached by the last reach round run; [4] masked vertices; [5 .. 7] 0; then 4 words per channel c at
+ *     8 + 4 c: iterations, the bits of rr, the bits of bb, flags (bit 0 done, bit 1 breakdown, bit 2 not converged). Words of
+ *     channels >= C are 0.
+ * Call sequence: reach (until state[3] == 0; the host then knows n_U = state[1]), setup, iterate (any grouping), finish - all with
+ *     the same flag, state and workspace (>= stin_harmonic_workspace_bytes(N, E2, n_U, C), 0 = unsupported sizes). */
+#define STIN_HARMONIC_MAX_C 16
+#define STIN_HARMONIC_STATE 72
+size_t stin_harmonic_workspace_bytes(int64_t N, int64_t E2, int64_t n_unknown, int C);
+int stin_harmonic_reach_u8(const int32_t* rowptr, const int32_t* col, int64_t N, int64_t E2, const uint8_t* masked, int first_round,
+                           int rounds, uint8_t* flag, int64_t* state, stin_stream_t stream);
+int stin_harmonic_setup_f64(const int32_t* rowptr, const int32_t* col, const double* weight, int64_t N, int64_t E2,
+                            const float* values, int C, const uint8_t* flag, int64_t n_unknown, int64_t* state, void* workspace,
+                            size_t workspace_bytes, stin_stream_t stream);
+int stin_harmonic_iterate_f64(const double* weight, int64_t N, int64_t E2, int C, int64_t n_unknown, double tol, int first_iteration,
+                              int count, int64_t* state, void* workspace, size_t workspace_bytes, stin_stream_t stream);
+int stin_harmonic_finish_f32(const float* values, const uint8_t* flag, int64_t N, int64_t E2, int C, int64_t n_unknown, double tol,
+                             float fill, float* out, int64_t* state, void* workspace, size_t workspace_bytes, stin_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -85,6 +85,12 @@
   same bytes on every schedule and equal to heap Dijkstra's.  The Dijkstra metric of the edge graph, NOT the exact polyhedral
   geodesic.  A contract of this project's own (include/stin_hip.h, "Geodesic distances").
 
+* ``harmonic_fill`` / ``harmonic_inpaint`` / ``harmonic_adjacency`` - the classic non-learned inpainting baseline: harmonic
+  (diffusion, Laplace) fill, every masked vertex the weighted mean of its neighbours with the known vertices as boundary values,
+  by Jacobi-preconditioned CG in fp64 with every sum in a fixed order (``stin_harmonic_*``: two ordinary launches per iteration,
+  channels frozen when done), the same bytes on every run.  Uniform or inverse-length weights, NOT cotangent weights.  A contract
+  of this project's own (include/stin_hip.h, "Harmonic fill").
+
 All take and return tensors in the reference's own formats.  Out of scope: reading mesh files (neither open3d nor plyfile exists
 here to pin a reader against: vertices, faces and colours are inputs), and the Matterport and S3DIS label paths.
 """
@@ -2924,3 +2930,188 @@ def circle_masks_geodesic(vertices, faces, radius, frac_masked_vertices=0.25, nu
         return masks
     return masks, dict(centres=centres, sizes=sizes, counts=counts, batches=batches, masked=masked_out, capped=capped,
                        exhausted=exhausted, candidates=cand)
+
+
+# ----------------------------------------------------------------------------------------------------------------- harmonic fill
+_HARMONIC_REACH_GROUP = 16           # reach rounds per host read
+_HARMONIC_CALL = 4096                # iterations per stin_harmonic_iterate_f64 call (its upper bound)
+_HARMONIC_STATUS = ((1, 'a weight of an edge at a masked vertex is not finite or not positive'),
+                    (2, 'a known value next to a masked vertex is not finite'),
+                    (4, 'the adjacency refers to a vertex outside [0, N) or its rowptr is malformed'))
+
+
+def _harmonic_info(state, C):
+    """The device table (int64 [STIN_HARMONIC_STATE], on the host) -> a dict."""
+    st = [int(v) for v in state]
+    ch = [st[8 + 4 * c:12 + 4 * c] for c in range(C)]
+    bits = lambda w: float(torch.tensor([w], dtype=torch.int64).view(torch.float64)[0])     # the word holds a double's bits
+    return dict(status=st[0], n_unknown=st[1], n_unreached=st[2], n_masked=st[4], iterations=[w[0] for w in ch],
+                rr=[bits(w[1]) for w in ch], bb=[bits(w[2]) for w in ch], flags=[w[3] for w in ch],
+                converged=all(w[3] & 1 for w in ch), state=st)
+
+
+def harmonic_adjacency(edge_index, num_nodes, vertices=None):
+    """The CSR ``harmonic_fill`` builds when it is given edge_index: ``mask_adjacency``'s (or, with `vertices`,
+    ``geodesic_adjacency``'s with its lengths) with the slots of every row put in ascending neighbour id.  ``mask_adjacency`` fills
+    its rows with atomics, so its slot order changes from call to call, and the fixed-order sums of the harmonic fill follow the
+    slot order: sorted rows make the bytes of the result a function of the graph alone.  (Equal slots - a duplicate edge - carry
+    equal lengths, so their order among themselves does not matter.)"""
+    n = int(num_nodes)
+    if not edge_index.is_cuda:
+        raise TypeError('edge_index must be a CUDA tensor (no CPU fallback exists)')
+    if vertices is not None:
+        rowptr, col, length = geodesic_adjacency(vertices, edge_index=edge_index)
+    else:
+        rowptr, col = mask_adjacency(edge_index, n)
+        col, length = col[:2 * int(edge_index.shape[1])], None
+    rows = torch.repeat_interleave(torch.arange(n, device=col.device), (rowptr[1:] - rowptr[:-1]).long())
+    order = torch.argsort(rows * max(n, 1) + col.long(), stable=True)
+    col = col[order].contiguous()
+    return (rowptr, col) if length is None else (rowptr, col, length[order].contiguous())
+
+
+def harmonic_fill(values, masked, edge_index=None, adjacency=None, vertices=None, weights='uniform', tol=1e-6, max_iterations=None,
+                  fill=0.0, iterations_per_sync=16, return_info=False):
+    """Harmonic (diffusion, Laplace) inpainting on a graph: every masked vertex becomes the weighted mean of its neighbours, with
+    the known vertices as boundary values - the zero of the graph Laplacian on the hole, the minimiser of sum_edges w (x_i - x_j)^2
+    - by Jacobi-preconditioned CG in fp64 with every sum in a fixed order: the same bytes on every run and every grouping of the
+    launches, equal to the numpy restatement of include/stin_hip.h, "Harmonic fill" (csrc/stin_harmonic.hip).
+    values float32 [N, C] (C <= 16, CUDA); masked [N] (non-zero / True = fill it); the graph is edge_index [2, E] taken as
+    undirected (``harmonic_adjacency``: rows sorted, so the bytes depend on the graph alone), or a ready `adjacency` from
+    ``mask_adjacency`` / ``geodesic_adjacency`` / ``harmonic_adjacency`` (the sums follow its slot order).  weights: 'uniform' (every edge 1.0),
+    'inverse_length' (1.0 / length in torch fp64 from ``geodesic_adjacency``: needs `vertices` or an adjacency with lengths; a
+    zero-length edge gives inf and is an error) or a float64 tensor [2E] aligned with the adjacency's `col`.
+    -> float32 [N, C]: known rows bit for bit, masked rows the solution, masked vertices no path of masked vertices joins to a known
+    one (an isolated vertex, an island without a rim) `fill`.  A channel stops when ||r|| <= tol ||b||; max_iterations=None allows
+    n_U (the number of unknowns) iterations, launched `iterations_per_sync` at a time with one small host read per group.  An integer
+    max_iterations with iterations_per_sync=None launches exactly that many iterations with no host read between them and returns
+    (out, status) with the device table int64 [STIN_HARMONIC_STATE] (the reach pass before them still reads one count per group
+    of rounds).  return_info=True: (out, dict) with 'iterations', 'rr', 'bb', 'flags' per channel (bit 0 done, bit 1 breakdown, bit 2
+    not converged), 'n_unknown', 'n_unreached', 'converged' and 'state' (the whole table).  ValueError for a weight that is not finite or not positive and for a
+    non-finite known value on the rim.  Runs on the GPU only.
+    A graph Laplacian with uniform or inverse-length weights, not cotangent weights; one global solve, zero start."""
+    what = 'harmonic_fill'
+    if not (torch.is_tensor(values) and values.is_cuda and torch.is_tensor(masked) and masked.is_cuda):
+        raise TypeError('values and masked must be CUDA tensors (no CPU fallback exists)')
+    if values.dtype != torch.float32:
+        raise TypeError('values must be float32')
+    cmax = _lib.CONSTANTS['STIN_HARMONIC_MAX_C']
+    if values.dim() != 2 or not 1 <= int(values.shape[1]) <= cmax:
+        raise ValueError('values must be [N, C] with 1 <= C <= %d' % cmax)
+    n, C, dev = int(values.shape[0]), int(values.shape[1]), values.device
+    if int(masked.numel()) != n:
+        raise ValueError('masked needs one entry per vertex')
+    tol = float(tol)
+    if not tol >= 0.0:
+        raise ValueError('%s: tol must be >= 0' % what)
+    if max_iterations is not None and int(max_iterations) < 0:
+        raise ValueError('%s: max_iterations must be >= 0' % what)
+    if iterations_per_sync is None and max_iterations is None:
+        raise ValueError('%s: iterations_per_sync=None needs an integer max_iterations' % what)
+    if iterations_per_sync is not None and int(iterations_per_sync) < 1:
+        raise ValueError('%s: iterations_per_sync must be >= 1' % what)
+    lib = _lib.load()
+    # ---- the graph and its weights
+    length = None
+    if adjacency is not None:
+        adj = tuple(adjacency)
+        if not (len(adj) in (2, 3) and adj[0].is_cuda and adj[0].dtype == torch.int32 and adj[1].dtype == torch.int32):
+            raise TypeError('%s: adjacency must be what mask_adjacency or geodesic_adjacency returns (int32 on the GPU)' % what)
+        rowptr, col = adj[0].contiguous(), adj[1].contiguous()
+        length = adj[2] if len(adj) == 3 else None
+    else:
+        if edge_index is None:
+            raise ValueError('%s: give edge_index or adjacency' % what)
+        inv_len = isinstance(weights, str) and weights == 'inverse_length'
+        if inv_len and vertices is None:
+            raise ValueError("%s: weights='inverse_length' needs vertices (or an adjacency from geodesic_adjacency)" % what)
+        adj = harmonic_adjacency(edge_index.to(dev), n, vertices=vertices if inv_len else None)
+        rowptr, col, length = adj[0], adj[1], (adj[2] if inv_len else None)
+    if int(rowptr.numel()) != n + 1:
+        raise ValueError('%s: adjacency does not belong to %d vertices' % (what, n))
+    e2 = int(col.numel())
+    if isinstance(weights, str):
+        if weights == 'uniform':
+            w = None
+        elif weights == 'inverse_length':
+            if length is None:
+                raise ValueError("%s: weights='inverse_length' needs vertices or an adjacency from geodesic_adjacency" % what)
+            w = (1.0 / length.to(device=dev, dtype=torch.float64)).contiguous()
+        else:
+            raise ValueError("%s: weights must be 'uniform', 'inverse_length' or a float64 tensor" % what)
+    else:
+        if not (torch.is_tensor(weights) and weights.is_cuda and weights.dtype == torch.float64):
+            raise TypeError('%s: weights must be a float64 CUDA tensor' % what)
+        w = weights.reshape(-1).contiguous()
+    if w is not None and int(w.numel()) != e2:
+        raise ValueError('%s: one weight per adjacency slot (%d), got %d' % (what, e2, int(w.numel())))
+    vals = values.contiguous()
+    m8 = (masked.reshape(-1) != 0).to(torch.uint8).contiguous()
+    stream = _stream(vals)
+    flag = torch.empty(max(n, 1), dtype=torch.uint8, device=dev)
+    nstate = _lib.CONSTANTS['STIN_HARMONIC_STATE']
+    state = torch.zeros(nstate, dtype=torch.int64, device=dev)
+    # ---- reached: rounds until one changes nothing (a path of masked vertices has fewer than N of them)
+    launched = 0
+    while True:
+        _lib.check(lib.stin_harmonic_reach_u8(_ptr(rowptr), _ptr(col) if e2 else None, n, e2, _ptr(m8) if n else None, launched,
+                                              _HARMONIC_REACH_GROUP, _ptr(flag), _ptr(state), stream), 'stin_harmonic_reach_u8')
+        launched += _HARMONIC_REACH_GROUP
+        head = state[:5].tolist()
+        if head[3] == 0:
+            break
+        if launched >= n + _HARMONIC_REACH_GROUP:
+            raise RuntimeError('%s: the reach pass still changes after %d rounds' % (what, launched))
+    n_u = int(head[1])
+    ws_bytes = lib.stin_harmonic_workspace_bytes(n, e2, n_u, C)
+    if ws_bytes == 0:
+        raise ValueError('%s: sizes beyond the int32 CSR' % what)
+    ws = torch.empty(ws_bytes, dtype=torch.uint8, device=dev)
+    _lib.check(lib.stin_harmonic_setup_f64(_ptr(rowptr), _ptr(col) if e2 else None, _ptr(w), n, e2, _ptr(vals) if n else None, C,
+                                           _ptr(flag), n_u, _ptr(state), _ptr(ws), ws_bytes, stream), 'stin_harmonic_setup_f64')
+    budget = n_u if max_iterations is None else int(max_iterations)
+    done = 0
+
+    def iterate(k):
+        nonlocal done
+        while k > 0:
+            step = min(k, _HARMONIC_CALL)
+            _lib.check(lib.stin_harmonic_iterate_f64(_ptr(w), n, e2, C, n_u, tol, done, step, _ptr(state), _ptr(ws), ws_bytes,
+                                                     stream), 'stin_harmonic_iterate_f64')
+            done, k = done + step, k - step
+
+    if iterations_per_sync is None:
+        iterate(budget)
+    else:
+        while done < budget:
+            iterate(min(int(iterations_per_sync), budget - done))
+            st = state.tolist()
+            if st[0] or all(st[8 + 4 * c + 3] & 3 for c in range(C)):
+                break
+    out = torch.empty(n, C, dtype=torch.float32, device=dev)
+    _lib.check(lib.stin_harmonic_finish_f32(_ptr(vals) if n else None, _ptr(flag), n, e2, C, n_u, tol, float(fill),
+                                            _ptr(out) if n else None, _ptr(state), _ptr(ws), ws_bytes, stream),
+               'stin_harmonic_finish_f32')
+    if iterations_per_sync is None:
+        return out, state
+    st = state.tolist()
+    for bit, text in _HARMONIC_STATUS:
+        if st[0] & bit:
+            raise ValueError('%s: %s' % (what, text))
+    return (out, _harmonic_info(st, C)) if return_info else out
+
+
+def harmonic_inpaint(sample, weights='uniform', **kw):
+    """The classic non-learned inpainting baseline: every masked vertex (mask > 0) of a sample gets the harmonic extension of the
+    known colours over the sample's own graph (``harmonic_fill``).  sample: anything with `color` [N, C], `mask` [N] or [N, 1] and
+    `edge_index` [2, E] - a 3-D training sample, a collated batch (a disjoint union needs nothing special) or an ``imagegraph``
+    sample; positions (`pos`, or failing that x[:, 6:9]) are read only for weights='inverse_length'.
+    -> the composite float32 [N, C]: `color` itself outside the mask, bit for bit - what StepMetrics.update and
+    ImageStepMetrics.update accept as `out` (composite=True and False alike), beside ``knn_inpaint``.  Further keywords go to
+    ``harmonic_fill`` (tol, max_iterations, fill, return_info, ...)."""
+    color, mask, ei = sample.color, sample.mask, sample.edge_index
+    pos = None
+    if isinstance(weights, str) and weights == 'inverse_length':
+        pos = getattr(sample, 'pos', None)
+        pos = sample.x[:, 6:9] if pos is None else pos
+    return harmonic_fill(color.float(), mask.reshape(-1) > 0, edge_index=ei, vertices=pos, weights=weights, **kw)
