@@ -13,8 +13,9 @@
 //               contract's halving tree: the steps 128 and 64 through LDS, the steps 32 .. 1 inside wave 0 with shuffles - the same
 //               pairs in the same order, and a + b is b + a.  A tile without a contributing pair for a pose writes its row of +0.0
 //               without folding (a workgroup-uniform test).  k_colormap_fold: one thread per (pose, value), tiles ascending.
+//               The pair test, the sampler and the Jacobian are stin_view.h's, shared with the frame colours and the non-rigid kernels.
 // No float atomics; the order of every sum is a function of N alone.
-#include "stin_common.h"
+#include "stin_view.h"
 
 namespace {
 
@@ -23,9 +24,6 @@ constexpr int U = STIN_COLORMAP_U;                        // vertices per lane a
 constexpr int ROW = STIN_COLORMAP_ROW_DOUBLES;            // 21 + 6 + 1
 constexpr int TW = 64, TH = 16;                           // gradient tile
 constexpr int MIN_POSES = 8;                              // poses per chunk, at least
-constexpr int64_t FILL_GROUPS = 1024;                     // workgroups that fill the chip (256 CUs x 4)
-
-inline bool size_ok(int H, int W) { return H >= 1 && W >= 1 && H <= STIN_FRAMES_MAX_SIZE && W <= STIN_FRAMES_MAX_SIZE; }
 
 __global__ __launch_bounds__(CB) void k_colormap_gradients(const uint8_t* __restrict__ color, int H, int W, int4* __restrict__ images) {
     __shared__ int g[(TH + 2) * (TW + 2)];
@@ -78,8 +76,7 @@ struct NormalArgs {
     double* part;                                         // [tiles][B][ROW]
     int32_t* part_n;                                      // [tiles][B]
     int64_t N, first_pose, words;
-    double fx, fy, cx, cy, z_near;
-    double u_lo, u_hi, v_lo, v_hi;                        // margin, W - 1 - margin, margin, H - 1 - margin
+    View C;
     int B, H, W, per_chunk;
 };
 
@@ -117,36 +114,13 @@ __global__ __launch_bounds__(CB) void k_colormap_partial(const NormalArgs A) {
             for (int i = 0; i < U; ++i) {
                 if (!live[i]) continue;
                 if (!((brow[i][p >> 5] >> (p & 31)) & 1u)) continue;
-                const double zv = ((m[8] * x[i] + m[9] * y[i]) + m[10] * z[i]) + m[11];
-                if (zv < A.z_near) continue;
-                const double xv = ((m[0] * x[i] + m[1] * y[i]) + m[2] * z[i]) + m[3];
-                const double yv = ((m[4] * x[i] + m[5] * y[i]) + m[6] * z[i]) + m[7];
-                const double u = A.fx * xv / zv + A.cx, w = A.fy * yv / zv + A.cy;
-                if (!isfinite(u) || !isfinite(w)) continue;
-                if (!(u >= A.u_lo && u <= A.u_hi && w >= A.v_lo && w <= A.v_hi)) continue;
-                const double fx0 = floor(u), fy0 = floor(w);
-                const double a = u - fx0, c = w - fy0;
-                const int ix0 = (int)fx0, iy0 = (int)fy0;     // in [1, W - 2], [1, H - 2]: margin >= 1
-                const int ix1 = ix0 + 1 < A.W ? ix0 + 1 : A.W - 1, iy1 = iy0 + 1 < A.H ? iy0 + 1 : A.H - 1;
-                const int4 t00 = img[(int64_t)iy0 * A.W + ix0], t01 = img[(int64_t)iy0 * A.W + ix1];
-                const int4 t10 = img[(int64_t)iy1 * A.W + ix0], t11 = img[(int64_t)iy1 * A.W + ix1];
-                const double w00 = (1.0 - a) * (1.0 - c), w01 = a * (1.0 - c), w10 = (1.0 - a) * c, w11 = a * c;
-                const double sI = (w00 * (double)t00.x + w01 * (double)t01.x) + (w10 * (double)t10.x + w11 * (double)t11.x);
-                const double sX = (w00 * (double)t00.y + w01 * (double)t01.y) + (w10 * (double)t10.y + w11 * (double)t11.y);
-                const double sY = (w00 * (double)t00.z + w01 * (double)t01.z) + (w10 * (double)t10.z + w11 * (double)t11.z);
-                const double I = sI / 255000.0, dIdx = sX / 2040000.0, dIdy = sY / 2040000.0;
+                double xv, yv, zv, u, w, I, dIdx, dIdy, J[6];
+                if (!view_transform(A.C, m, x[i], y[i], z[i], xv, yv, zv)) continue;
+                if (!view_project(A.C.fx, A.C.fy, A.C.cx, A.C.cy, xv, yv, zv, u, w)) continue;
+                if (!view_inside(A.C, u, w)) continue;
+                sample_gradients(img, A.W, taps_of(u, w, A.H, A.W), I, dIdx, dIdy);   // margin >= 1: the taps are in [1, W - 2], [1, H - 2]
                 const double r = I - px[i];
-                const double iz = 1.0 / zv;
-                const double v0 = (dIdx * A.fx) * iz;
-                const double v1 = (dIdy * A.fy) * iz;
-                const double v2 = -((v0 * xv + v1 * yv) * iz);
-                double J[6];
-                J[0] = (-zv * v1) + yv * v2;
-                J[1] = zv * v0 - xv * v2;
-                J[2] = (-yv * v0) + xv * v1;
-                J[3] = v0;
-                J[4] = v1;
-                J[5] = v2;
+                pose_jacobian(xv, yv, zv, A.C.fx, A.C.fy, dIdx, dIdy, J);
                 int k = 0;
 #pragma unroll
                 for (int i0 = 0; i0 < 6; ++i0)
@@ -223,7 +197,7 @@ inline int64_t tiles_of(int64_t N) { return (N + (int64_t)CB * U - 1) / ((int64_
 }  // namespace
 
 extern "C" int stin_colormap_gradients_u8(const uint8_t* color, int B, int H, int W, int32_t* images, stin_stream_t stream_) {
-    STIN_REQUIRE(B >= 0 && B <= STIN_FRAMES_MAX_BATCH && size_ok(H, W), STIN_E_SIZE);
+    STIN_REQUIRE(B >= 0 && B <= STIN_FRAMES_MAX_BATCH && frame_size_ok(H, W, 1), STIN_E_SIZE);
     if (B == 0) return STIN_OK;
     STIN_REQUIRE(color != nullptr && images != nullptr, STIN_E_NULL);
     STIN_REQUIRE(((uintptr_t)images & 15u) == 0, STIN_E_SIZE);
@@ -255,7 +229,7 @@ extern "C" int stin_colormap_normal_f64(const double* vertices, int64_t N, const
     STIN_REQUIRE(camera != nullptr, STIN_E_NULL);
     STIN_REQUIRE(N >= 0 && N < (int64_t)INT32_MAX && B >= 0 && B <= STIN_FRAMES_MAX_BATCH, STIN_E_SIZE);
     STIN_REQUIRE(first_pose >= 0 && first_pose + B < (int64_t)INT32_MAX, STIN_E_SIZE);
-    STIN_REQUIRE(size_ok(H, W) && margin >= 1 && z_near > 0.0, STIN_E_SIZE);
+    STIN_REQUIRE(frame_size_ok(H, W, 1) && margin >= 1 && z_near > 0.0, STIN_E_SIZE);
     STIN_REQUIRE(words >= (first_pose + B + 31) / 32 || N == 0 || B == 0, STIN_E_SIZE);
     if (B == 0) return STIN_OK;
     STIN_REQUIRE(rows != nullptr && counts != nullptr, STIN_E_NULL);
@@ -273,16 +247,11 @@ extern "C" int stin_colormap_normal_f64(const double* vertices, int64_t N, const
         A.vertices = vertices; A.RT = RT; A.valid = valid; A.images = (const int4*)images; A.bits = bits; A.proxy = proxy;
         A.part = part; A.part_n = part_n;
         A.N = N; A.first_pose = first_pose; A.words = words;
-        A.fx = camera[0]; A.fy = camera[1]; A.cx = camera[2]; A.cy = camera[3]; A.z_near = z_near;
-        A.u_lo = (double)margin; A.u_hi = (double)(W - 1 - margin); A.v_lo = (double)margin; A.v_hi = (double)(H - 1 - margin);
+        A.C = view_of(camera, z_near, margin, H, W);
         A.B = B; A.H = H; A.W = W;
-        // chunks of poses over a second grid dimension until the chip is full: a launch decision, the sums do not see it
-        int64_t chunks = (FILL_GROUPS + tiles - 1) / tiles;
-        const int64_t most = (B + MIN_POSES - 1) / MIN_POSES;
-        if (chunks > most) chunks = most;
-        A.per_chunk = (int)((B + chunks - 1) / chunks);
-        const dim3 grid((unsigned)tiles, (unsigned)((B + A.per_chunk - 1) / A.per_chunk));
-        hipLaunchKernelGGL(k_colormap_partial, grid, dim3(CB), 0, stream, A);
+        const PoseChunks ch = pose_chunks(tiles, B, MIN_POSES, STIN_FRAMES_ROUTE_AUTO);   // every (tile, pose) has its own row: no split to handle
+        A.per_chunk = ch.per_chunk;
+        hipLaunchKernelGGL(k_colormap_partial, dim3((unsigned)tiles, ch.count), dim3(CB), 0, stream, A);
     }
     hipLaunchKernelGGL(k_colormap_fold, dim3((unsigned)(((int64_t)B * (ROW + 1) + CB - 1) / CB)), dim3(CB), 0, stream, part, part_n, tiles, B,
                        rows, counts);

@@ -9,11 +9,14 @@
 //               wave-uniform), a loop over a chunk of the batch's poses, three int64 sums and a count in registers.
 //               Owner route: the chunk is the whole batch, the thread adds to its vertex's row with plain loads and stores.
 //               Split route (few vertices, many poses): blockIdx.y picks the chunk, every value is added with one integer atomicAdd.
+//               One kernel template, three visibility modes: the depth test, observer bits, and bits with the colour frame sampled
+//               at the position a warp lattice moves the projection to (stin_nonrigid_accumulate_f64, the colour pass of the
+//               non-rigid optimiser, defined here beside the kernel it launches).  The pair test and the sampler are stin_view.h's.
 //   finish:     one thread per vertex.
 // "raw / depth_scale > depth_trunc" is monotone in raw for depth_scale > 0: the host finds the largest raw value that stays (a
 // binary search with the contract's own expression) and the kernels compare integers.
 // Integer sums and integer atomics only: the result does not depend on the schedule, the route or the batching.
-#include "stin_common.h"
+#include "stin_view.h"
 
 namespace {
 
@@ -21,7 +24,6 @@ constexpr int FB = 256;                                   // threads per workgro
 constexpr int TW = 64, TH = 16;                           // dilation tile
 constexpr int KMAX = STIN_FRAMES_MAX_HALF_KERNEL;
 constexpr int SPLIT_MIN_POSES = 8;                        // poses per chunk of the split route, at least
-constexpr int64_t FILL_GROUPS = 1024;                     // workgroups that fill the chip (256 CUs x 4)
 
 // The largest raw value r with !((double)r / depth_scale > depth_trunc); -1: none stays, 65535: all stay (also for a NaN limit).
 int keep_max_raw(double depth_scale, double depth_trunc) {
@@ -85,6 +87,8 @@ __global__ __launch_bounds__(FB) void k_frames_dilate(const uint8_t* __restrict_
     }
 }
 
+enum AccMode { ACC_DEPTH, ACC_BITS, ACC_WARP };           // visibility from the depth frames; from bits; from bits, sampled at the warped position
+
 struct FrameArgs {
     const double* vertices;
     const double* RT;
@@ -93,29 +97,25 @@ struct FrameArgs {
     const uint16_t* depth;
     const uint8_t* edge;
     const uint32_t* bits;
+    const double* flow;                                   // ACC_WARP: [B][Ah][Aw][2]
     int64_t* sum;
     int32_t* count;
     uint32_t* seen;
     int64_t N, first_pose, words, seen_words;
-    double cfx, cfy, ccx, ccy, dfx, dfy, dcx, dcy;
-    double depth_scale, max_depth, depth_threshold, z_near;
-    double u_lo, u_hi, v_lo, v_hi;                        // margin, Wc - 1 - margin, margin, Hc - 1 - margin
+    View C;                                               // the colour camera and frame
+    double dfx, dfy, dcx, dcy;
+    double depth_scale, max_depth, depth_threshold;
     int B, Hc, Wc, Hd, Wd, keep_max, per_chunk;
 };
 
-template <bool ATOMIC> __device__ inline void seen_flush(const FrameArgs& A, int64_t v, int64_t word, uint32_t acc) {
-    if (acc == 0u) return;
-    uint32_t* w = A.seen + v * A.seen_words + word;
-    if (ATOMIC) atomicOr(w, acc); else *w |= acc;
-}
-
-template <bool DEPTH, bool ATOMIC> __global__ __launch_bounds__(FB) void k_frames_accumulate(const FrameArgs A) {
+template <AccMode MODE, bool ATOMIC> __global__ __launch_bounds__(FB) void k_frames_accumulate(const FrameArgs A) {
     const int64_t v = (int64_t)blockIdx.x * FB + threadIdx.x;
     if (v >= A.N) return;
     const int b0 = (int)blockIdx.y * A.per_chunk;
     const int b1 = b0 + A.per_chunk < A.B ? b0 + A.per_chunk : A.B;
     const double x = A.vertices[3 * v], y = A.vertices[3 * v + 1], z = A.vertices[3 * v + 2];
-    const uint32_t* brow = DEPTH ? nullptr : A.bits + v * A.words;
+    const uint32_t* brow = MODE == ACC_DEPTH ? nullptr : A.bits + v * A.words;
+    const int64_t per_flow = (int64_t)A.C.Ah * A.C.Aw * 2;
     int64_t s0 = 0, s1 = 0, s2 = 0;
     int32_t cnt = 0;
     uint32_t sacc = 0u;
@@ -123,17 +123,13 @@ template <bool DEPTH, bool ATOMIC> __global__ __launch_bounds__(FB) void k_frame
     for (int b = b0; b < b1; ++b) {
         if (!A.valid[b]) continue;
         const int64_t p = A.first_pose + b;
-        if (!DEPTH && !((brow[p >> 5] >> (p & 31)) & 1u)) continue;
-        const double* m = A.RT + (int64_t)b * 12;
-        const double zv = ((m[8] * x + m[9] * y) + m[10] * z) + m[11];
-        if (zv < A.z_near) continue;
-        const double xv = ((m[0] * x + m[1] * y) + m[2] * z) + m[3];
-        const double yv = ((m[4] * x + m[5] * y) + m[6] * z) + m[7];
-        const double u = A.cfx * xv / zv + A.ccx, w = A.cfy * yv / zv + A.ccy;
-        if (!isfinite(u) || !isfinite(w)) continue;
-        if (DEPTH) {
-            const double ud = A.dfx * xv / zv + A.dcx, vd = A.dfy * yv / zv + A.dcy;
-            if (!isfinite(ud) || !isfinite(vd)) continue;
+        if (MODE != ACC_DEPTH && !((brow[p >> 5] >> (p & 31)) & 1u)) continue;
+        double xv, yv, zv, u, w;
+        if (!view_transform(A.C, A.RT + (int64_t)b * 12, x, y, z, xv, yv, zv)) continue;
+        if (!view_project(A.C.fx, A.C.fy, A.C.cx, A.C.cy, xv, yv, zv, u, w)) continue;
+        if (MODE == ACC_DEPTH) {
+            double ud, vd;
+            if (!view_project(A.dfx, A.dfy, A.dcx, A.dcy, xv, yv, zv, ud, vd)) continue;
             const double ui = rint(ud), vi = rint(vd);
             if (!(ui >= 0.0 && ui < (double)A.Wd && vi >= 0.0 && vi < (double)A.Hd)) continue;
             const int64_t at = ((int64_t)b * A.Hd + (int64_t)vi) * A.Wd + (int64_t)ui;
@@ -144,50 +140,25 @@ template <bool DEPTH, bool ATOMIC> __global__ __launch_bounds__(FB) void k_frame
             if (A.edge[at]) continue;
             if (!(fabs(zv - d) < A.depth_threshold)) continue;
         }
-        if (!(u >= A.u_lo && u <= A.u_hi && w >= A.v_lo && w <= A.v_hi)) continue;
-        const double fx0 = floor(u), fy0 = floor(w);
-        const double a = u - fx0, c = w - fy0;
-        const int ix0 = (int)fx0, iy0 = (int)fy0;         // in [0, Wc - 1], [0, Hc - 1]: margin >= 0
-        const int ix1 = ix0 + 1 < A.Wc ? ix0 + 1 : A.Wc - 1, iy1 = iy0 + 1 < A.Hc ? iy0 + 1 : A.Hc - 1;
-        const uint8_t* img = A.color + (int64_t)b * A.Hc * A.Wc * 3;
-        const uint8_t* p00 = img + ((int64_t)iy0 * A.Wc + ix0) * 3;
-        const uint8_t* p01 = img + ((int64_t)iy0 * A.Wc + ix1) * 3;
-        const uint8_t* p10 = img + ((int64_t)iy1 * A.Wc + ix0) * 3;
-        const uint8_t* p11 = img + ((int64_t)iy1 * A.Wc + ix1) * 3;
-        const double w00 = (1.0 - a) * (1.0 - c), w01 = a * (1.0 - c), w10 = (1.0 - a) * c, w11 = a * c;
-        int64_t q[3];
-#pragma unroll
-        for (int ch = 0; ch < 3; ++ch) {
-            const double val = (w00 * (double)p00[ch] + w01 * (double)p01[ch]) + (w10 * (double)p10[ch] + w11 * (double)p11[ch]);
-            q[ch] = (int64_t)rint(val * 65536.0);
+        if (!view_inside(A.C, u, w)) continue;
+        if (MODE == ACC_WARP) {
+            double wts[4], uw, vw;
+            int cell;
+            if (!view_warp(A.C, A.flow + (int64_t)b * per_flow, u, w, wts, uw, vw, cell)) continue;
+            u = uw;
+            w = vw;
         }
+        int64_t q[3];
+        sample_rgb(A.color + (int64_t)b * A.Hc * A.Wc * 3, A.Wc, taps_of(u, w, A.Hc, A.Wc), q);
         s0 += q[0];
         s1 += q[1];
         s2 += q[2];
         cnt += 1;
-        if (A.seen != nullptr) {
-            if ((p >> 5) != sword) {
-                seen_flush<ATOMIC>(A, v, sword, sacc);
-                sword = p >> 5;
-                sacc = 0u;
-            }
-            sacc |= 1u << (p & 31);
-        }
+        if (A.seen != nullptr) seen_mark<ATOMIC>(A.seen + v * A.seen_words, p, sword, sacc);
     }
     if (cnt == 0) return;
-    if (A.seen != nullptr) seen_flush<ATOMIC>(A, v, sword, sacc);
-    if (ATOMIC) {
-        unsigned long long* s = (unsigned long long*)(A.sum + 3 * v);   // two's complement: the unsigned add is the signed add
-        atomicAdd(s, (unsigned long long)s0);
-        atomicAdd(s + 1, (unsigned long long)s1);
-        atomicAdd(s + 2, (unsigned long long)s2);
-        atomicAdd(A.count + v, cnt);
-    } else {
-        A.sum[3 * v] += s0;
-        A.sum[3 * v + 1] += s1;
-        A.sum[3 * v + 2] += s2;
-        A.count[v] += cnt;
-    }
+    if (A.seen != nullptr) seen_flush<ATOMIC>(A.seen + v * A.seen_words, sword, sacc);
+    sums_commit<ATOMIC>(A.sum + 3 * v, A.count + v, s0, s1, s2, cnt);
 }
 
 __global__ void k_frames_finish(const int64_t* __restrict__ sum, const int32_t* __restrict__ count, int64_t N, float f0, float f1,
@@ -209,19 +180,32 @@ __global__ void k_frames_finish(const int64_t* __restrict__ sum, const int32_t* 
     }
 }
 
-inline bool frame_size_ok(int H, int W) { return H >= 1 && W >= 1 && H <= STIN_FRAMES_MAX_SIZE && W <= STIN_FRAMES_MAX_SIZE; }
+// The route, from N and B alone (pose_chunks), and the instantiation of (mode, split); fills A.per_chunk.
+int launch_accumulate(FrameArgs& A, AccMode mode, int route, hipStream_t stream) {
+    const int64_t groups = (A.N + FB - 1) / FB;
+    const PoseChunks ch = pose_chunks(groups, A.B, SPLIT_MIN_POSES, route);
+    A.per_chunk = ch.per_chunk;
+    const dim3 grid((unsigned)groups, ch.count);
+    void (*kernel)(const FrameArgs) =
+        mode == ACC_DEPTH  ? (ch.split ? k_frames_accumulate<ACC_DEPTH, true> : k_frames_accumulate<ACC_DEPTH, false>)
+        : mode == ACC_BITS ? (ch.split ? k_frames_accumulate<ACC_BITS, true> : k_frames_accumulate<ACC_BITS, false>)
+                           : (ch.split ? k_frames_accumulate<ACC_WARP, true> : k_frames_accumulate<ACC_WARP, false>);
+    stin_clear_stale_error();
+    hipLaunchKernelGGL(kernel, grid, dim3(FB), 0, stream, A);
+    return stin_launch_status();
+}
 
 }  // namespace
 
 extern "C" size_t stin_frames_edges_workspace_bytes(int B, int Hd, int Wd) {
-    if (B < 0 || B > STIN_FRAMES_MAX_BATCH || !frame_size_ok(Hd, Wd)) return 0;
+    if (B < 0 || B > STIN_FRAMES_MAX_BATCH || !frame_size_ok(Hd, Wd, 1)) return 0;
     return stin_up256((size_t)(B > 0 ? B : 1) * (size_t)Hd * (size_t)Wd);
 }
 
 extern "C" int stin_frames_depth_edges_u16(const uint16_t* depth, int B, int Hd, int Wd, double depth_scale, double depth_trunc,
                                            double discontinuity_threshold, int half_kernel, uint8_t* edge, void* workspace,
                                            size_t workspace_bytes, stin_stream_t stream_) {
-    STIN_REQUIRE(B >= 0 && B <= STIN_FRAMES_MAX_BATCH && frame_size_ok(Hd, Wd), STIN_E_SIZE);
+    STIN_REQUIRE(B >= 0 && B <= STIN_FRAMES_MAX_BATCH && frame_size_ok(Hd, Wd, 1), STIN_E_SIZE);
     STIN_REQUIRE(half_kernel >= 0 && half_kernel <= STIN_FRAMES_MAX_HALF_KERNEL && depth_scale > 0.0, STIN_E_SIZE);
     if (B == 0) return STIN_OK;
     STIN_REQUIRE(depth != nullptr && edge != nullptr, STIN_E_NULL);
@@ -244,50 +228,53 @@ extern "C" int stin_frames_accumulate_f64(const double* vertices, int64_t N, con
                                           const uint32_t* bits, int64_t words, int margin, int route, int64_t* sum, int32_t* count,
                                           uint32_t* seen, int64_t seen_words, stin_stream_t stream_) {
     STIN_REQUIRE(cameras != nullptr && params != nullptr, STIN_E_NULL);
-    const double cfx = cameras[0], cfy = cameras[1], ccx = cameras[2], ccy = cameras[3];
-    const double dfx = cameras[4], dfy = cameras[5], dcx = cameras[6], dcy = cameras[7];
     const double depth_scale = params[0], depth_trunc = params[1], max_depth = params[2], depth_threshold = params[3], z_near = params[4];
     STIN_REQUIRE(N >= 0 && N < (int64_t)INT32_MAX && B >= 0 && B <= STIN_FRAMES_MAX_BATCH, STIN_E_SIZE);
     STIN_REQUIRE(first_pose >= 0 && first_pose + B < (int64_t)INT32_MAX, STIN_E_SIZE);
-    STIN_REQUIRE(frame_size_ok(Hc, Wc) && margin >= 0 && z_near > 0.0, STIN_E_SIZE);
+    STIN_REQUIRE(frame_size_ok(Hc, Wc, 1) && margin >= 0 && z_near > 0.0, STIN_E_SIZE);
     STIN_REQUIRE(route == STIN_FRAMES_ROUTE_AUTO || route == STIN_FRAMES_ROUTE_OWNER || route == STIN_FRAMES_ROUTE_SPLIT, STIN_E_SIZE);
     STIN_REQUIRE((depth != nullptr) != (bits != nullptr) || N == 0 || B == 0, STIN_E_UNSUPPORTED);   // exactly one visibility source
     const int64_t need_words = (first_pose + B + 31) / 32;
-    if (depth != nullptr) STIN_REQUIRE(frame_size_ok(Hd, Wd) && depth_scale > 0.0, STIN_E_SIZE);
+    if (depth != nullptr) STIN_REQUIRE(frame_size_ok(Hd, Wd, 1) && depth_scale > 0.0, STIN_E_SIZE);
     if (depth == nullptr && bits != nullptr) STIN_REQUIRE(words >= need_words, STIN_E_SIZE);
     if (seen != nullptr) STIN_REQUIRE(seen_words >= need_words, STIN_E_SIZE);
     if (N == 0 || B == 0) return STIN_OK;
     STIN_REQUIRE(vertices && RT && valid && color && sum && count, STIN_E_NULL);
     STIN_REQUIRE(depth == nullptr || edge != nullptr, STIN_E_NULL);
-    hipStream_t stream = (hipStream_t)stream_;
-    stin_clear_stale_error();
-    FrameArgs A;
+    FrameArgs A = {};
     A.vertices = vertices; A.RT = RT; A.valid = valid; A.color = color; A.depth = depth; A.edge = edge; A.bits = bits;
     A.sum = sum; A.count = count; A.seen = seen;
     A.N = N; A.first_pose = first_pose; A.words = words; A.seen_words = seen_words;
-    A.cfx = cfx; A.cfy = cfy; A.ccx = ccx; A.ccy = ccy; A.dfx = dfx; A.dfy = dfy; A.dcx = dcx; A.dcy = dcy;
-    A.depth_scale = depth_scale; A.max_depth = max_depth; A.depth_threshold = depth_threshold; A.z_near = z_near;
-    A.u_lo = (double)margin; A.u_hi = (double)(Wc - 1 - margin); A.v_lo = (double)margin; A.v_hi = (double)(Hc - 1 - margin);
+    A.C = view_of(cameras, z_near, margin, Hc, Wc);
+    A.dfx = cameras[4]; A.dfy = cameras[5]; A.dcx = cameras[6]; A.dcy = cameras[7];
+    A.depth_scale = depth_scale; A.max_depth = max_depth; A.depth_threshold = depth_threshold;
     A.B = B; A.Hc = Hc; A.Wc = Wc; A.Hd = Hd; A.Wd = Wd;
     A.keep_max = depth != nullptr ? keep_max_raw(depth_scale, depth_trunc) : 0;
-    // The route, from N and B alone: as many chunks of at least SPLIT_MIN_POSES poses as it takes to reach FILL_GROUPS workgroups.
-    const int64_t groups = (N + FB - 1) / FB;
-    int64_t chunks = (FILL_GROUPS + groups - 1) / groups;
-    const int64_t most = (B + SPLIT_MIN_POSES - 1) / SPLIT_MIN_POSES;
-    if (chunks > most) chunks = most;
-    if (route == STIN_FRAMES_ROUTE_OWNER) chunks = 1;
-    if (route == STIN_FRAMES_ROUTE_SPLIT && chunks < 2) chunks = B < 2 ? 1 : 2;
-    const bool atomic = route == STIN_FRAMES_ROUTE_SPLIT || chunks > 1;
-    A.per_chunk = (int)((B + chunks - 1) / chunks);
-    const dim3 grid((unsigned)groups, (unsigned)((B + A.per_chunk - 1) / A.per_chunk));
-    if (depth != nullptr) {
-        if (atomic) hipLaunchKernelGGL((k_frames_accumulate<true, true>), grid, dim3(FB), 0, stream, A);
-        else hipLaunchKernelGGL((k_frames_accumulate<true, false>), grid, dim3(FB), 0, stream, A);
-    } else {
-        if (atomic) hipLaunchKernelGGL((k_frames_accumulate<false, true>), grid, dim3(FB), 0, stream, A);
-        else hipLaunchKernelGGL((k_frames_accumulate<false, false>), grid, dim3(FB), 0, stream, A);
-    }
-    return stin_launch_status();
+    return launch_accumulate(A, depth != nullptr ? ACC_DEPTH : ACC_BITS, route, (hipStream_t)stream_);
+}
+
+extern "C" int stin_nonrigid_accumulate_f64(const double* vertices, int64_t N, const double* RT, const uint8_t* valid, int B,
+                                            int64_t first_pose, const uint8_t* color, int H, int W, const double* flow, int lattice_step,
+                                            const double* camera, double z_near, const uint32_t* bits, int64_t words, int margin,
+                                            int route, int64_t* sum, int32_t* count, uint32_t* seen, int64_t seen_words,
+                                            stin_stream_t stream_) {
+    STIN_REQUIRE(camera != nullptr, STIN_E_NULL);
+    STIN_REQUIRE(N >= 0 && N < (int64_t)INT32_MAX && B >= 0 && B <= STIN_FRAMES_MAX_BATCH, STIN_E_SIZE);
+    STIN_REQUIRE(first_pose >= 0 && first_pose + B < (int64_t)INT32_MAX, STIN_E_SIZE);
+    STIN_REQUIRE(frame_size_ok(H, W, 2) && lattice_step >= 1 && margin >= 0 && z_near > 0.0, STIN_E_SIZE);
+    STIN_REQUIRE(route == STIN_FRAMES_ROUTE_AUTO || route == STIN_FRAMES_ROUTE_OWNER || route == STIN_FRAMES_ROUTE_SPLIT, STIN_E_SIZE);
+    const int64_t need_words = (first_pose + B + 31) / 32;
+    STIN_REQUIRE(words >= need_words || N == 0 || B == 0, STIN_E_SIZE);
+    if (seen != nullptr) STIN_REQUIRE(seen_words >= need_words, STIN_E_SIZE);
+    if (N == 0 || B == 0) return STIN_OK;
+    STIN_REQUIRE(vertices && RT && valid && color && flow && bits && sum && count, STIN_E_NULL);
+    FrameArgs A = {};
+    A.vertices = vertices; A.RT = RT; A.valid = valid; A.color = color; A.bits = bits; A.flow = flow;
+    A.sum = sum; A.count = count; A.seen = seen;
+    A.N = N; A.first_pose = first_pose; A.words = words; A.seen_words = seen_words;
+    A.C = view_of(camera, z_near, margin, H, W, lattice_step);
+    A.B = B; A.Hc = H; A.Wc = W;
+    return launch_accumulate(A, ACC_WARP, route, (hipStream_t)stream_);
 }
 
 extern "C" int stin_frames_finish_f32(const int64_t* sum, const int32_t* count, int64_t N, float fill_r, float fill_g, float fill_b,

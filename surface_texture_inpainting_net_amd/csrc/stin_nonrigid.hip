@@ -3,9 +3,8 @@
 // Contract: include/stin_hip.h ("Non-rigid colour-map optimisation"); tests/_nonrigid_oracle.py restates it in numpy, pose-major,
 // and agrees byte for byte.
 //
-//   accumulate: stin_frames.hip's bits-mode kernel with the colour frame sampled at the warped position: one thread per vertex, a
-//               loop over a chunk of the batch's poses, three int64 sums and a count in registers; owner route (plain stores) or
-//               split route (integer atomics), identical bits.
+//   accumulate: stin_nonrigid_accumulate_f64 is the warp mode of the frame colours' accumulate kernel and lives beside it in
+//               stin_frames.hip; the pair test here (pair_of) and there are built from the same pieces of stin_view.h.
 //   keys:       one thread per (vertex, pose): the pair test, the cell of the projection, one int64 key
 //               (pose-in-batch cells + cell) << 31 | vertex, or the sentinel for a pair that does not contribute.  The caller sorts
 //               the keys (rocPRIM through torch.sort): every (pose, cell) becomes one run of keys in ascending vertex id.
@@ -15,29 +14,17 @@
 //               z[a_i] z[b_i] over the staged pairs IN ORDER.  The sum of every entry is therefore the contract's: ascending
 //               vertex id from +0.0, whatever the batching.  15 KB of LDS and two waves per workgroup: ten workgroups per CU.
 // No float atomics.  Nothing is contracted (the file is built with -ffp-contract=off like every other).
-#include "stin_common.h"
+#include "stin_view.h"
 
 namespace {
 
-constexpr int FB = 256;                                   // threads per workgroup: accumulate, keys
+constexpr int FB = 256;                                   // threads per workgroup: keys
 constexpr int NB = 128;                                   // threads per workgroup = pairs per staging round: blocks
 constexpr int LOCAL = 14;                                 // local unknowns: 6 of the pose, 2 x 4 of the cell's anchors
 constexpr int ZW = LOCAL + 1;                             // a staged pair: J[14], r
 constexpr int BLOCK = STIN_NONRIGID_BLOCK_DOUBLES;        // 105 + 14 + 1
-constexpr int SPLIT_MIN_POSES = 8;                        // poses per chunk of the split route, at least
-constexpr int64_t FILL_GROUPS = 1024;                     // workgroups that fill the chip (256 CUs x 4)
 constexpr int64_t SENTINEL = INT64_MAX;                   // the key of a pair that does not contribute
 static_assert(BLOCK == LOCAL * (LOCAL + 1) / 2 + LOCAL + 1 && BLOCK <= NB, "one thread per entry of a block");
-
-inline bool size_ok(int H, int W) { return H >= 2 && W >= 2 && H <= STIN_FRAMES_MAX_SIZE && W <= STIN_FRAMES_MAX_SIZE; }
-inline int anchors_of(int n, int S) { return (n - 1 + S - 1) / S + 1; }      // ceil((n - 1) / S) + 1
-
-struct View {                                             // what the pair test and the warp need besides the pose and the vertex
-    double fx, fy, cx, cy, z_near;
-    double u_lo, u_hi, v_lo, v_hi;                        // margin, W - 1 - margin, margin, H - 1 - margin
-    double S;
-    int Ah, Aw;
-};
 
 struct Pair {
     double xv, yv, zv, uw, vw;                            // the view, unwarped; the warped position
@@ -48,115 +35,11 @@ struct Pair {
 // The contract's pair test, minus the pose's validity and the visibility bit; f: the pose's flow [Ah][Aw][2].
 __device__ inline bool pair_of(const View& C, const double* __restrict__ m, const double* __restrict__ f, double x, double y, double z,
                                Pair& o) {
-    o.zv = ((m[8] * x + m[9] * y) + m[10] * z) + m[11];
-    if (o.zv < C.z_near) return false;
-    o.xv = ((m[0] * x + m[1] * y) + m[2] * z) + m[3];
-    o.yv = ((m[4] * x + m[5] * y) + m[6] * z) + m[7];
-    const double u = C.fx * o.xv / o.zv + C.cx, v = C.fy * o.yv / o.zv + C.cy;
-    if (!isfinite(u) || !isfinite(v)) return false;
-    if (!(u >= C.u_lo && u <= C.u_hi && v >= C.v_lo && v <= C.v_hi)) return false;
-    const double gu = u / C.S, gv = v / C.S;
-    int cj = (int)floor(gu), ci = (int)floor(gv);         // u, v >= 0 here: margin >= 0
-    cj = cj < C.Aw - 2 ? cj : C.Aw - 2;
-    ci = ci < C.Ah - 2 ? ci : C.Ah - 2;
-    const double a = gu - (double)cj, b = gv - (double)ci;
-    o.w[0] = (1.0 - a) * (1.0 - b);
-    o.w[1] = a * (1.0 - b);
-    o.w[2] = (1.0 - a) * b;
-    o.w[3] = a * b;
-    const double* f0 = f + ((int64_t)ci * C.Aw + cj) * 2;
-    const double* f1 = f0 + (int64_t)C.Aw * 2;
-    o.uw = u + ((o.w[0] * f0[0] + o.w[1] * f0[2]) + (o.w[2] * f1[0] + o.w[3] * f1[2]));
-    o.vw = v + ((o.w[0] * f0[1] + o.w[1] * f0[3]) + (o.w[2] * f1[1] + o.w[3] * f1[3]));
-    if (!isfinite(o.uw) || !isfinite(o.vw)) return false;
-    if (!(o.uw >= C.u_lo && o.uw <= C.u_hi && o.vw >= C.v_lo && o.vw <= C.v_hi)) return false;
-    o.cell = ci * (C.Aw - 1) + cj;
-    return true;
-}
-
-// ------------------------------------------------------------------------------------------------------------------ accumulate
-struct AccArgs {
-    const double* vertices;
-    const double* RT;
-    const uint8_t* valid;
-    const uint8_t* color;
-    const double* flow;
-    const uint32_t* bits;
-    int64_t* sum;
-    int32_t* count;
-    uint32_t* seen;
-    int64_t N, first_pose, words, seen_words;
-    View C;
-    int B, H, W, per_chunk;
-};
-
-template <bool ATOMIC> __device__ inline void seen_flush(const AccArgs& A, int64_t v, int64_t word, uint32_t acc) {
-    if (acc == 0u) return;
-    uint32_t* w = A.seen + v * A.seen_words + word;
-    if (ATOMIC) atomicOr(w, acc); else *w |= acc;
-}
-
-template <bool ATOMIC> __global__ __launch_bounds__(FB) void k_nonrigid_accumulate(const AccArgs A) {
-    const int64_t v = (int64_t)blockIdx.x * FB + threadIdx.x;
-    if (v >= A.N) return;
-    const int b0 = (int)blockIdx.y * A.per_chunk;
-    const int b1 = b0 + A.per_chunk < A.B ? b0 + A.per_chunk : A.B;
-    const double x = A.vertices[3 * v], y = A.vertices[3 * v + 1], z = A.vertices[3 * v + 2];
-    const uint32_t* brow = A.bits + v * A.words;
-    const int64_t per_flow = (int64_t)A.C.Ah * A.C.Aw * 2;
-    int64_t s0 = 0, s1 = 0, s2 = 0;
-    int32_t cnt = 0;
-    uint32_t sacc = 0u;
-    int64_t sword = 0;
-    for (int b = b0; b < b1; ++b) {
-        if (!A.valid[b]) continue;
-        const int64_t p = A.first_pose + b;
-        if (!((brow[p >> 5] >> (p & 31)) & 1u)) continue;
-        Pair q;
-        if (!pair_of(A.C, A.RT + (int64_t)b * 12, A.flow + (int64_t)b * per_flow, x, y, z, q)) continue;
-        const double fx0 = floor(q.uw), fy0 = floor(q.vw);
-        const double a = q.uw - fx0, c = q.vw - fy0;
-        const int ix0 = (int)fx0, iy0 = (int)fy0;         // in [0, W - 1], [0, H - 1]: margin >= 0
-        const int ix1 = ix0 + 1 < A.W ? ix0 + 1 : A.W - 1, iy1 = iy0 + 1 < A.H ? iy0 + 1 : A.H - 1;
-        const uint8_t* img = A.color + (int64_t)b * A.H * A.W * 3;
-        const uint8_t* p00 = img + ((int64_t)iy0 * A.W + ix0) * 3;
-        const uint8_t* p01 = img + ((int64_t)iy0 * A.W + ix1) * 3;
-        const uint8_t* p10 = img + ((int64_t)iy1 * A.W + ix0) * 3;
-        const uint8_t* p11 = img + ((int64_t)iy1 * A.W + ix1) * 3;
-        const double w00 = (1.0 - a) * (1.0 - c), w01 = a * (1.0 - c), w10 = (1.0 - a) * c, w11 = a * c;
-        int64_t qs[3];
-#pragma unroll
-        for (int ch = 0; ch < 3; ++ch) {
-            const double val = (w00 * (double)p00[ch] + w01 * (double)p01[ch]) + (w10 * (double)p10[ch] + w11 * (double)p11[ch]);
-            qs[ch] = (int64_t)rint(val * 65536.0);
-        }
-        s0 += qs[0];
-        s1 += qs[1];
-        s2 += qs[2];
-        cnt += 1;
-        if (A.seen != nullptr) {
-            if ((p >> 5) != sword) {
-                seen_flush<ATOMIC>(A, v, sword, sacc);
-                sword = p >> 5;
-                sacc = 0u;
-            }
-            sacc |= 1u << (p & 31);
-        }
-    }
-    if (cnt == 0) return;
-    if (A.seen != nullptr) seen_flush<ATOMIC>(A, v, sword, sacc);
-    if (ATOMIC) {
-        unsigned long long* s = (unsigned long long*)(A.sum + 3 * v);   // two's complement: the unsigned add is the signed add
-        atomicAdd(s, (unsigned long long)s0);
-        atomicAdd(s + 1, (unsigned long long)s1);
-        atomicAdd(s + 2, (unsigned long long)s2);
-        atomicAdd(A.count + v, cnt);
-    } else {
-        A.sum[3 * v] += s0;
-        A.sum[3 * v + 1] += s1;
-        A.sum[3 * v + 2] += s2;
-        A.count[v] += cnt;
-    }
+    double u, v;
+    if (!view_transform(C, m, x, y, z, o.xv, o.yv, o.zv)) return false;
+    if (!view_project(C.fx, C.fy, C.cx, C.cy, o.xv, o.yv, o.zv, u, v)) return false;
+    if (!view_inside(C, u, v)) return false;
+    return view_warp(C, f, u, v, o.w, o.uw, o.vw, o.cell);
 }
 
 // ------------------------------------------------------------------------------------------------------------ keys and blocks
@@ -234,27 +117,9 @@ __global__ __launch_bounds__(NB) void k_nonrigid_blocks(const NormalArgs A) {
             Pair q;
             double* z = st[t];
             if (v < A.N && pair_of(A.C, m, f, A.vertices[3 * v], A.vertices[3 * v + 1], A.vertices[3 * v + 2], q)) {
-                const double fx0 = floor(q.uw), fy0 = floor(q.vw);
-                const double a = q.uw - fx0, c = q.vw - fy0;
-                const int ix0 = (int)fx0, iy0 = (int)fy0; // in [1, W - 2], [1, H - 2]: margin >= 1
-                const int ix1 = ix0 + 1 < A.W ? ix0 + 1 : A.W - 1, iy1 = iy0 + 1 < A.H ? iy0 + 1 : A.H - 1;
-                const int4 t00 = img[(int64_t)iy0 * A.W + ix0], t01 = img[(int64_t)iy0 * A.W + ix1];
-                const int4 t10 = img[(int64_t)iy1 * A.W + ix0], t11 = img[(int64_t)iy1 * A.W + ix1];
-                const double w00 = (1.0 - a) * (1.0 - c), w01 = a * (1.0 - c), w10 = (1.0 - a) * c, w11 = a * c;
-                const double sI = (w00 * (double)t00.x + w01 * (double)t01.x) + (w10 * (double)t10.x + w11 * (double)t11.x);
-                const double sX = (w00 * (double)t00.y + w01 * (double)t01.y) + (w10 * (double)t10.y + w11 * (double)t11.y);
-                const double sY = (w00 * (double)t00.z + w01 * (double)t01.z) + (w10 * (double)t10.z + w11 * (double)t11.z);
-                const double I = sI / 255000.0, dIdx = sX / 2040000.0, dIdy = sY / 2040000.0;
-                const double iz = 1.0 / q.zv;
-                const double v0 = (dIdx * A.C.fx) * iz;
-                const double v1 = (dIdy * A.C.fy) * iz;
-                const double v2 = -((v0 * q.xv + v1 * q.yv) * iz);
-                z[0] = (-q.zv * v1) + q.yv * v2;
-                z[1] = q.zv * v0 - q.xv * v2;
-                z[2] = (-q.yv * v0) + q.xv * v1;
-                z[3] = v0;
-                z[4] = v1;
-                z[5] = v2;
+                double I, dIdx, dIdy;
+                sample_gradients(img, A.W, taps_of(q.uw, q.vw, A.H, A.W), I, dIdx, dIdy);   // margin >= 1: the taps are in [1, W - 2], [1, H - 2]
+                pose_jacobian(q.xv, q.yv, q.zv, A.C.fx, A.C.fy, dIdx, dIdy, z);
 #pragma unroll
                 for (int k = 0; k < 4; ++k) {
                     z[6 + 2 * k] = dIdx * q.w[k];
@@ -275,59 +140,12 @@ __global__ __launch_bounds__(NB) void k_nonrigid_blocks(const NormalArgs A) {
     if (t == BLOCK) A.counts[seg] = (int32_t)(hi - lo);
 }
 
-inline View view_of(const double* camera, double z_near, int margin, int H, int W, int S) {
-    View C;
-    C.fx = camera[0]; C.fy = camera[1]; C.cx = camera[2]; C.cy = camera[3]; C.z_near = z_near;
-    C.u_lo = (double)margin; C.u_hi = (double)(W - 1 - margin); C.v_lo = (double)margin; C.v_hi = (double)(H - 1 - margin);
-    C.S = (double)S;
-    C.Ah = anchors_of(H, S);
-    C.Aw = anchors_of(W, S);
-    return C;
-}
-
 inline int64_t cells_of(int H, int W, int S) { return (int64_t)(anchors_of(H, S) - 1) * (anchors_of(W, S) - 1); }
 
 }  // namespace
 
-extern "C" int stin_nonrigid_accumulate_f64(const double* vertices, int64_t N, const double* RT, const uint8_t* valid, int B,
-                                            int64_t first_pose, const uint8_t* color, int H, int W, const double* flow, int lattice_step,
-                                            const double* camera, double z_near, const uint32_t* bits, int64_t words, int margin,
-                                            int route, int64_t* sum, int32_t* count, uint32_t* seen, int64_t seen_words,
-                                            stin_stream_t stream_) {
-    STIN_REQUIRE(camera != nullptr, STIN_E_NULL);
-    STIN_REQUIRE(N >= 0 && N < (int64_t)INT32_MAX && B >= 0 && B <= STIN_FRAMES_MAX_BATCH, STIN_E_SIZE);
-    STIN_REQUIRE(first_pose >= 0 && first_pose + B < (int64_t)INT32_MAX, STIN_E_SIZE);
-    STIN_REQUIRE(size_ok(H, W) && lattice_step >= 1 && margin >= 0 && z_near > 0.0, STIN_E_SIZE);
-    STIN_REQUIRE(route == STIN_FRAMES_ROUTE_AUTO || route == STIN_FRAMES_ROUTE_OWNER || route == STIN_FRAMES_ROUTE_SPLIT, STIN_E_SIZE);
-    const int64_t need_words = (first_pose + B + 31) / 32;
-    STIN_REQUIRE(words >= need_words || N == 0 || B == 0, STIN_E_SIZE);
-    if (seen != nullptr) STIN_REQUIRE(seen_words >= need_words, STIN_E_SIZE);
-    if (N == 0 || B == 0) return STIN_OK;
-    STIN_REQUIRE(vertices && RT && valid && color && flow && bits && sum && count, STIN_E_NULL);
-    stin_clear_stale_error();
-    AccArgs A;
-    A.vertices = vertices; A.RT = RT; A.valid = valid; A.color = color; A.flow = flow; A.bits = bits;
-    A.sum = sum; A.count = count; A.seen = seen;
-    A.N = N; A.first_pose = first_pose; A.words = words; A.seen_words = seen_words;
-    A.C = view_of(camera, z_near, margin, H, W, lattice_step);
-    A.B = B; A.H = H; A.W = W;
-    // The route, from N and B alone, as stin_frames_accumulate_f64 decides it.
-    const int64_t groups = (N + FB - 1) / FB;
-    int64_t chunks = (FILL_GROUPS + groups - 1) / groups;
-    const int64_t most = (B + SPLIT_MIN_POSES - 1) / SPLIT_MIN_POSES;
-    if (chunks > most) chunks = most;
-    if (route == STIN_FRAMES_ROUTE_OWNER) chunks = 1;
-    if (route == STIN_FRAMES_ROUTE_SPLIT && chunks < 2) chunks = B < 2 ? 1 : 2;
-    const bool atomic = route == STIN_FRAMES_ROUTE_SPLIT || chunks > 1;
-    A.per_chunk = (int)((B + chunks - 1) / chunks);
-    const dim3 grid((unsigned)groups, (unsigned)((B + A.per_chunk - 1) / A.per_chunk));
-    if (atomic) hipLaunchKernelGGL((k_nonrigid_accumulate<true>), grid, dim3(FB), 0, (hipStream_t)stream_, A);
-    else hipLaunchKernelGGL((k_nonrigid_accumulate<false>), grid, dim3(FB), 0, (hipStream_t)stream_, A);
-    return stin_launch_status();
-}
-
 extern "C" size_t stin_nonrigid_workspace_bytes(int64_t N, int B, int H, int W, int lattice_step) {
-    if (N < 0 || N >= (int64_t)INT32_MAX || B < 0 || B > STIN_FRAMES_MAX_BATCH || !size_ok(H, W) || lattice_step < 1) return 0;
+    if (N < 0 || N >= (int64_t)INT32_MAX || B < 0 || B > STIN_FRAMES_MAX_BATCH || !frame_size_ok(H, W, 2) || lattice_step < 1) return 0;
     if ((int64_t)(B > 0 ? B : 1) * cells_of(H, W, lattice_step) >= (int64_t)INT32_MAX) return 0;
     return (size_t)(N > 0 ? N : 1) * (size_t)(B > 0 ? B : 1) * sizeof(int64_t);      // not rounded: a sorted copy is exactly this long
 }
@@ -341,7 +159,7 @@ int normal_args(NormalArgs& A, const double* vertices, int64_t N, const double* 
     STIN_REQUIRE(camera != nullptr, STIN_E_NULL);
     STIN_REQUIRE(N >= 0 && N < (int64_t)INT32_MAX && B >= 0 && B <= STIN_FRAMES_MAX_BATCH, STIN_E_SIZE);
     STIN_REQUIRE(first_pose >= 0 && first_pose + B < (int64_t)INT32_MAX, STIN_E_SIZE);
-    STIN_REQUIRE(size_ok(H, W) && lattice_step >= 1 && margin >= 1 && z_near > 0.0, STIN_E_SIZE);
+    STIN_REQUIRE(frame_size_ok(H, W, 2) && lattice_step >= 1 && margin >= 1 && z_near > 0.0, STIN_E_SIZE);
     STIN_REQUIRE(stin_nonrigid_workspace_bytes(N, B, H, W, lattice_step) != 0, STIN_E_SIZE);
     if (B == 0) return STIN_OK;
     if (N > 0) {

@@ -18,6 +18,7 @@
 //              expressions, same atomicMin: which kernel rasterises a face cannot change a key.
 // Integer min only: the keys do not depend on the schedule, the batch size or `large_box`.
 #include "stin_raster.h"
+#include "stin_view.h"
 
 static_assert(STIN_OBSERVE_BAD_INDEX == 1 && STIN_RENDER_BAD_INDEX == 1, "the face kernel sets bit 1 for both callers");
 static_assert(STIN_OBSERVE_LARGE_FACE == 2 && STIN_RENDER_LARGE_FACE == 2, "the large-face kernel sets bit 2 for both callers");
@@ -73,9 +74,7 @@ __global__ void k_raster_transform(const double* __restrict__ vertices, int64_t 
     if (v >= N || !valid[p]) return;
     const double* m = RT + p * 12;
     const double x = vertices[3 * v], y = vertices[3 * v + 1], z = vertices[3 * v + 2];
-    const double xv = ((m[0] * x + m[1] * y) + m[2] * z) + m[3];
-    const double yv = ((m[4] * x + m[5] * y) + m[6] * z) + m[7];
-    const double zv = ((m[8] * x + m[9] * y) + m[10] * z) + m[11];
+    const double xv = view_x(m, x, y, z), yv = view_y(m, x, y, z), zv = view_z(m, x, y, z);   // no near-plane test here: the raster stage culls
     double* o = coords + ((int64_t)blockIdx.y * N + v) * 3;
     screen(xv, yv, zv, o);
     o[2] = zv;

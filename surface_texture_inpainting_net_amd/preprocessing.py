@@ -1551,6 +1551,32 @@ def _frames_u(t, dtype, tail, what):
     return t.contiguous()
 
 
+def _camera_doubles(camera, constant='STIN_COLORMAP_CAMERA_DOUBLES'):
+    """(fx, fy, cx, cy), or the colour camera followed by the depth camera, as the C ABI takes it."""
+    return (ctypes.c_double * _lib.CONSTANTS[constant])(*camera)
+
+
+def _depth_frames(depth, P):
+    """depth as FrameColors.add takes it, one frame per pose -> contiguous."""
+    d = _frames_u(depth, torch.uint16, (), 'depth')
+    if int(d.shape[0]) != P:
+        raise ValueError('%d poses but %d depth frames' % (P, int(d.shape[0])))
+    return d
+
+
+def _pose_bits(bits, n, poses, counted):
+    """bits as observe_vertices returns it for n vertices, with a bit for every pose below `poses` (`counted`: how the message
+    words that number) -> contiguous."""
+    if not (torch.is_tensor(bits) and bits.is_cuda):
+        raise TypeError('bits must be a CUDA tensor (no CPU fallback exists)')
+    if bits.dtype != torch.uint32 or bits.dim() != 2 or int(bits.shape[0]) != n:
+        raise TypeError('bits must be uint32 [N, words], as observe_vertices returns it')
+    words, need = int(bits.shape[1]), (poses + 31) // 32
+    if words < need:
+        raise ValueError('bits has %d words per vertex, %s need %d' % (words, counted % poses, need))
+    return bits.contiguous()
+
+
 class FrameColors:
     """Per-vertex colours of a mesh from a scan's colour and depth frames and its camera trajectory, on the GPU
     (csrc/stin_frames.hip) - the step the reference's preprocessing/texture_map_optimization.py hands to Open3D's colour-map
@@ -1643,17 +1669,9 @@ class FrameColors:
         _lib.load()
         d = edge = b = None
         if depth is not None:
-            d = _frames_u(depth, torch.uint16, (), 'depth')
-            if int(d.shape[0]) != B:
-                raise ValueError('%d poses but %d depth frames' % (B, int(d.shape[0])))
+            d = _depth_frames(depth, B)
         else:
-            if not (torch.is_tensor(bits) and bits.is_cuda):
-                raise TypeError('bits must be a CUDA tensor (no CPU fallback exists)')
-            if bits.dtype != torch.uint32 or bits.dim() != 2 or int(bits.shape[0]) != n:
-                raise TypeError('bits must be uint32 [N, words], as observe_vertices returns it')
-            b, words = bits.contiguous(), int(bits.shape[1])
-            if words < (first + B + 31) // 32:
-                raise ValueError('bits has %d words per vertex, poses up to %d need %d' % (words, first + B, (first + B + 31) // 32))
+            b = _pose_bits(bits, n, first + B, 'poses up to %d')
         if flow is not None:
             flow, lattice_step = _nonrigid_flow(flow, lattice_step, B, int(c.shape[1]), int(c.shape[2]))
         if B == 0 or n == 0:
@@ -1678,7 +1696,7 @@ class FrameColors:
             return self
         route = _lib.CONSTANTS['STIN_FRAMES_ROUTE_AUTO'] if route is None else int(route)
         if flow is not None:
-            cam = (ctypes.c_double * _lib.CONSTANTS['STIN_COLORMAP_CAMERA_DOUBLES'])(*self.color_camera)
+            cam = _camera_doubles(self.color_camera)
             _lib.check(_lib.load().stin_nonrigid_accumulate_f64(_ptr(self.vertices), n, _ptr(rt_d), _ptr(valid_d), B, int(first_pose),
                                                                 _ptr(color), int(color.shape[1]), int(color.shape[2]), _ptr(flow),
                                                                 int(lattice_step), cam, self.z_near, _ptr(bits), int(bits.shape[1]),
@@ -1686,7 +1704,7 @@ class FrameColors:
                                                                 0 if seen is None else int(seen.shape[1]), _stream(self.vertices)),
                        'stin_nonrigid_accumulate_f64')
             return self
-        cameras = (ctypes.c_double * _lib.CONSTANTS['STIN_FRAMES_CAMERA_DOUBLES'])(*(self.color_camera + self.depth_camera))
+        cameras = _camera_doubles(self.color_camera + self.depth_camera, 'STIN_FRAMES_CAMERA_DOUBLES')
         params = (ctypes.c_double * _lib.CONSTANTS['STIN_FRAMES_PARAM_DOUBLES'])(self.depth_scale, self.depth_trunc, self.max_depth,
                                                                                  self.depth_threshold, self.z_near)
         Hd, Wd = (int(depth.shape[1]), int(depth.shape[2])) if depth is not None else (0, 0)
@@ -1745,16 +1763,17 @@ def vertex_colors_from_frames(vertices, poses, color, depth=None, bits=None, bat
         raise ValueError('exactly one of depth and bits must be given')
     if flow is not None:
         flow, lattice_step = _nonrigid_flow(flow, lattice_step, P, int(color.shape[1]), int(color.shape[2]))
-    for p0 in range(0, P, step):
-        p1 = min(p0 + step, P)
-        fc.add(poses[p0:p1], color[p0:p1], None if depth is None else depth[p0:p1], bits, first_pose=p0, _route=_route,
-               flow=None if flow is None or two_passes else flow[p0:p1], lattice_step=lattice_step)
-    if two_passes:                                                     # the visibility of the unwarped pass, the colours of a warped one
-        bits = fc.seen
-        fc = FrameColors(vertices, color_camera, depth_camera, num_poses=P if return_seen else None, **params)
+
+    def add_all(fc, depth, bits, flow):
         for p0 in range(0, P, step):
             p1 = min(p0 + step, P)
-            fc.add(poses[p0:p1], color[p0:p1], bits=bits, first_pose=p0, _route=_route, flow=flow[p0:p1], lattice_step=lattice_step)
+            fc.add(poses[p0:p1], color[p0:p1], None if depth is None else depth[p0:p1], bits, first_pose=p0, _route=_route,
+                   flow=None if flow is None else flow[p0:p1], lattice_step=lattice_step)
+        return fc
+
+    add_all(fc, depth, bits, None if two_passes else flow)
+    if two_passes:                                                     # the visibility of the unwarped pass, the colours of a warped one
+        fc = add_all(FrameColors(vertices, color_camera, depth_camera, num_poses=P if return_seen else None, **params), None, fc.seen, flow)
     colors, count = fc.result(fill, knn=knn)
     return (colors, count, fc.seen) if return_seen else (colors, count)
 
@@ -2030,7 +2049,7 @@ def _colormap_workspace(n, batch, device):
 def _colormap_normal(v64, rt_d, valid_d, first_pose, images, camera, z_near, bits, margin, proxy, rows, counts, ws):
     """One batch of poses -> rows fp64 [B, 28], counts int32 [B] (written in place): stin_colormap_normal_f64 on device arrays."""
     n, B = int(v64.shape[0]), int(rt_d.shape[0])
-    cam = (ctypes.c_double * _lib.CONSTANTS['STIN_COLORMAP_CAMERA_DOUBLES'])(*camera)
+    cam = _camera_doubles(camera)
     _lib.check(_lib.load().stin_colormap_normal_f64(_ptr(v64), n, _ptr(rt_d), _ptr(valid_d), B, int(first_pose), _ptr(images),
                                                     int(images.shape[1]), int(images.shape[2]), cam, float(z_near),
                                                     _ptr(bits) if n else None, int(bits.shape[1]), int(margin), _ptr(proxy), _ptr(rows),
@@ -2061,19 +2080,10 @@ def _colormap_inputs(vertices, poses, color, depth, bits, color_camera, depth_ca
     fc = FrameColors(vertices, color_camera, depth_camera, num_poses=P if depth is not None else None, **params)
     v, n, dev = fc.vertices, int(fc.vertices.shape[0]), fc.vertices.device
     step = max(1, min(step, P, _lib.CONSTANTS['STIN_FRAMES_MAX_BATCH']))
-    words = (P + 31) // 32
     if depth is not None:
-        d = _frames_u(depth, torch.uint16, (), 'depth')
-        if int(d.shape[0]) != P:
-            raise ValueError('%d poses but %d depth frames' % (P, int(d.shape[0])))
+        d = _depth_frames(depth, P)
     else:
-        if not (torch.is_tensor(bits) and bits.is_cuda):
-            raise TypeError('bits must be a CUDA tensor (no CPU fallback exists)')
-        if bits.dtype != torch.uint32 or bits.dim() != 2 or int(bits.shape[0]) != n:
-            raise TypeError('bits must be uint32 [N, words], as observe_vertices returns it')
-        if int(bits.shape[1]) < words:
-            raise ValueError('bits has %d words per vertex, %d poses need %d' % (int(bits.shape[1]), P, words))
-        vis = bits.contiguous()
+        vis = _pose_bits(bits, n, P, '%d poses')
     if P and 0 in c.shape:
         raise ValueError('empty frames')
     RT, valid = pose_extrinsics(poses)
@@ -2084,6 +2094,50 @@ def _colormap_inputs(vertices, poses, color, depth, bits, color_camera, depth_ca
             fc.add(given[p0:p0 + step], c[p0:p0 + step], depth=d[p0:p0 + step], first_pose=p0)
         vis = fc.seen
     return fc, c, vis, free, RT, valid, given, status, step, margin
+
+
+def _optimize_poses(fc, color, vis, RT, valid, given, step, info, normal, solve, flow=None, lattice_step=None):
+    """The iteration of both colour-map optimisers, on the output of _colormap_inputs: the gradient images of all P > 0 frames once;
+    then iterations + 1 times (the rows of info['residual']): the extrinsics (and the lattices `flow`, float64 [P, Ah, Aw, 2], changed
+    in place) to the device, the colour sums at them in batches of `step` poses, the proxy, the normal equations in batches, and
+    one read-back.  The optimiser brings its buffers and two functions:
+    normal(batch, rt_d, valid_d, images, flow_d, proxy) launches the normal equations of the poses in the slice `batch`;
+    solve(E, flow_d, valid_d, update) reads back -> (residual [P], pairs [P], moved bool [P] or None) and, where `update` (every
+    iteration but the last), moves E float64 [P, 4, 4] (and flow) in place.
+    Fills info['residual'], info['pairs'] (and info['flow_norm']) -> poses float64 [P, 4, 4]: the inverse of every extrinsic that
+    ever moved, the given pose otherwise."""
+    import numpy as np
+    P, n, dev = len(given), int(fc.vertices.shape[0]), fc.vertices.device
+    iters = info['residual'].shape[0] - 1
+    images = torch.empty(P, int(color.shape[1]), int(color.shape[2]), 4, dtype=torch.int32, device=dev)
+    for p0 in range(0, P, step):
+        _colormap_gradients(color[p0:p0 + step], images[p0:p0 + step])
+    proxy = torch.empty(n, dtype=torch.float64, device=dev)
+    valid_d = torch.from_numpy(valid).to(dev)
+    E = np.zeros((P, 4, 4), dtype=np.float64)
+    E[:, :3, :] = RT.reshape(P, 3, 4)
+    E[:, 3, 3] = 1.0
+    ever = np.zeros(P, dtype=bool)
+    for it in range(iters + 1):
+        rt_d = torch.from_numpy(np.ascontiguousarray(E[:, :3, :]).reshape(P, 12)).to(dev)
+        flow_d = None if flow is None else torch.from_numpy(flow).to(dev)
+        fc.sum.zero_()
+        fc.count.zero_()
+        for p0 in range(0, P, step):
+            fc._add_extrinsics(rt_d[p0:p0 + step], valid_d[p0:p0 + step], color[p0:p0 + step], p0, bits=vis,
+                               flow=None if flow is None else flow_d[p0:p0 + step], lattice_step=lattice_step)
+        _colormap_proxy(fc.sum, fc.count, proxy)
+        for p0 in range(0, P, step):
+            normal(slice(p0, p0 + step), rt_d, valid_d, images, flow_d, proxy)
+        if flow is not None:
+            info['flow_norm'][it] = np.abs(flow).reshape(P, -1).max(axis=1)
+        info['residual'][it], info['pairs'][it], moved = solve(E, flow_d, valid_d, it < iters)
+        if moved is not None:
+            ever |= moved
+    out = given.copy()
+    for p in np.flatnonzero(ever):
+        out[p] = np.linalg.inv(E[p])
+    return out
 
 
 def optimize_poses_rigid(vertices, poses, color, depth=None, bits=None, *, color_camera=None, depth_camera=None, iterations=30,
@@ -2119,41 +2173,22 @@ def optimize_poses_rigid(vertices, poses, color, depth=None, bits=None, *, color
                                                                                 depth_camera, iterations, free, batch, params)
     P, iters, min_pairs = len(given), int(iterations), int(min_pairs)
     v, n, dev = fc.vertices, int(fc.vertices.shape[0]), fc.vertices.device
-    residual, pairs = np.zeros((iters + 1, P), dtype=np.float64), np.zeros((iters + 1, P), dtype=np.int64)
-    info = dict(residual=residual, pairs=pairs, status=status)
+    info = dict(residual=np.zeros((iters + 1, P), dtype=np.float64), pairs=np.zeros((iters + 1, P), dtype=np.int64), status=status)
     if P == 0:
         return given, info
-    H, W = int(c.shape[1]), int(c.shape[2])
-    images = torch.empty(P, H, W, 4, dtype=torch.int32, device=dev)
-    for p0 in range(0, P, step):
-        _colormap_gradients(c[p0:p0 + step], images[p0:p0 + step])
-    proxy = torch.empty(n, dtype=torch.float64, device=dev)
     rows = torch.empty(P, _lib.CONSTANTS['STIN_COLORMAP_ROW_DOUBLES'], dtype=torch.float64, device=dev)
     counts = torch.empty(P, dtype=torch.int32, device=dev)
     ws = _colormap_workspace(n, step, dev)
-    valid_d = torch.from_numpy(valid).to(dev)
-    E = np.zeros((P, 4, 4), dtype=np.float64)
-    E[:, :3, :] = RT.reshape(P, 3, 4)
-    E[:, 3, 3] = 1.0
-    ever = np.zeros(P, dtype=bool)
-    for it in range(iters + 1):
-        rt_d = torch.from_numpy(np.ascontiguousarray(E[:, :3, :]).reshape(P, 12)).to(dev)
-        fc.sum.zero_()
-        fc.count.zero_()
-        for p0 in range(0, P, step):
-            fc._add_extrinsics(rt_d[p0:p0 + step], valid_d[p0:p0 + step], c[p0:p0 + step], p0, bits=vis)
-        _colormap_proxy(fc.sum, fc.count, proxy)
-        for p0 in range(0, P, step):
-            _colormap_normal(v, rt_d[p0:p0 + step], valid_d[p0:p0 + step], p0, images[p0:p0 + step], fc.color_camera, fc.z_near, vis,
-                             margin, proxy, rows[p0:p0 + step], counts[p0:p0 + step], ws)
+
+    def normal(batch, rt_d, valid_d, images, flow_d, proxy):
+        _colormap_normal(v, rt_d[batch], valid_d[batch], batch.start, images[batch], fc.color_camera, fc.z_near, vis, margin, proxy,
+                         rows[batch], counts[batch], ws)
+
+    def solve(E, flow_d, valid_d, update):
         r, k = rows.cpu().numpy(), counts.cpu().numpy()
-        residual[it], pairs[it] = r[:, 27], k
-        if it < iters:
-            ever |= rigid_update(E, valid, free, r, k, min_pairs, status)
-    out = given.copy()
-    for p in np.flatnonzero(ever):
-        out[p] = np.linalg.inv(E[p])
-    return out, info
+        return r[:, 27], k, rigid_update(E, valid, free, r, k, min_pairs, status) if update else None
+
+    return _optimize_poses(fc, c, vis, RT, valid, given, step, info, normal, solve), info
 
 
 # --------------------------------------------------------------------------------------- non-rigid colour-map optimisation
@@ -2182,6 +2217,13 @@ def _nonrigid_flow(flow, lattice_step, P, H, W):
 
 
 _NONRIGID_TRI = tuple((i, j) for i in range(14) for j in range(i, 14))
+
+
+def _nonrigid_move(E, flow, p, x):
+    """Pose p takes the step x of a solve: E[p] = D(x[:6]) E[p], flow[p] += x[6:], both in place."""
+    import numpy as np
+    E[p] = rigid_increment(x[:6]) @ np.ascontiguousarray(E[p])
+    flow[p] += x[6:].reshape(flow.shape[1:])
 
 
 def nonrigid_update(E, flow, valid, free, blocks, counts, n_vertices, anchor_weight, min_pairs, status):
@@ -2227,8 +2269,7 @@ def nonrigid_update(E, flow, valid, free, blocks, counts, n_vertices, anchor_wei
         if x is None or not np.isfinite(x).all():
             status[p] |= COLORMAP_SINGULAR
             continue
-        E[p] = rigid_increment(x[:6]) @ np.ascontiguousarray(E[p])
-        flow[p] += x[6:].reshape(Ah, Aw, 2)
+        _nonrigid_move(E, flow, p, x)
         moved[p] = True
     return moved
 
@@ -2245,7 +2286,7 @@ def _nonrigid_workspace(n, batch, H, W, lattice_step, device):
 def _nonrigid_keys(v64, rt_d, valid_d, first_pose, H, W, flow_d, lattice_step, camera, z_near, bits, margin, keys):
     """One batch of poses -> keys int64 [B * N] (the head of `keys`, written in place): stin_nonrigid_keys_f64 on device arrays."""
     n, B = int(v64.shape[0]), int(rt_d.shape[0])
-    cam = (ctypes.c_double * _lib.CONSTANTS['STIN_COLORMAP_CAMERA_DOUBLES'])(*camera)
+    cam = _camera_doubles(camera)
     _lib.check(_lib.load().stin_nonrigid_keys_f64(_ptr(v64), n, _ptr(rt_d), _ptr(valid_d), B, int(first_pose), int(H), int(W),
                                                   _ptr(flow_d), int(lattice_step), cam, float(z_near), _ptr(bits) if n else None,
                                                   int(bits.shape[1]), int(margin), _ptr(keys), int(keys.numel()) * 8, _stream(v64)),
@@ -2256,7 +2297,7 @@ def _nonrigid_keys(v64, rt_d, valid_d, first_pose, H, W, flow_d, lattice_step, c
 def _nonrigid_blocks(v64, rt_d, valid_d, first_pose, images, flow_d, lattice_step, camera, z_near, margin, proxy, ordered, blocks, counts):
     """One batch of poses and its SORTED keys -> blocks fp64 [B, cells, 120], counts int32 [B, cells] (written in place)."""
     n, B = int(v64.shape[0]), int(rt_d.shape[0])
-    cam = (ctypes.c_double * _lib.CONSTANTS['STIN_COLORMAP_CAMERA_DOUBLES'])(*camera)
+    cam = _camera_doubles(camera)
     _lib.check(_lib.load().stin_nonrigid_normal_f64(_ptr(v64), n, _ptr(rt_d), _ptr(valid_d), B, int(first_pose), _ptr(images),
                                                     int(images.shape[1]), int(images.shape[2]), _ptr(flow_d), int(lattice_step), cam,
                                                     float(z_near), int(margin), _ptr(proxy), _ptr(ordered), int(ordered.numel()) * 8,
@@ -2384,10 +2425,9 @@ def optimize_poses_nonrigid(vertices, poses, color, depth=None, bits=None, *, co
     S = -(-(H - 1) // (int(vertical_anchors) - 1)) if lattice_step is None else int(lattice_step)
     Ah, Aw = nonrigid_lattice(H, W, max(S, 1))
     cells = (Ah - 1) * (Aw - 1)
-    residual, pairs = np.zeros((iters + 1, P), dtype=np.float64), np.zeros((iters + 1, P), dtype=np.int64)
-    flow_norm = np.zeros((iters + 1, P), dtype=np.float64)
     flow = np.zeros((P, Ah, Aw, 2), dtype=np.float64)
-    info = dict(residual=residual, pairs=pairs, status=status, flow_norm=flow_norm, lattice_step=S, solver=solver)
+    info = dict(residual=np.zeros((iters + 1, P), dtype=np.float64), pairs=np.zeros((iters + 1, P), dtype=np.int64), status=status,
+                flow_norm=np.zeros((iters + 1, P), dtype=np.float64), lattice_step=S, solver=solver)
     if solver == 'banded' and Aw > _lib.CONSTANTS['STIN_NONRIGID_SOLVE_MAX_AW']:
         raise ValueError("a lattice of %d columns is wider than the %d the banded solve supports: use solver='dense'"
                          % (Aw, _lib.CONSTANTS['STIN_NONRIGID_SOLVE_MAX_AW']))
@@ -2399,48 +2439,31 @@ def optimize_poses_nonrigid(vertices, poses, color, depth=None, bits=None, *, co
         status |= info['rigid']['status']
         RT, valid = pose_extrinsics(given)
     keys = _nonrigid_workspace(n, step, H, W, S, dev)
-    images = torch.empty(P, H, W, 4, dtype=torch.int32, device=dev)
-    for p0 in range(0, P, step):
-        _colormap_gradients(c[p0:p0 + step], images[p0:p0 + step])
-    proxy = torch.empty(n, dtype=torch.float64, device=dev)
     blocks = torch.empty(P, cells, _lib.CONSTANTS['STIN_NONRIGID_BLOCK_DOUBLES'], dtype=torch.float64, device=dev)
     counts = torch.empty(P, cells, dtype=torch.int32, device=dev)
-    valid_d = torch.from_numpy(valid).to(dev)
     free_d = torch.from_numpy(free.astype(np.uint8)).to(dev) if solver == 'banded' else None
-    E = np.zeros((P, 4, 4), dtype=np.float64)
-    E[:, :3, :] = RT.reshape(P, 3, 4)
-    E[:, 3, 3] = 1.0
-    ever = np.zeros(P, dtype=bool)
-    for it in range(iters + 1):
-        rt_d = torch.from_numpy(np.ascontiguousarray(E[:, :3, :]).reshape(P, 12)).to(dev)
-        flow_d = torch.from_numpy(flow).to(dev)
-        fc.sum.zero_()
-        fc.count.zero_()
-        for p0 in range(0, P, step):
-            fc._add_extrinsics(rt_d[p0:p0 + step], valid_d[p0:p0 + step], c[p0:p0 + step], p0, bits=vis, flow=flow_d[p0:p0 + step],
-                               lattice_step=S)
-        _colormap_proxy(fc.sum, fc.count, proxy)
-        for p0 in range(0, P, step):
-            _nonrigid_normal(v, rt_d[p0:p0 + step], valid_d[p0:p0 + step], p0, images[p0:p0 + step], flow_d[p0:p0 + step], S,
-                             fc.color_camera, fc.z_near, vis, margin, proxy, blocks[p0:p0 + step], counts[p0:p0 + step], keys)
-        if solver == 'banded':                                         # the solve on the device: x comes back, not the blocks
-            x, e, k, st = (t.cpu().numpy() for t in nonrigid_solve(blocks, counts, flow_d, valid_d, free_d, n, anchor_weight, min_pairs))
-            residual[it], pairs[it], flow_norm[it] = e, k, np.abs(flow).reshape(P, -1).max(axis=1)
-            if it < iters:
-                status |= st
-                for p in np.flatnonzero((st == 0) & free & (valid != 0)):
-                    E[p] = rigid_increment(x[p, :6]) @ np.ascontiguousarray(E[p])
-                    flow[p] += x[p, 6:].reshape(Ah, Aw, 2)
-                    ever[p] = True
-            continue
+
+    def normal(batch, rt_d, valid_d, images, flow_d, proxy):
+        _nonrigid_normal(v, rt_d[batch], valid_d[batch], batch.start, images[batch], flow_d[batch], S, fc.color_camera, fc.z_near, vis,
+                         margin, proxy, blocks[batch], counts[batch], keys)
+
+    def solve_dense(E, flow_d, valid_d, update):
         blk, k = blocks.cpu().numpy(), counts.cpu().numpy()
-        residual[it] = np.cumsum(blk[:, :, 119], axis=1)[:, -1]           # cells ascending
-        pairs[it], flow_norm[it] = k.sum(axis=1), np.abs(flow).reshape(P, -1).max(axis=1)
-        if it < iters:
-            ever |= nonrigid_update(E, flow, valid, free, blk, k, n, anchor_weight, min_pairs, status)
-    out = given.copy()
-    for p in np.flatnonzero(ever):
-        out[p] = np.linalg.inv(E[p])
+        moved = nonrigid_update(E, flow, valid, free, blk, k, n, anchor_weight, min_pairs, status) if update else None
+        return np.cumsum(blk[:, :, 119], axis=1)[:, -1], k.sum(axis=1), moved           # cells ascending
+
+    def solve_banded(E, flow_d, valid_d, update):                      # the solve on the device: x comes back, not the blocks
+        x, e, k, st = (t.cpu().numpy() for t in nonrigid_solve(blocks, counts, flow_d, valid_d, free_d, n, anchor_weight, min_pairs))
+        if not update:
+            return e, k, None
+        status[:] |= st
+        moved = (st == 0) & free & (valid != 0)
+        for p in np.flatnonzero(moved):
+            _nonrigid_move(E, flow, p, x[p])
+        return e, k, moved
+
+    out = _optimize_poses(fc, c, vis, RT, valid, given, step, info, normal, solve_banded if solver == 'banded' else solve_dense,
+                          flow=flow, lattice_step=S)
     return out, flow, info
 
 
