@@ -321,7 +321,43 @@ int stin_colreduce_f32(int mode, const float* x, int64_t ldx, const float* gout,
                        const float* mean, const float* rstd, const float* coef, int post,
                        const float* inv_cnt, float eps, float* out0, float* out1,
                        void* workspace, size_t workspace_bytes, stin_stream_t stream);
+/* The arithmetic of the reductions, operation by operation (every line one IEEE operation, fp32 unless it says fp64; no fused
+ * multiply-add; bf16 rows are widened to fp32 first, which is exact).  Per element, then added in fp64:
+ *   SUM      t = double(x)
+ *   CSQ      d = x - mean[gid];  t = double(d * d)
+ *   DOT_ELU  xc = x - mean[gid];  n = xc * rstd[gid];  e = n > 0 ? 1 : exp(n);  dy = gout * e;  t0 = double(dy * xc), t1 = double(dy)
+ *   COEF_XC  t = double(coef[sid] * (x - mean[gid]))
+ *   MOMENTS  d = double(x);  t0 = d, t1 = d * d (fp64)
+ *   DOT_BN   n = (x - mean) * rstd;  d = gout, or 0 where DOT_BN_RELU and not (gamma * n + beta > 0);  t0 = double(d * n), t1 = double(d)
+ * (exp is the device's fast exponential, not correctly rounded: exact only where its argument is 0 or its result rounds to 0).
+ * The fp64 sums are formed in a fixed order that depends on the route, so they are reproducible but defined to the bit only where
+ * every partial sum is exact.  A range without rows gives the sum 0.  From the fp64 sum s of range b:
+ *   POST_NONE       float(s)
+ *   POST_SCALE      float(s) * inv_cnt[b]
+ *   POST_RSTD       1 / sqrt(float(s) * inv_cnt[b] + eps)
+ *   POST_NORM_COEF  r = rstd[b, c]:  out0 = ((-((r * r) * r)) * float(s0)) * inv_cnt[b],  out1 = (-(r * float(s1))) * inv_cnt[b]
+ *   MOMENTS         all fp64: ic = double(inv_cnt[b]);  mu = s0 * ic;  var = s1 * ic - mu * mu, raised to 0 where negative;
+ *                   mean = float(mu);  rstd = float(1 / sqrt(var + double(eps)))
+ *
+ * stin_colreduce_route: the route a reduction takes, host only - nothing is launched, no device is touched; stin_colreduce_*
+ * launch from the same function.  nout = 1 or 2 outputs (2: DOT_ELU, MOMENTS, DOT_BN*); vec4 = the operands allow four channels
+ * per lane (C % 4 == 0, rows of x / gout start on four elements at pitches that are multiples of four, mean / rstd / coef on 16
+ * bytes); f32_rows = fp32 storage; cu > 0 = the compute units of the device the rules are asked for.  out8 (eight int64) =
+ * { family (STIN_COLREDUCE_*), GC - the columns of a column group (one launch) - or the channels per lane 4 / 1 (two stages), row
+ * chunks R (one launch) or nch (two stages), grid x, y, z of the first launch, fp64 partials the route writes into the workspace,
+ * column groups ncg (one launch; else 0) }.  partials * 8 + 256 <= stin_colreduce_workspace_bytes(C, B) on every route.  Returns
+ * STIN_E_UNSUPPORTED for bf16 rows without vec4, as the reduction itself does, or an argument error, and then writes nothing. */
+#define STIN_COLREDUCE_ONE_LAUNCH 1     /* k_colreduce_t: partial [B][ncg][R][nout][GC], folded by the last block of a column group */
+#define STIN_COLREDUCE_TWO_STAGE 2      /* k_colreduce: partial [B][nch][nout][C], then k_colreduce_final / k_moments_final */
+int stin_colreduce_route(int64_t N, int C, int B, int nout, int vec4, int f32_rows, int cu, int64_t* out8);
+/* Channels per lane of the elementwise passes stin_norm_act_res_fwd_* / stin_norm_act_bwd_*: 8 (bf16 rows, C % 8 == 0, data
+ * pointers on 16 bytes, pitches multiples of 8), 4 (C % 4 == 0, data pointers on four elements, pitches multiples of 4), 1 (fp32
+ * rows otherwise) or STIN_E_UNSUPPORTED (bf16 rows otherwise); 8 and 4 also need the per-group vectors on 16 bytes.  Host only.
+ * elem_bytes 4 / 2; data_align: bytes that divide every data pointer; ld_align: elements that divide every row pitch. */
+int stin_norm_lane_class(int C, int elem_bytes, int data_align, int stats_aligned16, int ld_align);
 /* y = res + ELU((x - mean[gid]) * rstd[gid])    (res may be NULL; act: 1 = ELU, 0 = none)
+ * In operations: n = (x - mean[gid]) * rstd[gid];  act: n = n > 0 ? n : expm1(n) (the device's expm1f);  y = n + res.  bf16 rows:
+ * fp32 arithmetic on the widened values, y rounded to nearest-even once.
  * GraphResnetBlock epilogue (models/surfacetextureinpaintingnet.py:510-521) and the
  * tail norm+ELU (:465-466). */
 int stin_norm_act_res_fwd_f32(const float* x, int64_t ldx, const float* mean, const float* rstd,
@@ -331,7 +367,8 @@ int stin_norm_act_res_fwd_f32(const float* x, int64_t ldx, const float* mean, co
 int stin_norm_act_res_fwd_map_f32(const float* x, int64_t ldx, const float* mean, const float* rstd, const int32_t* gid,
                                   const float* res, int64_t ldres, const int32_t* row_map, int64_t N, int C, int act, float* y,
                                   int64_t ldy, stin_stream_t stream);
-/* dx = a[gid] * dY + k[sid] * (x - mean[gid]) + m[sid],  dY = gout * act'((x-mean[gid])*rstd[gid]) */
+/* dx = a[gid] * dY + k[sid] * (x - mean[gid]) + m[sid],  dY = gout * act'((x-mean[gid])*rstd[gid])
+ * In operations: xc = x - mean[gid];  dY = gout (act 0), or gout * e with e of DOT_ELU above;  dx = (a[gid] * dY + k[sid] * xc) + m[sid]. */
 int stin_norm_act_bwd_f32(const float* x, int64_t ldx, const float* gout, int64_t ldg, const float* mean,
                           const float* rstd, const float* a, const float* k, const float* m,
                           const int32_t* gid, const int32_t* sid, int64_t N, int C, int act, float* dx,
@@ -499,6 +536,8 @@ int stin_norm_coef_from_partials_f32(const double* partial, int64_t groups, int 
  *   bwd: dx = rstd * gamma * (d - Q * inv_n - n * P * inv_n)   d = gout * act'(.), n = (x - mean) * rstd,
  *        P = sum d n (= dgamma), Q = sum d (= dbeta) from stin_colreduce_f32(STIN_RED_DOT_BN[_RELU]).
  * act: 0 = none, 1 = ReLU.
+ * In operations (fp32, no fused multiply-add): n = (x - mean) * rstd;  z = gamma * n + beta;  y = z, or 0 where act and not (z > 0);
+ *   bwd: d = gout, or 0 where act and not (z > 0);  dx = (rstd * gamma) * ((d - Q * inv_n) - n * (P * inv_n)).
  */
 int stin_bn_act_fwd_f32(const float* x, int64_t ldx, const float* mean, const float* rstd, const float* gamma,
                         const float* beta, int64_t N, int C, int act, float* y, int64_t ldy, stin_stream_t stream);
@@ -518,7 +557,8 @@ int stin_bn_mean_bwd_f32(const float* m, int64_t ldm, const float* g, int64_t ld
 
 /* nn.BatchNorm1d's running-statistics update from the batch statistics (mean, rstd = 1/sqrt(biased var + eps)) in one
  * launch: running_mean <- (1 - m) running_mean + m mean; running_var <- (1 - m) running_var + m * unbias * max(1/rstd^2 -
- * eps, 0), unbias = n / (n - 1). */
+ * eps, 0), unbias = n / (n - 1).  In operations: var = max(1 / (rstd * rstd) - eps, 0);  running_mean = (1 - m) * running_mean
+ * + m * mean;  running_var = (1 - m) * running_var + m * (var * unbias). */
 int stin_bn_running_stats_f32(const float* mean, const float* rstd, int C, float eps, float unbias, float momentum,
                               float* running_mean, float* running_var, stin_stream_t stream);
 

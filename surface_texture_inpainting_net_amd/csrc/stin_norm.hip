@@ -750,17 +750,28 @@ inline bool vec4_ok(int C, std::initializer_list<const void*> data, std::initial
     return true;
 }
 
-template <typename T>
-inline bool vec8_ok(int C, std::initializer_list<const void*> data, std::initializer_list<const void*> stats,
-                    std::initializer_list<int64_t> lds) {
-    if (sizeof(T) != 2 || C % 8 != 0) return false;
+// The alignment facts of an elementwise call: the largest power of two, at most 16 (bytes), that divides every data pointer;
+// "every statistics vector starts on 16 bytes"; the largest power of two, at most 8 (elements), that divides every row pitch.
+struct LaneFacts {
+    int data_align, stats16, ld_align;
+};
+inline LaneFacts lane_facts(std::initializer_list<const void*> data, std::initializer_list<const void*> stats,
+                            std::initializer_list<int64_t> lds) {
+    LaneFacts f{16, 1, 8};
     for (const void* p : data)
-        if (p != nullptr && !stin_aligned16(p)) return false;
+        while (p != nullptr && (reinterpret_cast<uintptr_t>(p) & (uintptr_t)(f.data_align - 1)) != 0) f.data_align /= 2;
     for (const void* p : stats)
-        if (p != nullptr && !stin_aligned16(p)) return false;
+        if (p != nullptr && !stin_aligned16(p)) f.stats16 = 0;
     for (int64_t ld : lds)
-        if (ld % 8 != 0) return false;
-    return true;
+        while (ld % f.ld_align != 0) f.ld_align /= 2;
+    return f;
+}
+// Channels per lane of norm_fwd_impl / norm_bwd_impl (stin_norm_lane_class): 8 - bf16 rows as 16-byte vectors; 4 - rows as vectors
+// of four elements; 1 - fp32 rows only; STIN_E_UNSUPPORTED - bf16 rows that allow neither vector
+inline int norm_lane_class(int C, int elem_bytes, const LaneFacts& f) {
+    if (elem_bytes == 2 && C % 8 == 0 && f.data_align >= 16 && f.stats16 && f.ld_align % 8 == 0) return 8;
+    if (C % 4 == 0 && f.data_align >= 4 * elem_bytes && f.stats16 && f.ld_align % 4 == 0) return 4;
+    return elem_bytes == 4 ? 1 : STIN_E_UNSUPPORTED;
 }
 
 constexpr bool is_f32(const float*) { return true; }
@@ -803,6 +814,53 @@ inline void launch_rows(void (*kernel)(P...), int64_t rows, int C, int VW, hipSt
     hipLaunchKernelGGL(kernel, dim3((unsigned)((n + BLOCK - 1) / BLOCK)), dim3(BLOCK), 0, stream, args...);
 }
 
+// The route of a column reduction, host only: a pure function of the shape, the number of outputs (1 or 2), the fact "4 channels
+// per lane" (vec4_ok) and the CU count.  colreduce_impl launches from it, stin_colreduce_route shows it (tests/_norm_table.py: the
+// points it must reach).  chunks = R (one launch) / nch (two stages); partial_doubles = the fp64 partials the route writes, which
+// stay inside stin_colreduce_workspace_bytes(C, B) on every route.
+struct ColreduceRoute {
+    int family, width, chunks, ncg;     // STIN_COLREDUCE_*; GC / VW; R / nch; column groups of the one-launch form (else 0)
+    unsigned gx, gy, gz;
+    int64_t partial_doubles;
+};
+inline ColreduceRoute colreduce_route(int64_t N, int C, int B, int nout, bool vec, int cu) {
+    const int64_t slabs = B > MAX_SLABS ? B : MAX_SLABS;                           // the workspace holds slabs x 2 x C doubles
+    // one-launch form (k_colreduce_t): 16-byte fp32 rows, few enough (range, column group) pairs for one row of ticket words;
+    // Column groups of 64 / 32 / 16 so that narrow
+    // matrices still fold on four blocks side by side.
+    if (vec && N > 0) {                                // (fp32 and bf16 rows: 4 channels per lane either way)
+        const int GC = C >= 256 ? 64 : (C >= 128 ? 32 : 16);
+        const int ncg = (C + GC - 1) / GC;
+        if ((int64_t)B * ncg <= RED_WORDS) {
+            const int RLN = BLOCK / (GC / 4);
+            // row chunks: ~8 row trips per block, at most ~2 blocks per CU over all column groups and ranges, and within the workspace
+            int64_t R = (N / B + (int64_t)RLN * 8 - 1) / ((int64_t)RLN * 8);
+            constexpr int per_cu = 2;
+            const int64_t cap = (per_cu * (int64_t)cu + (int64_t)B * ncg - 1) / ((int64_t)B * ncg);
+            if (R > cap) R = cap;
+            // partial [B][ncg][R][2][GC] doubles must fit the caller's workspace of max(B, MAX_SLABS) x 2 x C doubles
+            const int64_t ws_cap = slabs * C / ((int64_t)ncg * GC);
+            if (R > ws_cap / B) R = ws_cap / B;
+            if (R < 1) R = 1;
+            // R = 1 past that bound (C = 4 with more than 256 ranges: a column group is four times as wide as the matrix): taken
+            // only where the [B][ncg][1][nout][GC] partial still fits, else the two-stage route below
+            const int64_t doubles = (int64_t)B * ncg * R * nout * GC;
+            if (doubles <= slabs * 2 * C) return {STIN_COLREDUCE_ONE_LAUNCH, GC, (int)R, ncg, (unsigned)R, (unsigned)ncg, (unsigned)B, doubles};
+        }
+    }
+    const int VW = vec ? 4 : 1;
+    const int CV = C / VW;
+    const int CG = CV < BLOCK ? CV : BLOCK;
+    const int RL = BLOCK / CG;
+    // row iterations per block: 8 (2 blocks per CU at the 18 k-row level) measured 0.3 % faster on the step than 16; 32 is 2 % slower
+    constexpr int rows_mul = 8;
+    const int64_t want = (N / B + (int64_t)RL * rows_mul - 1) / ((int64_t)RL * rows_mul);
+    int cap = MAX_SLABS / B;
+    if (cap < 1) cap = 1;
+    const int nch = (int)(want < 1 ? 1 : (want > cap ? cap : want));
+    return {STIN_COLREDUCE_TWO_STAGE, VW, nch, 0, (unsigned)nch, (unsigned)B, 1u, (int64_t)B * nch * nout * C};
+}
+
 template <typename T>
 int colreduce_impl(int mode, const T* x, int64_t ldx, const T* gout, int64_t ldg, int64_t N, int C, const int32_t* ptr,
                    int B, const int32_t* gid, const int32_t* sid, const float* mean, const float* rstd,
@@ -826,50 +884,24 @@ int colreduce_impl(int mode, const T* x, int64_t ldx, const T* gout, int64_t ldg
 
     const bool vec = vec4_ok<T>(C, {x, gout}, {mean, rstd, coef}, {ldx, gout ? ldg : 0});
     if (!vec && !is_f32((const T*)nullptr)) return STIN_E_UNSUPPORTED;
-    // one-launch form (k_colreduce_t): 16-byte fp32 rows, few enough (range, column group) pairs for one row of ticket words;
-    // Column groups of 64 / 32 / 16 so that narrow
-    // matrices still fold on four blocks side by side.
-    if (vec && N > 0) {                                // (fp32 and bf16 rows: 4 channels per lane either way)
-        const int GC = C >= 256 ? 64 : (C >= 128 ? 32 : 16);
-        const int ncg = (C + GC - 1) / GC;
-        if ((int64_t)B * ncg <= RED_WORDS) {
-            static std::atomic<unsigned> seq{0}, seq_cap{0};
-            const int slot = stin_ticket_slot(seq, seq_cap, RED_SLOTS, stream);
-            const int RLN = BLOCK / (GC / 4);
-            // row chunks: ~8 row trips per block, at most ~2 blocks per CU over all column groups and ranges, and within the workspace
-            int64_t R = (N / B + (int64_t)RLN * 8 - 1) / ((int64_t)RLN * 8);
-            constexpr int per_cu = 2;
-            const int64_t cap = (per_cu * (int64_t)norm_cu_count() + (int64_t)B * ncg - 1) / ((int64_t)B * ncg);
-            if (R > cap) R = cap;
-            // partial [B][ncg][R][2][GC] doubles must fit the caller's workspace of max(B, MAX_SLABS) x 2 x C doubles
-            const int64_t ws_cap = (int64_t)(B > MAX_SLABS ? B : MAX_SLABS) * C / ((int64_t)ncg * GC);
-            if (R > ws_cap / B) R = ws_cap / B;
-            if (R < 1) R = 1;
-            dim3 grid((unsigned)R, (unsigned)ncg, (unsigned)B);
-            for_mode(mode, [&](auto m) {
-                auto launch = [&](auto gc) {
-                    hipLaunchKernelGGL((k_colreduce_t<T, decltype(m)::value, decltype(gc)::value>), grid, dim3(BLOCK), 0, stream, x, ldx, gout,
-                                       ldg, N, C, ptr, gid, sid, mean, rstd, coef, partial, slot, post, inv_cnt, eps, out0, out1);
-                };
-                if (GC == 64) launch(int_c<64>{});
-                else if (GC == 32) launch(int_c<32>{});
-                else launch(int_c<16>{});
-            });
-            return stin_launch_status();
-        }
-    }
-    const int VW = vec ? 4 : 1;
-    const int CV = C / VW;
-    const int CG = CV < BLOCK ? CV : BLOCK;
-    const int RL = BLOCK / CG;
-    // row iterations per block: 8 (2 blocks per CU at the 18 k-row level) measured 0.3 % faster on the step than 16; 32 is 2 % slower
-    constexpr int rows_mul = 8;
-    int64_t want = (N / B + (int64_t)RL * rows_mul - 1) / ((int64_t)RL * rows_mul);
-    int cap = MAX_SLABS / B;
-    if (cap < 1) cap = 1;
-    int nch = (int)(want < 1 ? 1 : (want > cap ? cap : want));
     const int nout = (mode == STIN_RED_DOT_ELU || mode == STIN_RED_MOMENTS || mode >= STIN_RED_DOT_BN) ? 2 : 1;
-    dim3 grid((unsigned)nch, (unsigned)B);
+    const ColreduceRoute rt = colreduce_route(N, C, B, nout, vec, norm_cu_count());
+    const dim3 grid(rt.gx, rt.gy, rt.gz);
+    if (rt.family == STIN_COLREDUCE_ONE_LAUNCH) {
+        static std::atomic<unsigned> seq{0}, seq_cap{0};
+        const int slot = stin_ticket_slot(seq, seq_cap, RED_SLOTS, stream);
+        for_mode(mode, [&](auto m) {
+            auto launch = [&](auto gc) {
+                hipLaunchKernelGGL((k_colreduce_t<T, decltype(m)::value, decltype(gc)::value>), grid, dim3(BLOCK), 0, stream, x, ldx, gout,
+                                   ldg, N, C, ptr, gid, sid, mean, rstd, coef, partial, slot, post, inv_cnt, eps, out0, out1);
+            };
+            if (rt.width == 64) launch(int_c<64>{});
+            else if (rt.width == 32) launch(int_c<32>{});
+            else launch(int_c<16>{});
+        });
+        return stin_launch_status();
+    }
+    const int nch = rt.chunks;
     for_mode(mode, [&](auto m) {
         for_vw<T>(vec, [&](auto vw) {
             hipLaunchKernelGGL((k_colreduce<T, decltype(m)::value, decltype(vw)::value>), grid, dim3(BLOCK), 0, stream, x, ldx, gout, ldg, N,
@@ -900,8 +932,9 @@ int norm_fwd_impl(const T* x, int64_t ldx, const float* mean, const float* rstd,
         else
             launch_rows(k_norm_fwd<T, VW>, N, C, VW, stream, x, ldx, mean, rstd, gid, res, ldres, N, C, act, y, ldy);
     };
-    if (vec8_ok<T>(C, {x, res, y}, {mean, rstd}, {ldx, ldy, res ? ldres : 0})) launch(int_c<8>{});
-    else if (!for_vw<T>(vec4_ok<T>(C, {x, res, y}, {mean, rstd}, {ldx, ldy, res ? ldres : 0}), launch)) return STIN_E_UNSUPPORTED;
+    const int cls = norm_lane_class(C, (int)sizeof(T), lane_facts({x, res, y}, {mean, rstd}, {ldx, ldy, res ? ldres : 0}));
+    if (cls == 8) launch(int_c<8>{});
+    else if (cls < 0 || !for_vw<T>(cls == 4, launch)) return STIN_E_UNSUPPORTED;
     return stin_launch_status();
 }
 
@@ -916,8 +949,9 @@ int norm_bwd_impl(const T* x, int64_t ldx, const T* gout, int64_t ldg, const flo
         constexpr int VW = decltype(vw)::value;
         launch_rows(k_norm_bwd<T, VW>, N, C, VW, stream, x, ldx, gout, ldg, mean, rstd, a, k, m, gid, sid, N, C, act, dx, lddx);
     };
-    if (vec8_ok<T>(C, {x, gout, dx}, {mean, rstd, a, k, m}, {ldx, ldg, lddx})) launch(int_c<8>{});
-    else if (!for_vw<T>(vec4_ok<T>(C, {x, gout, dx}, {mean, rstd, a, k, m}, {ldx, ldg, lddx}), launch)) return STIN_E_UNSUPPORTED;
+    const int cls = norm_lane_class(C, (int)sizeof(T), lane_facts({x, gout, dx}, {mean, rstd, a, k, m}, {ldx, ldg, lddx}));
+    if (cls == 8) launch(int_c<8>{});
+    else if (cls < 0 || !for_vw<T>(cls == 4, launch)) return STIN_E_UNSUPPORTED;
     return stin_launch_status();
 }
 
@@ -991,7 +1025,23 @@ extern "C" size_t stin_colreduce_workspace_bytes(int C, int B) {
     return slabs * 2 * (size_t)C * sizeof(double) + 256;
 }
 
-extern "C" int stin_colreduce_f32(int mode, const float* x, int64_t ldx, const float* gout, int64_t ldg, int64_t N, int C,
+extern "C" int stin_colreduce_route(int64_t N, int C, int B, int nout, int vec4, int f32_rows, int cu, int64_t* out8) {
+    STIN_REQUIRE(out8 != nullptr, STIN_E_NULL);
+    STIN_REQUIRE(N >= 0 && C > 0 && B > 0 && cu > 0 && (nout == 1 || nout == 2), STIN_E_SIZE);
+    STIN_REQUIRE(!vec4 || C % 4 == 0, STIN_E_SIZE);
+    if (!vec4 && !f32_rows) return STIN_E_UNSUPPORTED;
+    const ColreduceRoute rt = colreduce_route(N, C, B, nout, vec4 != 0, cu);
+    const int64_t v[8] = {rt.family, rt.width, rt.chunks, rt.gx, rt.gy, rt.gz, rt.partial_doubles, rt.ncg};
+    for (int i = 0; i < 8; ++i) out8[i] = v[i];
+    return STIN_OK;
+}
+
+extern "C" int stin_norm_lane_class(int C, int elem_bytes, int data_align, int stats_aligned16, int ld_align) {
+    STIN_REQUIRE(C > 0 && (elem_bytes == 2 || elem_bytes == 4) && data_align > 0 && ld_align > 0, STIN_E_SIZE);
+    return norm_lane_class(C, elem_bytes, LaneFacts{data_align, stats_aligned16 != 0, ld_align});
+}
+
+extern "C" int stin_colreduce_f32(int mode,const float* x, int64_t ldx, const float* gout, int64_t ldg, int64_t N, int C,
                                   const int32_t* ptr, int B, const int32_t* gid, const int32_t* sid, const float* mean,
                                   const float* rstd, const float* coef, int post, const float* inv_cnt, float eps,
                                   float* out0, float* out1, void* workspace, size_t workspace_bytes, stin_stream_t stream) {
