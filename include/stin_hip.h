@@ -1690,6 +1690,46 @@ int stin_render_poses_f64(const double* vertices, int64_t N, const int64_t* face
                           uint8_t* color_u8, uint16_t* depth, int32_t* face_ids, int32_t* status, void* workspace,
                           size_t workspace_bytes, stin_stream_t stream);
 
+/* View metrics: PSNR and SSIM (Wang et al. 2004) of two sets of rendered views, prediction against ground truth, per pose
+ * (stin_view_metrics.hip) - what an evaluation run asks of the images "Render" makes, without reading them back.  A contract of the
+ * project's own: it is NOT pinned against skimage or piq.  The window has INTEGER taps; there is no padding, no luma conversion and
+ * no multi-scale SSIM.  Every quantity that is summed is an integer, so the table is the same bytes for every tiling, batch size and
+ * launch order; no float atomics.  tests/_viewmetrics_oracle.py restates it in numpy (one 121-tap sum per window) and agrees
+ * byte for byte.
+ *
+ *   inputs    a, b uint8 [P][H][W][K], 1 <= K <= 4; covered, region uint8 [P][H][W], each optional: NULL = every pixel is covered /
+ *             in the region.  A pixel is covered when covered != 0 and in the region when region != 0.
+ *   pixels    per pose, over the pixels that are covered and in the region: n_pix their number, sum_abs = sum_k |a - b|,
+ *             sum_sq = sum_k (a - b)^2.
+ *   window    11 x 11, separable, taps w = {67, 498, 2359, 7167, 13960, 17434, 13960, 7167, 2359, 498, 67}: the Gaussian of
+ *             sigma 1.5 scaled to 2^16 and rounded, the centre tap raised by 1 so that they sum to 65536; the 2-D weight
+ *             w[i] w[j] sums to 2^32.  A window counts for its pose when all 121 pixels lie inside the image ('valid' mode), all 121
+ *             are covered, and its CENTRE pixel is in the region.
+ *   moments   per counted window and channel, exact integers: Sa = sum w a, Sb = sum w b, Saa = sum w a^2, Sbb = sum w b^2,
+ *             Sab = sum w a b (a 1-D row sum is below 2^32, a 2-D sum below 2^48).
+ *   value     fp64, IEEE, in the order written, nothing contracted: s = 2^-32; ma = Sa s; mb = Sb s; va = Saa s - ma ma;
+ *             vb = Sbb s - mb mb; c = Sab s - ma mb;
+ *             v = ((2.0 ma mb + C1) (2.0 c + C2)) / ((ma ma + mb mb + C1) (va + vb + C2)), C1 = 6.5025 = (0.01 255)^2,
+ *             C2 = 58.5225 = (0.03 255)^2;  q = (int64) rint(v 2^32), ties to even.
+ *             n_win = the pose's counted windows, ssim_q = sum of q over them and the channels.
+ *   table     int64 [P][STIN_VIEW_METRICS_COLS] = n_pix, sum_abs, sum_sq, n_win, ssim_q.  Written by the call: the caller need not
+ *             clear it.  (In [0, 1] colour units: l1 = sum_abs / (255 K n_pix), mse = sum_sq / (255^2 K n_pix),
+ *             ssim = ssim_q / (2^32 K n_win): views.view_metrics.)
+ * stin_view_metrics_u8: one kernel.  A workgroup owns 16 x 32 window corners of one pose; it stages their 26 x 42 pixels of a, b and
+ *     the masks in LDS with 16-byte loads of the 16-byte lines the rows lie in (a line that is not wholly inside its array goes by
+ *     element, so no byte outside an array is read and no base or row needs an alignment), makes the horizontal pass of one channel
+ *     at a time into five uint32 planes, the vertical pass in 64-bit registers, evaluates v and q, counts a window's covered pixels
+ *     as an integer box sum that must be 121, sums the tile's own 16 x 32 pixels, reduces in integers and adds the five figures to
+ *     the pose's row with one 64-bit integer atomic each.
+ *     H, W in [1, STIN_RENDER_MAX_SIZE] (below 11: n_win = 0), 0 <= P < 2^31 - 1, 1 <= K <= 4 (STIN_E_SIZE otherwise); a, b, table
+ *     missing with P > 0: STIN_E_NULL.  stin_view_metrics_workspace_bytes is 0 today (and for sizes out of range): workspace may be
+ *     NULL.  Nothing allocates or synchronises. */
+#define STIN_VIEW_METRICS_COLS 5
+#define STIN_VIEW_METRICS_WINDOW 11
+size_t stin_view_metrics_workspace_bytes(int64_t P, int H, int W, int K);
+int stin_view_metrics_u8(const uint8_t* a, const uint8_t* b, const uint8_t* covered, const uint8_t* region, int64_t P, int H, int W,
+                         int K, int64_t* table, void* workspace, size_t workspace_bytes, stin_stream_t stream);
+
 /* ------------------------------------------------- 2-D image-graph inpainting experiment --
  * What the reference's ImageGraphTextureDataSet builds per item on CPU workers (datasets/imagegraph_dataloader.py:46-160) and what
  * the graph branch of its 2-D trainer reads back per step (trainers/inpainting2d_trainer.py:382-398, without lpips), stin_image.hip.

@@ -10,12 +10,18 @@ screenshot key `P`, a "save the PLYs" key `D`), for machines without a display a
 * ``write_png``, ``write_ply``   8-bit PNG (stdlib zlib + struct) and binary little-endian PLY with uchar colours.
 * ``write_result_views`` one PLY per colouring (the `D` key) and, with poses, one PNG per colouring and pose (the `P` key, from the
                          scan's own viewpoints).
+* ``view_metrics``       PSNR and SSIM of two sets of such images, per pose, in one HIP pass (csrc/stin_view_metrics.hip; contract:
+                         include/stin_hip.h, "View metrics"); ``result_view_metrics`` renders prediction and ground truth from every
+                         pose, a chunk of poses at a time, and measures them.  Not pinned against skimage or piq: the 11 x 11 window
+                         has integer taps, and there is no padding, no luma conversion and no multi-scale SSIM.
 
 Out of scope: lighting, anti-aliasing, textures, clipping at the near plane (a face that crosses it is dropped), reading meshes or
 images, the interactive viewer, SemSegVisualizer's palette (pass label colours as vertex colours), a CPU fallback.  Faces come from
 the caller: graphs/<scene>.pt holds none."""
 import collections
 import ctypes
+import json
+import math
 import os
 import struct
 import zlib
@@ -29,6 +35,38 @@ from .preprocessing import _camera4, _xyz64, pose_extrinsics
 RenderResult = collections.namedtuple('RenderResult', 'color depth face_ids status')
 
 VIEWS = ('rgb', 'pred', 'gt', 'mask', 'diff')
+VIEW_METRICS_COLUMNS = ('n_pix', 'sum_abs', 'sum_sq', 'n_win', 'ssim_q')
+
+
+class ViewMetrics(collections.namedtuple('ViewMetrics', 'table l1 mse psnr ssim')):
+    """view_metrics' result: `table` int64 [P, 5] (VIEW_METRICS_COLUMNS: the exact integer sums of every pose) and what follows from it
+    per pose, fp64 [P] on the table's device, in [0, 1] colour units: l1 = sum_abs / (255 K n_pix), mse = sum_sq / (255^2 K n_pix),
+    psnr = 10 log10(1 / mse) in dB (inf where mse == 0; the trainer's psnr(data_range=2) of the same colours in [-1, 1]),
+    ssim = ssim_q / (2^32 K n_win).  A pose with a zero denominator has NaN.  `channels` is K."""
+
+    def __new__(cls, table, l1, mse, psnr, ssim, channels=3):
+        self = super().__new__(cls, table, l1, mse, psnr, ssim)
+        self.channels = int(channels)
+        return self
+
+    @classmethod
+    def from_table(cls, table, channels):
+        """The derived figures in torch, on the table's device: no read-back."""
+        t = table.double()
+        pix, win = (255.0 * channels) * t[:, 0], (4294967296.0 * channels) * t[:, 3]
+        mse = t[:, 2] / (255.0 * pix)
+        return cls(table, t[:, 1] / pix, mse, 10.0 * torch.log10(1.0 / mse), t[:, 4] / win, channels)
+
+    def total(self):
+        """The scene's figures from the column sums - every pixel and every window weighs the same, whichever pose it is in (a
+        micro-average) - as a dict of Python ints and floats.  One read-back."""
+        n_pix, sum_abs, sum_sq, n_win, ssim_q = (int(v) for v in self.table.sum(dim=0).cpu().tolist())
+        K, nan = self.channels, float('nan')
+        l1 = sum_abs / (255.0 * K * n_pix) if n_pix else nan
+        mse = sum_sq / (255.0 * (255.0 * K * n_pix)) if n_pix else nan
+        psnr = nan if not n_pix else float('inf') if sum_sq == 0 else 10.0 * math.log10(1.0 / mse)
+        return {'poses': int(self.table.shape[0]), 'channels': K, 'n_pix': n_pix, 'sum_abs': sum_abs, 'sum_sq': sum_sq, 'n_win': n_win,
+                'ssim_q': ssim_q, 'l1': l1, 'mse': mse, 'psnr': psnr, 'ssim': ssim_q / (4294967296.0 * K * n_win) if n_win else nan}
 
 
 def render_mesh(vertices, faces, colors, poses, camera, height, width, *, dtype=torch.uint8, background=(0, 0, 0), depth=False,
@@ -133,6 +171,84 @@ def result_colorings(pred, gt, mask, rgb=None):
     return out
 
 
+def _mask_u8(m, shape, name):
+    """A [P, H, W] mask as contiguous bytes: uint8 as it is, bool and integer masks as `!= 0`."""
+    if m is None:
+        return None
+    if not (torch.is_tensor(m) and m.is_cuda):
+        raise TypeError('%s must be a CUDA tensor (no CPU fallback exists)' % name)
+    if tuple(m.shape) != tuple(shape):
+        raise ValueError('%s must be [P, H, W] like the images' % name)
+    if m.dtype != torch.uint8:
+        m = (m != 0).view(torch.uint8)
+    return m.contiguous()
+
+
+def view_metrics(a, b, covered=None, region=None):
+    """PSNR and SSIM of the images `a` against `b`, per pose, on the GPU (csrc/stin_view_metrics.hip).  a, b: CUDA uint8 [P, H, W, K],
+    1 <= K <= 4, or [P, H, W]; covered, region: optional CUDA masks [P, H, W], uint8, bool or integer (non-zero = set; for instance
+    RenderResult.face_ids >= 0).  -> ViewMetrics(table int64 [P, 5], l1, mse, psnr, ssim fp64 [P]), all on the device: nothing is
+    read back.
+
+    The contract (include/stin_hip.h, "View metrics"; restated in numpy by the test suite, which `table` reproduces byte for byte):
+    n_pix, sum_abs = sum |a - b| and sum_sq = sum (a - b)^2 over the pixels that are covered and in the region; SSIM over 11 x 11
+    windows with the INTEGER taps of a sigma 1.5 Gaussian scaled to 2^16, no padding (a window counts when it lies inside the image,
+    all its 121 pixels are covered and its centre is in the region; none in an image under 11 pixels), per channel (no luma
+    conversion), one scale; every window's value is rounded to 2^-32 and summed as an integer, so the table does not depend on how
+    the work is split.  It is a contract of the project's own, not pinned against skimage or piq."""
+    if not (torch.is_tensor(a) and a.is_cuda and torch.is_tensor(b) and b.is_cuda):
+        raise TypeError('a and b must be CUDA tensors (no CPU fallback exists)')
+    if a.dtype != torch.uint8 or b.dtype != torch.uint8:
+        raise TypeError('a and b must be uint8 images')
+    if a.shape != b.shape or a.dim() not in (3, 4):
+        raise ValueError('a and b must both be [P, H, W, K] or [P, H, W]')
+    P, H, W = (int(n) for n in a.shape[:3])
+    K = 1 if a.dim() == 3 else int(a.shape[3])
+    C = _lib.CONSTANTS
+    if not 1 <= K <= 4:
+        raise ValueError('the images must have 1 to 4 channels')
+    if not 1 <= H <= C['STIN_RENDER_MAX_SIZE'] or not 1 <= W <= C['STIN_RENDER_MAX_SIZE']:
+        raise ValueError('height and width must be in [1, %d]' % C['STIN_RENDER_MAX_SIZE'])
+    cov, reg = _mask_u8(covered, a.shape[:3], 'covered'), _mask_u8(region, a.shape[:3], 'region')
+    lib = _lib.load()
+    a, b = a.contiguous(), b.contiguous()
+    table = torch.empty(P, C['STIN_VIEW_METRICS_COLS'], dtype=torch.int64, device=a.device)
+    if P:
+        ws_bytes = lib.stin_view_metrics_workspace_bytes(P, H, W, K)
+        ws = torch.empty(ws_bytes, dtype=torch.uint8, device=a.device) if ws_bytes else None
+        _lib.check(lib.stin_view_metrics_u8(_ptr(a), _ptr(b), _ptr(cov), _ptr(reg), P, H, W, K, _ptr(table), _ptr(ws), ws_bytes, _stream(a)),
+                   'stin_view_metrics_u8')
+    return ViewMetrics.from_table(table, K)
+
+
+def result_view_metrics(vertices, faces, pred, gt, mask, poses, camera, height, width, *, region='mask', chunk=32, **render):
+    """How good a prediction is as seen from the scan's cameras: result_colorings(pred, gt, mask)['pred'] against ['gt'], rendered by
+    render_mesh from every pose (camera, height, width and further keywords are its) and measured by view_metrics -> ViewMetrics for
+    the P poses.  A pixel is covered where a face was drawn (face_ids >= 0).  region='mask': only what the inpainted vertices reach -
+    (mask > 0) is rendered as a one-channel colour on a black background, and a pixel is in the region where that image is non-zero;
+    region='all': every covered pixel.  Poses are rendered `chunk` at a time, so at most 3 chunk H W 4 bytes of images exist at
+    once; the result does not depend on `chunk`."""
+    if region not in ('mask', 'all'):
+        raise ValueError("region must be 'mask' or 'all'")
+    if int(chunk) < 1:
+        raise ValueError('chunk must be positive')
+    colorings = result_colorings(pred, gt, mask)
+    inpainted = (mask.detach().reshape(-1) > 0).float()
+    P = len(poses)
+    tables = []
+    for p0 in range(0, P, int(chunk)):
+        some = poses[p0:p0 + int(chunk)]
+        shown = render_mesh(vertices, faces, colorings['pred'], some, camera, height, width, face_ids=True, **render)
+        truth = render_mesh(vertices, faces, colorings['gt'], some, camera, height, width, **render)
+        where = None
+        if region == 'mask':
+            where = render_mesh(vertices, faces, inpainted, some, camera, height, width, **dict(render, background=(0.0,)))[..., 0]
+        tables.append(view_metrics(shown.color, truth, shown.face_ids >= 0, where).table)
+    if not tables:
+        tables.append(torch.zeros(0, len(VIEW_METRICS_COLUMNS), dtype=torch.int64, device=colorings['pred'].device))
+    return ViewMetrics.from_table(torch.cat(tables), 3)
+
+
 def _chunk(tag, data):
     return struct.pack('>I', len(data)) + tag + data + struct.pack('>I', zlib.crc32(tag + data) & 0xFFFFFFFF)
 
@@ -188,10 +304,18 @@ def write_ply(path, vertices, faces, colors):
         out.write(header.encode('ascii') + vert.tobytes() + face.tobytes())
 
 
-def write_result_views(out_dir, name, vertices, faces, colorings, poses=None, camera=None, height=None, width=None, **render):
+def _finite(values):
+    """Floats for a JSON file: a value that is not finite (NaN, inf) becomes null - the integer rows beside it say which it was."""
+    return [v if math.isfinite(v) else None for v in values]
+
+
+def write_result_views(out_dir, name, vertices, faces, colorings, poses=None, camera=None, height=None, width=None, metrics=None,
+                       **render):
     """The visualiser's `D` key - one PLY per colouring, <out_dir>/<name>_<view>.ply - and, with poses, its `P` key from the scan's own
     viewpoints: <name>_<view>_<pose id>.png, rendered by render_mesh (camera, height, width and further keywords are its).
-    colorings: result_colorings' dict (any dict of [N, 3] float colours).  -> the list of the files written."""
+    colorings: result_colorings' dict (any dict of [N, 3] float colours).  metrics: a ViewMetrics (result_view_metrics) to write
+    beside them as <name>_view_metrics.json - 'columns' and 'table' (the integer row of every pose), 'l1', 'mse', 'psnr', 'ssim' per
+    pose and 'total' (ViewMetrics.total()); a figure that is not finite is written as null.  -> the list of the files written."""
     if poses is not None and (camera is None or height is None or width is None):
         raise ValueError('rendering from poses needs camera, height and width')
     os.makedirs(out_dir, exist_ok=True)
@@ -207,4 +331,14 @@ def write_result_views(out_dir, name, vertices, faces, colorings, poses=None, ca
             path = os.path.join(out_dir, '%s_%s_%d.png' % (name, view, p))
             write_png(path, images[p])
             written.append(path)
+    if metrics is not None:
+        path = os.path.join(out_dir, '%s_view_metrics.json' % name)
+        doc = {'columns': list(VIEW_METRICS_COLUMNS), 'channels': metrics.channels, 'table': metrics.table.cpu().tolist()}
+        for key in ('l1', 'mse', 'psnr', 'ssim'):
+            doc[key] = _finite(getattr(metrics, key).cpu().tolist())
+        total = metrics.total()
+        doc['total'] = dict(zip(total, _finite(total.values())))
+        with open(path, 'w') as f:
+            json.dump(doc, f, indent=1, allow_nan=False)
+        written.append(path)
     return written
