@@ -1999,6 +1999,86 @@ int stin_harmonic_iterate_f64(const double* weight, int64_t N, int64_t E2, int C
 int stin_harmonic_finish_f32(const float* values, const uint8_t* flag, int64_t N, int64_t E2, int C, int64_t n_unknown, double tol,
                              float fill, float* out, int64_t* state, void* workspace, size_t workspace_bytes, stin_stream_t stream);
 
+/* ------------------------------------------------------------------------------------ Mesh files --
+ * The body of a binary PLY file decoded on the device, and the per-face label vote of the Matterport scans (stin_ply.hip).  The
+ * header of the file is text and is parsed on the host (scene_io.read_ply_header); what it yields - where an element's records
+ * start, how long a record is, where each property sits in it - is the input here.  The file's bytes are uploaded once as they
+ * are: `body` [body_bytes] is a DEVICE buffer whose base is 16-byte aligned; `first`, `stride` and every offset may have any
+ * alignment.  A contract of the project's own; tests/_ply_oracle.py restates it with numpy structured dtypes and the device
+ * agrees byte for byte.  Not pinned against open3d or plyfile themselves (neither is installed here).
+ *
+ * Both decoders check on the HOST, before any launch, that 0 <= first, 1 <= stride <= STIN_PLY_MAX_STRIDE, 0 <= count <=
+ * STIN_PLY_MAX_RECORDS and first + count * stride <= body_bytes (without overflow), and that every field lies inside its record;
+ * they return STIN_E_SIZE / _NULL / _ALIGN / _UNSUPPORTED otherwise.  A workgroup owns 256 consecutive records: it copies the
+ * 16-byte chunks that cover them into LDS with aligned loads (a chunk that would cross the end of the buffer byte by byte) and
+ * takes the fields from there, so no byte outside [0, body_bytes) is read for any input.
+ *
+ * stin_ply_decode.  `count` records of `stride` bytes from byte `first`, unpacked into typed columns in one launch.  `fields`
+ *     is a HOST table of n_fields <= STIN_PLY_MAX_FIELDS rows of STIN_PLY_FIELD_WORDS int64 words:
+ *         [0] byte offset of the scalar in the record   [1] its type, STIN_PLY_INT8 .. STIN_PLY_FLOAT64 (the eight PLY scalars)
+ *         [2] destination DEVICE pointer (aligned to its element)   [3] destination type, STIN_PLY_TO_*
+ *         [4] destination row stride in elements, 1 .. STIN_PLY_MAX_FIELDS   [5] destination column, 0 <= column < row stride
+ *     Record r goes to destination[r * row_stride + column].  Multi-byte scalars are little endian, or big endian with
+ *     big_endian = 1.  The conversions are value preserving and nothing else is accepted (STIN_E_UNSUPPORTED):
+ *         _TO_F64  any scalar (integers are below 2^32 in magnitude: exact; float32 widens exactly)
+ *         _TO_F32  float32 only, bit for bit            _TO_I64  any integer scalar
+ *         _TO_I32  any integer scalar but uint32         _TO_U8   uint8 only
+ *         _TO_UNORM_F64  uint8 only: (double) v / 255.0 with one IEEE division - numpy's u8.astype(float64) / 255.0
+ *     row_stride consecutive rows of the table that fill the columns 0, 1, ... of one destination in order (an [N, 3] position,
+ *     colour or normal matrix; any single column) leave as one dense matrix with consecutive lanes on consecutive elements; any
+ *     other row is written with its stride.  Destinations must not overlap.
+ *
+ * stin_ply_faces.  The face element when every list has K entries, K = 3 or 4: each record is scalar properties and ONE list
+ *     property, stride = the scalars + the count field + K indices.  list_offset = byte offset of the count field in the record;
+ *     count_type and index_type are integer scalar types.  Signed fields are sign extended, uint32 is not.  A record whose count
+ *     field is not K sets STIN_PLY_COUNT_DIFFERS and writes -1 into its rows (the stride assumption is void: the caller parses the
+ *     file another way); a record with an index outside [0, n_vertices) sets STIN_PLY_BAD_INDEX and is written as decoded.
+ *     faces: int64 [count * (K - 2), 3] in record order, a quad (a, b, c, d) as (a, b, c), (a, c, d).
+ *     status: 4 x int64 DEVICE words written by the call: [0] the flags (an integer atomic or), [1] the lowest record whose count
+ *     differs, [2] the lowest record with a bad index (integer atomic minima; 2^63 - 1 = none), [3] 0.  No float atomics.
+ *
+ * stin_face_label_vote.  Per-face labels to per-vertex labels, the Matterport step of the reference (preprocessing/
+ *     graph_level_generation.py:328-336): hist[v][l] = the number of corners (f, i) with faces[f][i] = v and face_labels[f] = l;
+ *     vertex_labels[v] = the lowest l that attains max_l hist[v][l] - np.argmax over the rows, 0 for a vertex without faces.
+ *     faces [F, 3] int64, face_labels [F] int64 in [0, C), 1 <= C <= STIN_VOTE_MAX_CLASSES, vertex_labels [N] int64.  Integer
+ *     counts (int32 atomic adds) only: the same bytes for every launch order.  A corner whose label lies outside [0, C) sets
+ *     STIN_VOTE_BAD_LABEL and is not counted; a corner whose vertex lies outside [0, N) sets STIN_VOTE_BAD_INDEX and is not
+ *     counted.  status: 4 x int64 DEVICE words: [0] flags, [1] / [2] the lowest face with a bad label / a bad index (2^63 - 1 =
+ *     none), [3] 0.  Workspace >= stin_face_label_vote_workspace_bytes(N, C) (the histogram; 0 = unsupported sizes). */
+#define STIN_PLY_INT8 0
+#define STIN_PLY_UINT8 1
+#define STIN_PLY_INT16 2
+#define STIN_PLY_UINT16 3
+#define STIN_PLY_INT32 4
+#define STIN_PLY_UINT32 5
+#define STIN_PLY_FLOAT32 6
+#define STIN_PLY_FLOAT64 7
+#define STIN_PLY_TO_F64 0
+#define STIN_PLY_TO_F32 1
+#define STIN_PLY_TO_I64 2
+#define STIN_PLY_TO_I32 3
+#define STIN_PLY_TO_U8 4
+#define STIN_PLY_TO_UNORM_F64 5
+#define STIN_PLY_FIELD_WORDS 6
+#define STIN_PLY_MAX_FIELDS 32
+#define STIN_PLY_MAX_STRIDE 240
+#define STIN_PLY_MAX_RECORDS 2147483647
+#define STIN_PLY_COUNT_DIFFERS 1
+#define STIN_PLY_BAD_INDEX 2
+#define STIN_VOTE_BAD_LABEL 1
+#define STIN_VOTE_BAD_INDEX 2
+#define STIN_VOTE_MAX_CLASSES 64
+#define STIN_VOTE_MAX_FACES 536870912
+#define STIN_VOTE_MAX_VERTICES 1073741824
+int stin_ply_decode(const uint8_t* body, int64_t body_bytes, int64_t first, int64_t stride, int64_t count, int big_endian,
+                    const int64_t* fields, int n_fields, stin_stream_t stream);
+int stin_ply_faces(const uint8_t* body, int64_t body_bytes, int64_t first, int64_t stride, int64_t count, int big_endian,
+                   int list_offset, int count_type, int index_type, int K, int64_t n_vertices, int64_t* faces, int64_t* status,
+                   stin_stream_t stream);
+size_t stin_face_label_vote_workspace_bytes(int64_t N, int C);
+int stin_face_label_vote(const int64_t* faces, const int64_t* face_labels, int64_t F, int64_t N, int C, int64_t* vertex_labels,
+                         int64_t* status, void* workspace, size_t workspace_bytes, stin_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -91,8 +91,9 @@
   channels frozen when done), the same bytes on every run.  Uniform or inverse-length weights, NOT cotangent weights.  A contract
   of this project's own (include/stin_hip.h, "Harmonic fill").
 
-All take and return tensors in the reference's own formats.  Out of scope: reading mesh files (neither open3d nor plyfile exists
-here to pin a reader against: vertices, faces and colours are inputs), and the Matterport and S3DIS label paths.
+All take and return tensors in the reference's own formats.  Mesh files are read by scene_io.read_ply (PLY, decoded on the GPU:
+its dict is the `mesh` argument of the functions here; read_scannet_mesh adds the labels of a ScanNet scan, vertex_labels_from_faces
+the per-face vote of the Matterport path).  Out of scope: the Matterport category tables and the S3DIS label path.
 """
 import ctypes
 import re
@@ -1267,7 +1268,8 @@ def graph_levels(mesh, levels, dilated_levels, dilation_dists, labels=None, refe
     mesh (reference_vc_normals=True reproduces that for file parity); and a cell-size level's trace is the membership trace of the
     clustering of the previous level, where the reference takes nearest(ORIGINAL mesh vertices, clustered vertices) whatever the
     previous level was (the dict-without-'csv' branch keeps the reference's rule).
-    Out of scope: reading mesh files and the Matterport / S3DIS label paths.  A dict level still takes the output of an external
+    `mesh` is what scene_io.read_ply returns for a PLY file (scene_io.write_scene_from_ply chains the two); out of scope: the Matterport
+    category tables (scene_io.vertex_labels_from_faces is its vote) and the S3DIS label path.  A dict level still takes the output of an external
     decimator (vcglib's tridecimator or trimesh_clustering in the reference) as it is."""
     if len(levels) != len(dilated_levels):
         raise ValueError('levels and dilated_levels need one entry per level')

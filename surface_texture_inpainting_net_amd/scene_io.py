@@ -382,3 +382,596 @@ def read_observers(path, device=None):
     if device is not None:
         bits = torch.from_numpy(bits).to(device)
     return bits, ids, num_poses
+
+
+# ---------------------------------------------------------------------------------------------------------------- mesh files
+# PLY (the Stanford polygon format): a text header that names the elements, their counts and their properties in file order, then
+# the body - ascii numbers, or fixed-stride binary records in either byte order.  read_ply returns the `mesh` dict every
+# preprocessing entry point starts from (graph_levels, decimate_qem, cluster_mesh, observe_vertices, FrameColors, sample_surface,
+# circle_masks_geodesic, views.render_mesh): what the reference gets from open3d.io.read_triangle_mesh and PlyData.read.  A
+# contract of the project's own (include/stin_hip.h, "Mesh files"), restated with numpy structured dtypes by the test suite and
+# NOT pinned against open3d or plyfile themselves: neither is installed here.
+PLY_SCALARS = ('int8', 'uint8', 'int16', 'uint16', 'int32', 'uint32', 'float32', 'float64')      # position = STIN_PLY_* code
+PLY_TYPE_NAMES = dict({t: t for t in PLY_SCALARS}, char='int8', uchar='uint8', short='int16', ushort='uint16', int='int32',
+                      uint='uint32', float='float32', double='float64')
+PLY_FORMATS = ('ascii', 'binary_little_endian', 'binary_big_endian')
+PLY_MAX_HEADER_BYTES = 1 << 20
+_PLY_WIDTH = dict(zip(PLY_SCALARS, (1, 1, 2, 2, 4, 4, 4, 8)))
+_PLY_COUNT = dict(zip(PLY_SCALARS, 'i1 u1 i2 u2 i4 u4 f4 f8'.split()))
+
+
+def read_ply_header(path_or_bytes):
+    """The header of a PLY file (a path, or the bytes of the file or of its beginning) ->
+        {'format': 'ascii' | 'binary_little_endian' | 'binary_big_endian', 'version': str, 'comments': [str], 'obj_info': [str],
+         'elements': [{'name': str, 'count': int, 'properties': [{'name': str, 'type': str, 'count_type': str or None}]}],
+         'body_offset': int}
+    with elements and properties in file order.  Types are the eight canonical names of PLY_SCALARS - the aliases char, uchar,
+    short, ushort, int, uint, float, double and int8 .. float64 are both read; a list property has the type of its entries as
+    'type' and the type of its count as 'count_type'.  body_offset is the byte after the end_header line.  Standard library only.
+    ValueError with the offending line for a malformed header, an unknown type name, or a missing end_header."""
+    if isinstance(path_or_bytes, (bytes, bytearray, memoryview)):
+        data = bytes(path_or_bytes[:PLY_MAX_HEADER_BYTES])
+    else:
+        data = b''
+        with open(path_or_bytes, 'rb') as f:
+            while b'end_header' not in data and len(data) < PLY_MAX_HEADER_BYTES:
+                chunk = f.read(1 << 16)
+                if not chunk:
+                    break
+                data += chunk
+            if b'end_header' in data:
+                data += f.readline()                                    # the rest of the end_header line, if a chunk cut it
+
+    def bad(number, text, why):
+        return ValueError('PLY header line %d: %r: %s' % (number, text, why))
+
+    header = {'format': None, 'version': None, 'comments': [], 'obj_info': [], 'elements': [], 'body_offset': None}
+    pos, number = 0, 0
+    while True:
+        end = data.find(b'\n', pos)
+        if end < 0:
+            raise ValueError('PLY header: no end_header line in the first %d bytes' % len(data))
+        text = data[pos:end].rstrip(b'\r').decode('latin-1')
+        pos, number = end + 1, number + 1
+        words = text.split()
+        if number == 1:
+            if text.strip() != 'ply':
+                raise bad(number, text, "the first line must be 'ply'")
+            continue
+        if not words:
+            continue
+        key = words[0]
+        if key == 'end_header':
+            break
+        if key == 'comment' or key == 'obj_info':
+            header['comments' if key == 'comment' else 'obj_info'].append(text.strip()[len(key):].strip())
+        elif key == 'format':
+            if len(words) != 3 or words[1] not in PLY_FORMATS or header['format'] is not None:
+                raise bad(number, text, 'expected one line `format <%s> <version>`' % ' | '.join(PLY_FORMATS))
+            header['format'], header['version'] = words[1], words[2]
+        elif key == 'element':
+            if len(words) != 3 or not words[2].isdigit():
+                raise bad(number, text, 'expected `element <name> <count>`')
+            if any(e['name'] == words[1] for e in header['elements']):
+                raise bad(number, text, 'second element of that name')
+            header['elements'].append({'name': words[1], 'count': int(words[2]), 'properties': []})
+        elif key == 'property':
+            if not header['elements']:
+                raise bad(number, text, 'a property before the first element')
+            is_list = len(words) > 1 and words[1] == 'list'
+            if len(words) != (5 if is_list else 3):
+                raise bad(number, text, 'expected `property <type> <name>` or `property list <count type> <type> <name>`')
+            for t in words[1 + is_list:-1]:
+                if t not in PLY_TYPE_NAMES:
+                    raise bad(number, text, 'unknown type %r' % t)
+            count_type = PLY_TYPE_NAMES[words[2]] if is_list else None
+            if is_list and count_type in ('float32', 'float64'):
+                raise bad(number, text, 'the count of a list must be an integer type')
+            props = header['elements'][-1]['properties']
+            if any(p['name'] == words[-1] for p in props):
+                raise bad(number, text, 'second property of that name')
+            props.append({'name': words[-1], 'type': PLY_TYPE_NAMES[words[-2]], 'count_type': count_type})
+        else:
+            raise bad(number, text, 'unknown keyword %r' % key)
+    if header['format'] is None:
+        raise ValueError('PLY header: no format line before end_header (line %d)' % number)
+    header['body_offset'] = pos
+    return header
+
+
+def _ply_record(props, list_len=None):
+    """Byte layout of one binary record of an element: ({property name: offset}, list offset or None, record bytes); a list
+    property counts as its count field plus list_len entries.  None when a list is present and list_len is not given."""
+    offsets, at, list_at = {}, 0, None
+    for p in props:
+        offsets[p['name']] = at
+        if p['count_type'] is None:
+            at += _PLY_WIDTH[p['type']]
+        elif list_len is None:
+            return None
+        else:
+            list_at = at
+            at += _PLY_WIDTH[p['count_type']] + list_len * _PLY_WIDTH[p['type']]
+    return offsets, list_at, at
+
+
+def _ply_plan(header):
+    """The elements read_ply decodes and the rules every decode path shares -> (vertex element or None, face element or None)."""
+    vertex = face = None
+    for el in header['elements']:
+        lists = [p for p in el['properties'] if p['count_type'] is not None]
+        if el['name'] == 'vertex':
+            if lists:
+                raise ValueError('read_ply: the vertex element has a list property (%r)' % lists[0]['name'])
+            vertex = el
+        elif el['name'] == 'face':
+            if len(lists) > 1:
+                raise ValueError('read_ply: the face element has %d list properties; one is supported' % len(lists))
+            if lists and lists[0]['type'] in ('float32', 'float64'):
+                raise ValueError('read_ply: the face list %r holds floats' % lists[0]['name'])
+            face = el
+        elif lists:
+            raise ValueError('read_ply: element %r has a list property, so its size is not fixed by the header and it cannot '
+                             'be skipped' % el['name'])
+    if vertex is not None and vertex['count'] > 0:
+        names = [p['name'] for p in vertex['properties']]
+        if not all(k in names for k in 'xyz'):
+            raise ValueError('read_ply: the vertex element lacks x, y or z')
+    return vertex, face
+
+
+def _ply_roles(props):
+    """Which scalar properties of the vertex element become which key: x y z -> vertices, uint8 red green blue -> colors and
+    colors_u8, nx ny nz -> normals, every other one (colours of another type included) -> vertex_properties."""
+    by_name = {p['name']: p for p in props}
+    roles = {}
+    if all(k in by_name for k in 'xyz'):
+        roles['vertices'] = ('x', 'y', 'z')
+    if all(k in by_name and by_name[k]['type'] == 'uint8' for k in ('red', 'green', 'blue')):
+        roles['colors'] = ('red', 'green', 'blue')
+    if all(k in by_name for k in ('nx', 'ny', 'nz')):
+        roles['normals'] = ('nx', 'ny', 'nz')
+    taken = {k for names in roles.values() for k in names}
+    return roles, [p for p in props if p['count_type'] is None and p['name'] not in taken]
+
+
+def _ply_is_float(t):
+    return t in ('float32', 'float64')
+
+
+def _ply_fans(counts, flat, triangulate):
+    """Polygons (counts [R], their indices one after the other in `flat`, int64 numpy) -> (triangles int64 [F, 3] in record order,
+    a polygon (v0, v1, ..., vk-1) as the fan (v0, v1, v2), (v0, v2, v3), ..., and the record of every triangle [F])."""
+    if counts.size and int(counts.min()) < 3:
+        r = int(np.argmax(counts < 3))
+        raise ValueError('read_ply: face %d has %d vertices; a polygon needs at least 3' % (r, int(counts[r])))
+    if not triangulate and counts.size and int(counts.max()) != 3:
+        r = int(np.argmax(counts != 3))
+        raise ValueError('read_ply: face %d has %d vertices and triangulate=False' % (r, int(counts[r])))
+    per = counts - 2
+    start = np.cumsum(counts) - counts                                   # first entry of every record in flat
+    rec = np.repeat(np.arange(counts.size, dtype=np.int64), per)
+    t = np.arange(int(per.sum()), dtype=np.int64) - np.repeat(np.cumsum(per) - per, per)
+    base = start[rec]
+    tri = np.stack([flat[base], flat[base + t + 1], flat[base + t + 2]], axis=1) if rec.size else np.zeros((0, 3), dtype=np.int64)
+    return tri.astype(np.int64), rec
+
+
+def _ply_ascii_column(tokens, t, what):
+    """Ascii tokens (numpy 'S' array) -> the numpy array of PLY type t: a number is read as a python float (floats) or int
+    (integers, which must fit the type) and then stored in the property's type."""
+    try:
+        if _ply_is_float(t):
+            return tokens.astype(np.float64).astype(_PLY_COUNT[t])
+        wide = tokens.astype(np.int64)
+    except ValueError as e:
+        raise ValueError('read_ply: %s: %s' % (what, e)) from None
+    info = np.iinfo(_PLY_COUNT[t])
+    if wide.size and (int(wide.min()) < info.min or int(wide.max()) > info.max):
+        raise ValueError('read_ply: %s: a value does not fit %s' % (what, t))
+    return wide.astype(_PLY_COUNT[t])
+
+
+def _ply_parse_host(data, header):
+    """The body on the host -> ({vertex property: numpy array in its own type}, {face scalar property: array}, counts, flat)."""
+    order = '>' if header['format'] == 'binary_big_endian' else '<'
+    ascii_body = header['format'] == 'ascii'
+    at = header['body_offset']
+    tokens = np.array(data[at:].tobytes().split(), dtype='S') if ascii_body else None
+    at = 0 if ascii_body else at
+    columns = {'vertex': {}, 'face': {}}
+    counts, flat = np.zeros(0, dtype=np.int64), np.zeros(0, dtype=np.int64)
+
+    def short(el):
+        return ValueError('read_ply: the file ends inside element %r (%d records expected): truncated' % (el['name'], el['count']))
+
+    for el in header['elements']:
+        props, n = el['properties'], el['count']
+        lists = [i for i, p in enumerate(props) if p['count_type'] is not None]
+        keep = el['name'] in columns
+        if not lists:
+            if ascii_body:
+                need = n * len(props)
+                if at + need > tokens.size:
+                    raise short(el)
+                if keep:
+                    block = tokens[at:at + need].reshape(n, len(props))
+                    for i, p in enumerate(props):
+                        columns[el['name']][p['name']] = _ply_ascii_column(block[:, i], p['type'], '%s.%s' % (el['name'], p['name']))
+                at += need
+            else:
+                dt = np.dtype([(p['name'], order + _PLY_COUNT[p['type']]) for p in props]) if props else np.dtype([])
+                need = n * dt.itemsize
+                if at + need > data.size:
+                    raise short(el)
+                if keep and props:
+                    block = np.frombuffer(data, dtype=dt, count=n, offset=at)
+                    for p in props:
+                        columns[el['name']][p['name']] = np.ascontiguousarray(block[p['name']]).astype(_PLY_COUNT[p['type']])
+                at += need
+            continue
+        # the face element with its one list
+        li = lists[0]
+        lp = props[li]
+        scalars = [p for p in props if p['count_type'] is None]
+        if n == 0:
+            for p in scalars:
+                columns['face'][p['name']] = np.zeros(0, dtype=_PLY_COUNT[p['type']])
+            continue
+        if ascii_body:
+            if at >= tokens.size:
+                raise short(el)
+            k0 = int(_ply_ascii_column(tokens[at + li:at + li + 1], lp['count_type'], 'face count')[0]) if at + li < tokens.size else -1
+            w = len(props) + k0
+            uniform = k0 >= 0 and at + n * w <= tokens.size
+            if uniform:
+                block = tokens[at:at + n * w].reshape(n, w)
+                try:
+                    c = _ply_ascii_column(block[:, li], lp['count_type'], 'face count').astype(np.int64)
+                    uniform = bool((c == k0).all())
+                except ValueError:                                          # not a column of counts: the lists differ in length
+                    uniform = False
+            if uniform:
+                counts = c
+                flat = _ply_ascii_column(block[:, li + 1:li + 1 + k0].reshape(-1), lp['type'], 'face indices').astype(np.int64)
+                for i, p in enumerate(props):
+                    if i != li:
+                        columns['face'][p['name']] = _ply_ascii_column(block[:, i if i < li else i + k0], p['type'], 'face.' + p['name'])
+                at += n * w
+                continue
+            rows, cs, ids = {p['name']: [] for p in scalars}, [], []
+            for r in range(n):
+                for i, p in enumerate(props):
+                    if at >= tokens.size:
+                        raise short(el)
+                    if i != li:
+                        rows[p['name']].append(tokens[at])
+                        at += 1
+                        continue
+                    k = int(_ply_ascii_column(tokens[at:at + 1], lp['count_type'], 'face count')[0])
+                    if k < 0 or at + 1 + k > tokens.size:
+                        raise short(el)
+                    cs.append(k)
+                    ids.append(tokens[at + 1:at + 1 + k])
+                    at += 1 + k
+            counts = np.asarray(cs, dtype=np.int64)
+            flat = _ply_ascii_column(np.concatenate(ids), lp['type'], 'face indices').astype(np.int64)
+            for p in scalars:
+                columns['face'][p['name']] = _ply_ascii_column(np.array(rows[p['name']], dtype='S'), p['type'], 'face.' + p['name'])
+            continue
+        ct, it = order + _PLY_COUNT[lp['count_type']], order + _PLY_COUNT[lp['type']]
+        list_at = _ply_record(props, 0)[1]
+        if at + list_at + _PLY_WIDTH[lp['count_type']] > data.size:
+            raise short(el)
+        k0 = int(np.frombuffer(data, dtype=ct, count=1, offset=at + list_at)[0])
+        stride = _ply_record(props, max(k0, 0))[2]
+        uniform = 0 <= k0 <= 255 and at + n * stride <= data.size
+        if uniform:
+            dt = np.dtype([(p['name'], order + _PLY_COUNT[p['type']]) if p['count_type'] is None else (p['name'], [('n', ct), ('ids', it, (k0,))])
+                           for p in props])
+            block = np.frombuffer(data, dtype=dt, count=n, offset=at)
+            c = block[lp['name']]['n'].astype(np.int64)
+            uniform = bool((c == k0).all())
+        if uniform:
+            counts = c
+            flat = np.ascontiguousarray(block[lp['name']]['ids']).astype(np.int64).reshape(-1)
+            for p in scalars:
+                columns['face'][p['name']] = np.ascontiguousarray(block[p['name']]).astype(_PLY_COUNT[p['type']])
+            at += n * stride
+            continue
+        before = np.dtype([(p['name'], order + _PLY_COUNT[p['type']]) for p in props[:li]])       # lists of different lengths:
+        after = np.dtype([(p['name'], order + _PLY_COUNT[p['type']]) for p in props[li + 1:]])    # one record at a time
+        rows, cs, ids = {p['name']: [] for p in scalars}, [], []
+        cw, iw = _PLY_WIDTH[lp['count_type']], _PLY_WIDTH[lp['type']]
+        for r in range(n):
+            if at + before.itemsize + cw > data.size:
+                raise short(el)
+            head = np.frombuffer(data, dtype=before, count=1, offset=at) if li else None
+            k = int(np.frombuffer(data, dtype=ct, count=1, offset=at + before.itemsize)[0])
+            at += before.itemsize + cw
+            if k < 0 or at + k * iw + after.itemsize > data.size:
+                raise short(el)
+            cs.append(k)
+            ids.append(np.frombuffer(data, dtype=it, count=k, offset=at))
+            at += k * iw
+            tail = np.frombuffer(data, dtype=after, count=1, offset=at) if li + 1 < len(props) else None
+            at += after.itemsize
+            for p in props[:li]:
+                rows[p['name']].append(head[p['name']][0])
+            for p in props[li + 1:]:
+                rows[p['name']].append(tail[p['name']][0])
+        counts = np.asarray(cs, dtype=np.int64)
+        flat = np.concatenate(ids).astype(np.int64)
+        for p in scalars:
+            columns['face'][p['name']] = np.asarray(rows[p['name']], dtype=_PLY_COUNT[p['type']])
+    return columns['vertex'], columns['face'], counts, flat
+
+
+def _ply_widen(a):
+    return a.astype(np.float64) if a.dtype.kind == 'f' else a.astype(np.int64)
+
+
+def _ply_bad_index(record, n):
+    return IndexError('read_ply: face %d has a vertex index outside [0, %d)' % (record, n))
+
+
+def _ply_host(data, header, vertex, face, triangulate, device):
+    vcols, fcols, counts, flat = _ply_parse_host(data, header)
+    n = vertex['count'] if vertex is not None else 0
+    tri, rec = _ply_fans(counts, flat, triangulate)
+    wrong = (tri < 0) | (tri >= n)
+    if wrong.any():
+        raise _ply_bad_index(int(rec[int(np.argmax(wrong.any(axis=1)))]), n)
+    up = lambda a: torch.from_numpy(np.ascontiguousarray(a)).to(device)
+    roles, others = _ply_roles(vertex['properties']) if vertex is not None else ({}, [])
+    mesh = {}
+    stack = lambda names, dtype: (np.stack([vcols[k].astype(dtype) for k in names], axis=1) if n else np.zeros((0, 3), dtype=dtype))
+    mesh['vertices'] = up(stack(roles['vertices'], np.float64) if 'vertices' in roles else np.zeros((0, 3), dtype=np.float64))
+    mesh['faces'] = up(tri)
+    if 'colors' in roles:
+        u8 = stack(roles['colors'], np.uint8)
+        mesh['colors'], mesh['colors_u8'] = up(u8.astype(np.float64) / 255.0), up(u8)
+    if 'normals' in roles:
+        mesh['normals'] = up(stack(roles['normals'], np.float64))
+    mesh['vertex_properties'] = {p['name']: up(_ply_widen(vcols[p['name']])) for p in others}
+    mesh['face_properties'] = {k: up(_ply_widen(v)) for k, v in fcols.items()}
+    mesh['header'] = header
+    return mesh
+
+
+def _ply_device_layout(data_bytes, header, vertex, face):
+    """Where every element's records start when the file can be decoded on the device -> ({element name: (first, stride)},
+    K or None); or a str: the reason why it cannot (ascii, lists of different lengths, a record the kernels do not take)."""
+    from . import _lib
+    if header['format'] == 'ascii':
+        return 'an ascii file'
+    fixed, face_el = 0, None
+    for el in header['elements']:
+        if el is face and any(p['count_type'] is not None for p in el['properties']):
+            face_el = el
+        else:
+            fixed += el['count'] * _ply_record(el['properties'])[2]
+    K = None
+    if face_el is not None and face_el['count'] > 0:
+        lp = [p for p in face_el['properties'] if p['count_type'] is not None][0]
+        left = data_bytes - header['body_offset'] - fixed - face_el['count'] * _ply_record(face_el['properties'], 0)[2]
+        per = face_el['count'] * _PLY_WIDTH[lp['type']]
+        if left < 0 or left % per != 0 or left // per not in (3, 4):
+            return 'the size of the file does not fit %d faces of 3 or of 4 vertices each' % face_el['count']
+        K = left // per
+    elif data_bytes - header['body_offset'] < fixed:
+        return 'a truncated body'
+    layout, at = {}, header['body_offset']
+    for el in header['elements']:
+        stride = _ply_record(el['properties'], (K or 0) if el is face_el else None)[2]
+        layout[el['name']] = (at, stride)
+        at += el['count'] * stride
+        if el in (vertex, face) and el['count'] > 0:
+            scalars = sum(p['count_type'] is None for p in el['properties'])
+            if stride > _lib.CONSTANTS['STIN_PLY_MAX_STRIDE'] or scalars + 3 > _lib.CONSTANTS['STIN_PLY_MAX_FIELDS']:
+                return 'a %s record of %d bytes and %d properties is more than the decode kernel takes' % (el['name'], stride, scalars)
+            if el['count'] > _lib.CONSTANTS['STIN_PLY_MAX_RECORDS']:
+                return 'too many %s records' % el['name']
+    return layout, K
+
+
+def _ply_decode_call(lib, buf, first, stride, count, big, rows):
+    """rows: [(offset, PLY type, destination tensor, STIN_PLY_TO_* name, column)] -> one stin_ply_decode launch."""
+    import ctypes
+    from . import _lib
+    from .plan import _ptr, _stream
+    if count == 0 or not rows:
+        return
+    words = []
+    for offset, t, dst, to, col in rows:
+        words += [offset, PLY_SCALARS.index(t), _ptr(dst), _lib.CONSTANTS['STIN_PLY_TO_' + to], dst.shape[1] if dst.dim() == 2 else 1, col]
+    table = (ctypes.c_int64 * len(words))(*words)
+    _lib.check(lib.stin_ply_decode(_ptr(buf), int(buf.numel()), first, stride, count, big, table, len(rows), _stream(buf)),
+               'stin_ply_decode')
+
+
+def _ply_device(data, header, vertex, face, layout, K, triangulate, device):
+    """-> the mesh dict, or None when the device status says that a face's count differs from K."""
+    from . import _lib
+    from .plan import _ptr, _stream
+    lib = _lib.load()
+    dev = torch.device(device)
+    if dev.type != 'cuda':
+        raise TypeError("read_ply: decode='device' needs a CUDA device")
+    buf = torch.from_numpy(data).to(dev)                                   # the file's bytes, once
+    big = int(header['format'] == 'binary_big_endian')
+    n = vertex['count'] if vertex is not None else 0
+    mesh = {'vertices': torch.empty(n, 3, dtype=torch.float64, device=dev)}
+    props, face_props = {}, {}
+    if vertex is not None:
+        roles, others = _ply_roles(vertex['properties'])
+        types = {p['name']: p['type'] for p in vertex['properties']}
+        offsets, _, stride = _ply_record(vertex['properties'])
+        rows = []
+        for key, to, dtype in (('vertices', 'F64', torch.float64), ('colors', 'UNORM_F64', torch.float64), ('normals', 'F64', torch.float64)):
+            if key in roles:
+                mesh[key] = mesh.get(key) if key == 'vertices' else torch.empty(n, 3, dtype=dtype, device=dev)
+                rows += [(offsets[k], types[k], mesh[key], to, c) for c, k in enumerate(roles[key])]
+        if 'colors' in roles:
+            mesh['colors_u8'] = torch.empty(n, 3, dtype=torch.uint8, device=dev)
+            rows += [(offsets[k], types[k], mesh['colors_u8'], 'U8', c) for c, k in enumerate(roles['colors'])]
+        for p in others:
+            wide = _ply_is_float(p['type'])
+            props[p['name']] = torch.empty(n, dtype=torch.float64 if wide else torch.int64, device=dev)
+            rows.append((offsets[p['name']], p['type'], props[p['name']], 'F64' if wide else 'I64', 0))
+        _ply_decode_call(lib, buf, layout['vertex'][0], stride, n, big, rows)
+    nf = face['count'] if face is not None else 0
+    lists = [p for p in face['properties'] if p['count_type'] is not None] if face is not None else []
+    faces = torch.empty(0, 3, dtype=torch.int64, device=dev)
+    status = None
+    if face is not None:
+        offsets, list_at, stride = _ply_record(face['properties'], K if lists and nf else 0)
+        rows = []
+        for p in face['properties']:
+            if p['count_type'] is None:
+                wide = _ply_is_float(p['type'])
+                face_props[p['name']] = torch.empty(nf, dtype=torch.float64 if wide else torch.int64, device=dev)
+                rows.append((offsets[p['name']], p['type'], face_props[p['name']], 'F64' if wide else 'I64', 0))
+        _ply_decode_call(lib, buf, layout['face'][0], stride, nf, big, rows)
+        if lists and nf:
+            if K != 3 and not triangulate:
+                raise ValueError('read_ply: the faces have %d vertices and triangulate=False' % K)
+            faces = torch.empty(nf * (K - 2), 3, dtype=torch.int64, device=dev)
+            status = torch.empty(4, dtype=torch.int64, device=dev)
+            _lib.check(lib.stin_ply_faces(_ptr(buf), int(buf.numel()), layout['face'][0], stride, nf, big, list_at,
+                                          PLY_SCALARS.index(lists[0]['count_type']), PLY_SCALARS.index(lists[0]['type']), K, n,
+                                          _ptr(faces), _ptr(status), _stream(buf)), 'stin_ply_faces')
+    if status is not None:
+        st = status.cpu().tolist()                                         # the one read-back of the file
+        if st[0] & _lib.CONSTANTS['STIN_PLY_COUNT_DIFFERS']:
+            return None
+        if st[0] & _lib.CONSTANTS['STIN_PLY_BAD_INDEX']:
+            raise _ply_bad_index(st[2], n)
+    mesh['faces'] = faces
+    mesh['vertex_properties'], mesh['face_properties'], mesh['header'] = props, face_props, header
+    order = ('vertices', 'faces', 'colors', 'colors_u8', 'normals', 'vertex_properties', 'face_properties', 'header')
+    return {k: mesh[k] for k in order if k in mesh}
+
+
+def read_ply(path, device='cuda', decode='auto', triangulate=True):
+    """A PLY mesh file -> the `mesh` dict of tensors on `device` that preprocessing.graph_levels (and write_graph_levels,
+    decimate_qem, cluster_mesh, vertex_normals, observe_vertices, FrameColors, sample_surface, views.render_mesh) take as it is:
+        vertices [N, 3] float64 (x y z);  faces [F, 3] int64;
+        colors [N, 3] float64 = uint8 / 255 (one IEEE division: open3d's vertex_colors) and colors_u8 [N, 3] uint8, when red, green
+            and blue are uchar properties;  normals [N, 3] float64, when nx, ny and nz are present;
+        vertex_properties / face_properties: every other scalar property under its own name, [N] / [records], widened to int64
+            or float64 (`label`, `alpha`, `category_id`, ...);  header: read_ply_header's dict.
+    Polygons with more than three vertices are cut into fans (v0, v1, v2), (v0, v2, v3), ... in record order (triangulate=False:
+    ValueError instead); face_properties stay one entry per RECORD of the file.  Elements other than vertex and face are skipped
+    when the header fixes their size; one with a list property is a ValueError that names it.  In an ascii file a number is read
+    as a python float or int and then stored in the property's type.
+    decode='device': the file's bytes are uploaded once and two kernels unpack them (stin_ply_decode for the scalar columns,
+        stin_ply_faces for the list; include/stin_hip.h, "Mesh files"); the host parses nothing but the header.  For binary files
+        whose lists all have 3 or all have 4 entries - which the host knows from the header and the size of the file alone.
+    decode='host': numpy structured dtypes, then one upload per tensor: the same bytes on the same device (device='cpu' works).
+    decode='auto': the device path when it applies; the host path for ascii files, for lists of different lengths, for records
+        beyond the kernel's limits, and when the device status reports a count that differs (a file whose size fits by accident).
+    ValueError for a truncated body (found from the header and the file size, before any launch), a polygon of fewer than 3
+    vertices; IndexError, naming the first such face, for a vertex index outside [0, N)."""
+    if decode not in ('auto', 'device', 'host'):
+        raise ValueError("read_ply: decode is 'auto', 'device' or 'host'")
+    data = np.fromfile(path, dtype=np.uint8)
+    header = read_ply_header(data[:PLY_MAX_HEADER_BYTES].tobytes())
+    vertex, face = _ply_plan(header)
+    if decode == 'device' or (decode == 'auto' and torch.device(device).type == 'cuda'):
+        plan = _ply_device_layout(int(data.size), header, vertex, face)
+        if isinstance(plan, str):
+            if decode == 'device':
+                raise ValueError('read_ply: %s cannot be decoded on the device: %s' % (path, plan))
+        else:
+            mesh = _ply_device(data, header, vertex, face, plan[0], plan[1], triangulate, device)
+            if mesh is not None:
+                return mesh
+            if decode == 'device':
+                raise ValueError('read_ply: %s: the faces do not all have %d vertices' % (path, plan[1]))
+    return _ply_host(data, header, vertex, face, triangulate, device)
+
+
+def read_scannet_mesh(scan_dir, scan_name, with_labels=True, device='cuda', decode='auto'):
+    """A ScanNet scan directory -> (mesh, labels): read_ply of <scan_dir>/<scan_name>_vh_clean_2.ply and, with_labels, the `label`
+    vertex property of <scan_name>_vh_clean_2.labels.ply through preprocessing.remap_scannet_labels (ids above 40 -> 0, then the
+    class table) as int64 [N] on the device - what graph_levels takes as `labels` in train mode; labels is None otherwise.
+    ValueError when the label file has another number of vertices than the mesh.  The segs.json / aggregation.json route to
+    instance labels is out of scope."""
+    import os
+    from .preprocessing import remap_scannet_labels
+    mesh = read_ply(os.path.join(str(scan_dir), '%s_vh_clean_2.ply' % scan_name), device=device, decode=decode)
+    if not with_labels:
+        return mesh, None
+    path = os.path.join(str(scan_dir), '%s_vh_clean_2.labels.ply' % scan_name)
+    labelled = read_ply(path, device=device, decode=decode)
+    if 'label' not in labelled['vertex_properties']:
+        raise ValueError('%s has no vertex property `label`' % path)
+    labels = labelled['vertex_properties']['label']
+    if int(labels.shape[0]) != int(mesh['vertices'].shape[0]):
+        raise ValueError('%s has %d vertices, the mesh has %d' % (path, int(labels.shape[0]), int(mesh['vertices'].shape[0])))
+    return mesh, remap_scannet_labels(labels)
+
+
+def vertex_labels_from_faces(faces, face_labels, num_vertices, num_classes, strict=True):
+    """Per-face labels -> per-vertex labels, the Matterport step of the reference (preprocessing/graph_level_generation.py:328-336):
+    every face votes with its label at its three corners and a vertex takes the class with the most votes, the lowest one on a
+    tie, 0 without faces (np.argmax over the rows of the histogram).  faces [F, 3] int, face_labels [F] int in [0, num_classes)
+    (CUDA), num_classes <= STIN_VOTE_MAX_CLASSES -> int64 [num_vertices].  Integer counts: the same bytes on every run
+    (stin_face_label_vote).  A label outside [0, num_classes) or a vertex outside [0, num_vertices) is not counted; strict:
+    ValueError / IndexError that names the first such face; strict=False: -> (labels, flags) with the STIN_VOTE_BAD_* bits.
+    Out of scope: the Matterport category tables that produce face_labels from `category_id` (premapping,
+    MATTERPORT_CLASS_REMAP) and the ScanNet segs.json / aggregation.json route."""
+    from . import _lib
+    from .plan import _ptr, _stream
+    if not (torch.is_tensor(faces) and faces.is_cuda and torch.is_tensor(face_labels) and face_labels.is_cuda):
+        raise TypeError('faces and face_labels must be CUDA tensors (no CPU fallback exists)')
+    lib = _lib.load()
+    f = faces.long().reshape(-1, 3).contiguous()
+    l = face_labels.long().reshape(-1).contiguous()
+    nf, n, c, dev = int(f.shape[0]), int(num_vertices), int(num_classes), f.device
+    if int(l.shape[0]) != nf:
+        raise ValueError('vertex_labels_from_faces: %d faces and %d face labels' % (nf, int(l.shape[0])))
+    if n < 0 or not 1 <= c <= _lib.CONSTANTS['STIN_VOTE_MAX_CLASSES']:
+        raise ValueError('vertex_labels_from_faces: num_vertices >= 0 and 1 <= num_classes <= %d' % _lib.CONSTANTS['STIN_VOTE_MAX_CLASSES'])
+    out = torch.empty(max(n, 1), dtype=torch.int64, device=dev)[:n]
+    status = torch.empty(4, dtype=torch.int64, device=dev)
+    ws_bytes = lib.stin_face_label_vote_workspace_bytes(n, c)
+    ws = torch.empty(max(ws_bytes, 1), dtype=torch.uint8, device=dev)
+    _lib.check(lib.stin_face_label_vote(_ptr(f), _ptr(l), nf, n, c, _ptr(out), _ptr(status), _ptr(ws), ws_bytes, _stream(f)),
+               'stin_face_label_vote')
+    st = status.cpu().tolist()
+    if not strict:
+        return out, st[0]
+    if st[0] & _lib.CONSTANTS['STIN_VOTE_BAD_LABEL']:
+        raise ValueError('vertex_labels_from_faces: the label of face %d lies outside [0, %d)' % (st[1], c))
+    if st[0] & _lib.CONSTANTS['STIN_VOTE_BAD_INDEX']:
+        raise IndexError('vertex_labels_from_faces: face %d has a vertex outside [0, %d)' % (st[2], n))
+    return out
+
+
+def write_scene_from_ply(out_dir, ply_path, levels, dilated_levels, dilation_dists, labels_path=None, crops=None, masks=None):
+    """One scene from its mesh file to the files training reads, a chain of existing calls and nothing else:
+    read_ply(ply_path) -> write_graph_levels(<out_dir>/graphs, <scene>, ...) (scene = the file name without `.ply`; labels_path: a
+    ScanNet `.labels.ply` whose `label` property goes through remap_scannet_labels - train mode); then, when `crops` is a dict,
+    write_crops(graph file, crops.pop('out_dir', <out_dir>/crops), **crops); then, when `masks` is a dict,
+    write_circle_masks(graph file, masks.pop('masks_dir', <out_dir>/masks/<scene>), circle_masks(edges of the mesh's faces, N,
+    **masks)).  -> the list of the files written, the graph file first."""
+    import os
+    from .preprocessing import circle_masks, edges_from_faces, remap_scannet_labels
+    mesh = read_ply(ply_path)
+    labels = None
+    if labels_path is not None:
+        labels = remap_scannet_labels(read_ply(labels_path)['vertex_properties']['label'])
+    scene = os.path.basename(str(ply_path)).rsplit('.', 1)[0]
+    graph = write_graph_levels(os.path.join(str(out_dir), 'graphs'), scene, mesh, levels, dilated_levels, dilation_dists, labels=labels)
+    written = [graph]
+    if crops is not None:
+        kw = dict(crops)
+        written += write_crops(graph, kw.pop('out_dir', os.path.join(str(out_dir), 'crops')), **kw)
+    if masks is not None:
+        kw = dict(masks)
+        masks_dir = kw.pop('masks_dir', os.path.join(str(out_dir), 'masks', scene))
+        n = int(mesh['vertices'].shape[0])
+        written += write_circle_masks(graph, masks_dir, circle_masks(edges_from_faces(mesh['faces'], n), n, **kw))
+    return written

@@ -15,9 +15,10 @@ screenshot key `P`, a "save the PLYs" key `D`), for machines without a display a
                          pose, a chunk of poses at a time, and measures them.  Not pinned against skimage or piq: the 11 x 11 window
                          has integer taps, and there is no padding, no luma conversion and no multi-scale SSIM.
 
-Out of scope: lighting, anti-aliasing, textures, clipping at the near plane (a face that crosses it is dropped), reading meshes or
+Out of scope: lighting, anti-aliasing, textures, clipping at the near plane (a face that crosses it is dropped), reading
 images, the interactive viewer, SemSegVisualizer's palette (pass label colours as vertex colours), a CPU fallback.  Faces come from
-the caller: graphs/<scene>.pt holds none."""
+the caller: graphs/<scene>.pt holds none.  Mesh files - write_ply's own included - are read by scene_io.read_ply, whose dict holds the
+vertices, faces and colours render_mesh takes."""
 import collections
 import ctypes
 import json
